@@ -18,9 +18,6 @@ import os
 import sys
 import time
 
-# (before torch is imported: the HIP runtime reads it when it initialises; big_dreamer_amd/__init__.py has the measurements)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
 import numpy as np
 import torch
 
@@ -281,6 +278,39 @@ def surface_ms_per_step(d, dev, steps, warmup, bursts_of=(5, 50)):
     return res, {k: round(float(v), 5) for k, v in logs.items()}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(eng, logs, out_dir):
+    """What the timed path hands its caller after its last step: the log dict of that step and the parameters the three
+    optimiser steps left behind (every tensor of every group, the critic's target copy included), one float64 / float32
+    .npy per name under `out_dir`.  A tensor is written whole unless the total would exceed 64 MB; then the largest
+    tensors are replaced by a fixed, seeded sample of their elements (recorded in `_sampled.json`)."""
+    os.makedirs(out_dir, exist_ok=True)
+    eng.join()
+    torch.cuda.synchronize()
+    arrays = {f"log.{k}": np.asarray(v, dtype=np.float64) for k, v in sorted(logs.items())}
+    for gname in sorted(eng.groups):
+        g = eng.groups[gname]
+        for mod, name, _ in g.specs:
+            arrays[f"{gname}.{mod}.{name}"] = g.p[(mod, name)].detach().contiguous().cpu().numpy().astype(np.float32)
+    sampled, total = {}, sum(a.nbytes for a in arrays.values())
+    for k in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        if total <= DUMP_BUDGET_BYTES:
+            break
+        a = arrays[k]
+        keep = max(1, a.size - (total - DUMP_BUDGET_BYTES) // a.itemsize)
+        idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+        arrays[k] = a.reshape(-1)[idx]
+        sampled[k] = {"shape": list(a.shape), "flat_indices_seed": 0, "kept": int(keep)}
+        total -= a.nbytes - arrays[k].nbytes
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    if sampled:
+        json.dump(sampled, open(os.path.join(out_dir, "_sampled.json"), "w"), indent=1)
+    log(f"dumped {len(arrays)} arrays ({total / 2**20:.1f} MB) to {out_dir}")
+
+
 def child_json(extra_args, timeout=600):
     """Run this script again as a CHILD process (fresh HIP context) and return the JSON object it prints: the legs of the
     default run are separate processes, one after the other, while this one holds no engine.  (Round 2 needed this because
@@ -314,6 +344,9 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo: tests only)")
     ap.add_argument("--same-device", action="store_true",
                     help="tests only: every rank on cuda:0 (needs --backend gloo: RCCL refuses two ranks on one device)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's logs and the updated parameters as DIR/<name>.npy "
+                         "(rank 0; at most 64 MB)")
     args = ap.parse_args()
 
     from big_dreamer_amd import launch
@@ -367,6 +400,9 @@ def main():
     # (one communicator: the engine issues the actor / critic all-reduces one host step late so that they never sit in
     # front of the next step's world-model all-reduce -- engine._optimizer_step_or_defer)
     dt, kt, logs, eng = run_workload(d, args.pixel, args, rank, world, dev, dist_on, args.steps, args.warmup)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, logs, args.dump_outputs)
 
     out = None
     if rank == 0:
