@@ -100,7 +100,7 @@ class ImagineFwdArgs(C.Structure):
         ["w_a4m", "w_a4s", "b_a4", "start_feat", "eps_action", "eps_entropy", "eps_prior"]) + [
         ("min_std", F32), ("act_raw_init_std", F32), ("act_min_std", F32), ("act_mean_scale", F32)] + _ptr_fields(
         ["feat", "prior_mean", "prior_std", "entropy", "action", "sv_actor", "sv_act_stats", "sv_x", "sv_gates",
-         "sv_p"]) + [("sv_actor_stride", C.c_size_t)])
+         "sv_p"]) + [("sv_actor_stride", C.c_size_t)] + _ptr_fields(["sv_act_us"]))
 
 
 class ImagineBwdArgs(C.Structure):
@@ -135,7 +135,8 @@ class ImagineCatFwdArgs(C.Structure):
          "b_p1", "w_p2", "b_p2", "w_a0h", "w_a0sT"]) + [("w_a", P * 3), ("b_a", P * 4)] + _ptr_fields(
         ["w_a4m", "w_a4s", "b_a4", "start_feat", "start_sidx", "eps_action", "eps_entropy", "q_prior"]) + [
         ("act_raw_init_std", F32), ("act_min_std", F32), ("act_mean_scale", F32)] + _ptr_fields(
-        ["feat", "sidx", "prior_logits", "entropy", "action", "sv_actor", "sv_act_stats", "sv_x", "sv_gates", "sv_p"]))
+        ["feat", "sidx", "prior_logits", "entropy", "action", "sv_actor", "sv_act_stats", "sv_x", "sv_gates", "sv_p",
+         "sv_act_us"]))
 
 
 class ImagineCatBwdArgs(C.Structure):
@@ -212,6 +213,7 @@ _SIGS = {
     "bd_plan_rollout": (I32, [C.POINTER(PlanArgs), P]),
     "bd_cem_refit": (I32, [P, I32, P, I32, I32, I32, I32, I32, P, P, P]),
     "bd_lambda_return_backward": (I32, [P, F32, I32, I32, F32, F32, P, P, P]),
+    "bd_actor_reinforce": (I32, [P, P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, I32, P, P, I32, P, P]),
     "bd_normal_nll": (I32, [P, I32, P, I32, I32, I32, F32, P, I32, P, I32, P, P]),
     "bd_bernoulli_nll": (I32, [P, P, C.c_size_t, F32, P, P, I32, P, P]),
     "bd_kl_forward": (I32, [P, P, P, P, I32, I32, F32, I32, P, I32, P, P]),

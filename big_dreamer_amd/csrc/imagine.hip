@@ -119,7 +119,8 @@ __global__ __launch_bounds__(kThreads) void imagine_fwd_kernel(bd_imagine_fwd_ar
                         const float mean = a.act_mean_scale * th;
                         const float pre = Rw + a.act_raw_init_std;
                         const float sd = softplusf(pre) + a.act_min_std;
-                        act = tanh_act(mean + sd * eps);
+                        const float u = mean + sd * eps;
+                        act = tanh_act(u);
                         a.action[(tn + grow) * A + col] = act;
                         mean_s[row * A + col] = mean;
                         std_s[row * A + col] = sd;
@@ -129,6 +130,11 @@ __global__ __launch_bounds__(kThreads) void imagine_fwd_kernel(bd_imagine_fwd_ar
                             st[A] = sigmoidf(pre);
                             st[2 * A] = mean;
                             st[3 * A] = sd;
+                        }
+                        if (a.sv_act_us) {         // exact (u, std) for bd_actor_reinforce (gradient_mixing != -1)
+                            float* us = a.sv_act_us + (tn + grow) * 2 * A + col;
+                            us[0] = u;
+                            us[A] = sd;
                         }
                     }
                     af[frag_idx(row, col)] = act;

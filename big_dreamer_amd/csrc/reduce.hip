@@ -211,6 +211,52 @@ __global__ __launch_bounds__(256) void lambda_bwd_kernel(const float* __restrict
     }
 }
 
+// ---- REINFORCE term of the mixed actor gradient (bd_actor_reinforce; one lane per imagined decision) ----------
+// l = sum_a log N(u; mean, std) - log(1 - tanh^2 u) with (u - mean) / std = eps; log(1 - tanh^2 u) in the stable form
+// 2 (log 2 - u - softplus(-2u)).  Only the value of l needs u (the Jacobian term is constant in the actor's weights).
+__global__ __launch_bounds__(256) void actor_reinforce_kernel(
+    const float* __restrict__ eps, const float* __restrict__ us, const float* __restrict__ stats,
+    const float* __restrict__ ret, const float* __restrict__ base0, const float* __restrict__ value,
+    const float* __restrict__ weight, int rows, int N, int A, float scale, float dentropy, int write,
+    float* __restrict__ dout, double* __restrict__ partials) {
+    __shared__ double red[kWaves];
+    constexpr float kLn2 = 0.69314718055994531f;
+    double s = 0.0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += gridDim.x * blockDim.x) {
+        const float w = weight ? weight[i] : 1.f;
+        const float adv = ret[i] - (i < N ? base0[i] : value[i - N]);
+        const float c = scale * w * adv;
+        const float dent = dentropy * w;
+        const float* e = eps + (size_t)i * A;
+        const float* uu = us + (size_t)i * 2 * A;
+        const float* st = stats + (size_t)i * 4 * A;
+        float* d = dout + (size_t)i * 2 * A;
+        float l = 0.f;
+        for (int j = 0; j < A; ++j) {
+            const float ej = e[j], u = uu[j], sd = uu[A + j];
+            const float th = st[j], sg = st[A + j];
+            const float x = -2.f * u;
+            const float sp = fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));       // softplus(-2u)
+            l += -0.5f * ej * ej - logf(sd) - kHalfLog2Pi - 2.f * (kLn2 - u - sp);
+            const float inv = 1.f / sd, dth = 1.f - th * th;
+            float gm = c * (ej * inv) * dth;                  // d l / d mean = eps / std; mean = 5 tanh(m / 5)
+            float gr = c * ((ej * ej - 1.f) * inv) * sg;      // d l / d std = (eps^2 - 1) / std; std = softplus(r + c0) + min
+            if (write) {
+                gm += (dent * st[2 * A + j]) * dth;
+                gr += (dent * st[3 * A + j]) * sg;
+            } else {
+                gm += d[j];
+                gr += d[A + j];
+            }
+            d[j] = gm;
+            d[A + j] = gr;
+        }
+        s += (double)(w * l * adv);
+    }
+    s = block_sum_d(s, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
 // ---- clip_grad_norm_ + Adam ------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, size_t n, float beta1, float beta2, float eps,
@@ -452,6 +498,24 @@ int bd_sum(const float* x, size_t n, float* scalars, int slot, float* ws, void* 
     hipLaunchKernelGGL(sum_kernel<0>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, n, (double*)ws);
     BD_CHECK_LAUNCH("bd_sum");
     return finish((double*)ws, nb, scalars, slot, (hipStream_t)stream, "bd_sum(final)");
+}
+
+int bd_actor_reinforce(const float* eps_action, const float* act_us, const float* act_stats, const float* returns,
+                       const float* base0, const float* value, const float* weight, int Hm, int N, int A, float rho,
+                       float grad_scale, float dentropy, int write, float* d_actor_out, float* scalars, int slot, float* ws,
+                       void* stream) {
+    BD_REQUIRE(eps_action && act_us && act_stats && returns && base0 && (value || Hm == 1) && d_actor_out && scalars && ws,
+               "bd_actor_reinforce: missing pointers");
+    BD_REQUIRE(Hm > 0 && N > 0 && A > 0 && (size_t)Hm * N <= (size_t)INT32_MAX / 4 && slot >= 0,
+               "bd_actor_reinforce: bad dims (Hm=%d N=%d A=%d slot=%d)", Hm, N, A, slot);
+    BD_REQUIRE(rho >= 0.f && rho <= 1.f, "bd_actor_reinforce: gradient mixing %g outside [0, 1]", (double)rho);
+    const int rows = Hm * N;
+    const int nb = red_blocks((size_t)rows);
+    hipLaunchKernelGGL(actor_reinforce_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, eps_action, act_us, act_stats,
+                       returns, base0, value, weight, rows, N, A, -(1.f - rho) * grad_scale, dentropy, write, d_actor_out,
+                       (double*)ws);
+    BD_CHECK_LAUNCH("bd_actor_reinforce");
+    return finish((double*)ws, nb, scalars, slot, (hipStream_t)stream, "bd_actor_reinforce(final)");
 }
 
 int bd_sumsq(const float* x, size_t n, float* scalars, int slot, float* ws, void* stream) {

@@ -14,7 +14,7 @@ import torch
 from torch import Tensor
 
 from . import _cabi as cabi
-from .engine import DreamerEngine
+from .engine import DreamerEngine, check_gradient_mixing
 from .memory import ExperienceReplay
 from .models import ActorModel, CnnImageEncoder, DenseModel, ObservationModel, TransitionModel, encoder_for
 from .synth import Dims
@@ -28,7 +28,7 @@ def _hp_from_params(params: Dict[str, Any]) -> Dict[str, float]:
         model_learning_rate=params["model_learning_rate"], actor_learning_rate=ac["actor_learning_rate"],
         value_learning_rate=ac["value_learning_rate"], adam_epsilon=params["adam_epsilon"],
         weight_decay=params["weight_decay"], entropy_weight=ac["entropy_weight"], polyak_avg=ac["polyak_avg"],
-        discount_weight=params.get("discount_weight", 5.0))
+        discount_weight=params.get("discount_weight", 5.0), gradient_mixing=ac.get("gradient_mixing", -1))
 
 
 class Dreamer:
@@ -40,8 +40,9 @@ class Dreamer:
         self.latent_distribution = params.get("latent_distribution", "Gaussian")
         if self.latent_distribution not in ("Gaussian", "Categorical"):
             raise NotImplementedError(f"{self.latent_distribution}  is yet yet implemented")     # as src/dreamer.py:108
-        if params["ActorCritic"]["gradient_mixing"] != -1:
-            raise NotImplementedError("gradient_mixing not yet implemented ")      # as src/dreamer.py:339
+        # -1: the reference's dynamics-backprop actor gradient; rho in [0, 1]: DreamerV2's REINFORCE / dynamics mix
+        # (the reference raises for anything but -1, src/dreamer.py:336-339)
+        check_gradient_mixing(params["ActorCritic"].get("gradient_mixing", -1))
         self.use_discount = bool(params.get("use_discount", False))
         if params.get("disable_cuda", False) or not torch.cuda.is_available():
             raise RuntimeError("big_dreamer_amd runs on MI355X only: there is no CPU path (disable_cuda=True is the "

@@ -33,6 +33,7 @@ DEFAULT_HP = dict(
     kl_balance=0.8, kl_loss_weight=0.1, free_nats=3.0, grad_clip_norm=100.0, discount=0.995, disclam=0.95,
     model_learning_rate=2e-4, actor_learning_rate=4e-5, value_learning_rate=1e-4, adam_epsilon=1e-5,
     weight_decay=1e-6, entropy_weight=1e-5, polyak_avg=1.0, min_std_dev=0.1, discount_weight=5.0,
+    gradient_mixing=-1,
 )
 
 # actor constants (src/models.py:479-503)
@@ -43,7 +44,20 @@ ACT_MEAN_SCALE = 5.0
 # scalar-board slots (raw sums; see include/bigdreamer_hip.h "losses")
 SLOT_OBS, SLOT_REW, SLOT_KL, SLOT_RET, SLOT_ENT, SLOT_VAL, SLOT_GN_MODEL, SLOT_GN_ACTOR, SLOT_GN_CRITIC = range(9)
 SLOT_DISC, SLOT_WOBJ = 9, 10       # use_discount=True: Bernoulli loss sum (model phase); weighted actor objective sum
+SLOT_RF = 11                       # gradient_mixing in [0, 1): sum of w * log pi(a) * (R - b), the REINFORCE objective
 N_SLOTS = 16
+
+
+def check_gradient_mixing(value) -> float:
+    """ActorCritic.gradient_mixing: -1 (the reference's objective, backpropagation through the learned dynamics) or
+    rho in [0, 1], DreamerV2's ``actor_grad_mix`` -- the weight of the dynamics term against REINFORCE (1 = -1)."""
+    try:
+        rho = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"gradient_mixing must be -1 or a number in [0, 1], got {value!r}") from None
+    if not (rho == -1 or 0.0 <= rho <= 1.0):
+        raise ValueError(f"gradient_mixing must be -1 or a number in [0, 1], got {value!r}")
+    return rho
 
 
 class ParamGroup:
@@ -268,6 +282,7 @@ class DreamerEngine:
         self.hp = dict(DEFAULT_HP)
         if hp:
             self.hp.update({k: v for k, v in hp.items() if k in self.hp})
+        self.hp["gradient_mixing"] = check_gradient_mixing(self.hp["gradient_mixing"])
         self.dev = torch.device(device)
         assert self.dev.type == "cuda", "the HIP path needs a GPU (there is no CPU fallback)"
         self.world_size = world_size
@@ -711,7 +726,7 @@ class DreamerEngine:
             rec.events[row].synchronize()
         h = rec.host.numpy()
         s = h[0, :N_SLOTS].copy()
-        for slot in (SLOT_RET, SLOT_ENT, SLOT_GN_ACTOR, SLOT_WOBJ):
+        for slot in (SLOT_RET, SLOT_ENT, SLOT_GN_ACTOR, SLOT_WOBJ, SLOT_RF):
             s[slot] = h[1, slot]
         for slot in (SLOT_VAL, SLOT_GN_CRITIC):
             s[slot] = h[2, slot]
@@ -882,7 +897,8 @@ class DreamerEngine:
             self._buf[name] = t
         return t
 
-    def _imagine_cat(self, start_feat, start_sidx, N: int, Hm: int, noise, save: bool, tag: str, feat_tag: str):
+    def _imagine_cat(self, start_feat, start_sidx, N: int, Hm: int, noise, save: bool, tag: str, feat_tag: str,
+                     rec_saves: bool = True, act_us: Optional[torch.Tensor] = None):
         d, pk = self.d, self.pk
         tm = lambda n: self.W("transition_model", n)
         ac = lambda n: self.W("actor", n)
@@ -914,8 +930,10 @@ class DreamerEngine:
         if save:
             a.sv_actor = ptr(self.buf("sv_actor", DENSE_LAYERS, Mi, d.Hd))
             a.sv_act_stats = ptr(self.buf("sv_act_stats", Mi, 4 * d.A))
-            a.sv_x, a.sv_gates = ptr(self.buf("isv_x", Mi, d.Be)), ptr(self.buf("isv_gates", Mi, 4 * d.Be))
-            a.sv_p = ptr(self.buf("isv_p", Mi, d.Hd))
+            if rec_saves:
+                a.sv_x, a.sv_gates = ptr(self.buf("isv_x", Mi, d.Be)), ptr(self.buf("isv_gates", Mi, 4 * d.Be))
+                a.sv_p = ptr(self.buf("isv_p", Mi, d.Hd))
+            a.sv_act_us = ptr(act_us)
         with self.span("imagine_fwd"):
             cabi.check(lib.bd_imagine_cat_forward(C.byref(a), cabi.stream()))
         if save and noise.get("entropy") is None:       # perf mode: the scan alone ran; the estimator draws in-kernel
@@ -992,7 +1010,11 @@ class DreamerEngine:
         return out, acts, layers
 
     def imagine(self, start_feat, N: int, Hm: int, noise, save: bool = True, tag: str = "", feat_tag: str = "",
-                split: bool = False, start_sidx: Optional[torch.Tensor] = None):
+                split: bool = False, start_sidx: Optional[torch.Tensor] = None, rec_saves: bool = True,
+                act_us: Optional[torch.Tensor] = None):
+        """Imagination rollout.  save: keep what the actor update needs; rec_saves=False leaves out the recurrence saves
+        (only the imagination backward reads them); act_us [Mi x 2A]: also keep the exact (u, std) of every action
+        (bd_actor_reinforce)."""
         d, pk = self.d, self.pk
         if d.categorical:
             if start_sidx is None:
@@ -1004,7 +1026,7 @@ class DreamerEngine:
                 if int(((st != 0).sum(-1) > 1).any()):
                     raise ValueError("Categorical latents: the start state must be all-zero or one-hot per factor "
                                      f"({d.cat_D} x {d.cat_C}); got a factor with more than one non-zero class")
-            return self._imagine_cat(start_feat, start_sidx, N, Hm, noise, save, tag, feat_tag)
+            return self._imagine_cat(start_feat, start_sidx, N, Hm, noise, save, tag, feat_tag, rec_saves, act_us)
         tm = lambda n: self.W("transition_model", n)
         ac = lambda n: self.W("actor", n)
         Mi = Hm * N
@@ -1035,8 +1057,10 @@ class DreamerEngine:
         if save:
             a.sv_actor = ptr(self.buf("sv_actor", DENSE_LAYERS, Mi, d.Hd))
             a.sv_act_stats = ptr(self.buf("sv_act_stats", Mi, 4 * d.A))
-            a.sv_x, a.sv_gates = ptr(self.buf("isv_x", Mi, d.Be)), ptr(self.buf("isv_gates", Mi, 4 * d.Be))
-            a.sv_p = ptr(self.buf("isv_p", Mi, d.Hd))
+            if rec_saves:
+                a.sv_x, a.sv_gates = ptr(self.buf("isv_x", Mi, d.Be)), ptr(self.buf("isv_gates", Mi, 4 * d.Be))
+                a.sv_p = ptr(self.buf("isv_p", Mi, d.Hd))
+            a.sv_act_us = ptr(act_us)
         H1 = Hm // 2 if (split and Hm >= 2) else 0
         with self.span("imagine_fwd"):
             if not H1:
@@ -1064,8 +1088,11 @@ class DreamerEngine:
                 if save:
                     a.sv_actor = a.sv_actor + r0 * d.Hd * f4
                     a.sv_act_stats = a.sv_act_stats + r0 * 4 * d.A * f4
-                    a.sv_x, a.sv_gates = a.sv_x + r0 * d.Be * f4, a.sv_gates + r0 * 4 * d.Be * f4
-                    a.sv_p = a.sv_p + r0 * d.Hd * f4
+                    if rec_saves:
+                        a.sv_x, a.sv_gates = a.sv_x + r0 * d.Be * f4, a.sv_gates + r0 * 4 * d.Be * f4
+                        a.sv_p = a.sv_p + r0 * d.Hd * f4
+                    if act_us is not None:
+                        a.sv_act_us = a.sv_act_us + r0 * 2 * d.A * f4
                 cabi.check(lib.bd_imagine_forward_scan(C.byref(a), cabi.stream()))
         if save:        # the entropy estimate of all Hm x N rows: off the recurrence (bd_actor_entropy), outside the scan's span
             self._entropy_estimate(noise, ent, Hm, N)
@@ -1538,8 +1565,14 @@ class DreamerEngine:
         ptag = "" if par is None else f"p{par}_"
         if par is not None and self._ev_cr_done[par] is not None:
             torch.cuda.current_stream().wait_event(self._ev_cr_done[par])     # critic of two steps ago: last reader
-        ifeat, ent, act = self.imagine(feat, N, Hm, noise, feat_tag=ptag, split=self.img_split,
-                                       start_sidx=self._buf[ptag + "sidx"] if d.categorical else None)
+        # gradient_mixing rho ("Mixed actor gradient"): None = -1 / 1, today's dynamics-backprop objective and
+        # launches; in (0, 1) both terms; 0 = REINFORCE alone: no lambda-return / head / imagination backward at all
+        mix = self._mix
+        dyn = mix is None or mix > 0
+        start_sidx = self._buf[ptag + "sidx"] if d.categorical else None
+        act_us = self.buf("act_us", Mi, 2 * d.A) if mix is not None else None
+        ifeat, ent, act = self.imagine(feat, N, Hm, noise, feat_tag=ptag, split=self.img_split, start_sidx=start_sidx,
+                                       rec_saves=dyn, act_us=act_us)
         r0 = self._img_split_rows
         isidx = self._buf[ptag + "isidx"] if d.categorical else None
         with self.span("img_heads_fwd"):
@@ -1571,9 +1604,15 @@ class DreamerEngine:
             wts = self.buf(ptag + "disc_w", Mi)
             wts.view(Hm, N).copy_(torch.cumprod(arr, 0))
             ew_ = hp["entropy_weight"] if hp["entropy_weight"] != -1 else 0.0
-            self.scalars[SLOT_WOBJ] = (wts * (returns + ew_ * ent)).sum()
-            dret = self.buf("dret_w", Mi)
-            torch.mul(wts, -inv_mi, out=dret)
+            if mix is None:
+                self.scalars[SLOT_WOBJ] = (wts * (returns + ew_ * ent)).sum()
+                dret = self.buf("dret_w", Mi)
+                torch.mul(wts, -inv_mi, out=dret)
+            else:       # the REINFORCE part of the objective joins in _logs_from (SLOT_RF)
+                self.scalars[SLOT_WOBJ] = (wts * (mix * returns + ew_ * ent)).sum()
+                if dyn:
+                    dret = self.buf("dret_w", Mi)
+                    torch.mul(wts, -mix * inv_mi, out=dret)
         if par is not None:
             ev_ret = torch.cuda.Event()
             ev_ret.record(torch.cuda.current_stream())
@@ -1586,44 +1625,57 @@ class DreamerEngine:
             self._side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self._side):
                 self._critic_phase(ifeat, returns, Mi, F, inv_mi, self.red_ws_side, isidx, wts)
-        d_r, d_v = self.buf("d_ir_out", Mi), self.buf("d_iv_out", Mi)
-        cabi.check(lib.bd_lambda_return_backward(ptr(dret), -inv_mi, Hm, N, hp["discount"], hp["disclam"], ptr(d_r), ptr(d_v), st))
-        difeat = self.buf("difeat", Mi, F)
-        with self.span("img_heads_bwd"):
-            self.mlp_backward(Mi, d_r, 1, r_layers, r_acts + [None], None, din0=difeat, ld0=F, w0=F)
-            self.mlp_backward(Mi, d_v, 1, v_layers, v_acts + [None], None, din0=difeat, ld0=F, w0=F, accumulate=True)
-        if d.categorical:
-            c = cabi.ImagineCatBwdArgs()
-            c.N, c.Hm, c.Be, c.D, c.C, c.A, c.Hd = N, Hm, d.Be, d.cat_D, d.cat_C, d.A, d.Hd
-            c.wt_p2 = ptr(pk["p2.T"])
-            c.prior_logits = ptr(self._buf["iprior_logits"])
-        else:
-            c = cabi.ImagineBwdArgs()
-            c.N, c.Hm, c.Be, c.S, c.A, c.Hd = N, Hm, d.Be, d.S, d.A, d.Hd
-            c.wt_p2m, c.wt_p2s = ptr(pk["p2m.T"]), ptr(pk["p2s.T"])
-            c.prior_std, c.eps_prior, c.min_std = ptr(self._buf["iprior_std"]), ptr(noise["img_prior"]), hp["min_std_dev"]
-        c.wt_embed_s, c.wt_embed_a = ptr(pk["embed_s.T"]), ptr(pk["embed_a.T"])
-        c.wt_ir, c.wt_iz, c.wt_in = ptr(pk["ir.T"]), ptr(pk["iz.T"]), ptr(pk["in.T"])
-        c.wt_hr, c.wt_hz, c.wt_hn = ptr(pk["hr.T"]), ptr(pk["hz.T"]), ptr(pk["hn.T"])
-        c.wt_p1 = ptr(pk["p1.T"])
-        for l in range(1, DENSE_LAYERS):
-            c.wt_a[l - 1] = ptr(pk[f"a{l}.T"])
-        c.wt_a4m, c.wt_a4s = ptr(pk["a4m.T"]), ptr(pk["a4s.T"])
-        c.start_feat, c.feat, c.action = ptr(feat), ptr(ifeat), ptr(act)
-        c.eps_action = ptr(noise["action"])
-        sv_actor = self._buf["sv_actor"]
-        c.sv_actor, c.sv_act_stats = ptr(sv_actor), ptr(self._buf["sv_act_stats"])
-        c.sv_x, c.sv_gates, c.sv_p = ptr(self._buf["isv_x"]), ptr(self._buf["isv_gates"]), ptr(self._buf["isv_p"])
-        c.dfeat = ptr(difeat)
-        c.dentropy = -hp["entropy_weight"] * inv_mi if hp["entropy_weight"] != -1 else 0.0
+        dentropy = -hp["entropy_weight"] * inv_mi if hp["entropy_weight"] != -1 else 0.0
         d_apre, d_aout = self.buf("d_actor_pre", DENSE_LAYERS, Mi, d.Hd), self.buf("d_actor_out", Mi, 2 * d.A)
+        sv_actor = self._buf["sv_actor"]
         # the actor's hidden layers leave the backward scan (their result feeds nothing on the recurrence: detached
         # input) and run as one dense chain over all Hm x N rows from d_actor_out
-        actor_chain = os.environ.get("BD_ACTOR_BWD_CHAIN", "1") == "1"
-        c.d_actor_pre, c.d_actor_out = (None if actor_chain else ptr(d_apre)), ptr(d_aout)
-        c.ent_weight = ptr(wts)
-        with self.span("imagine_bwd"):
-            cabi.check((lib.bd_imagine_cat_backward if d.categorical else lib.bd_imagine_backward)(C.byref(c), st))
+        # (always with mixing: bd_actor_reinforce adds to d_actor_out after the scan)
+        actor_chain = os.environ.get("BD_ACTOR_BWD_CHAIN", "1") == "1" or mix is not None
+        if dyn:
+            d_r, d_v = self.buf("d_ir_out", Mi), self.buf("d_iv_out", Mi)
+            dconst = -inv_mi if mix is None else -mix * inv_mi
+            cabi.check(lib.bd_lambda_return_backward(ptr(dret), dconst, Hm, N, hp["discount"], hp["disclam"], ptr(d_r),
+                                                     ptr(d_v), st))
+            difeat = self.buf("difeat", Mi, F)
+            with self.span("img_heads_bwd"):
+                self.mlp_backward(Mi, d_r, 1, r_layers, r_acts + [None], None, din0=difeat, ld0=F, w0=F)
+                self.mlp_backward(Mi, d_v, 1, v_layers, v_acts + [None], None, din0=difeat, ld0=F, w0=F, accumulate=True)
+            if d.categorical:
+                c = cabi.ImagineCatBwdArgs()
+                c.N, c.Hm, c.Be, c.D, c.C, c.A, c.Hd = N, Hm, d.Be, d.cat_D, d.cat_C, d.A, d.Hd
+                c.wt_p2 = ptr(pk["p2.T"])
+                c.prior_logits = ptr(self._buf["iprior_logits"])
+            else:
+                c = cabi.ImagineBwdArgs()
+                c.N, c.Hm, c.Be, c.S, c.A, c.Hd = N, Hm, d.Be, d.S, d.A, d.Hd
+                c.wt_p2m, c.wt_p2s = ptr(pk["p2m.T"]), ptr(pk["p2s.T"])
+                c.prior_std, c.eps_prior, c.min_std = ptr(self._buf["iprior_std"]), ptr(noise["img_prior"]), hp["min_std_dev"]
+            c.wt_embed_s, c.wt_embed_a = ptr(pk["embed_s.T"]), ptr(pk["embed_a.T"])
+            c.wt_ir, c.wt_iz, c.wt_in = ptr(pk["ir.T"]), ptr(pk["iz.T"]), ptr(pk["in.T"])
+            c.wt_hr, c.wt_hz, c.wt_hn = ptr(pk["hr.T"]), ptr(pk["hz.T"]), ptr(pk["hn.T"])
+            c.wt_p1 = ptr(pk["p1.T"])
+            for l in range(1, DENSE_LAYERS):
+                c.wt_a[l - 1] = ptr(pk[f"a{l}.T"])
+            c.wt_a4m, c.wt_a4s = ptr(pk["a4m.T"]), ptr(pk["a4s.T"])
+            c.start_feat, c.feat, c.action = ptr(feat), ptr(ifeat), ptr(act)
+            c.eps_action = ptr(noise["action"])
+            c.sv_actor, c.sv_act_stats = ptr(sv_actor), ptr(self._buf["sv_act_stats"])
+            c.sv_x, c.sv_gates, c.sv_p = ptr(self._buf["isv_x"]), ptr(self._buf["isv_gates"]), ptr(self._buf["isv_p"])
+            c.dfeat = ptr(difeat)
+            c.dentropy = dentropy
+            c.d_actor_pre, c.d_actor_out = (None if actor_chain else ptr(d_apre)), ptr(d_aout)
+            c.ent_weight = ptr(wts)
+            with self.span("imagine_bwd"):
+                cabi.check((lib.bd_imagine_cat_backward if d.categorical else lib.bd_imagine_backward)(C.byref(c), st))
+        if mix is not None:
+            # REINFORCE: the baseline of slot k is the target value of the state its action was taken in -- the start
+            # features for k = 0 (one dense forward over the N start rows), value_pred[k - 1] after (read shifted by N)
+            with self.span("actor_reinforce"):
+                b0, _, _ = self.dense_forward("critic_target", "tgt", "ib0", feat, F, N, 1, sidx=start_sidx)
+                cabi.check(lib.bd_actor_reinforce(ptr(noise["action"]), ptr(act_us), ptr(self._buf["sv_act_stats"]),
+                                                  ptr(returns), ptr(b0), ptr(v_out), ptr(wts), Hm, N, d.A, mix, inv_mi,
+                                                  dentropy, int(not dyn), ptr(d_aout), sc, SLOT_RF, ws, st))
         if actor_chain:
             a_layers = [("a0h", None, d.Hd, F, cabi.ACT_ELU)] + [(f"a{l}", None, d.Hd, d.Hd, cabi.ACT_ELU)
                                                                   for l in range(1, DENSE_LAYERS)] + \
@@ -1676,6 +1728,12 @@ class DreamerEngine:
             wc.run()
         self._optimizer_step_or_defer("opt_critic", "critic", SLOT_GN_CRITIC, hp["value_learning_rate"], red_ws)
 
+    @property
+    def _mix(self) -> Optional[float]:
+        """gradient_mixing rho when it changes the schedule (0 <= rho < 1); None for -1 and 1 (today's objective)."""
+        rho = self.hp["gradient_mixing"]
+        return None if rho in (-1, 1) else float(rho)
+
     def logs(self) -> Dict[str, float]:
         """One D2H copy of the scalar board -> the reference's log dict (src/dreamer.py:293-296,359-360,383).
         Values are this rank's shard means (fp32 arithmetic as in the reference)."""
@@ -1702,13 +1760,17 @@ class DreamerEngine:
             kl = f32(hp["kl_balance"]) * x + f32(1 - hp["kl_balance"]) * x
         ew = f32(hp["entropy_weight"]) if hp["entropy_weight"] != -1 else f32(0)
         model_loss = obs + rew + kl * f32(hp["kl_loss_weight"])
-        objective = s[SLOT_RET] + ew * s[SLOT_ENT]
+        mix = self._mix
+        if mix is None:
+            objective = s[SLOT_RET] + ew * s[SLOT_ENT]
+        else:           # w (rho R + (1 - rho) log pi(a) sg(R - b) + eta H), summed ("Mixed actor gradient")
+            objective = f32(mix) * s[SLOT_RET] + f32(1 - mix) * s[SLOT_RF] + ew * s[SLOT_ENT]
         out = {}
         if self.d.use_discount:         # src/dreamer.py:287-290, 346-352
             disc = s[SLOT_DISC] / N
             model_loss = model_loss + disc * f32(hp["discount_weight"])
             out["discount_loss"] = float(disc)
-            objective = s[SLOT_WOBJ]
+            objective = s[SLOT_WOBJ] if mix is None else s[SLOT_WOBJ] + f32(1 - mix) * s[SLOT_RF]
         out.update({
             "observation_loss": float(obs), "reward_loss": float(rew), "kl_loss": float(kl),
             "model_loss": float(model_loss),

@@ -322,6 +322,9 @@ typedef struct {
     float* sv_p;          /* [Hm x N x Hd]                                                          */
     size_t sv_actor_stride; /* floats between the layers of sv_actor; 0 = Hm*N*Hd.  Lets a rollout be launched in
                                two time segments (second segment: Hm, start_feat and every [Hm x ...] pointer shifted) */
+    float* sv_act_us;     /* [Hm x N x 2A] or NULL: the exact pre-tanh sample u = mean + std*eps (columns 0..A-1) and
+                             std (columns A..2A-1) of every action, for bd_actor_reinforce (slot 3 of sv_act_stats
+                             holds std only until bd_actor_entropy replaces it) */
 } bd_imagine_fwd_args;
 int bd_imagine_forward(const bd_imagine_fwd_args* a, void* stream);
 /* The two launches of bd_imagine_forward separately (a caller that saves the actor statistics may run the entropy
@@ -368,6 +371,24 @@ int bd_lambda_return_forward(const float* reward, const float* value, int Hm, in
  * value[Hm-1] is folded into dvalue[Hm-1]). */
 int bd_lambda_return_backward(const float* dreturns, float dret_const, int Hm, int N, float discount,
                               float lambda_, float* dreward, float* dvalue, void* stream);
+
+/* ---- REINFORCE term of the mixed actor gradient (ActorCritic.gradient_mixing = rho; DreamerV2 eq. 6) ----------
+ * Row i of the Hm*N imagined decisions (slot k = i / N) took u = mean + std*eps (act_us), baseline
+ * b_i = base0[i] for i < N (critic_target on the start features) and value[i - N] after (the target value of the
+ * state the action was taken in), advantage adv = returns[i] - b_i (a constant), weight w = weight[i] (NULL: 1), and
+ *   l_i = sum_a [ log N(u; mean, std) - log(1 - tanh^2 u) ]      (tanh-Normal log-density of the taken action).
+ * d_actor_out [Hm*N x 2A] (the layout bd_imagine_backward writes) receives the head gradient of c * l with
+ * c = -(1 - rho) * grad_scale * w * adv (grad_scale = 1 / element count of the objective's mean):
+ *   d mean-half += c * (eps/std) * (1 - th^2),   d std-half += c * ((eps^2 - 1)/std) * sg
+ * with th, sg = slots 0, 1 of act_stats, rho in [0, 1].  write != 0: d_actor_out is written from scratch as that plus
+ * the entropy term bd_imagine_backward would add (dentropy * w * slots 2, 3 of act_stats, through th / sg), i.e. the
+ * gradient of the rho = 0 objective without the imagination backward.  value may be NULL when Hm = 1.
+ * scalars[slot] = sum_i w * l_i * adv (RAW sum; per-workgroup fp64 partials in ws, fixed-order final sum: the same
+ * bits in either mode). */
+int bd_actor_reinforce(const float* eps_action, const float* act_us, const float* act_stats, const float* returns,
+                       const float* base0, const float* value, const float* weight, int Hm, int N, int A, float rho,
+                       float grad_scale, float dentropy, int write, float* d_actor_out, float* scalars, int slot, float* ws,
+                       void* stream);
 
 /* ---- perf-mode noise: Philox4x32-10, counter-based (csrc/bd_rng.h).  key = seed, counter = (index of a group of four
  * values, stream id, step): any element of any stream of any step is computable on its own.  The parity path never uses
@@ -517,6 +538,7 @@ typedef struct {
     float* prior_logits;                                       /* out [Hm x N x S]                            */
     float* entropy; float* action;
     float* sv_actor; float* sv_act_stats; float* sv_x; float* sv_gates; float* sv_p;   /* or NULL            */
+    float* sv_act_us;                                          /* as bd_imagine_fwd_args, or NULL             */
 } bd_imagine_cat_fwd_args;
 int bd_imagine_cat_forward(const bd_imagine_cat_fwd_args* a, void* stream);
 /* (eps_entropy == NULL with sv_act_stats != NULL: the scan alone -- the caller runs the entropy estimate itself,
