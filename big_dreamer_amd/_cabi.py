@@ -100,7 +100,7 @@ class ImagineFwdArgs(C.Structure):
         ["w_a4m", "w_a4s", "b_a4", "start_feat", "eps_action", "eps_entropy", "eps_prior"]) + [
         ("min_std", F32), ("act_raw_init_std", F32), ("act_min_std", F32), ("act_mean_scale", F32)] + _ptr_fields(
         ["feat", "prior_mean", "prior_std", "entropy", "action", "sv_actor", "sv_act_stats", "sv_x", "sv_gates",
-         "sv_p"]) + [("sv_actor_stride", C.c_size_t)] + _ptr_fields(["sv_act_us"]))
+         "sv_p"]) + [("sv_actor_stride", C.c_size_t)] + _ptr_fields(["sv_act_us"]) + [("discrete_actions", I32)])
 
 
 class ImagineBwdArgs(C.Structure):
@@ -109,7 +109,7 @@ class ImagineBwdArgs(C.Structure):
          "wt_p2s"]) + [("wt_a", P * 3)] + _ptr_fields(
         ["wt_a4m", "wt_a4s", "start_feat", "feat", "prior_std", "action", "eps_action", "eps_prior", "sv_actor",
          "sv_act_stats", "sv_x", "sv_gates", "sv_p"]) + [("min_std", F32)] + _ptr_fields(["dfeat"]) + [
-        ("dentropy", F32)] + _ptr_fields(["d_actor_pre", "d_actor_out", "ent_weight"]))
+        ("dentropy", F32)] + _ptr_fields(["d_actor_pre", "d_actor_out", "ent_weight"]) + [("discrete_actions", I32)])
 
 
 U8P = C.c_void_p
@@ -136,7 +136,7 @@ class ImagineCatFwdArgs(C.Structure):
         ["w_a4m", "w_a4s", "b_a4", "start_feat", "start_sidx", "eps_action", "eps_entropy", "q_prior"]) + [
         ("act_raw_init_std", F32), ("act_min_std", F32), ("act_mean_scale", F32)] + _ptr_fields(
         ["feat", "sidx", "prior_logits", "entropy", "action", "sv_actor", "sv_act_stats", "sv_x", "sv_gates", "sv_p",
-         "sv_act_us"]))
+         "sv_act_us"]) + [("discrete_actions", I32)])
 
 
 class ImagineCatBwdArgs(C.Structure):
@@ -144,7 +144,8 @@ class ImagineCatBwdArgs(C.Structure):
         ["wt_embed_s", "wt_embed_a", "wt_ir", "wt_iz", "wt_in", "wt_hr", "wt_hz", "wt_hn", "wt_p1", "wt_p2"]) + [
         ("wt_a", P * 3)] + _ptr_fields(
         ["wt_a4m", "wt_a4s", "start_feat", "feat", "prior_logits", "action", "eps_action", "sv_actor", "sv_act_stats",
-         "sv_x", "sv_gates", "sv_p", "dfeat"]) + [("dentropy", F32)] + _ptr_fields(["d_actor_pre", "d_actor_out", "ent_weight"]))
+         "sv_x", "sv_gates", "sv_p", "dfeat"]) + [("dentropy", F32)] + _ptr_fields(["d_actor_pre", "d_actor_out", "ent_weight"]) + [
+        ("discrete_actions", I32)])
 
 
 class PlanArgs(C.Structure):
@@ -214,6 +215,7 @@ _SIGS = {
     "bd_cem_refit": (I32, [P, I32, P, I32, I32, I32, I32, I32, P, P, P]),
     "bd_lambda_return_backward": (I32, [P, F32, I32, I32, F32, F32, P, P, P]),
     "bd_actor_reinforce": (I32, [P, P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, I32, P, P, I32, P, P]),
+    "bd_actor_reinforce_cat": (I32, [P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, I32, P, P, I32, P, P]),
     "bd_normal_nll": (I32, [P, I32, P, I32, I32, I32, F32, P, I32, P, I32, P, P]),
     "bd_bernoulli_nll": (I32, [P, P, C.c_size_t, F32, P, P, I32, P, P]),
     "bd_kl_forward": (I32, [P, P, P, P, I32, I32, F32, I32, P, I32, P, P]),

@@ -13,6 +13,7 @@
 #include "bd_host.h"
 #include "bd_scan.h"
 #include "bd_rng.h"
+#include "bd_discrete.h"
 
 namespace bd {
 
@@ -106,7 +107,18 @@ __global__ __launch_bounds__(kThreads) void imagine_fwd_kernel(bd_imagine_fwd_ar
         BD_STAMP(3);
         BD_KARGS_FRESH(ap);
         // ---- actor output, action sample ----
-        {
+        if (a.discrete_actions) {
+            // Categorical actor: A logits -> LDS image mean_s [16][A]; then one wave per row, one lane per class
+            const Seg segs[1] = {{bufB, a.w_a4m, d.Kb_hd}};
+            tile_linear_pre<1, 1>(segs, a.b_a4, A, NoPre{}, [&](int, int nb, floatx4 acc, NoPreVal) {
+                const int col = nb * 16 + (lane & 15);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (col < A) mean_s[(4 * (lane >> 4) + r) * A + col] = acc[r];
+            }, scratch);
+            lds_barrier();
+            disc_rows(mean_s, af, a.eps_action, a.action, a.entropy, a.sv_act_stats, tn, row0, a.N, A, lane, wave);
+        } else {
             const Seg2 segs[1] = {{bufB, a.w_a4m, a.w_a4s, d.Kb_hd}};
             tile_dual_head_elem<1>(
                 segs, a.b_a4, a.b_a4 + A, A, scratch,
@@ -150,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void imagine_fwd_kernel(bd_imagine_fwd_ar
         // step, so it runs after the scan as one elementwise launch over all Hm x N rows (actor_entropy_kernel) instead of
         // 10k cycles of every step of every tile (s_memtime stamps: 7 % of the step).  Without them (acting: one step, no
         // backward) the estimate stays here; thread = (row, sample lane).
-        if (a.sv_act_stats == nullptr) {
+        if (a.sv_act_stats == nullptr && !a.discrete_actions) {
             const int row = tid & 15, sl = tid >> 4;   // 16 sample lanes
             const int grow = row0 + row;
             for (int j = 0; j < A; ++j) {
@@ -392,7 +404,7 @@ __global__ __launch_bounds__(kThreads) void imagine_bwd_kernel(bd_imagine_bwd_ar
     for (int t = a.Hm - 1; t >= 0; --t) {
         const size_t tn = (size_t)t * a.N;
         const int tid = bd_tid();                   // opaque: nothing thread-dependent leaves this step (bd_tid)
-        const int lane = tid & 63;
+        const int lane = tid & 63, wave = bd_wave(tid);
         auto dpre_epi = [&](float* dst, float* out, size_t tn_, int width) {
             return DpreEpi{dst, out, tn_, width, a.N, row0, lane};
         };
@@ -515,7 +527,18 @@ __global__ __launch_bounds__(kThreads) void imagine_bwd_kernel(bd_imagine_bwd_ar
             }
         }, scratch);
         lds_barrier();   // the split-K scratch is reused by the next contraction
-        {
+        if (a.discrete_actions) {
+            // Categorical actor: d action -> LDS image dAr [16][A], then one wave per row (softmax Jacobian + entropy)
+            const Seg segs5[1] = {{dE, a.wt_embed_a, d.Kb_h}};
+            tile_linear_pre<1, 1>(segs5, nullptr, A, NoPre{}, [&](int, int nb, floatx4 acc, NoPreVal) {
+                const int col = nb * 16 + (lane & 15);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (col < A) dAr[(4 * (lane >> 4) + r) * A + col] = acc[r];
+            }, scratch);
+            lds_barrier();
+            disc_rows_bwd(dAr, a.sv_act_stats, a.dentropy, a.ent_weight, a.d_actor_out, tn, row0, a.N, A, lane, wave);
+        } else {
             const Seg segs5[1] = {{dE, a.wt_embed_a, d.Kb_h}};
             tile_linear_pre<1, 1>(
                 segs5, nullptr, A,
@@ -623,8 +646,11 @@ static int imagine_forward_scan(const bd_imagine_fwd_args* a, void* stream) {
                    a->w_hn && a->b_ih && a->b_hh && a->w_p1 && a->b_p1 && a->w_p2m && a->w_p2s && a->b_p2,
                "bd_imagine_forward: missing world-model weights");
     BD_REQUIRE(a->w_a0h && a->w_a0s && a->w_a[0] && a->w_a[1] && a->w_a[2] && a->b_a[0] && a->b_a[1] && a->b_a[2] &&
-                   a->b_a[3] && a->w_a4m && a->w_a4s && a->b_a4, "bd_imagine_forward: missing actor weights");
-    BD_REQUIRE(a->start_feat && a->eps_action && a->eps_prior && (a->eps_entropy || a->sv_act_stats),
+                   a->b_a[3] && a->w_a4m && (a->w_a4s || a->discrete_actions) && a->b_a4,
+               "bd_imagine_forward: missing actor weights");
+    BD_REQUIRE(!a->discrete_actions || a->sv_act_us == nullptr,
+               "bd_imagine_forward: sv_act_us is for the tanh-Normal actor only (discrete_actions = 1 saves norm in sv_act_stats)");
+    BD_REQUIRE(a->start_feat && a->eps_action && a->eps_prior && (a->eps_entropy || a->sv_act_stats || a->discrete_actions),
                "bd_imagine_forward: missing inputs (eps_entropy may be NULL only with sv_act_stats: the entropy estimate is then "
                "the caller's bd_actor_entropy / bd_actor_entropy_rng launch)");
     BD_REQUIRE(a->feat && a->prior_std && a->entropy && a->action, "bd_imagine_forward: missing outputs");
@@ -667,7 +693,7 @@ int bd_imagine_forward_scan(const bd_imagine_fwd_args* a, void* stream) { return
 int bd_imagine_forward(const bd_imagine_fwd_args* a, void* stream) {
     if (int rc = imagine_forward_scan(a, stream)) return rc;
     // with saved actor statistics the scan leaves (mean, std) in their slots 2, 3 and the estimate is one more launch
-    if (a->sv_act_stats != nullptr && a->eps_entropy != nullptr)
+    if (a->sv_act_stats != nullptr && a->eps_entropy != nullptr && !a->discrete_actions)
         return bd_actor_entropy(a->eps_entropy, a->sv_act_stats, a->entropy, a->Hm, a->N, a->A, a->n_samples, stream);
     return 0;
 }
@@ -676,9 +702,13 @@ int bd_imagine_backward(const bd_imagine_bwd_args* a, void* stream) {
     BD_REQUIRE(a && a->N > 0 && a->Hm > 0 && a->Be > 0 && a->S > 0 && a->A > 0 && a->A <= kMaxA && a->Hd > 0,
                "bd_imagine_backward: bad dims");
     BD_REQUIRE(a->wt_embed_s && a->wt_embed_a && a->wt_ir && a->wt_iz && a->wt_in && a->wt_hr && a->wt_hz && a->wt_hn &&
-                   a->wt_p1 && a->wt_p2m && a->wt_p2s && a->wt_a[0] && a->wt_a[1] && a->wt_a[2] && a->wt_a4m && a->wt_a4s,
+                   a->wt_p1 && a->wt_p2m && a->wt_p2s && a->wt_a[0] && a->wt_a[1] && a->wt_a[2] &&
+                   (a->discrete_actions || (a->wt_a4m && a->wt_a4s)),
                "bd_imagine_backward: missing weights");
-    BD_REQUIRE(a->start_feat && a->feat && a->prior_std && a->action && a->eps_action && a->eps_prior && a->sv_actor &&
+    BD_REQUIRE(!a->discrete_actions || a->d_actor_pre == nullptr,
+               "bd_imagine_backward: the Categorical actor's hidden layers run as the caller's chain (d_actor_pre = NULL)");
+    BD_REQUIRE(a->start_feat && a->feat && a->prior_std && a->action && (a->eps_action || a->discrete_actions) &&
+                   a->eps_prior && a->sv_actor &&
                    a->sv_act_stats && a->sv_x && a->sv_gates && a->sv_p && a->dfeat,
                "bd_imagine_backward: missing forward tensors");
     BD_REQUIRE(a->d_actor_out, "bd_imagine_backward: missing outputs");

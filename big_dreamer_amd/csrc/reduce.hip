@@ -3,6 +3,7 @@
 // fp64 partials summed in fixed order (deterministic).
 #include "bd_device.h"
 #include "bd_host.h"
+#include "bd_discrete.h"
 
 namespace bd {
 
@@ -252,6 +253,41 @@ __global__ __launch_bounds__(256) void actor_reinforce_kernel(
             d[A + j] = gr;
         }
         s += (double)(w * l * adv);
+    }
+    s = block_sum_d(s, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// The same for the Categorical actor (bd_actor_reinforce_cat): one wave per imagined decision, one lane per class.
+// l = norm[k] (k: the hot column of the straight-through one-hot action), d l / d out = onehot(k) - p.
+__global__ __launch_bounds__(256) void actor_reinforce_cat_kernel(
+    const float* __restrict__ action, const float* __restrict__ stats, const float* __restrict__ ret,
+    const float* __restrict__ base0, const float* __restrict__ value, const float* __restrict__ weight, int rows, int N,
+    int A, float scale, float dentropy, int write, float* __restrict__ dout, double* __restrict__ partials) {
+    __shared__ double red[kWaves];
+    const int lane = threadIdx.x & 63;
+    const int nw = gridDim.x * (blockDim.x >> 6);
+    const bool valid = lane < A;
+    double s = 0.0;
+    for (int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < rows; i += nw) {    // wave-uniform row
+        const float w = weight ? weight[i] : 1.f;
+        const float adv = ret[i] - (i < N ? base0[i] : value[i - N]);
+        const float c = scale * w * adv;
+        const size_t j = (size_t)i * A + lane;
+        const float norm = valid ? stats[j] : -INFINITY;
+        const unsigned long long hot = __ballot(valid && action[j] > 0.5f);
+        const int k = hot ? __builtin_ctzll(hot) : 0;
+        const float p = disc_probs(norm, valid);
+        const float l = __shfl(norm, k, 64);
+        float g = c * ((lane == k ? 1.f : 0.f) - p);
+        if (write) {
+            const float H = disc_entropy(norm, p, valid);
+            g += (dentropy * w) * (-p * (norm + H));
+        } else if (valid) {
+            g += dout[j];
+        }
+        if (valid) dout[j] = g;
+        if (lane == 0) s += (double)(w * l * adv);
     }
     s = block_sum_d(s, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
@@ -516,6 +552,23 @@ int bd_actor_reinforce(const float* eps_action, const float* act_us, const float
                        (double*)ws);
     BD_CHECK_LAUNCH("bd_actor_reinforce");
     return finish((double*)ws, nb, scalars, slot, (hipStream_t)stream, "bd_actor_reinforce(final)");
+}
+
+int bd_actor_reinforce_cat(const float* action, const float* act_stats, const float* returns, const float* base0,
+                           const float* value, const float* weight, int Hm, int N, int A, float rho, float grad_scale,
+                           float dentropy, int write, float* d_actor_out, float* scalars, int slot, float* ws,
+                           void* stream) {
+    BD_REQUIRE(action && act_stats && returns && base0 && (value || Hm == 1) && d_actor_out && scalars && ws,
+               "bd_actor_reinforce_cat: missing pointers");
+    BD_REQUIRE(Hm > 0 && N > 0 && A > 0 && A <= 64 && (size_t)Hm * N <= (size_t)INT32_MAX / 4 && slot >= 0,
+               "bd_actor_reinforce_cat: bad dims (Hm=%d N=%d A=%d slot=%d)", Hm, N, A, slot);
+    BD_REQUIRE(rho >= 0.f && rho <= 1.f, "bd_actor_reinforce_cat: gradient mixing %g outside [0, 1]", (double)rho);
+    const int rows = Hm * N;
+    const int nb = red_blocks((size_t)rows);
+    hipLaunchKernelGGL(actor_reinforce_cat_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, action, act_stats, returns,
+                       base0, value, weight, rows, N, A, -(1.f - rho) * grad_scale, dentropy, write, d_actor_out, (double*)ws);
+    BD_CHECK_LAUNCH("bd_actor_reinforce_cat");
+    return finish((double*)ws, nb, scalars, slot, (hipStream_t)stream, "bd_actor_reinforce_cat(final)");
 }
 
 int bd_sumsq(const float* x, size_t n, float* scalars, int slot, float* ws, void* stream) {

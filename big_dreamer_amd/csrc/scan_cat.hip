@@ -16,6 +16,7 @@
 #include "bd_host.h"
 #include "bd_scan.h"
 #include "bd_categorical.h"
+#include "bd_discrete.h"
 
 namespace bd {
 
@@ -503,7 +504,18 @@ __global__ __launch_bounds__(kThreads) void imagine_cat_fwd_kernel(bd_imagine_ca
         }
         BD_KARGS_FRESH(ap);
         // ---- actor output, action sample (layer-3 activations are in bufB) ----
-        {
+        if (a.discrete_actions) {
+            // Categorical actor: A logits -> LDS image mean_s [16][A]; then one wave per row, one lane per class
+            const Seg segs[1] = {{bufB, a.w_a4m, Kb_hd}};
+            tile_linear_pre<1, 1>(segs, a.b_a4, A, NoPre{}, [&](int, int nb, floatx4 acc, NoPreVal) {
+                const int col = nb * 16 + (lane & 15);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (col < A) mean_s[(4 * (lane >> 4) + r) * A + col] = acc[r];
+            }, scratch);
+            lds_barrier();
+            disc_rows(mean_s, af, a.eps_action, a.action, a.entropy, a.sv_act_stats, tn, row0, a.N, A, lane, wave);
+        } else {
             const Seg2 segs[1] = {{bufB, a.w_a4m, a.w_a4s, Kb_hd}};
             tile_dual_head_elem<1>(
                 segs, a.b_a4, a.b_a4 + A, A, scratch,
@@ -541,7 +553,7 @@ __global__ __launch_bounds__(kThreads) void imagine_cat_fwd_kernel(bd_imagine_ca
         BD_KARGS_FRESH(ap);
         // ---- entropy: n_samples draws per (row, action dim); thread = (row, sample lane) ----
         // (off the recurrence when the actor statistics are saved: bd_actor_entropy after the scan, see imagine.hip)
-        const bool ent_inline = a.sv_act_stats == nullptr;
+        const bool ent_inline = a.sv_act_stats == nullptr && !a.discrete_actions;
         if (ent_inline) {
             const int row = tid & 15, sl = tid >> 4;
             const int grow = row0 + row;
@@ -796,7 +808,18 @@ __global__ __launch_bounds__(kThreads) void imagine_cat_bwd_kernel(bd_imagine_ca
         lds_barrier();
         BD_KARGS_FRESH(ap);
         // ---- 5: embed layer -> d action_t -> actor output gradients (d state_t is taken by the next iteration's head) ----
-        {
+        if (a.discrete_actions) {
+            // Categorical actor: d action -> LDS image dAr [16][A], then one wave per row (softmax Jacobian + entropy)
+            const Seg segs5[1] = {{dE, a.wt_embed_a, Kb_h}};
+            tile_linear_pre<1, 1>(segs5, nullptr, A, NoPre{}, [&](int, int nb, floatx4 acc, NoPreVal) {
+                const int col = nb * 16 + (lane & 15);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (col < A) dAr[(4 * (lane >> 4) + r) * A + col] = acc[r];
+            }, scratch);
+            lds_barrier();
+            disc_rows_bwd(dAr, a.sv_act_stats, a.dentropy, a.ent_weight, a.d_actor_out, tn, row0, a.N, A, lane, wave);
+        } else {
             const Seg segs5[1] = {{dE, a.wt_embed_a, Kb_h}};
             tile_linear_pre<1, 1>(
                 segs5, nullptr, A,
@@ -951,10 +974,13 @@ int bd_imagine_cat_forward(const bd_imagine_cat_fwd_args* a, void* stream) {
     BD_REQUIRE(a->A <= kHeadMaxN, "bd_imagine_cat_forward: action width %d above %d", a->A, kHeadMaxN);
     BD_REQUIRE(a->w_embed_sT && a->w_embed_a && a->b_embed && a->w_ir && a->w_iz && a->w_in && a->w_hr && a->w_hz && a->w_hn &&
                    a->b_ih && a->b_hh && a->w_p1 && a->b_p1 && a->w_p2 && a->b_p2 && a->w_a0h && a->w_a0sT && a->w_a[0] &&
-                   a->w_a[1] && a->w_a[2] && a->b_a[0] && a->b_a[1] && a->b_a[2] && a->b_a[3] && a->w_a4m && a->w_a4s && a->b_a4,
+                   a->w_a[1] && a->w_a[2] && a->b_a[0] && a->b_a[1] && a->b_a[2] && a->b_a[3] && a->w_a4m &&
+                   (a->w_a4s || a->discrete_actions) && a->b_a4,
                "bd_imagine_cat_forward: missing weights");
-    BD_REQUIRE(a->start_feat && a->eps_action && a->q_prior && (a->eps_entropy || a->sv_act_stats),
+    BD_REQUIRE(a->start_feat && a->eps_action && a->q_prior && (a->eps_entropy || a->sv_act_stats || a->discrete_actions),
                "bd_imagine_cat_forward: missing inputs");
+    BD_REQUIRE(!a->discrete_actions || a->sv_act_us == nullptr,
+               "bd_imagine_cat_forward: sv_act_us is for the tanh-Normal actor only");
     BD_REQUIRE(a->feat && a->sidx && a->prior_logits && a->entropy && a->action, "bd_imagine_cat_forward: missing outputs");
     const int Kb_h = cdiv(a->Be, 16), Kb_a = cdiv(a->A, 16), Kb_hd = cdiv(a->Hd, 16);
     const int wmax = a->Be > a->Hd ? a->Be : a->Hd;
@@ -970,7 +996,7 @@ int bd_imagine_cat_forward(const bd_imagine_cat_fwd_args* a, void* stream) {
     if (!dyn) return -1;
     hipLaunchKernelGGL(imagine_cat_fwd_kernel, dim3(grid), dim3(kThreads), dyn, (hipStream_t)stream, *a);
     BD_CHECK_LAUNCH("bd_imagine_cat_forward");
-    if (a->sv_act_stats != nullptr && a->eps_entropy != nullptr)     // the entropy estimate is off the recurrence (imagine.hip)
+    if (a->sv_act_stats != nullptr && a->eps_entropy != nullptr && !a->discrete_actions)   // off the recurrence (imagine.hip)
         return bd_actor_entropy(a->eps_entropy, a->sv_act_stats, a->entropy, a->Hm, a->N, a->A, a->n_samples, stream);
     return 0;
 }
@@ -979,9 +1005,13 @@ int bd_imagine_cat_backward(const bd_imagine_cat_bwd_args* a, void* stream) {
     BD_REQUIRE(a && a->N > 0 && a->Hm > 0 && a->Be > 0 && a->A > 0 && a->Hd > 0, "bd_imagine_cat_backward: bad dims");
     BD_CAT_GEO("bd_imagine_cat_backward");
     BD_REQUIRE(a->wt_embed_s && a->wt_embed_a && a->wt_ir && a->wt_iz && a->wt_in && a->wt_hr && a->wt_hz && a->wt_hn &&
-                   a->wt_p1 && a->wt_p2 && a->wt_a[0] && a->wt_a[1] && a->wt_a[2] && a->wt_a4m && a->wt_a4s,
+                   a->wt_p1 && a->wt_p2 && a->wt_a[0] && a->wt_a[1] && a->wt_a[2] &&
+                   (a->discrete_actions || (a->wt_a4m && a->wt_a4s)),
                "bd_imagine_cat_backward: missing weights");
-    BD_REQUIRE(a->start_feat && a->feat && a->prior_logits && a->action && a->eps_action && a->sv_actor && a->sv_act_stats &&
+    BD_REQUIRE(!a->discrete_actions || a->d_actor_pre == nullptr,
+               "bd_imagine_cat_backward: the Categorical actor's hidden layers run as the caller's chain (d_actor_pre = NULL)");
+    BD_REQUIRE(a->start_feat && a->feat && a->prior_logits && a->action && (a->eps_action || a->discrete_actions) &&
+                   a->sv_actor && a->sv_act_stats &&
                    a->sv_x && a->sv_gates && a->sv_p && a->dfeat, "bd_imagine_cat_backward: missing forward tensors");
     BD_REQUIRE(a->d_actor_out, "bd_imagine_cat_backward: missing outputs");
     const int Kb_h = cdiv(a->Be, 16), Kb_a = cdiv(a->A, 16), Kb_hd = cdiv(a->Hd, 16);

@@ -14,7 +14,7 @@ import torch
 from torch import Tensor
 
 from . import _cabi as cabi
-from .engine import DreamerEngine, check_gradient_mixing
+from .engine import DreamerEngine, check_action_distribution, check_gradient_mixing
 from .memory import ExperienceReplay
 from .models import ActorModel, CnnImageEncoder, DenseModel, ObservationModel, TransitionModel, encoder_for
 from .synth import Dims
@@ -43,6 +43,9 @@ class Dreamer:
         # -1: the reference's dynamics-backprop actor gradient; rho in [0, 1]: DreamerV2's REINFORCE / dynamics mix
         # (the reference raises for anything but -1, src/dreamer.py:336-339)
         check_gradient_mixing(params["ActorCritic"].get("gradient_mixing", -1))
+        self.action_distribution = check_action_distribution(params.get("action_distribution", "Gaussian"))
+        if self.action_distribution == "Categorical" and params.get("algorithm") == "planet":
+            raise ValueError("action_distribution=Categorical: PlaNet's CEM planner searches a continuous action space")
         self.use_discount = bool(params.get("use_discount", False))
         if params.get("disable_cuda", False) or not torch.cuda.is_available():
             raise RuntimeError("big_dreamer_amd runs on MI355X only: there is no CPU path (disable_cuda=True is the "
@@ -67,7 +70,7 @@ class Dreamer:
         self.dims = Dims(B=self.batch_size, L=self.seq_len, H=self.planning_horizon, Be=self.belief_size,
                          S=self.state_size, Hd=self.hidden_size, E=self.embedding_size, A=self.action_size,
                          O=obs_size, pixel=self.pixel_observation, cat_D=cat_D, cat_C=cat_C,
-                         use_discount=self.use_discount)
+                         use_discount=self.use_discount, discrete_actions=self.action_distribution == "Categorical")
         self.engine = DreamerEngine(self.dims, _hp_from_params(params), self.device, world_size=world_size,
                                     process_group=process_group)
         e = self.engine
@@ -83,7 +86,7 @@ class Dreamer:
             ("reward_model", lambda: _ref_init_dense(feat, self.hidden_size, 1)),
             ("encoder", (lambda: _ref_init_cnn(E)) if px else
              (lambda: _ref_init_dense(env.observation_size, self.hidden_size, self.embedding_size))),
-            ("actor", lambda: _ref_init_dense(feat, self.hidden_size, 2 * self.action_size)),
+            ("actor", lambda: _ref_init_dense(feat, self.hidden_size, self.dims.actor_out)),
             ("critic", lambda: _ref_init_dense(feat, self.hidden_size, 1)),
         ) + ((("discount_model", lambda: _ref_init_dense(feat, self.hidden_size, 1)),) if self.use_discount else ()):
             init[mod] = {k: v.detach().numpy() for k, v in build().state_dict().items()}
@@ -103,7 +106,8 @@ class Dreamer:
                                                 module="observation_model", prefix="obs")
             self.encoder = encoder_for(e, env.observation_size, self.hidden_size, self.embedding_size)
         self.reward_model = DenseModel(feat, self.hidden_size, 1, engine=e, module="reward_model", prefix="rew")
-        self.actor = ActorModel(self.belief_size, self.state_size, self.hidden_size, self.action_size, engine=e)
+        self.actor = ActorModel(self.belief_size, self.state_size, self.hidden_size, self.action_size,
+                                action_distribution=self.action_distribution, engine=e)
         self.critic = DenseModel(feat, self.hidden_size, 1, engine=e, module="critic", prefix="cri")
         self.critic_target = DenseModel(feat, self.hidden_size, 1, engine=e, module="critic_target", prefix="tgt")
         if self.use_discount:       # src/dreamer.py:80-85
@@ -205,9 +209,7 @@ class Dreamer:
         N = prev_state.shape[0] * prev_state.shape[1]
         start = torch.cat([prev_belief.reshape(N, d.Be), prev_state.reshape(N, d.S)], dim=1).contiguous().float()
         Hm = self.planning_horizon - 1
-        noise = _noise or {"action": torch.randn(Hm, N, d.A, device=e.dev),
-                           "entropy": torch.randn(Hm, d.n_entropy, N, d.A, device=e.dev),
-                           "img_prior": self._state_draw(Hm, N)}
+        noise = _noise or dict(self._action_draw(Hm, N), img_prior=self._state_draw(Hm, N))
         ifeat, ent, _ = e.imagine(start, N, Hm, noise, save=False, tag="api_")
         f = ifeat.view(Hm, N, d.Be + d.S)
         if d.categorical:
@@ -222,13 +224,36 @@ class Dreamer:
         t = torch.empty(steps, rows, self.dims.S, device=self.engine.dev)
         return t.exponential_() if self.dims.categorical else t.normal_()
 
+    def _action_draw(self, steps: int, rows: int) -> Dict[str, Tensor]:
+        """Noise of the actor's samples: standard normals and the entropy estimator's draws (tanh-Normal), or the
+        sampler's Exp(1) variates per class (Categorical: the entropy is exact)."""
+        e, d = self.engine, self.dims
+        if d.discrete_actions:
+            return {"action": torch.empty(steps, rows, d.A, device=e.dev).exponential_()}
+        return {"action": torch.randn(steps, rows, d.A, device=e.dev),
+                "entropy": torch.randn(steps, d.n_entropy, rows, d.A, device=e.dev)}
+
     @torch.no_grad()
     def get_action(self, belief: Tensor, state: Tensor, deterministic: bool = False,
                    _noise: Optional[Dict[str, Tensor]] = None) -> Tuple[Tensor, Tensor]:
-        """src/dreamer.py:429-444: tanh-Normal sample and its 100-sample entropy estimate."""
+        """src/dreamer.py:429-444: tanh-Normal sample and its 100-sample entropy estimate.  Categorical actor: the
+        straight-through one-hot sample (src/models.py:518-522) and the exact entropy; deterministic: the one-hot mode."""
         e, d = self.engine, self.dims
         e.join()
         N = belief.shape[0]
+        if d.discrete_actions:
+            start = torch.cat([belief, state], dim=1).contiguous().float()
+            if deterministic:       # q = 1 for every class: argmax(p / q) is argmax p, the first maximum winning
+                noise = {"action": torch.ones(1, N, d.A, device=e.dev)}
+            else:
+                noise = {"action": _noise["action"].to(e.dev).float().reshape(1, N, d.A).contiguous()} if _noise \
+                    else self._action_draw(1, N)
+            noise["img_prior"] = torch.ones(1, N, d.S, device=e.dev)
+            _, ent, act = e.imagine(start, N, 1, noise, save=False, tag="act_")
+            act = act.view(N, d.A)
+            if deterministic:
+                act = torch.nn.functional.one_hot(act.argmax(-1), d.A).float()
+            return act.clone(), ent.view(N).clone()
         if deterministic:
             # SampleDist.mode (src/models.py:709-723): of n_samples draws, the one with the highest log-density per row;
             # then the entropy estimate on fresh draws (RNG order: mode, entropy).  Never used by the reference loop --
@@ -267,10 +292,18 @@ class Dreamer:
             posterior_state, action.unsqueeze(dim=0), belief, embedding,
             _noise=None if nz is None else (nz["prior"].unsqueeze(0), nz["post"].unsqueeze(0)))
         belief, posterior_state = belief.squeeze(dim=0), posterior_state.squeeze(dim=0)
-        action, _ = self.get_action(belief, posterior_state, _noise=None if nz is None else {
-            "action": nz["action"].unsqueeze(0).contiguous(), "entropy": nz["entropy"].unsqueeze(0).contiguous(),
-            "img_prior": torch.ones(1, belief.shape[0], self.state_size, device=self.device)})
-        if explore:
+        action, _ = self.get_action(belief, posterior_state, _noise=None if nz is None else dict(
+            {k: nz[k].unsqueeze(0).contiguous() for k in ("action", "entropy") if k in nz},
+            img_prior=torch.ones(1, belief.shape[0], self.state_size, device=self.device)))
+        if explore and self.dims.discrete_actions:
+            # epsilon-greedy: with probability action_noise a uniformly random one-hot (Gaussian noise would leave the
+            # simplex); `_noise`: "explore_u" (B,) uniforms, "explore_k" (B,) classes
+            B, A = action.shape
+            u = torch.rand(B, device=action.device) if nz is None else nz["explore_u"].to(action.device)
+            k = torch.randint(A, (B,), device=action.device) if nz is None else nz["explore_k"].to(action.device)
+            rnd = torch.nn.functional.one_hot(k.long(), A).to(action.dtype)
+            action = torch.where((u < self.action_noise).unsqueeze(1), rnd, action)
+        elif explore:
             eps = torch.randn_like(action) if nz is None else nz["explore"]
             action = torch.clamp(action + self.action_noise * eps, -1, 1)
         batched = hasattr(env, "n") and hasattr(env, "envs")          # EnvBatcher (src/env.py:343)

@@ -60,6 +60,17 @@ def check_gradient_mixing(value) -> float:
     return rho
 
 
+ACTION_DISTRIBUTIONS = ("Gaussian", "Categorical")
+
+
+def check_action_distribution(value) -> str:
+    """action_distribution: "Gaussian" (the tanh-Normal actor) or "Categorical" (one-hot actions over A classes with a
+    straight-through sample, DESIGN.md "Discrete actions")."""
+    if value not in ACTION_DISTRIBUTIONS:
+        raise ValueError(f"action_distribution must be one of {ACTION_DISTRIBUTIONS}, got {value!r}")
+    return value
+
+
 class ParamGroup:
     """Flat parameter / gradient / Adam-moment buffers of one optimiser, with named views.
 
@@ -576,9 +587,12 @@ class DreamerEngine:
         for l in range(1, DENSE_LAYERS):
             add("actor", f"a{l}", self.W("actor", f"model.{2 * l}.weight"), tr=True)
         Wa4 = self.W("actor", f"model.{2 * DENSE_LAYERS}.weight")
-        add("actor", "a4m", Wa4[:A], tr=True)
-        add("actor", "a4s", Wa4[A:], tr=True)
-        add("actor", "a4", Wa4, fwd=False, tr=True)     # (mean | raw) rows together: the hidden-layer backward as one chain
+        if d.discrete_actions:      # Categorical actor: one head of A logits (the scans' single-width head)
+            add("actor", "a4", Wa4, tr=True)
+        else:
+            add("actor", "a4m", Wa4[:A], tr=True)
+            add("actor", "a4s", Wa4[A:], tr=True)
+            add("actor", "a4", Wa4, fwd=False, tr=True)     # (mean | raw) rows together: the hidden-layer backward as one chain
 
         self.pk: Dict[str, torch.Tensor] = {}
         self._pack_tables = {}
@@ -917,7 +931,7 @@ class DreamerEngine:
             a.w_a[l - 1] = ptr(pk[f"a{l}"])
         for l in range(DENSE_LAYERS):
             a.b_a[l] = ptr(ac(f"model.{2 * l}.bias"))
-        a.w_a4m, a.w_a4s, a.b_a4 = ptr(pk["a4m"]), ptr(pk["a4s"]), ptr(ac(f"model.{2 * DENSE_LAYERS}.bias"))
+        self._actor_head_args(a)
         a.start_feat, a.start_sidx = ptr(start_feat), ptr(start_sidx)
         a.eps_action, a.eps_entropy, a.q_prior = ptr(noise["action"]), ptr(noise.get("entropy")), ptr(noise["img_prior"])
         a.act_raw_init_std, a.act_min_std, a.act_mean_scale = ACT_RAW_INIT_STD, ACT_MIN_STD, ACT_MEAN_SCALE
@@ -929,14 +943,14 @@ class DreamerEngine:
         a.entropy, a.action = ptr(ent), ptr(act)
         if save:
             a.sv_actor = ptr(self.buf("sv_actor", DENSE_LAYERS, Mi, d.Hd))
-            a.sv_act_stats = ptr(self.buf("sv_act_stats", Mi, 4 * d.A))
+            a.sv_act_stats = ptr(self.buf("sv_act_stats", Mi, self.act_stats_width))
             if rec_saves:
                 a.sv_x, a.sv_gates = ptr(self.buf("isv_x", Mi, d.Be)), ptr(self.buf("isv_gates", Mi, 4 * d.Be))
                 a.sv_p = ptr(self.buf("isv_p", Mi, d.Hd))
             a.sv_act_us = ptr(act_us)
         with self.span("imagine_fwd"):
             cabi.check(lib.bd_imagine_cat_forward(C.byref(a), cabi.stream()))
-        if save and noise.get("entropy") is None:       # perf mode: the scan alone ran; the estimator draws in-kernel
+        if save and noise.get("entropy") is None and not d.discrete_actions:   # perf mode: the estimator draws in-kernel
             self._entropy_estimate(noise, ent, Hm, N)
         self._img_split_rows = 0
         return ifeat, ent, act
@@ -1043,7 +1057,7 @@ class DreamerEngine:
             a.w_a[l - 1] = ptr(pk[f"a{l}"])
         for l in range(DENSE_LAYERS):
             a.b_a[l] = ptr(ac(f"model.{2 * l}.bias"))
-        a.w_a4m, a.w_a4s, a.b_a4 = ptr(pk["a4m"]), ptr(pk["a4s"]), ptr(ac(f"model.{2 * DENSE_LAYERS}.bias"))
+        self._actor_head_args(a)
         a.start_feat = ptr(start_feat)
         a.eps_action, a.eps_entropy, a.eps_prior = ptr(noise["action"]), ptr(noise.get("entropy")), ptr(noise["img_prior"])
         a.min_std, a.act_raw_init_std = self.hp["min_std_dev"], ACT_RAW_INIT_STD
@@ -1056,7 +1070,7 @@ class DreamerEngine:
         a.entropy, a.action = ptr(ent), ptr(act)
         if save:
             a.sv_actor = ptr(self.buf("sv_actor", DENSE_LAYERS, Mi, d.Hd))
-            a.sv_act_stats = ptr(self.buf("sv_act_stats", Mi, 4 * d.A))
+            a.sv_act_stats = ptr(self.buf("sv_act_stats", Mi, self.act_stats_width))
             if rec_saves:
                 a.sv_x, a.sv_gates = ptr(self.buf("isv_x", Mi, d.Be)), ptr(self.buf("isv_gates", Mi, 4 * d.Be))
                 a.sv_p = ptr(self.buf("isv_p", Mi, d.Hd))
@@ -1087,17 +1101,32 @@ class DreamerEngine:
                 a.entropy, a.action = ptr(ent) + r0 * f4, ptr(act) + r0 * d.A * f4
                 if save:
                     a.sv_actor = a.sv_actor + r0 * d.Hd * f4
-                    a.sv_act_stats = a.sv_act_stats + r0 * 4 * d.A * f4
+                    a.sv_act_stats = a.sv_act_stats + r0 * self.act_stats_width * f4
                     if rec_saves:
                         a.sv_x, a.sv_gates = a.sv_x + r0 * d.Be * f4, a.sv_gates + r0 * 4 * d.Be * f4
                         a.sv_p = a.sv_p + r0 * d.Hd * f4
                     if act_us is not None:
                         a.sv_act_us = a.sv_act_us + r0 * 2 * d.A * f4
                 cabi.check(lib.bd_imagine_forward_scan(C.byref(a), cabi.stream()))
-        if save:        # the entropy estimate of all Hm x N rows: off the recurrence (bd_actor_entropy), outside the scan's span
-            self._entropy_estimate(noise, ent, Hm, N)
+        if save and not d.discrete_actions:     # the entropy estimate of all Hm x N rows: off the recurrence
+            self._entropy_estimate(noise, ent, Hm, N)     # (bd_actor_entropy), outside the scan's span
         self._img_split_rows = H1 * N
         return ifeat, ent, act
+
+    @property
+    def act_stats_width(self) -> int:
+        """Floats per imagined row of sv_act_stats: 4A for the tanh-Normal actor, the A log-probabilities (norm) of the
+        Categorical one."""
+        return self.d.A if self.d.discrete_actions else 4 * self.d.A
+
+    def _actor_head_args(self, a) -> None:
+        """The actor output layer of an imagination forward's arguments (bd_imagine_fwd_args / _cat_)."""
+        pk = self.pk
+        a.b_a4 = ptr(self.W("actor", f"model.{2 * DENSE_LAYERS}.bias"))
+        if self.d.discrete_actions:
+            a.w_a4m, a.w_a4s, a.discrete_actions = ptr(pk["a4"]), None, 1
+        else:
+            a.w_a4m, a.w_a4s = ptr(pk["a4m"]), ptr(pk["a4s"])
 
     def _entropy_estimate(self, noise, ent: torch.Tensor, Hm: int, N: int) -> None:
         """SampleDist.entropy of every imagined action (src/models.py:725-733) from the (mean, std) the scan left in
@@ -1195,6 +1224,8 @@ class DreamerEngine:
         if part in ("all", "bh"):
             shapes.update(action=(Hm, N, d.A), img_prior=(Hm, N, d.S))
         exp_kind = ("obs_post", "img_prior") if d.categorical else ()       # the sampler's Exp(1) variates, one per class
+        if d.discrete_actions:
+            exp_kind += ("action",)
         out: Dict[str, Optional[torch.Tensor]] = {}
         a = cabi.RngFillArgs()
         a.n, a.seed, a.step = len(shapes), self.rng_seed, self._rng_step[part if part != "all" else "wm"]
@@ -1570,7 +1601,7 @@ class DreamerEngine:
         mix = self._mix
         dyn = mix is None or mix > 0
         start_sidx = self._buf[ptag + "sidx"] if d.categorical else None
-        act_us = self.buf("act_us", Mi, 2 * d.A) if mix is not None else None
+        act_us = self.buf("act_us", Mi, 2 * d.A) if mix is not None and not d.discrete_actions else None
         ifeat, ent, act = self.imagine(feat, N, Hm, noise, feat_tag=ptag, split=self.img_split, start_sidx=start_sidx,
                                        rec_saves=dyn, act_us=act_us)
         r0 = self._img_split_rows
@@ -1626,12 +1657,13 @@ class DreamerEngine:
             with torch.cuda.stream(self._side):
                 self._critic_phase(ifeat, returns, Mi, F, inv_mi, self.red_ws_side, isidx, wts)
         dentropy = -hp["entropy_weight"] * inv_mi if hp["entropy_weight"] != -1 else 0.0
-        d_apre, d_aout = self.buf("d_actor_pre", DENSE_LAYERS, Mi, d.Hd), self.buf("d_actor_out", Mi, 2 * d.A)
+        d_apre, d_aout = self.buf("d_actor_pre", DENSE_LAYERS, Mi, d.Hd), self.buf("d_actor_out", Mi, d.actor_out)
         sv_actor = self._buf["sv_actor"]
         # the actor's hidden layers leave the backward scan (their result feeds nothing on the recurrence: detached
         # input) and run as one dense chain over all Hm x N rows from d_actor_out
         # (always with mixing: bd_actor_reinforce adds to d_actor_out after the scan)
-        actor_chain = os.environ.get("BD_ACTOR_BWD_CHAIN", "1") == "1" or mix is not None
+        # (always with mixing and with the Categorical actor, whose scans only write d_actor_out)
+        actor_chain = os.environ.get("BD_ACTOR_BWD_CHAIN", "1") == "1" or mix is not None or d.discrete_actions
         if dyn:
             d_r, d_v = self.buf("d_ir_out", Mi), self.buf("d_iv_out", Mi)
             dconst = -inv_mi if mix is None else -mix * inv_mi
@@ -1657,7 +1689,10 @@ class DreamerEngine:
             c.wt_p1 = ptr(pk["p1.T"])
             for l in range(1, DENSE_LAYERS):
                 c.wt_a[l - 1] = ptr(pk[f"a{l}.T"])
-            c.wt_a4m, c.wt_a4s = ptr(pk["a4m.T"]), ptr(pk["a4s.T"])
+            if d.discrete_actions:
+                c.wt_a4m, c.discrete_actions = ptr(pk["a4.T"]), 1
+            else:
+                c.wt_a4m, c.wt_a4s = ptr(pk["a4m.T"]), ptr(pk["a4s.T"])
             c.start_feat, c.feat, c.action = ptr(feat), ptr(ifeat), ptr(act)
             c.eps_action = ptr(noise["action"])
             c.sv_actor, c.sv_act_stats = ptr(sv_actor), ptr(self._buf["sv_act_stats"])
@@ -1673,15 +1708,20 @@ class DreamerEngine:
             # features for k = 0 (one dense forward over the N start rows), value_pred[k - 1] after (read shifted by N)
             with self.span("actor_reinforce"):
                 b0, _, _ = self.dense_forward("critic_target", "tgt", "ib0", feat, F, N, 1, sidx=start_sidx)
-                cabi.check(lib.bd_actor_reinforce(ptr(noise["action"]), ptr(act_us), ptr(self._buf["sv_act_stats"]),
-                                                  ptr(returns), ptr(b0), ptr(v_out), ptr(wts), Hm, N, d.A, mix, inv_mi,
-                                                  dentropy, int(not dyn), ptr(d_aout), sc, SLOT_RF, ws, st))
+                if d.discrete_actions:
+                    cabi.check(lib.bd_actor_reinforce_cat(ptr(act), ptr(self._buf["sv_act_stats"]), ptr(returns), ptr(b0),
+                                                          ptr(v_out), ptr(wts), Hm, N, d.A, mix, inv_mi, dentropy,
+                                                          int(not dyn), ptr(d_aout), sc, SLOT_RF, ws, st))
+                else:
+                    cabi.check(lib.bd_actor_reinforce(ptr(noise["action"]), ptr(act_us), ptr(self._buf["sv_act_stats"]),
+                                                      ptr(returns), ptr(b0), ptr(v_out), ptr(wts), Hm, N, d.A, mix, inv_mi,
+                                                      dentropy, int(not dyn), ptr(d_aout), sc, SLOT_RF, ws, st))
         if actor_chain:
             a_layers = [("a0h", None, d.Hd, F, cabi.ACT_ELU)] + [(f"a{l}", None, d.Hd, d.Hd, cabi.ACT_ELU)
                                                                   for l in range(1, DENSE_LAYERS)] + \
-                       [("a4", None, 2 * d.A, d.Hd, cabi.ACT_NONE)]
+                       [("a4", None, d.actor_out, d.Hd, cabi.ACT_NONE)]
             with self.span("actor_hidden_bwd"):
-                self.mlp_backward(Mi, d_aout, 2 * d.A, a_layers, [sv_actor[l] for l in range(DENSE_LAYERS)] + [None],
+                self.mlp_backward(Mi, d_aout, d.actor_out, a_layers, [sv_actor[l] for l in range(DENSE_LAYERS)] + [None],
                                   [d_apre[l] for l in range(DENSE_LAYERS)] + [None])
         if self.pipeline:       # last reader of the world model in this step
             self._ev_bh_wm_free = torch.cuda.Event()
@@ -1693,7 +1733,7 @@ class DreamerEngine:
         for l in range(1, DENSE_LAYERS):
             wa.add(d_apre[l], d.Hd, sv_actor[l - 1], d.Hd, Mi, d.Hd, d.Hd, Ga(f"model.{2 * l}.weight"), d.Hd,
                    Ga(f"model.{2 * l}.bias"))
-        wa.add(d_aout, 2 * d.A, sv_actor[DENSE_LAYERS - 1], d.Hd, Mi, 2 * d.A, d.Hd,
+        wa.add(d_aout, d.actor_out, sv_actor[DENSE_LAYERS - 1], d.Hd, Mi, d.actor_out, d.Hd,
                Ga(f"model.{2 * DENSE_LAYERS}.weight"), d.Hd, Ga(f"model.{2 * DENSE_LAYERS}.bias"))
         with self.span("wgrad_actor"):
             wa.run()

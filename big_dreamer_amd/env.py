@@ -30,8 +30,13 @@ class SyntheticEnv:
         return torch.from_numpy(self.x.copy()).unsqueeze(0)
 
     def step(self, action):
-        u = np.asarray(action.detach().cpu().numpy() if isinstance(action, torch.Tensor) else action,
-                       dtype=np.float32).reshape(-1)[: self.action_size]
+        return self._advance(self._control(action))
+
+    def _control(self, action) -> np.ndarray:
+        return np.asarray(action.detach().cpu().numpy() if isinstance(action, torch.Tensor) else action,
+                          dtype=np.float32).reshape(-1)[: self.action_size]
+
+    def _advance(self, u: np.ndarray):
         reward = 0.0
         for _ in range(self.action_repeat):
             self.x = self.A @ self.x + self.B @ u + 0.01 * self.rng.standard_normal(self._nx).astype(np.float32)
@@ -73,8 +78,51 @@ class SyntheticPixelEnv(SyntheticEnv):
         return self._img(), reward, done
 
 
+class _DiscreteControl:
+    """A discrete action set over the continuous dynamics: a one-hot (or straight-through) action vector selects the
+    control u = U[argmax(action)] from a fixed table U of A control vectors in [-1, 1]^m (m = control dimension);
+    actions are A-vectors, so action_size = A."""
+
+    def _discrete_init(self, n_actions: int, control_size: int) -> None:
+        self.control_size = control_size
+        self.U = self.rng.uniform(-1, 1, (n_actions, control_size)).astype(np.float32)
+        self.action_size = n_actions
+
+    def _control(self, action) -> np.ndarray:
+        a = np.asarray(action.detach().cpu().numpy() if isinstance(action, torch.Tensor) else action,
+                       dtype=np.float32).reshape(-1)[: self.action_size]
+        return self.U[int(np.argmax(a))]
+
+    def sample_random_action(self) -> torch.Tensor:
+        out = np.zeros(self.action_size, np.float32)
+        out[self.rng.integers(self.action_size)] = 1.0
+        return torch.from_numpy(out)
+
+
+class SyntheticDiscreteEnv(_DiscreteControl, SyntheticEnv):
+    """SyntheticEnv with A discrete actions (action_distribution=Categorical, state observations)."""
+
+    def __init__(self, observation_size: int = 3, n_actions: int = 3, max_episode_length: int = 1000,
+                 action_repeat: int = 2, seed: int = 0, control_size: int = 1):
+        SyntheticEnv.__init__(self, observation_size, control_size, max_episode_length, action_repeat, seed)
+        self._discrete_init(n_actions, control_size)
+
+
+class SyntheticDiscretePixelEnv(_DiscreteControl, SyntheticPixelEnv):
+    """SyntheticPixelEnv with A discrete actions (action_distribution=Categorical, 64x64 pixel observations)."""
+
+    def __init__(self, state_size: int = 3, n_actions: int = 3, max_episode_length: int = 1000, action_repeat: int = 2,
+                 seed: int = 0, control_size: int = 1):
+        SyntheticPixelEnv.__init__(self, state_size, control_size, max_episode_length, action_repeat, seed)
+        self._discrete_init(n_actions, control_size)
+
+
 def Env(params):
     """Factory with the reference's name (src/env.py:320-340)."""
+    if params.get("action_distribution", "Gaussian") == "Categorical":
+        cls = SyntheticDiscretePixelEnv if params.get("pixel_observation", False) else SyntheticDiscreteEnv
+        return cls(int(params.get("synthetic_env_observation_size", 3)), int(params.get("synthetic_env_action_size", 3)),
+                   int(params["max_episode_length"]), int(params["action_repeat"]), int(params["seed"]))
     if params.get("pixel_observation", False):
         return SyntheticPixelEnv(int(params.get("synthetic_env_observation_size", 3)),
                                  int(params.get("synthetic_env_action_size", 1)), int(params["max_episode_length"]),

@@ -160,29 +160,33 @@ class TransitionModel(_EngineBacked):
 
 
 class ActorModel(_EngineBacked):
-    """src/models.py:466-524 (Gaussian action distribution).  ``forward`` returns (action_mean, action_std)."""
+    """src/models.py:466-524.  Gaussian: ``forward`` returns (action_mean, action_std).  Categorical (A outputs,
+    src/models.py:485-490): ``forward`` returns (action, dist) as the reference's branch does (src/models.py:518-522):
+    dist = OneHotCategoricalStraightThrough over the logits, action = its sample + probs - probs.detach()."""
 
     def __init__(self, belief_size: int, state_size: int, hidden_size: int, action_size: int,
                  activation_function: str = "ELU", action_distribution: str = "Gaussian", min_std: float = 1e-4,
                  init_std: float = 5, mean_scale: float = 5, n_layers: int = DENSE_LAYERS, *, engine: DreamerEngine):
         super().__init__()
-        if action_distribution != "Gaussian":
-            raise NotImplementedError("only the Gaussian action distribution is on the hot path")
+        if action_distribution not in ("Gaussian", "Categorical"):
+            raise ValueError(f"action_distribution must be Gaussian or Categorical, got {action_distribution!r}")
+        out = 2 * action_size if action_distribution == "Gaussian" else action_size
         layers, i = [], belief_size + state_size
         for _ in range(n_layers):
             layers += [nn.Linear(i, hidden_size), nn.ELU()]
             i = hidden_size
-        layers += [nn.Linear(i, 2 * action_size), nn.Identity()]
+        layers += [nn.Linear(i, out), nn.Identity()]
         self.model = nn.Sequential(*layers)
         self._min_std, self._init_std, self._mean_scale = min_std, init_std, mean_scale
         self.raw_init_std = torch.log(torch.exp(torch.tensor(float(init_std))) - 1)
         self.action_distribution = action_distribution
-        self._sizes = (belief_size + state_size, hidden_size, 2 * action_size)
+        self._sizes = (belief_size + state_size, hidden_size, out)
         self._bind(engine, "actor", "actor")
 
     @torch.no_grad()
-    def forward(self, belief: Tensor, state: Tensor) -> Tuple[Tensor, Tensor]:
-        """src/models.py:506-517: (action_mean, action_std) = (5 tanh(m / 5), softplus(r + raw_init_std) + min_std).
+    def forward(self, belief: Tensor, state: Tensor):
+        """src/models.py:506-522.  Gaussian: (action_mean, action_std) = (5 tanh(m / 5), softplus(r + raw_init_std) +
+        min_std).  Categorical: (straight-through one-hot action, OneHotCategoricalStraightThrough(logits)).
         Inference entry point (the training step runs the actor inside the imagination kernels): the dense chain runs
         on bd_mlp_forward with the weights packed per call."""
         from . import _cabi as cabi
@@ -208,6 +212,10 @@ class ActorModel(_EngineBacked):
             k = n
         a.out, a.ldo = res.data_ptr(), out
         cabi.check(cabi.lib.bd_mlp_forward(C.byref(a), cabi.stream()))
+        if self.action_distribution == "Categorical":
+            dist = torch.distributions.OneHotCategoricalStraightThrough(logits=res.view(*lead, out))
+            action = dist.sample()
+            return action + dist.probs - dist.probs.detach(), dist
         m, r = torch.chunk(res, 2, dim=1)
         mean = self._mean_scale * torch.tanh(m / self._mean_scale)
         std = torch.nn.functional.softplus(r + self.raw_init_std.to(r.device)) + self._min_std

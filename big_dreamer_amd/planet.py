@@ -20,6 +20,8 @@ from .planner import MPCPlanner
 
 class Planet(Dreamer):
     def __init__(self, params: Dict[str, Any], env, **kw):
+        if params.get("action_distribution", "Gaussian") == "Categorical":
+            raise ValueError("action_distribution=Categorical: PlaNet's CEM planner searches a continuous action space")
         p = dict(params)
         p["kl_balance"] = -1           # Planet._kl_loss ignores kl_balance: max(KL.sum(2), free_nats).mean()
         super().__init__(p, env, **kw)

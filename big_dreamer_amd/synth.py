@@ -35,6 +35,7 @@ class Dims:
     cat_D: int = 0        # latent_distribution="Categorical": discrete_latent_dimensions (0 = Gaussian latents)
     cat_C: int = 0        #                                    discrete_latent_classes; S must equal cat_D * cat_C (src/planet.py:56-57)
     use_discount: bool = False   # discount_model head + Bernoulli loss + discounted actor objective (src/dreamer.py:80-86,239-251,346-351)
+    discrete_actions: bool = False   # action_distribution="Categorical": one-hot actions over A classes ("Discrete actions")
 
     def __post_init__(self):
         assert (self.cat_D == 0) == (self.cat_C == 0) and (self.cat_D == 0 or self.S == self.cat_D * self.cat_C), \
@@ -48,6 +49,11 @@ class Dims:
     def head_out(self) -> int:
         """Output width of belief_prior / belief_posterior: (mean, raw std) or D*C logits (src/models.py:44-117)."""
         return self.S if self.cat_D else 2 * self.S
+
+    @property
+    def actor_out(self) -> int:
+        """Output width of the actor: (mean, raw std) of a tanh-Normal, or the A logits of a Categorical."""
+        return self.A if self.discrete_actions else 2 * self.A
 
     @property
     def T(self) -> int:
@@ -139,7 +145,7 @@ def param_shapes(d: Dims) -> Dict[str, List[Tuple[str, Tuple[int, ...]]]]:
         "observation_model": obs,
         "reward_model": strip(_mlp_shapes("x", [feat] + hid + [1])),
         "encoder": enc,
-        "actor": strip(_mlp_shapes("x", [feat] + hid + [2 * d.A])),
+        "actor": strip(_mlp_shapes("x", [feat] + hid + [d.actor_out])),
         "critic": strip(_mlp_shapes("x", [feat] + hid + [1])),
     }
     if d.use_discount:      # DenseModel(belief + state, hidden) (src/dreamer.py:80-85); joins the model optimiser last (:167-169)
@@ -204,12 +210,15 @@ def make_batch(d: Dims, seed: int = 0, p_terminal: float = 0.02) -> Dict[str, np
         obs = q / 32.0 - 0.5 + rng.random((d.L, d.B) + PIXEL_SHAPE, dtype=np.float32) / 32.0
     else:
         obs = rng.standard_normal((d.L, d.B, d.O), dtype=np.float32)
-    return {
+    out = {
         "observations": obs,
         "actions": rng.uniform(-1.0, 1.0, size=(d.L, d.B, d.A)).astype(np.float32),
         "rewards": rng.standard_normal((d.L, d.B), dtype=np.float32),
         "nonterminals": (rng.random((d.L, d.B, 1)) >= p_terminal).astype(np.float32),
     }
+    if d.discrete_actions:      # the replay holds the one-hot actions the agent acted with (same draws, same stream)
+        out["actions"] = np.eye(d.A, dtype=np.float32)[out["actions"].argmax(-1)]
+    return out
 
 
 class NoiseStream:
@@ -235,6 +244,8 @@ def make_noise(d: Dims, seed: int = 0) -> Dict[str, np.ndarray]:
     """All noise of one train_step, drawn in reference order:
     for t<T: prior (B,S) then posterior (B,S)  (src/models.py:256,267 -> :72);
     for t<H': action (N,A), entropy (100,N,A) (src/dreamer.py:443-444), prior (N,S) (src/dreamer.py:223).
+    Discrete actions: the action draws are the sampler's Exp(1) variates, one per class, and there is no entropy noise
+    (the Categorical entropy is exact).
     """
     ns = NoiseStream(seed)
     # Categorical latents: the state draws are the Exp(1) variates of the sampler, one per class, viewed (rows*D, C) as
@@ -247,14 +258,19 @@ def make_noise(d: Dims, seed: int = 0) -> Dict[str, np.ndarray]:
         obs_prior[t] = state_draw(d.B)
         obs_post[t] = state_draw(d.B)
     act = np.empty((d.Hm, d.N, d.A), np.float32)
-    ent = np.empty((d.Hm, d.n_entropy, d.N, d.A), np.float32)
+    ent = None if d.discrete_actions else np.empty((d.Hm, d.n_entropy, d.N, d.A), np.float32)
     img = np.empty((d.Hm, d.N, d.S), np.float32)
     for t in range(d.Hm):
-        act[t] = ns.normal((d.N, d.A))
-        ent[t] = ns.normal((d.n_entropy, d.N, d.A))
+        if d.discrete_actions:
+            act[t] = ns.exponential((d.N, d.A))
+        else:
+            act[t] = ns.normal((d.N, d.A))
+            ent[t] = ns.normal((d.n_entropy, d.N, d.A))
         img[t] = state_draw(d.N)
-    return {"obs_prior": obs_prior, "obs_post": obs_post, "action": act, "entropy": ent,
-            "img_prior": img}
+    out = {"obs_prior": obs_prior, "obs_post": obs_post, "action": act, "img_prior": img}
+    if ent is not None:
+        out["entropy"] = ent
+    return out
 
 
 def make_planner_noise(d: Dims, B: int, horizon: int, iters: int, candidates: int, seed: int = 0) -> Dict[str, np.ndarray]:

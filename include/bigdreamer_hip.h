@@ -325,6 +325,12 @@ typedef struct {
     float* sv_act_us;     /* [Hm x N x 2A] or NULL: the exact pre-tanh sample u = mean + std*eps (columns 0..A-1) and
                              std (columns A..2A-1) of every action, for bd_actor_reinforce (slot 3 of sv_act_stats
                              holds std only until bd_actor_entropy replaces it) */
+    int discrete_actions; /* 0: tanh-Normal actor (everything above).  1: Categorical actor (action_distribution=
+                           * "Categorical"): the head w_a4m / b_a4 has A outputs `out` (w_a4s unused, may be NULL),
+                           * norm = out - logsumexp(out), p = softmax(norm), k = argmax(p / eps_action) (eps_action:
+                           * Exp(1) draws, the first maximum wins), action = (onehot(k) + p) - p (straight-through, in
+                           * that order), entropy = -sum p * norm exactly (eps_entropy unused, no bd_actor_entropy);
+                           * sv_act_stats is [Hm x N x A] and holds norm; sv_act_us must be NULL                   */
 } bd_imagine_fwd_args;
 int bd_imagine_forward(const bd_imagine_fwd_args* a, void* stream);
 /* The two launches of bd_imagine_forward separately (a caller that saves the actor statistics may run the entropy
@@ -360,6 +366,10 @@ typedef struct {
     float* d_actor_out;     /* [Hm x N x 2A]                                                        */
     const float* ent_weight; /* optional [Hm x N] per-element factor on dentropy (use_discount=True: the cumulative
                               * discount weights of the actor objective, src/dreamer.py:346-351), or NULL          */
+    int discrete_actions;   /* 1: Categorical actor (see bd_imagine_fwd_args): d_actor_out is [Hm x N x A],
+                             * d out = p * (g - p.g) + dent * (-p * (norm + H)) with g = d loss / d action and
+                             * dent = dentropy (* ent_weight); wt_a4m is the (Hd, A) head transpose, wt_a4s, eps_action
+                             * unused; d_actor_pre must be NULL (the hidden layers run as the caller's chain)         */
 } bd_imagine_bwd_args;
 int bd_imagine_backward(const bd_imagine_bwd_args* a, void* stream);
 
@@ -389,6 +399,15 @@ int bd_actor_reinforce(const float* eps_action, const float* act_us, const float
                        const float* base0, const float* value, const float* weight, int Hm, int N, int A, float rho,
                        float grad_scale, float dentropy, int write, float* d_actor_out, float* scalars, int slot, float* ws,
                        void* stream);
+/* The same for the Categorical actor (discrete_actions = 1): row i took class k_i (action: the straight-through
+ * one-hot, [Hm*N x A]; k_i = the column above 0.5), act_stats = the scan's norm [Hm*N x A], p = softmax(norm),
+ *   l_i = norm[k_i],   d l / d out = onehot(k_i) - p.
+ * d_actor_out [Hm*N x A] += c * (onehot(k_i) - p) with c as above; write != 0: written from scratch as that plus the
+ * entropy term dentropy * w * (-p * (norm + H)).  scalars[slot] as bd_actor_reinforce. */
+int bd_actor_reinforce_cat(const float* action, const float* act_stats, const float* returns, const float* base0,
+                           const float* value, const float* weight, int Hm, int N, int A, float rho, float grad_scale,
+                           float dentropy, int write, float* d_actor_out, float* scalars, int slot, float* ws,
+                           void* stream);
 
 /* ---- perf-mode noise: Philox4x32-10, counter-based (csrc/bd_rng.h).  key = seed, counter = (index of a group of four
  * values, stream id, step): any element of any stream of any step is computable on its own.  The parity path never uses
@@ -539,6 +558,7 @@ typedef struct {
     float* entropy; float* action;
     float* sv_actor; float* sv_act_stats; float* sv_x; float* sv_gates; float* sv_p;   /* or NULL            */
     float* sv_act_us;                                          /* as bd_imagine_fwd_args, or NULL             */
+    int discrete_actions;                                      /* as bd_imagine_fwd_args                      */
 } bd_imagine_cat_fwd_args;
 int bd_imagine_cat_forward(const bd_imagine_cat_fwd_args* a, void* stream);
 /* (eps_entropy == NULL with sv_act_stats != NULL: the scan alone -- the caller runs the entropy estimate itself,
@@ -559,6 +579,7 @@ typedef struct {
     float dentropy;
     float* d_actor_pre; float* d_actor_out;                    /* as bd_imagine_bwd_args                      */
     const float* ent_weight;     /* as bd_imagine_bwd_args, or NULL                                              */
+    int discrete_actions;        /* as bd_imagine_bwd_args                                                       */
 } bd_imagine_cat_bwd_args;
 int bd_imagine_cat_backward(const bd_imagine_cat_bwd_args* a, void* stream);
 
