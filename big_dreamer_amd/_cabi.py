@@ -52,6 +52,18 @@ class MlpBwdArgs(C.Structure):
                 ("din1", P), ("ld1", I32), ("w1", I32), ("accumulate", I32)]
 
 
+BD_HEAD_HIDDEN = 4
+
+
+class ImgHead(C.Structure):
+    _fields_ = [("w", P * BD_HEAD_HIDDEN), ("wt", P * BD_HEAD_HIDDEN), ("b", P * BD_HEAD_HIDDEN),
+                ("w_out", P), ("b_out", P), ("dout", P), ("out", P)]
+
+
+class ImgHeadsArgs(C.Structure):
+    _fields_ = [("M", I32), ("F", I32), ("Hd", I32), ("x", P), ("head", ImgHead * 2), ("dx", P)]
+
+
 BD_RNG_MAX_TENSORS = 6
 BD_RNG_NORMAL, BD_RNG_EXPONENTIAL = 0, 1
 
@@ -214,6 +226,8 @@ _SIGS = {
     "bd_plan_rollout": (I32, [C.POINTER(PlanArgs), P]),
     "bd_cem_refit": (I32, [P, I32, P, I32, I32, I32, I32, I32, P, P, P]),
     "bd_lambda_return_backward": (I32, [P, F32, I32, I32, F32, F32, P, P, P]),
+    "bd_img_heads_supported": (I32, [I32, I32]),
+    "bd_img_heads_fwd_bwd": (I32, [C.POINTER(ImgHeadsArgs), P]),
     "bd_actor_reinforce": (I32, [P, P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, I32, P, P, I32, P, P]),
     "bd_actor_reinforce_cat": (I32, [P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, I32, P, P, I32, P, P]),
     "bd_normal_nll": (I32, [P, I32, P, I32, I32, I32, F32, P, I32, P, I32, P, P]),

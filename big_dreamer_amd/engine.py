@@ -356,6 +356,11 @@ class DreamerEngine:
         self._s_heads = _engine_stream(self.dev, "heads", -1)     # heads of the first half of a split rollout
         self.img_split = os.environ.get("BD_IMG_SPLIT", "0") == "1"
         self._img_split_rows = 0
+        # Frozen imagined heads (reward_model, critic_target) forward + dgrad in one launch (csrc/heads.hip) on the
+        # dynamics-backprop path with Gaussian latents; BD_HEADS_FUSED=0 keeps the separate forward / backward chains
+        # (mlp.hip) for the A/B.
+        self.heads_fused = (os.environ.get("BD_HEADS_FUSED", "1") != "0" and not self.d.categorical
+                            and bool(lib.bd_img_heads_supported(self.d.Be + self.d.S, self.d.Hd)))
         # pixel mode: decoder weight gradients under the observe scan
         self._s_early = _engine_stream(self.dev, "early", int(os.environ.get("BD_EARLY_PRIO", "0")))
         # Cross-step software pipeline (on unless BD_PIPELINE=0).  Dynamics learning of step k+1 reads only the world
@@ -1578,6 +1583,23 @@ class DreamerEngine:
         with self.span("opt_model"):
             self.optimizer_step("model", SLOT_GN_MODEL, hp["model_learning_rate"])
 
+    def img_heads_fused(self, M: int, x, d_r, d_v, r_out, v_out, dx) -> None:
+        """reward_model and critic_target over M rows of x = [h; s] (ld F), forward and d/d x in one launch
+        (bd_img_heads_fwd_bwd): r_out / v_out [M], dx [M x F] = the two heads' input gradients for d_r / d_v (stored)."""
+        d = self.d
+        a = cabi.ImgHeadsArgs()
+        a.M, a.F, a.Hd, a.x, a.dx = M, d.Be + d.S, d.Hd, ptr(x), ptr(dx)
+        for h, (mod, prefix, dout, out) in enumerate((("reward_model", "rew", d_r, r_out),
+                                                      ("critic_target", "tgt", d_v, v_out))):
+            H = a.head[h]
+            for l in range(DENSE_LAYERS):
+                H.w[l], H.wt[l] = ptr(self.pk[f"{prefix}{l}"]), ptr(self.pk[f"{prefix}{l}.T"])
+                H.b[l] = ptr(self.W(mod, f"model.{2 * l}.bias"))
+            H.w_out = ptr(self.W(mod, f"model.{2 * DENSE_LAYERS}.weight"))
+            H.b_out = ptr(self.W(mod, f"model.{2 * DENSE_LAYERS}.bias"))
+            H.dout, H.out = ptr(dout), ptr(out)
+        cabi.check(lib.bd_img_heads_fwd_bwd(C.byref(a), cabi.stream()))
+
     def _behaviour_phase(self, feat: torch.Tensor, noise: Dict[str, torch.Tensor], T: int, B: int,
                          red_ws: torch.Tensor, par: Optional[int]) -> None:
         """Behaviour learning (src/dreamer.py:308-391) on the current stream: imagination with the post-update world
@@ -1606,22 +1628,6 @@ class DreamerEngine:
                                        rec_saves=dyn, act_us=act_us)
         r0 = self._img_split_rows
         isidx = self._buf[ptag + "isidx"] if d.categorical else None
-        with self.span("img_heads_fwd"):
-            if not r0:
-                r_out, r_acts, r_layers = self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1, sidx=isidx)
-                v_out, v_acts, v_layers = self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1, sidx=isidx)
-            else:       # rows of the first time segment on a helper stream, under the second segment of the rollout
-                with torch.cuda.stream(self._s_heads):
-                    self._s_heads.wait_event(self._ev_img_half)
-                    self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1, rows=(0, r0))
-                    self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1, rows=(0, r0))
-                r_out, r_acts, r_layers = self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1, rows=(r0, Mi))
-                v_out, v_acts, v_layers = self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1, rows=(r0, Mi))
-                torch.cuda.current_stream().wait_stream(self._s_heads)
-        returns = self.buf(ptag + "returns", Mi)
-        cabi.check(lib.bd_lambda_return_forward(ptr(r_out), ptr(v_out), Hm, N, hp["discount"], hp["disclam"], ptr(returns), st))
-        cabi.check(lib.bd_sum(ptr(returns), Mi, sc, SLOT_RET, ws, st))
-        cabi.check(lib.bd_sum(ptr(ent), Mi, sc, SLOT_ENT, ws, st))
         inv_mi = self.dp.mean_grad_scale(Mi)
         wts = dret = None
         if d.use_discount:
@@ -1634,16 +1640,52 @@ class DreamerEngine:
             arr[:, 0] = 1.0
             wts = self.buf(ptag + "disc_w", Mi)
             wts.view(Hm, N).copy_(torch.cumprod(arr, 0))
+            if mix is None:
+                dret = self.buf("dret_w", Mi)
+                torch.mul(wts, -inv_mi, out=dret)
+            elif dyn:
+                dret = self.buf("dret_w", Mi)
+                torch.mul(wts, -mix * inv_mi, out=dret)
+        # d returns does not depend on the rewards or values (bd_lambda_return_backward reads only dret / dconst), so
+        # with the fused heads their output gradients are known before the heads run.  A split rollout runs the fused
+        # heads once after its second segment: every row's result is independent of the launch it is in, so the split
+        # stays bit-identical to the single launch (test_pipelined_schedule_is_bit_identical_to_serial)
+        fused = dyn and self.heads_fused
+        if dyn:
+            d_r, d_v = self.buf("d_ir_out", Mi), self.buf("d_iv_out", Mi)
+            dconst = -inv_mi if mix is None else -mix * inv_mi
+            difeat = self.buf("difeat", Mi, F)
+        if fused:
+            cabi.check(lib.bd_lambda_return_backward(ptr(dret), dconst, Hm, N, hp["discount"], hp["disclam"], ptr(d_r),
+                                                     ptr(d_v), st))
+            r_out, v_out = self.buf("ir_out", Mi, 1), self.buf("iv_out", Mi, 1)
+            with self.span("img_heads_bwd"):
+                self.img_heads_fused(Mi, ifeat, d_r, d_v, r_out, v_out, difeat)
+        else:
+            with self.span("img_heads_fwd"):
+                if not r0:
+                    r_out, r_acts, r_layers = self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1, sidx=isidx)
+                    v_out, v_acts, v_layers = self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1, sidx=isidx)
+                else:       # rows of the first time segment on a helper stream, under the second segment of the rollout
+                    with torch.cuda.stream(self._s_heads):
+                        self._s_heads.wait_event(self._ev_img_half)
+                        self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1, rows=(0, r0))
+                        self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1, rows=(0, r0))
+                    r_out, r_acts, r_layers = self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1,
+                                                                 rows=(r0, Mi))
+                    v_out, v_acts, v_layers = self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1,
+                                                                 rows=(r0, Mi))
+                    torch.cuda.current_stream().wait_stream(self._s_heads)
+        returns = self.buf(ptag + "returns", Mi)
+        cabi.check(lib.bd_lambda_return_forward(ptr(r_out), ptr(v_out), Hm, N, hp["discount"], hp["disclam"], ptr(returns), st))
+        cabi.check(lib.bd_sum(ptr(returns), Mi, sc, SLOT_RET, ws, st))
+        cabi.check(lib.bd_sum(ptr(ent), Mi, sc, SLOT_ENT, ws, st))
+        if d.use_discount:
             ew_ = hp["entropy_weight"] if hp["entropy_weight"] != -1 else 0.0
             if mix is None:
                 self.scalars[SLOT_WOBJ] = (wts * (returns + ew_ * ent)).sum()
-                dret = self.buf("dret_w", Mi)
-                torch.mul(wts, -inv_mi, out=dret)
             else:       # the REINFORCE part of the objective joins in _logs_from (SLOT_RF)
                 self.scalars[SLOT_WOBJ] = (wts * (mix * returns + ew_ * ent)).sum()
-                if dyn:
-                    dret = self.buf("dret_w", Mi)
-                    torch.mul(wts, -mix * inv_mi, out=dret)
         if par is not None:
             ev_ret = torch.cuda.Event()
             ev_ret.record(torch.cuda.current_stream())
@@ -1665,14 +1707,13 @@ class DreamerEngine:
         # (always with mixing and with the Categorical actor, whose scans only write d_actor_out)
         actor_chain = os.environ.get("BD_ACTOR_BWD_CHAIN", "1") == "1" or mix is not None or d.discrete_actions
         if dyn:
-            d_r, d_v = self.buf("d_ir_out", Mi), self.buf("d_iv_out", Mi)
-            dconst = -inv_mi if mix is None else -mix * inv_mi
-            cabi.check(lib.bd_lambda_return_backward(ptr(dret), dconst, Hm, N, hp["discount"], hp["disclam"], ptr(d_r),
-                                                     ptr(d_v), st))
-            difeat = self.buf("difeat", Mi, F)
-            with self.span("img_heads_bwd"):
-                self.mlp_backward(Mi, d_r, 1, r_layers, r_acts + [None], None, din0=difeat, ld0=F, w0=F)
-                self.mlp_backward(Mi, d_v, 1, v_layers, v_acts + [None], None, din0=difeat, ld0=F, w0=F, accumulate=True)
+            if not fused:
+                cabi.check(lib.bd_lambda_return_backward(ptr(dret), dconst, Hm, N, hp["discount"], hp["disclam"],
+                                                         ptr(d_r), ptr(d_v), st))
+                with self.span("img_heads_bwd"):
+                    self.mlp_backward(Mi, d_r, 1, r_layers, r_acts + [None], None, din0=difeat, ld0=F, w0=F)
+                    self.mlp_backward(Mi, d_v, 1, v_layers, v_acts + [None], None, din0=difeat, ld0=F, w0=F,
+                                      accumulate=True)
             if d.categorical:
                 c = cabi.ImagineCatBwdArgs()
                 c.N, c.Hm, c.Be, c.D, c.C, c.A, c.Hd = N, Hm, d.Be, d.cat_D, d.cat_C, d.A, d.Hd

@@ -382,6 +382,30 @@ int bd_lambda_return_forward(const float* reward, const float* value, int Hm, in
 int bd_lambda_return_backward(const float* dreturns, float dret_const, int Hm, int N, float discount,
                               float lambda_, float* dreward, float* dvalue, void* stream);
 
+/* ---- frozen imagined heads, forward + dgrad in one launch (csrc/heads.hip) ---------------------------------------
+ * reward_model and critic_target (DenseModel: BD_HEAD_HIDDEN ELU layers of width Hd, then Hd -> 1) over M rows of
+ * x = [h; s] (row-major, ld = F):  out = head(x), and  dx = d out_r/dx^T dout_r + d out_v/dx^T dout_v  (plain store).
+ * The saved activations stay on chip; no weight gradients (the heads are frozen).  Returns -1 without launching for
+ * shapes bd_img_heads_supported(F, Hd) rejects. */
+#define BD_HEAD_HIDDEN 4
+typedef struct {
+    const float* w[BD_HEAD_HIDDEN];   /* packed W_l (forward): [Hd x F], then [Hd x Hd]                          */
+    const float* wt[BD_HEAD_HIDDEN];  /* packed W_l^T (dgrad): [F x Hd], then [Hd x Hd]                          */
+    const float* b[BD_HEAD_HIDDEN];   /* [Hd]                                                                    */
+    const float* w_out;               /* output layer weight, plain [Hd]                                         */
+    const float* b_out;               /* output layer bias [1]                                                   */
+    const float* dout;                /* d loss / d out [M]                                                      */
+    float* out;                       /* [M]                                                                     */
+} bd_img_head;
+typedef struct {
+    int M, F, Hd;
+    const float* x;                   /* [M x F]                                                                 */
+    bd_img_head head[2];
+    float* dx;                        /* [M x F]                                                                 */
+} bd_img_heads_args;
+int bd_img_heads_supported(int F, int Hd);
+int bd_img_heads_fwd_bwd(const bd_img_heads_args* a, void* stream);
+
 /* ---- REINFORCE term of the mixed actor gradient (ActorCritic.gradient_mixing = rho; DreamerV2 eq. 6) ----------
  * Row i of the Hm*N imagined decisions (slot k = i / N) took u = mean + std*eps (act_us), baseline
  * b_i = base0[i] for i < N (critic_target on the start features) and value[i - N] after (the target value of the

@@ -87,7 +87,8 @@ if os.path.exists(os.path.join(src, "bench.json")):
     shutil.copy(stats_csv, os.path.join(dst, f"{tag}_kernel_stats.csv"))
     names = {"imagine_fwd": "imagine_fwd_kernel", "imagine_bwd": "imagine_bwd_kernel", "observe_fwd": ["observe_kfwd_kernel", "observe_cfwd_kernel"],
              "observe_bwd": ["observe_kbwd_kernel", "observe_cbwd_kernel"], "mlp_fwd_tall (34 300-row chains, mean)": "mlp_fwd_tall_kernel",
-             "mlp_bwd_tall (34 300-row chains, mean)": "mlp_bwd_tall_kernel", "mlp_fwd (all launches, mean)": "mlp_fwd_kernel",
+             "mlp_bwd_tall (34 300-row chains, mean)": "mlp_bwd_tall_kernel",
+             "img_heads (fused reward + value heads, fwd + dgrad)": "img_heads_kernel", "mlp_fwd (all launches, mean)": "mlp_fwd_kernel",
              "mlp_bwd (all launches, mean)": "mlp_bwd_kernel", "wgrad_wide (all launches, mean)": "wgrad_wide_kernel",
              "actor_entropy (in-kernel Philox draws)": "actor_entropy_kernel"}
     traffic = traffic_of(pmc("pmc_fetch"), pmc("pmc_write"), pmc("pmc_sq"), names)
