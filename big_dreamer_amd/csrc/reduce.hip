@@ -102,8 +102,9 @@ __global__ __launch_bounds__(256) void kl_fwd_kernel(const float* __restrict__ q
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
-// gradient factor of torch.max(x, free_nats) w.r.t. x (ties split evenly, as torch.maximum's backward)
-__device__ __forceinline__ float max_grad(float x, float fn) { return x > fn ? 1.f : (x == fn ? 0.5f : 0.f); }
+// gradient factor of torch.max(x, free_nats) w.r.t. x, as torch.maximum's backward: ties split evenly, and a NaN x
+// (neither below nor tied) passes the whole gradient
+__device__ __forceinline__ float max_grad(float x, float fn) { return x < fn ? 0.f : (x == fn ? 0.5f : 1.f); }
 
 __global__ __launch_bounds__(256) void kl_bwd_kernel(const float* __restrict__ qm, const float* __restrict__ qs,
                                                      const float* __restrict__ pm, const float* __restrict__ ps,
@@ -299,7 +300,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
                                                    float wd, float step_size, float inv_sqrt_bc2, float max_norm,
                                                    const float* __restrict__ scalars, int sqnorm_slot) {
     const float total_norm = sqrtf(scalars[sqnorm_slot]);
-    const float coef = fminf(max_norm / (total_norm + 1e-6f), 1.f);
+    // torch.clamp(q, max=1) semantics: a NaN norm (a NaN gradient anywhere) makes every clipped gradient NaN
+    const float q = max_norm / (total_norm + 1e-6f);
+    const float coef = q > 1.f ? 1.f : q;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float gc = g[i] * coef;
         g[i] = gc;
