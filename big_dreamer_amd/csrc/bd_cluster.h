@@ -101,7 +101,7 @@ inline size_t launch_lds(K kernel, size_t need, const char* who) {
 }
 
 // K-split form of the Gaussian cluster scan (observe_ksplit.hip): used by bd_observe_forward_cluster / _backward_cluster when
-// the cluster has one member per 16-column belief block (ksplit_ok); BD_OBS_KSPLIT=0 keeps the round-1 form
+// the cluster has one member per 16-column belief block (ksplit_ok); bd_observe_cluster_set_ksplit(0) keeps the round-1 form
 size_t ksplit_ws_floats_per_tile(int C);
 bool ksplit_ok(int Be, int S, int A, int Hd, int C);
 int& ksplit_mode();

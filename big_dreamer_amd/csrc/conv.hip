@@ -652,11 +652,9 @@ int bd_conv_gemm(const bd_conv_args* a, void* stream) {
         }
     }
     // rows per workgroup: as many 16-row tiles as LDS holds (<= 8): the packed weights (K x N) are streamed once per
-    // workgroup, 8*RT FLOP per byte.  BD_CONV_RT caps it (tuning).
+    // workgroup, 8*RT FLOP per byte.
     const int Kb = cdiv(a->K, 16);
-    static const char* cap_env = getenv("BD_CONV_RT");
     int rt = 8;
-    if (cap_env && atoi(cap_env) >= 1 && atoi(cap_env) < 8) rt = atoi(cap_env) >= 4 ? 4 : (atoi(cap_env) >= 2 ? 2 : 1);
     while (rt > 1 && ((size_t)rt * Kb * kFragFloats + 32 * rt) * sizeof(float) > 150 * 1024) rt >>= 1;
     switch (rt) {
         case 8: return launch_conv<8>(*a, (hipStream_t)stream);

@@ -167,13 +167,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4 - RT
     });
 }
 
-// 32-row tiles where the Hd-wide pairs balance over the waves (tall_shape_ok), 16-row tiles otherwise;
-// BD_HEADS_RT=1 forces 16-row tiles (tuning experiments only)
-static int heads_rt(int Hd) {
-    static const char* force = getenv("BD_HEADS_RT");
-    const bool two = !(force && atoi(force) == 1) && tall_shape_ok(Hd, 2);
-    return two ? 2 : (tall_shape_ok(Hd, 1) ? 1 : 0);
-}
+// 32-row tiles where the Hd-wide pairs balance over the waves (tall_shape_ok), 16-row tiles otherwise
+static int heads_rt(int Hd) { return tall_shape_ok(Hd, 2) ? 2 : (tall_shape_ok(Hd, 1) ? 1 : 0); }
 
 static size_t heads_lds(int RT, int F, int Hd) {
     const int KbF = cdiv(F, 16), Nb = cdiv(Hd, 16);

@@ -393,9 +393,7 @@ static int launch_chain(K kernel, const char* name, int M, int RT, int KbA, int 
 static int pick_rt(int M, int KbA, int KbB, size_t extra_per_rt = 0) {
     const int tiles = cdiv(M, 16);
     int rt = tiles >= 1024 ? 2 : 1;
-    static const char* force = getenv("BD_MLP_RT");          // tuning experiments only
-    if (force) rt = atoi(force) >= 2 && tiles >= 1024 ? 2 : 1;
-    const size_t cap = force ? 80 * 1024 : 64 * 1024;         // 2 workgroups per CU
+    const size_t cap = 64 * 1024;         // 2 workgroups per CU
     while (rt > 1 && ((size_t)rt * ((KbA + KbB) * kFragFloats + extra_per_rt) + kSplitScratchFloats) * sizeof(float) > cap)
         rt >>= 1;
     return rt;

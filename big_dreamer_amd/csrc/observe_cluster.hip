@@ -537,8 +537,7 @@ __global__ __launch_bounds__(kThreads) void observe_cbwd_kernel(bd_observe_bwd_a
 // 13 CUs per tile at Be=200, B=50), else two blocks per member; 0 = not applicable (caller uses observe.hip).
 static int pick_cluster(int B, int Be) {
     const int Nb = cdiv(Be, 16), tiles = cdiv(B, 16);
-    static const char* force2 = getenv("BD_OBS_CLUSTER_BLOCKS");      // tuning: "2" forces two blocks per member
-    int C = (tiles * Nb <= 256 && !(force2 && force2[0] == '2')) ? Nb : cdiv(Nb, kLocalBlocks);
+    int C = tiles * Nb <= 256 ? Nb : cdiv(Nb, kLocalBlocks);
     if (C < 1) C = 1;
     return (C <= kMaxCluster && tiles * C <= 256) ? C : 0;
 }
@@ -580,12 +579,11 @@ size_t bd_observe_cluster_ws_floats(int B, int Be) {
 
 size_t bd_observe_cluster_err_offset(int B) { return cluster_ws_flag_floats(cdiv(B, 16)); }
 
-// which cluster form bd_observe_forward_cluster / _backward_cluster run wherever the K-split form applies: 3 = K-split with the
-// forward GRU split by output columns (observe_ksplit.hip, two hand-offs per forward step), 1 = K-split in both directions
-// (three hand-offs), 2 = as 1 with granule hand-offs (R2), 0 = the round-1 form (GRU columns split, the rest redundant),
-// -1 = default (environment BD_OBS_KSPLIT, else 3)
+// which cluster form bd_observe_forward_cluster / _backward_cluster run wherever the K-split form applies: -1 = the K-split
+// form (observe_ksplit.hip, the default), 0 = the round-1 form (GRU columns split, the rest redundant); anything else fails
 int bd_observe_cluster_set_ksplit(int mode) {
-    ksplit_mode() = mode < 0 ? -1 : (mode > 3 ? 3 : mode);
+    if (mode != -1 && mode != 0) return fail("bd_observe_cluster_set_ksplit: mode %d (expected -1 or 0)", mode);
+    ksplit_mode() = mode;
     return 0;
 }
 

@@ -17,12 +17,10 @@
 //   F7  s' = mean + (softplus(raw) + min_std) eps          every member, elementwise
 // Backward, mirrored:  (dm, draw) -> dQ_c (N-split, local) -> dh partial (RS) -> gate gradients of block c ->
 // (DX, DH) partials (RS) -> dE_c, carry_c (the belief-gradient carry stays with its member) -> ds partial (all-reduce).
-// (The DEFAULT forward is observe_kfwd_ns_kernel further down: it splits the GRU by output columns and needs two hand-offs
-// per step; the form described here stays selectable and is what the backward mirrors.)
-// Three hand-offs per step and direction instead of one, each a few KB per member pair; per member and step 4 + 13 + 4
-// (forward) weight fragments of 1 KiB feed 300 MFMAs -- all register-resident, so a phase is: LDS read, MFMAs,
-// write-through stores, flag.  Hand-off protocol, flags, sticky error word: bd_cluster.h.  Reductions run in member order:
-// results are bit-identical on every member and from launch to launch.
+// (The forward kernel, observe_kfwd_ns_kernel, splits the GRU by output columns instead of F2's K-split: two hand-offs per
+// step, see there.)  Three hand-offs per backward step instead of one, each a few KB per member pair; every weight fragment
+// is register-resident, so a phase is: LDS read, MFMAs, write-through stores, flag.  Hand-off protocol, flags, sticky error
+// word: bd_cluster.h.  Reductions run in member order: results are bit-identical on every member and from launch to launch.
 #include "bd_cluster.h"
 
 namespace bd {
@@ -57,126 +55,36 @@ __device__ __forceinline__ floatx4 ks_load4(const float* p) {
     return floatx4{__uint_as_float((unsigned)lo), __uint_as_float((unsigned)(lo >> 32)), __uint_as_float((unsigned)hi),
                    __uint_as_float((unsigned)(hi >> 32))};
 }
-// ---- hand-off forms ---------------------------------------------------------------------------------------------------------
-// GR = false: form R1 of bd_cluster.h (sc1 payload -> vmcnt(0) -> barrier -> flag; one wave polls the flags -> barrier -> sc1
-//   loads).  s_memtime: a hand-off costs ~7k cycles end to end (publish 2k, poll 2.5-3.4k, the payload's own round trip 2k).
-// GR = true (BD_OBS_KSPLIT=2; parity-tested, NOT the default -- measured below): form R2 of the guide ("the data IS the flag", cdna_hip_programming.md Guideline 16): every value travels in a
-//   naturally aligned 8-byte granule {tag = epoch, value}; a float4 of a lane becomes two 16-byte sc1 stores
-//   {tag, v0, tag, v1}, {tag, v2, tag, v3} (each 8-byte half of a 16-byte sc1 store is observed untorn on gfx950:
-//   MI355X_MICROARCH.md, Valid forms), and the consumer polls the granules it is about to sum until every tag carries the
-//   epoch -- no drain, no flag, no barrier, no second round trip.  Tags restart at 1 in every launch, so the launch function
-//   zeroes the exchange buffer (a memset node ahead of the kernel); spins are bounded and end in the sticky error word.
-//   Buffer reuse: every hand-off is all-to-all (a member passes hand-off k only when ALL members have stored for k, which
-//   they do after finishing their reads of hand-off k - 1), so a region is rewritten at the next time step at the earliest
-//   two full hand-offs after its last reader finished: one copy, no parity double-buffering.
-//   Measured (tools/ks_stamps.py, member 0, cycles per step): forward 34.0k (R1) vs 36.8k (R2), backward 32.9k vs 31.9k; the
-//   gate hand-off (52 KB of partials per member, 104 KB as granules) went from 12.3k to 15.1k, the two small ones gained 0.5k
-//   each.  So the floor of a hand-off here is NOT the flag's extra round trip: it is the ~6k cycles (2.5 us) that a
-//   write-through store takes to become readable from another CU while eight waves per CU keep the memory queue busy
-//   (the guide's handoff-1to1 row under load), and doubling the bytes costs more than the saved round trip returns.
-// An image = the float4 of 64 lanes: 256 floats (R1) or 512 (R2: chunk 0 = {tag, v0, tag, v1} of every lane, chunk 1 the rest).
-template <bool GR> struct KsImg { static constexpr int floats = GR ? 512 : 256; };
+// Hand-offs use form R1 of bd_cluster.h; why not the granule form (R2): DESIGN.md, "The floor of the K-split scan is the hand-off".
+constexpr int kKsImg = 256;        // an image = the float4 of 64 lanes
 
-template <bool GR>
-__device__ __forceinline__ void ks_emit(float* img, int lane, floatx4 v, unsigned epoch) {
-    if constexpr (GR) {
-        const float tg = __uint_as_float(epoch);
-        ks_store4(img + lane * 4, floatx4{tg, v[0], tg, v[1]});
-        ks_store4(img + 256 + lane * 4, floatx4{tg, v[2], tg, v[3]});
-    } else {
-        ks_store4(img + lane * 4, v);
-    }
-}
+__device__ __forceinline__ void ks_emit(float* img, int lane, floatx4 v) { ks_store4(img + lane * 4, v); }
 
 constexpr int kKsChunk = 8;        // members whose loads one poll / sum pass keeps in flight (64 VGPRs either way)
 
-// sum over the members src = first, first + stride, ... < C of one image (this lane's float4), in member order.
-// R1: the caller has passed wait_all; all loads of a chunk are issued before the first add.
-// R2: polls.  A probe pass re-reads ONE granule per member until its tag matches (cheap while the producers are still
-// busy), then the full sweep loads the other three and checks every tag again (a mismatch there just repeats the pass).
-template <bool GR>
-__device__ __forceinline__ floatx4 ks_reduce(const float* base, size_t src_stride, int first, int stride, int C, int lane,
-                                             unsigned epoch, unsigned* err, unsigned limit, unsigned code, bool& dead) {
+// sum over the members src = first, first + stride, ... < C of one image (this lane's float4), in member order.  The caller
+// has passed wait_all; all loads of a chunk are issued before the first add.
+__device__ __forceinline__ floatx4 ks_reduce(const float* base, size_t src_stride, int first, int stride, int C, int lane) {
     floatx4 s = floatx4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (!GR) {
-        const float* p = base + lane * 4;
-        for (int m0 = first; m0 < C; m0 += kKsChunk * stride) {
-            floatx4 v[kKsChunk];
+    const float* p = base + lane * 4;
+    for (int m0 = first; m0 < C; m0 += kKsChunk * stride) {
+        floatx4 v[kKsChunk];
 #pragma unroll
-            for (int i = 0; i < kKsChunk; ++i) {
-                const int src = m0 + i * stride;
-                v[i] = floatx4{0.f, 0.f, 0.f, 0.f};
-                if (src < C) v[i] = ks_load4(p + (size_t)src * src_stride);
-            }
-#pragma unroll
-            for (int i = 0; i < kKsChunk; ++i) s += v[i];
+        for (int i = 0; i < kKsChunk; ++i) {
+            const int src = m0 + i * stride;
+            v[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+            if (src < C) v[i] = ks_load4(p + (size_t)src * src_stride);
         }
-        return s;
-    } else {
-        const float* p = base + lane * 4;
-        unsigned spins = 0;       // `dead` is the wave's: after one time-out it never spins again (the launch still terminates)
-        auto timed_out = [&]() {
-            if (++spins <= limit) return false;
-            if (lane == 0) __hip_atomic_fetch_or(err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            dead = true;
-            return true;
-        };
-        for (int m0 = first; m0 < C; m0 += kKsChunk * stride) {
-            unsigned long long g0[kKsChunk];
-            // probe: granule 0 of every member of the chunk
-            for (;;) {
-                bool ok = true;
 #pragma unroll
-                for (int i = 0; i < kKsChunk; ++i)
-                    if (m0 + i * stride < C) g0[i] = ld_sc1_u64(p + (size_t)(m0 + i * stride) * src_stride);
-#pragma unroll
-                for (int i = 0; i < kKsChunk; ++i)
-                    if (m0 + i * stride < C) ok &= (unsigned)g0[i] == epoch;
-                if (__all(ok) || dead || timed_out()) break;
-                __builtin_amdgcn_s_sleep(1);
-            }
-            // sweep, four members at a time: the other three granules (granule 0 matched above)
-#pragma unroll
-            for (int j0 = 0; j0 < kKsChunk; j0 += 4) {
-                if (m0 + j0 * stride >= C) break;
-                unsigned long long g[4][3];
-                for (;;) {
-                    bool ok = true;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int src = m0 + (j0 + j) * stride;
-                        if (src < C) {
-                            const float* q = p + (size_t)src * src_stride;
-                            g[j][0] = ld_sc1_u64(q + 2);
-                            g[j][1] = ld_sc1_u64(q + 256);
-                            g[j][2] = ld_sc1_u64(q + 258);
-                        }
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (m0 + (j0 + j) * stride < C)
-                            ok &= (unsigned)g[j][0] == epoch && (unsigned)g[j][1] == epoch && (unsigned)g[j][2] == epoch;
-                    if (__all(ok) || dead || timed_out()) break;
-                    __builtin_amdgcn_s_sleep(1);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (m0 + (j0 + j) * stride < C)
-                        s += floatx4{__uint_as_float((unsigned)(g0[j0 + j] >> 32)), __uint_as_float((unsigned)(g[j][0] >> 32)),
-                                     __uint_as_float((unsigned)(g[j][1] >> 32)), __uint_as_float((unsigned)(g[j][2] >> 32))};
-            }
-        }
-        return s;
+        for (int i = 0; i < kKsChunk; ++i) s += v[i];
     }
+    return s;
 }
-// one hand-off: R1 publishes and waits; R2 has nothing to do here (ks_reduce polls)
-template <bool GR>
+// one hand-off: publish this member's stores, wait for every member's
 __device__ __forceinline__ void ks_handoff(unsigned* flags, int c, int C, unsigned epoch, unsigned* err, unsigned limit,
                                            unsigned code) {
-    if constexpr (!GR) {
-        publish(flags + c, epoch);
-        wait_all(flags, C, epoch, err, limit, code);
-    }
+    publish(flags + c, epoch);
+    wait_all(flags, C, epoch, err, limit, code);
 }
 __device__ __forceinline__ floatx4 mfma4(floatx4 a, floatx4 b, floatx4 acc) {
 #pragma unroll
@@ -201,17 +109,15 @@ __device__ __forceinline__ floatx4 ks_frag(const float* w, int nb, int Kb, int k
     return ok ? reinterpret_cast<const floatx4*>(w)[((size_t)nb * Kb + kb) * 64 + lane] : floatx4{0.f, 0.f, 0.f, 0.f};
 }
 
-// exchange buffers of one tile (floats); R1 keeps two copies (step parity), R2 one (see above)
+// exchange buffers of one tile (floats); two copies (step parity)
+constexpr int kKsCopies = 2;
 struct KsBuf {
     size_t g, q, s, total;
-    int copies;
-    __host__ __device__ KsBuf(int C, bool gr) {
-        const size_t img = gr ? 512 : 256;
+    __host__ __device__ KsBuf(int C) {
         g = 0;
-        q = g + (size_t)C * C * 4 * img;     // [dest][src][4 accumulators][image]
-        s = q + (size_t)C * C * img;         // [dest][src][image]
-        total = s + (size_t)C * 8 * img;     // [src][<= 8 (block, mean | raw) pairs][image]
-        copies = gr ? 1 : 2;
+        q = g + (size_t)C * C * 4 * kKsImg;     // [dest][src][4][image]: forward belief blocks, backward (DX, DH)
+        s = q + (size_t)C * C * kKsImg;         // [dest][src][image]
+        total = s + (size_t)C * 8 * kKsImg;     // [src][<= 8 (block, mean | raw) pairs][image]
     }
 };
 
@@ -251,278 +157,9 @@ __device__ __forceinline__ void ks_put4(float* p, floatx4 v, int n_valid) {
         if (i < n_valid) p[i] = v[i];
 }
 
-// ---- forward ---------------------------------------------------------------------------------------------------------
-template <bool GR>
-__global__ __launch_bounds__(kThreads) void observe_kfwd_kernel(bd_observe_fwd_args a_, float* __restrict__ ws, int C, int tiles,
-                                                                unsigned spin_limit) {
-    constexpr int IMG = KsImg<GR>::floats;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    BD_KARGS(bd_observe_fwd_args, ap);
-#define a (*ap)
-    const int Kb_h = cdiv(a.Be, 16), Kb_s = cdiv(a.S, 16), Kb_a = cdiv(a.A, 16), Kb_hd = cdiv(a.Hd, 16);
-    const int tile = blockIdx.x / C, c = blockIdx.x - tile * C;
-    const int row0 = tile * 16, F = a.Be + a.S, Np = Kb_s * 16;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    float* sf = smem;                               // masked state, fragment tiles
-    float* af = sf + Kb_s * kFragFloats;
-    float* s_plain = af + Kb_a * kFragFloats;       // [16][S]
-    float* red = s_plain + ((16 * a.S + 3) & ~3);   // [2][8 waves][64][4]: the two reductions of a step alternate
-    float* plain = red + 2 * kWaves * 256;          // [parts][2][16][Np]: head sums, one copy per helper wave group
-
-    unsigned* flags = reinterpret_cast<unsigned*>(ws) + tile * kMaxCluster;
-    unsigned* err = reinterpret_cast<unsigned*>(ws) + tiles * kMaxCluster;
-    const KsBuf kb_(C, GR);
-    float* xbase = ws + cluster_ws_header_floats(tiles) + (size_t)tile * kb_.copies * kb_.total;
-
-    // ---- resident weight slices (K block c of every layer) ----
-    floatx4 we_s[kKsMaxS], we_a[kKsMaxA];           // embed: output block c
-#pragma unroll
-    for (int kb = 0; kb < kKsMaxS; ++kb) we_s[kb] = ks_frag(a.w_embed_s, c, Kb_s, kb, lane, kb < Kb_s);
-#pragma unroll
-    for (int kb = 0; kb < kKsMaxA; ++kb) we_a[kb] = ks_frag(a.w_embed_a, c, Kb_a, kb, lane, kb < Kb_a);
-    floatx4 wg[2][6], wq[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int nbo = wave + kWaves * i;
-        const bool ok = nbo < Kb_h;
-        wg[i][0] = ks_frag(a.w_ir, nbo, Kb_h, c, lane, ok); wg[i][1] = ks_frag(a.w_iz, nbo, Kb_h, c, lane, ok);
-        wg[i][2] = ks_frag(a.w_in, nbo, Kb_h, c, lane, ok); wg[i][3] = ks_frag(a.w_hr, nbo, Kb_h, c, lane, ok);
-        wg[i][4] = ks_frag(a.w_hz, nbo, Kb_h, c, lane, ok); wg[i][5] = ks_frag(a.w_hn, nbo, Kb_h, c, lane, ok);
-        wq[i] = ks_frag(a.w_q1h, nbo, Kb_h, c, lane, nbo < Kb_hd);
-    }
-    // head pairs (state block, mean | raw): wave w works on pair w % npairs; the waves with part = w / npairs == 0 form the
-    // partial products, and all nparts groups share the sum over the members (group `part` takes members part, part + nparts, ..)
-    const int npairs = 2 * Kb_s, nparts = kWaves / npairs;
-    const int pair = wave % npairs, part = wave / npairs;
-    const int pair_nb = pair >> 1, pair_raw = pair & 1;
-    const bool has_pair = part == 0, sums_pair = part < nparts;
-    floatx4 wh = ks_frag(pair_raw ? a.w_q2s : a.w_q2m, pair_nb, Kb_hd, c, lane, has_pair && c < Kb_hd);
-    // this lane's elements: row frow, columns fcol0 .. fcol0 + 3 of block c
-    const int frow = lane & 15, fcol0 = c * 16 + 4 * (lane >> 4);
-    const int grow = row0 + frow;
-    const int nbe = a.Be - fcol0 < 0 ? 0 : (a.Be - fcol0 < 4 ? a.Be - fcol0 : 4);      // valid belief columns of this lane
-    const int nhd = a.Hd - fcol0 < 0 ? 0 : (a.Hd - fcol0 < 4 ? a.Hd - fcol0 : 4);
-    const bool rok = grow < a.B;
-    floatx4 br4 = floatx4{0.f, 0.f, 0.f, 0.f}, bz4 = br4, bni4 = br4, bnh4 = br4, be4 = br4, bq4 = br4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (i < nbe) {
-            const int col = fcol0 + i;
-            br4[i] = a.b_ih[col] + a.b_hh[col];
-            bz4[i] = a.b_ih[a.Be + col] + a.b_hh[a.Be + col];
-            bni4[i] = a.b_ih[2 * a.Be + col];
-            bnh4[i] = a.b_hh[2 * a.Be + col];
-            be4[i] = a.b_embed[col];
-        }
-        if (i < nhd) bq4[i] = a.b_q1[fcol0 + i];
-    }
-    floatx4 bh4 = floatx4{0.f, 0.f, 0.f, 0.f};
-    if (has_pair) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int col = pair_nb * 16 + 4 * (lane >> 4) + i;
-            if (col < a.S) bh4[i] = a.b_q2[pair_raw * a.S + col];
-        }
-    }
-    // ---- initial carries ----
-    floatx4 h4 = rok ? ks_row4(a.init_belief + (size_t)grow * a.Be + fcol0, nbe) : floatx4{0.f, 0.f, 0.f, 0.f};
-    for (int i = threadIdx.x; i < 16 * a.S; i += blockDim.x) {
-        const int r = i / a.S, k = i - r * a.S;
-        s_plain[i] = (row0 + r < a.B) ? a.init_state[(size_t)(row0 + r) * a.S + k] : 0.f;
-    }
-    lds_barrier();
-
-    KS_SETTLE_BEGIN();
-    ks_settle(we_s); ks_settle(we_a); ks_settle(wg[0]); ks_settle(wg[1]); ks_settle(wq);
-    ks_settle(wh);
-    ks_settle(br4); ks_settle(bz4); ks_settle(bni4); ks_settle(bnh4); ks_settle(be4); ks_settle(bq4); ks_settle(bh4); ks_settle(h4);
-    const bool lead = (c == 0);
-    floatx4* __restrict__ RED4 = reinterpret_cast<floatx4*>(red);
-    floatx4* __restrict__ REDB = RED4 + kWaves * 64;
-    const floatx4 z4 = floatx4{0.f, 0.f, 0.f, 0.f};
-    bool dead = false;
-
-    // this thread's first elements of phase A (nonterminal flag of its state element, its action element): requested one step
-    // ahead, so that a step does not start behind an HBM round trip
-    auto load_nt = [&](int t, int i) {
-        const int r = i / (Kb_s * 16), k = i - r * (Kb_s * 16);
-        return (a.nonterm && i < 16 * Kb_s * 16 && row0 + r < a.B && k < a.S) ? a.nonterm[(size_t)t * a.B + row0 + r] : 1.f;
-    };
-    auto load_ac = [&](int t, int i) {
-        const int r = i / (Kb_a * 16), k = i - r * (Kb_a * 16);
-        return (i < 16 * Kb_a * 16 && row0 + r < a.B && k < a.A) ? a.actions[((size_t)t * a.B + row0 + r) * a.A + k] : 0.f;
-    };
-    float n_nt = load_nt(0, (int)threadIdx.x), n_ac = load_ac(0, (int)threadIdx.x);
-
-    for (int t = 0; t < a.T; ++t) {
-        const size_t tb = (size_t)t * a.B;
-        const int tid = bd_tid();
-        float* xb = xbase + (size_t)(GR ? 0 : (t & 1)) * kb_.total;
-        BD_KSTAMP(0);
-        BD_KARGS_FRESH(ap);
-        const float c_nt = n_nt, c_ac = n_ac;
-        if (t + 1 < a.T) {
-            n_nt = load_nt(t + 1, tid);
-            n_ac = load_ac(t + 1, tid);
-        }
-        // ---- A: masked state / action fragments (every member; K of the embed layer is tiny) ----
-        // (ksplit_ok: 16 * S <= 512 threads, so these element loops are ONE pass and every thread uses the operands it
-        //  requested a step ahead -- a fallback load in the loop body would put a vmcnt wait on the common path)
-        if (tid < 16 * Kb_s * 16) {
-            const int i = tid;
-            const int r = i / (Kb_s * 16), k = i - r * (Kb_s * 16);
-            const int gr = row0 + r;
-            float v = 0.f;
-            if (gr < a.B && k < a.S) {
-                v = s_plain[r * a.S + k] * c_nt;
-                if (lead && a.sv_s) a.sv_s[(tb + gr) * a.S + k] = v;
-            }
-            sf[frag_idx(r, k)] = v;
-        }
-        if (tid < 16 * Kb_a * 16) af[frag_idx(tid / (Kb_a * 16), tid % (Kb_a * 16))] = c_ac;
-        // operands of the later epilogues: requested now, consumed after the hand-offs
-        const floatx4 pre4 = rok ? ks_row4(a.pre_emb + (tb + grow) * a.Hd + fcol0, nhd) : z4;
-        float eps = 0.f;
-        {
-            const int row = tid / a.S, col = tid - row * a.S;
-            if (tid < 16 * a.S && row0 + row < a.B) eps = a.eps_post[(tb + row0 + row) * a.S + col];
-        }
-        lds_barrier();
-        BD_KSTAMP(1);
-        // ---- F1: x_c = ELU(W_e[block c] [s; a] + b): every wave, in registers ----
-        floatx4 x4;
-        {
-            floatx4 acc = be4;
-            const floatx4* __restrict__ S4 = reinterpret_cast<const floatx4*>(sf) + lane;
-            const floatx4* __restrict__ A4 = reinterpret_cast<const floatx4*>(af) + lane;
-#pragma unroll
-            for (int kb = 0; kb < kKsMaxS; ++kb)
-                if (kb < Kb_s) acc = mfmaT(we_s[kb], S4[kb * 64], acc);
-#pragma unroll
-            for (int kb = 0; kb < kKsMaxA; ++kb)
-                if (kb < Kb_a) acc = mfmaT(we_a[kb], A4[kb * 64], acc);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x4[i] = (rok && i < nbe) ? elu(acc[i]) : 0.f;
-            if (wave == 0 && rok && a.sv_x) ks_put4(a.sv_x + (tb + grow) * a.Be + fcol0, x4, nbe);
-        }
-        BD_KSTAMP(2);
-        BD_KARGS_FRESH(ap);
-        // ---- F2: gate partials over K block c, for every output block; reduce-scatter #1 ----
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int nbo = wave + kWaves * i;
-            if (nbo < Kb_h) {
-                floatx4 R = mfmaT(wg[i][0], x4, z4), Z = mfmaT(wg[i][1], x4, z4);
-                const floatx4 NI = mfmaT(wg[i][2], x4, z4);
-                R = mfmaT(wg[i][3], h4, R);
-                Z = mfmaT(wg[i][4], h4, Z);
-                const floatx4 NH = mfmaT(wg[i][5], h4, z4);
-                float* dst = xb + kb_.g + ((size_t)(nbo * C + c) * 4) * IMG;
-                const unsigned ep = (unsigned)(3 * t + 1);
-                ks_emit<GR>(dst, lane, R, ep); ks_emit<GR>(dst + IMG, lane, Z, ep);
-                ks_emit<GR>(dst + 2 * IMG, lane, NI, ep); ks_emit<GR>(dst + 3 * IMG, lane, NH, ep);
-            }
-        }
-        BD_KSTAMP(3);
-        ks_handoff<GR>(flags, c, C, (unsigned)(3 * t + 1), err, spin_limit, kErrFwd);
-        BD_KSTAMP(4);
-        // ---- F3: sum the C partials of block c (wave = (gate, half of the members)); every wave finishes the GRU gates ----
-        {
-            const int g = wave & 3, half = wave >> 2;
-            RED4[wave * 64 + lane] = ks_reduce<GR>(xb + kb_.g + ((size_t)(c * C) * 4 + g) * IMG, (size_t)4 * IMG, half, 2, C, lane,
-                                                   (unsigned)(3 * t + 1), err, spin_limit, kErrFwd, dead);
-        }
-        lds_barrier();
-        {
-            const floatx4 R = RED4[0 * 64 + lane] + RED4[4 * 64 + lane] + br4, Z = RED4[1 * 64 + lane] + RED4[5 * 64 + lane] + bz4;
-            const floatx4 NI = RED4[2 * 64 + lane] + RED4[6 * 64 + lane] + bni4, NH = RED4[3 * 64 + lane] + RED4[7 * 64 + lane] + bnh4;
-            floatx4 rr4, zz4, nn4;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                rr4[i] = sigmoidf(R[i]);
-                zz4[i] = sigmoidf(Z[i]);
-                nn4[i] = tanh_act(NI[i] + rr4[i] * NH[i]);
-                h4[i] = (rok && i < nbe) ? (1.f - zz4[i]) * nn4[i] + zz4[i] * h4[i] : 0.f;
-            }
-            if (wave == 0 && rok) {
-                ks_put4(a.feat + (tb + grow) * F + fcol0, h4, nbe);
-                if (a.sv_gates) {
-                    float* gg = a.sv_gates + (tb + grow) * 4 * a.Be + fcol0;
-                    ks_put4(gg, rr4, nbe); ks_put4(gg + a.Be, zz4, nbe); ks_put4(gg + 2 * a.Be, nn4, nbe); ks_put4(gg + 3 * a.Be, NH, nbe);
-                }
-            }
-        }
-        BD_KSTAMP(5);
-        BD_KARGS_FRESH(ap);
-        // ---- F4: posterior-hidden partials over K block c; reduce-scatter #2 ----
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int nbo = wave + kWaves * i;
-            if (nbo < Kb_hd) ks_emit<GR>(xb + kb_.q + (size_t)(nbo * C + c) * IMG, lane, mfmaT(wq[i], h4, z4), (unsigned)(3 * t + 2));
-        }
-        BD_KSTAMP(6);
-        ks_handoff<GR>(flags, c, C, (unsigned)(3 * t + 2), err, spin_limit, kErrFwd);
-        BD_KSTAMP(7);
-        // ---- F5: q_c = ELU(sum + pre_emb_c + b): every wave (second RED buffer: a slow wave may still read the first) ----
-        REDB[wave * 64 + lane] = c < Kb_hd ? ks_reduce<GR>(xb + kb_.q + (size_t)(c * C) * IMG, IMG, wave, kWaves, C, lane,
-                                                          (unsigned)(3 * t + 2), err, spin_limit, kErrFwd, dead) : z4;
-        lds_barrier();
-        floatx4 q4 = bq4 + pre4;
-        for (int w = 0; w < kWaves; ++w) q4 += REDB[w * 64 + lane];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q4[i] = (rok && i < nhd) ? elu(q4[i]) : 0.f;
-        if (wave == 0 && rok && a.sv_q) ks_put4(a.sv_q + (tb + grow) * a.Hd + fcol0, q4, nhd);
-        BD_KSTAMP(8);
-        BD_KARGS_FRESH(ap);
-        // ---- F6: (mean, raw) partials over K block c; all-reduce ----
-        if (has_pair) ks_emit<GR>(xb + kb_.s + (size_t)(c * 8 + pair) * IMG, lane, mfmaT(wh, q4, z4), (unsigned)(3 * t + 3));
-        BD_KSTAMP(9);
-        ks_handoff<GR>(flags, c, C, (unsigned)(3 * t + 3), err, spin_limit, kErrFwd);
-        BD_KSTAMP(10);
-        BD_KARGS_FRESH(ap);
-        // ---- F7: every member sums the head partials (wave group `part` its share of the members), then samples s' ----
-        if (sums_pair) {
-            floatx4 v = ks_reduce<GR>(xb + kb_.s + (size_t)pair * IMG, (size_t)8 * IMG, part, nparts, C, lane, (unsigned)(3 * t + 3), err,
-                                      spin_limit, kErrFwd, dead);
-            if (part == 0) v += bh4;
-            float* pl = plain + (size_t)part * 2 * 16 * Np;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pl[pair_raw * 16 * Np + frow * Np + pair_nb * 16 + 4 * (lane >> 4) + i] = v[i];
-        }
-        lds_barrier();
-        if (tid < 16 * a.S) {
-            const int e = tid;
-            const int row = e / a.S, col = e - row * a.S;
-            const int gr = row0 + row;
-            float st = 0.f;
-            if (gr < a.B) {
-                float Mn = plain[row * Np + col], Rw = plain[16 * Np + row * Np + col];
-                for (int pt = 1; pt < nparts; ++pt) {
-                    Mn += plain[pt * 2 * 16 * Np + row * Np + col];
-                    Rw += plain[pt * 2 * 16 * Np + 16 * Np + row * Np + col];
-                }
-                const float ee = eps;
-                const float sd = softplusf(Rw) + a.min_std;
-                st = Mn + sd * ee;
-                if (lead) {
-                    const size_t ix = (tb + gr) * a.S + col;
-                    a.post_mean[ix] = Mn;
-                    a.post_std[ix] = sd;
-                    a.feat[(tb + gr) * F + a.Be + col] = st;
-                }
-            }
-            s_plain[row * a.S + col] = st;
-        }
-        lds_barrier();
-        BD_KSTAMP(11);
-    }
-#undef a
-}
-
 // ---- forward, GRU split by OUTPUT columns (two hand-offs per step) ---------------------------------------------------------
-// The K-split forward above pays three hand-offs per step, and the first one carries the gate partials of all 13 blocks
-// (52 KB per member).  Here member c forms the four gate pre-activations of ITS block over the full K instead:
+// Split along K as above, the forward paid three hand-offs per step, and the first one carried the gate partials of all 13
+// blocks (52 KB per member).  Here member c forms the four gate pre-activations of ITS block over the full K instead:
 //   F1  x (ALL blocks) = ELU(W_e [s; a] + b)      every member, redundantly: K = S + A is tiny (wave w: blocks w, w + 8) -> LDS
 //   F2  R, Z, NI, NH of block c = W_i*[block c, :] x + W_h*[block c, :] h      K split over the WAVES (wave w: K blocks w, w + 8),
 //       partial sums meet in LDS -- no hand-off; the weights are the same 2 x 6 fragments per wave, other slices of them
@@ -533,8 +170,6 @@ __global__ __launch_bounds__(kThreads) void observe_kfwd_kernel(bd_observe_fwd_a
 // The backward keeps its three hand-offs (its reduce-scatters carry gradients that no member can form alone).
 __global__ __launch_bounds__(kThreads) void observe_kfwd_ns_kernel(bd_observe_fwd_args a_, float* __restrict__ ws, int C, int tiles,
                                                                    unsigned spin_limit) {
-    constexpr bool GR = false;
-    constexpr int IMG = KsImg<GR>::floats;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     BD_KARGS(bd_observe_fwd_args, ap);
 #define a (*ap)
@@ -554,8 +189,8 @@ __global__ __launch_bounds__(kThreads) void observe_kfwd_ns_kernel(bd_observe_fw
 
     unsigned* flags = reinterpret_cast<unsigned*>(ws) + tile * kMaxCluster;
     unsigned* err = reinterpret_cast<unsigned*>(ws) + tiles * kMaxCluster;
-    const KsBuf kb_(C, GR);
-    float* xbase = ws + cluster_ws_header_floats(tiles) + (size_t)tile * kb_.copies * kb_.total;
+    const KsBuf kb_(C);
+    float* xbase = ws + cluster_ws_header_floats(tiles) + (size_t)tile * kKsCopies * kb_.total;
 
     // ---- resident weight slices ----
     floatx4 we_s[2][kKsMaxS], we_a[2][kKsMaxA], be4x[2];      // embed: output blocks wave, wave + 8
@@ -647,7 +282,6 @@ __global__ __launch_bounds__(kThreads) void observe_kfwd_ns_kernel(bd_observe_fw
     floatx4* __restrict__ REDB = RED4 + kWaves * 64;
     floatx4* __restrict__ GP4 = reinterpret_cast<floatx4*>(gpart);
     const floatx4 z4 = floatx4{0.f, 0.f, 0.f, 0.f};
-    bool dead = false;
 
     // operands of the NEXT step's fragments, in the sampling phase's element order (e -> row e / S), requested a step ahead
     auto load_nt = [&](int t, int e) {
@@ -761,14 +395,13 @@ __global__ __launch_bounds__(kThreads) void observe_kfwd_ns_kernel(bd_observe_fw
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int nbo = wave + kWaves * i;
-            if (nbo < Kb_hd) ks_emit<GR>(xb + kb_.q + (size_t)(nbo * C + c) * IMG, lane, mfmaT(wq[i], h4, z4), (unsigned)(3 * t + 2));
+            if (nbo < Kb_hd) ks_emit(xb + kb_.q + (size_t)(nbo * C + c) * kKsImg, lane, mfmaT(wq[i], h4, z4));
         }
         BD_KSTAMP(6);
-        ks_handoff<GR>(flags, c, C, (unsigned)(3 * t + 2), err, spin_limit, kErrFwd);
+        ks_handoff(flags, c, C, (unsigned)(3 * t + 2), err, spin_limit, kErrFwd);
         BD_KSTAMP(7);
         // ---- F5: q_c = ELU(sum + pre_emb_c + b); and the belief blocks of all members into LDS for the next step's F2 ----
-        REDB[wave * 64 + lane] = c < Kb_hd ? ks_reduce<GR>(xb + kb_.q + (size_t)(c * C) * IMG, IMG, wave, kWaves, C, lane,
-                                                          (unsigned)(3 * t + 2), err, spin_limit, kErrFwd, dead) : z4;
+        REDB[wave * 64 + lane] = c < Kb_hd ? ks_reduce(xb + kb_.q + (size_t)(c * C) * kKsImg, kKsImg, wave, kWaves, C, lane) : z4;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int nbo = wave + kWaves * i;
@@ -783,15 +416,14 @@ __global__ __launch_bounds__(kThreads) void observe_kfwd_ns_kernel(bd_observe_fw
         BD_KSTAMP(8);
         BD_KARGS_FRESH(ap);
         // ---- F6: (mean, raw) partials over K block c; all-reduce (hand-off 2) ----
-        if (has_pair) ks_emit<GR>(xb + kb_.s + (size_t)(c * 8 + pair) * IMG, lane, mfmaT(wh, q4, z4), (unsigned)(3 * t + 3));
+        if (has_pair) ks_emit(xb + kb_.s + (size_t)(c * 8 + pair) * kKsImg, lane, mfmaT(wh, q4, z4));
         BD_KSTAMP(9);
-        ks_handoff<GR>(flags, c, C, (unsigned)(3 * t + 3), err, spin_limit, kErrFwd);
+        ks_handoff(flags, c, C, (unsigned)(3 * t + 3), err, spin_limit, kErrFwd);
         BD_KSTAMP(10);
         BD_KARGS_FRESH(ap);
         // ---- F7: every member sums the head partials, then samples s' ----
         if (sums_pair) {
-            floatx4 v = ks_reduce<GR>(xb + kb_.s + (size_t)pair * IMG, (size_t)8 * IMG, part, nparts, C, lane, (unsigned)(3 * t + 3), err,
-                                      spin_limit, kErrFwd, dead);
+            floatx4 v = ks_reduce(xb + kb_.s + (size_t)pair * kKsImg, (size_t)8 * kKsImg, part, nparts, C, lane);
             if (part == 0) v += bh4;
             float* pl = plain + (size_t)part * 2 * 16 * Np;
 #pragma unroll
@@ -832,10 +464,8 @@ __global__ __launch_bounds__(kThreads) void observe_kfwd_ns_kernel(bd_observe_fw
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------
-template <bool GR>
 __global__ __launch_bounds__(kThreads) void observe_kbwd_kernel(bd_observe_bwd_args a_, float* __restrict__ ws, int C, int tiles,
                                                                 unsigned spin_limit) {
-    constexpr int IMG = KsImg<GR>::floats;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     BD_KARGS(bd_observe_bwd_args, ap);
 #define a (*ap)
@@ -853,8 +483,8 @@ __global__ __launch_bounds__(kThreads) void observe_kbwd_kernel(bd_observe_bwd_a
 
     unsigned* flags = reinterpret_cast<unsigned*>(ws) + tile * kMaxCluster;
     unsigned* err = reinterpret_cast<unsigned*>(ws) + tiles * kMaxCluster;
-    const KsBuf kb_(C, GR);                         // backward uses: g as [dest][src][2][image] (DX, DH), q as [dest][src][image] (dh),
-    float* xbase = ws + cluster_ws_header_floats(tiles) + (size_t)tile * kb_.copies * kb_.total;   // s as [src][Kb_s][image] (ds)
+    const KsBuf kb_(C);                         // backward uses: g as [dest][src][2][image] (DX, DH), q as [dest][src][image] (dh),
+    float* xbase = ws + cluster_ws_header_floats(tiles) + (size_t)tile * kKsCopies * kb_.total;   // s as [src][Kb_s][image] (ds)
 
     // ---- resident weight slices ----
     floatx4 w2m[kKsMaxS], w2s[kKsMaxS];             // dQ block c: wt_q2m / wt_q2s (out = Hd, in = S)
@@ -893,7 +523,6 @@ __global__ __launch_bounds__(kThreads) void observe_kbwd_kernel(bd_observe_bwd_a
     const floatx4 z4 = floatx4{0.f, 0.f, 0.f, 0.f};
     floatx4 dhc4 = z4;                               // belief-gradient carry of block c (every wave holds a copy)
     unsigned epoch = 0;
-    bool dead = false;
 
     // Operands that do not depend on the recurrence (saved activations, incoming gradients, noise) are requested ONE STEP AHEAD:
     // a step starts with them in registers instead of behind an HBM round trip (B1 was 6.4k of 32.9k cycles, tools/ks_stamps.py).
@@ -929,35 +558,25 @@ __global__ __launch_bounds__(kThreads) void observe_kbwd_kernel(bd_observe_bwd_a
         }
         return v;
     };
-    constexpr bool AHEAD = !GR;          // (the granule form has no registers to spare: it loads at the top of the step)
-    B1v nb1{0.f, 0.f, 0.f, 0.f, 0.f};
-    Svv nsv{z4, z4, z4, z4, z4, z4, z4, z4};
-    if constexpr (AHEAD) {
-        nb1 = load_b1(a.T - 1, (int)threadIdx.x);
-        nsv = load_sv(a.T - 1);
-    }
+    B1v nb1{0.f, 0.f, 0.f, 0.f, 0.f};         // zero first, then load: initialised by the load itself, the compiler
+    Svv nsv{z4, z4, z4, z4, z4, z4, z4, z4};  // renumbers the registers of the whole loop body (not measured)
+    nb1 = load_b1(a.T - 1, (int)threadIdx.x);
+    nsv = load_sv(a.T - 1);
 
     for (int t = a.T - 1; t >= 0; --t) {
         const size_t tb = (size_t)t * a.B;
         const int tid = bd_tid();
-        float* xb = xbase + (size_t)(GR ? 0 : (t & 1)) * kb_.total;
+        float* xb = xbase + (size_t)(t & 1) * kb_.total;
         BD_KSTAMP(16);
         BD_KARGS_FRESH(ap);
-        B1v cb1;
-        Svv sv;
-        if constexpr (AHEAD) {
-            cb1 = nb1;
-            sv = nsv;
-            if (t > 0) {
-                nb1 = load_b1(t - 1, tid);
-                nsv = load_sv(t - 1);
-            }
-        } else {
-            cb1 = load_b1(t, tid);
-            sv = load_sv(t);
+        const B1v cb1 = nb1;
+        const Svv sv = nsv;
+        if (t > 0) {
+            nb1 = load_b1(t - 1, tid);
+            nsv = load_sv(t - 1);
         }
         // ---- B1: through the sample / softplus into (mean, raw) (every member, elementwise) ----
-        if (tid < 16 * Kb_s * 16) {          // (one pass: see the forward kernels)
+        if (tid < 16 * Kb_s * 16) {          // (one pass: see the forward kernel)
             const int i = tid;
             const int r = i / (Kb_s * 16), k = i - r * (Kb_s * 16);
             const int gr = row0 + r;
@@ -1003,13 +622,13 @@ __global__ __launch_bounds__(kThreads) void observe_kbwd_kernel(bd_observe_bwd_a
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int nbo = wave + kWaves * i;
-            if (nbo < Kb_h) ks_emit<GR>(xb + kb_.q + (size_t)(nbo * C + c) * IMG, lane, mfmaT(w1[i], dq4, z4), epoch);
+            if (nbo < Kb_h) ks_emit(xb + kb_.q + (size_t)(nbo * C + c) * kKsImg, lane, mfmaT(w1[i], dq4, z4));
         }
         BD_KSTAMP(19);
-        ks_handoff<GR>(flags, c, C, epoch, err, spin_limit, kErrBwd);
+        ks_handoff(flags, c, C, epoch, err, spin_limit, kErrBwd);
         BD_KSTAMP(20);
         // ---- B4: total d belief of block c, gate gradients: every wave ----
-        RED4[wave * 64 + lane] = ks_reduce<GR>(xb + kb_.q + (size_t)(c * C) * IMG, IMG, wave, kWaves, C, lane, epoch, err, spin_limit, kErrBwd, dead);
+        RED4[wave * 64 + lane] = ks_reduce(xb + kb_.q + (size_t)(c * C) * kKsImg, kKsImg, wave, kWaves, C, lane);
         lds_barrier();
         floatx4 vr4, vz4, vni4, vnh4, carry4;
         {
@@ -1046,18 +665,17 @@ __global__ __launch_bounds__(kThreads) void observe_kbwd_kernel(bd_observe_bwd_a
                 floatx4 DX = mfmaT(wg[i][0], vr4, z4), DH = mfmaT(wg[i][3], vr4, z4);
                 DX = mfmaT(wg[i][1], vz4, DX); DH = mfmaT(wg[i][4], vz4, DH);
                 DX = mfmaT(wg[i][2], vni4, DX); DH = mfmaT(wg[i][5], vnh4, DH);
-                float* dst = xb + kb_.g + ((size_t)(nbo * C + c) * 2) * IMG;
-                ks_emit<GR>(dst, lane, DX, epoch); ks_emit<GR>(dst + IMG, lane, DH, epoch);
+                float* dst = xb + kb_.g + ((size_t)(nbo * C + c) * 2) * kKsImg;
+                ks_emit(dst, lane, DX); ks_emit(dst + kKsImg, lane, DH);
             }
         }
         BD_KSTAMP(22);
-        ks_handoff<GR>(flags, c, C, epoch, err, spin_limit, kErrBwd);
+        ks_handoff(flags, c, C, epoch, err, spin_limit, kErrBwd);
         BD_KSTAMP(23);
         // ---- B6: d embed pre-activation of block c, the carry's W_hh^T term: every wave ----
         {
             const int g = wave & 1, quarter = wave >> 1;
-            REDB[wave * 64 + lane] = ks_reduce<GR>(xb + kb_.g + ((size_t)(c * C) * 2 + g) * IMG, (size_t)2 * IMG, quarter, 4, C, lane, epoch,
-                                                   err, spin_limit, kErrBwd, dead);
+            REDB[wave * 64 + lane] = ks_reduce(xb + kb_.g + ((size_t)(c * C) * 2 + g) * kKsImg, (size_t)2 * kKsImg, quarter, 4, C, lane);
         }
         lds_barrier();
         floatx4 de4;
@@ -1076,15 +694,14 @@ __global__ __launch_bounds__(kThreads) void observe_kbwd_kernel(bd_observe_bwd_a
         BD_KARGS_FRESH(ap);
         // ---- B7: d state partials over K block c; all-reduce ----
         ++epoch;
-        if (spart == 0) ks_emit<GR>(xb + kb_.s + (size_t)(c * 8 + sblk) * IMG, lane, mfmaT(wes, de4, z4), epoch);
+        if (spart == 0) ks_emit(xb + kb_.s + (size_t)(c * 8 + sblk) * kKsImg, lane, mfmaT(wes, de4, z4));
         BD_KSTAMP(25);
-        ks_handoff<GR>(flags, c, C, epoch, err, spin_limit, kErrBwd);
+        ks_handoff(flags, c, C, epoch, err, spin_limit, kErrBwd);
         BD_KSTAMP(26);
         BD_KARGS_FRESH(ap);
         // ---- B8: d posterior_state_t (through the nonterminal mask of this step's input); wave group `spart` sums its members ----
         if (spart < nparts) {
-            const floatx4 v = ks_reduce<GR>(xb + kb_.s + (size_t)sblk * IMG, (size_t)8 * IMG, spart, nparts, C, lane, epoch, err, spin_limit,
-                                            kErrBwd, dead);
+            const floatx4 v = ks_reduce(xb + kb_.s + (size_t)sblk * kKsImg, (size_t)8 * kKsImg, spart, nparts, C, lane);
             const float mk = rok ? (a.nonterm ? a.nonterm[tb + grow] : 1.f) : 0.f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -1098,36 +715,25 @@ __global__ __launch_bounds__(kThreads) void observe_kbwd_kernel(bd_observe_bwd_a
 #undef a
 }
 
-size_t ksplit_ws_floats_per_tile(int C) {
-    const KsBuf r1(C, false), r2(C, true);
-    const size_t x = r1.copies * r1.total, y = r2.copies * r2.total;
-    return x > y ? x : y;
-}
+size_t ksplit_ws_floats_per_tile(int C) { return kKsCopies * KsBuf(C).total; }
 
-int& ksplit_mode() {               // -1: as the environment says, 0: off (round-1 cluster form), 1: K-split with R1 hand-offs,
-    static int m = -1;             //  2: K-split with granule (R2) hand-offs, 3: as 1 with the forward GRU split by output columns
+int& ksplit_mode() {               // -1: the K-split form wherever the shapes allow it, 0: off (round-1 cluster form)
+    static int m = -1;
     return m;
-}
-static int ksplit_form() {         // 0 / 1 / 2 / 3 as above, environment resolved (BD_OBS_KSPLIT, default 3)
-    static const char* e = getenv("BD_OBS_KSPLIT");
-    if (ksplit_mode() >= 0) return ksplit_mode();
-    if (e && e[0] >= '0' && e[0] <= '3') return e[0] - '0';
-    return 3;
 }
 
 bool ksplit_ok(int Be, int S, int A, int Hd, int C) {
-    if (ksplit_form() == 0) return false;
+    if (ksplit_mode() == 0) return false;
     return C == cdiv(Be, 16) && C <= 2 * kWaves && cdiv(Hd, 16) <= C && cdiv(S, 16) <= kKsMaxS && cdiv(A, 16) <= kKsMaxA &&
            S <= kHeadMaxN && 16 * S <= kThreads && 2 * cdiv(S, 16) <= kWaves;
 }
 
-static size_t ks_lds_fwd(int S, int A) {
+// sf, af, s_plain, red, plain, then the x and h fragment tiles and the waves' gate partials
+static size_t ks_lds_fwd(int S, int A, int Be) {
     const int Kb_s = cdiv(S, 16), Kb_a = cdiv(A, 16);
     const int nparts = kWaves / (2 * Kb_s);
-    return ((size_t)(Kb_s + Kb_a) * kFragFloats + ((16 * S + 3) & ~3) + 2 * kWaves * 256 + (size_t)nparts * 2 * 16 * Kb_s * 16) * sizeof(float);
-}
-static size_t ks_lds_fwd_ns(int S, int A, int Be) {       // + x and h fragment tiles + the waves' gate partials
-    return ks_lds_fwd(S, A) + ((size_t)2 * cdiv(Be, 16) * kFragFloats + (size_t)kWaves * 4 * 256) * sizeof(float);
+    return ((size_t)(Kb_s + Kb_a) * kFragFloats + ((16 * S + 3) & ~3) + 2 * kWaves * 256 + (size_t)nparts * 2 * 16 * Kb_s * 16 +
+            (size_t)2 * cdiv(Be, 16) * kFragFloats + (size_t)kWaves * 4 * 256) * sizeof(float);
 }
 static size_t ks_lds_bwd(int S) {
     const int Kb_s = cdiv(S, 16);
@@ -1135,56 +741,29 @@ static size_t ks_lds_bwd(int S) {
     return ((size_t)2 * Kb_s * kFragFloats + (size_t)nparts * ((16 * S + 3) & ~3) + 2 * kWaves * 256) * sizeof(float);
 }
 
-// zero what the form polls: the member flags (R1) or the whole exchange buffer, whose tags restart at 1 (R2)
-static int ks_reset(float* ws, int C, int tiles, bool gr, hipStream_t stream, const char* who) {
-    const size_t floats = gr ? cluster_ws_flag_floats(tiles) : cluster_ws_flag_floats(tiles);
-    if (hipMemsetAsync(ws, 0, floats * sizeof(float), stream) != hipSuccess) return fail("%s: memset failed", who);
-    if (gr) {
-        const KsBuf kb(C, true);
-        float* x = ws + cluster_ws_header_floats(tiles);
-        if (hipMemsetAsync(x, 0, (size_t)tiles * kb.copies * kb.total * sizeof(float), stream) != hipSuccess)
-            return fail("%s: memset failed", who);
-    }
-    return 0;
-}
-
-template <bool GR>
-static int launch_kfwd(const bd_observe_fwd_args* a, float* ws, int C, int tiles, hipStream_t stream) {
-    if (allow_big_lds(observe_kfwd_kernel<GR>)) return -1;
-    const size_t dyn = launch_lds(observe_kfwd_kernel<GR>, ks_lds_fwd(a->S, a->A), "bd_observe_forward_cluster");
-    if (!dyn) return -1;
-    if (ks_reset(ws, C, tiles, GR, stream, "bd_observe_forward_cluster")) return -1;
-    hipLaunchKernelGGL(observe_kfwd_kernel<GR>, dim3(tiles * C), dim3(kThreads), dyn, stream, *a, ws, C, tiles, cluster_spin_limit());
-    BD_CHECK_LAUNCH("bd_observe_forward_cluster");
-    return 0;
-}
-template <bool GR>
-static int launch_kbwd(const bd_observe_bwd_args* a, float* ws, int C, int tiles, hipStream_t stream) {
-    if (allow_big_lds(observe_kbwd_kernel<GR>)) return -1;
-    const size_t dyn = launch_lds(observe_kbwd_kernel<GR>, ks_lds_bwd(a->S), "bd_observe_backward_cluster");
-    if (!dyn) return -1;
-    if (ks_reset(ws, C, tiles, GR, stream, "bd_observe_backward_cluster")) return -1;
-    hipLaunchKernelGGL(observe_kbwd_kernel<GR>, dim3(tiles * C), dim3(kThreads), dyn, stream, *a, ws, C, tiles, cluster_spin_limit());
-    BD_CHECK_LAUNCH("bd_observe_backward_cluster");
-    return 0;
-}
-
-static int launch_kfwd_ns(const bd_observe_fwd_args* a, float* ws, int C, int tiles, hipStream_t stream) {
-    if (allow_big_lds(observe_kfwd_ns_kernel)) return -1;
-    const size_t dyn = launch_lds(observe_kfwd_ns_kernel, ks_lds_fwd_ns(a->S, a->A, a->Be), "bd_observe_forward_cluster");
-    if (!dyn) return -1;
-    if (ks_reset(ws, C, tiles, false, stream, "bd_observe_forward_cluster")) return -1;
-    hipLaunchKernelGGL(observe_kfwd_ns_kernel, dim3(tiles * C), dim3(kThreads), dyn, stream, *a, ws, C, tiles, cluster_spin_limit());
-    BD_CHECK_LAUNCH("bd_observe_forward_cluster");
+// zero what the kernels poll: the member flags
+static int ks_reset(float* ws, int tiles, hipStream_t stream, const char* who) {
+    if (hipMemsetAsync(ws, 0, cluster_ws_flag_floats(tiles) * sizeof(float), stream) != hipSuccess) return fail("%s: memset failed", who);
     return 0;
 }
 
 int launch_observe_kfwd(const bd_observe_fwd_args* a, float* ws, int C, int tiles, hipStream_t stream) {
-    if (ksplit_form() == 3) return launch_kfwd_ns(a, ws, C, tiles, stream);
-    return ksplit_form() == 2 ? launch_kfwd<true>(a, ws, C, tiles, stream) : launch_kfwd<false>(a, ws, C, tiles, stream);
+    if (allow_big_lds(observe_kfwd_ns_kernel)) return -1;
+    const size_t dyn = launch_lds(observe_kfwd_ns_kernel, ks_lds_fwd(a->S, a->A, a->Be), "bd_observe_forward_cluster");
+    if (!dyn) return -1;
+    if (ks_reset(ws, tiles, stream, "bd_observe_forward_cluster")) return -1;
+    hipLaunchKernelGGL(observe_kfwd_ns_kernel, dim3(tiles * C), dim3(kThreads), dyn, stream, *a, ws, C, tiles, cluster_spin_limit());
+    BD_CHECK_LAUNCH("bd_observe_forward_cluster");
+    return 0;
 }
 int launch_observe_kbwd(const bd_observe_bwd_args* a, float* ws, int C, int tiles, hipStream_t stream) {
-    return ksplit_form() == 2 ? launch_kbwd<true>(a, ws, C, tiles, stream) : launch_kbwd<false>(a, ws, C, tiles, stream);
+    if (allow_big_lds(observe_kbwd_kernel)) return -1;
+    const size_t dyn = launch_lds(observe_kbwd_kernel, ks_lds_bwd(a->S), "bd_observe_backward_cluster");
+    if (!dyn) return -1;
+    if (ks_reset(ws, tiles, stream, "bd_observe_backward_cluster")) return -1;
+    hipLaunchKernelGGL(observe_kbwd_kernel, dim3(tiles * C), dim3(kThreads), dyn, stream, *a, ws, C, tiles, cluster_spin_limit());
+    BD_CHECK_LAUNCH("bd_observe_backward_cluster");
+    return 0;
 }
 
 }  // namespace bd

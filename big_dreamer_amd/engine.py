@@ -302,7 +302,7 @@ class DreamerEngine:
         # collectives of ONE communicator run in issue order on its internal stream, so the critic's all-reduce of step k -- off
         # the critical path, at the end of a low-priority phase -- sat in front of the KL / world-model collectives of step k + 1
         # whenever the critic phase ran late, and dynamics learning stalled behind it: the one-rank rehearsal read 4.3 or
-        # 3.6 ms/step instead of 2.9 depending on how HIP had mapped the streams to hardware queues (tools/r03_dp_rehearsal.sh).
+        # 3.6 ms/step instead of 2.9 depending on how HIP had mapped the streams to hardware queues (tools/dp_rehearsal.py).
         # Issuing the actor / critic updates one host step late (below) fixes the ORDER of issue, separate communicators remove
         # the coupling.  Collective: every rank builds its engine at the same point.  BD_PHASE_GROUPS=0: one communicator.
         rehearsal = os.environ.get("BD_FORCE_DP", "0") == "1" and torch.distributed.is_initialized()
@@ -346,16 +346,7 @@ class DreamerEngine:
         self._wbatch = {"model": WgradBatch(self, "model"), "model_early": WgradBatch(self, "model_early", "_wgrad_ws_early"),
                         "actor": WgradBatch(self, "actor", "_wgrad_ws_bh"),
                         "critic": WgradBatch(self, "critic", "_wgrad_ws_side")}
-        # The critic update only needs the imagined features and the lambda-returns, and the actor's backward pass uses
-        # the critic TARGET: the two are independent, so the critic phase runs on a second HIP stream underneath the
-        # latency-bound imagination backward.  Measured on MI355X at batch=50: no gain (6.92 vs 6.85 ms/step; the
-        # head-chain and wgrad kernels already fill the chip and slow imagine_bwd down by contention), so it is off
-        # by default (BD_OVERLAP_CRITIC=1 enables it; parity-tested either way).
-        self.overlap_critic = os.environ.get("BD_OVERLAP_CRITIC", "0") == "1"
-        self._side = _engine_stream(self.dev, "side", int(os.environ.get("BD_SIDE_PRIO", "0")))
-        self._s_heads = _engine_stream(self.dev, "heads", -1)     # heads of the first half of a split rollout
-        self.img_split = os.environ.get("BD_IMG_SPLIT", "0") == "1"
-        self._img_split_rows = 0
+        self._side = _engine_stream(self.dev, "side", int(os.environ.get("BD_SIDE_PRIO", "0")))    # critic (pipelined)
         # Frozen imagined heads (reward_model, critic_target) forward + dgrad in one launch (csrc/heads.hip) on the
         # dynamics-backprop path with Gaussian latents; BD_HEADS_FUSED=0 keeps the separate forward / backward chains
         # (mlp.hip) for the A/B.
@@ -957,7 +948,6 @@ class DreamerEngine:
             cabi.check(lib.bd_imagine_cat_forward(C.byref(a), cabi.stream()))
         if save and noise.get("entropy") is None and not d.discrete_actions:   # perf mode: the estimator draws in-kernel
             self._entropy_estimate(noise, ent, Hm, N)
-        self._img_split_rows = 0
         return ifeat, ent, act
 
     def _cluster_ok(self, B: int) -> bool:
@@ -1005,8 +995,8 @@ class DreamerEngine:
                                              ptr(pst), cabi.stream()))
         return pst, pm, ps
 
-    def dense_forward(self, mod: str, prefix: str, tag: str, x, ldx: int, M: int, out_width: int, rows=None, sidx=None):
-        """DenseModel forward with saved activations; `rows` = (r0, r1) runs that row range only (same buffers).
+    def dense_forward(self, mod: str, prefix: str, tag: str, x, ldx: int, M: int, out_width: int, sidx=None):
+        """DenseModel forward with saved activations.
         `sidx` (Categorical latents, x = [h; one-hot s]): the state's class indices [M x D] -- layer 0 then contracts the
         belief columns only and gathers the state columns (bd_mlp_forward's one-hot segment).  The returned layer list is
         the full-width one (the backward's d/d x is dense over all of [h; s])."""
@@ -1018,18 +1008,11 @@ class DreamerEngine:
         if sidx is not None:
             fl = [(f"{prefix}0h", layers[0][1], layers[0][2], d.Be, layers[0][4])] + layers[1:]
             w_in, gather = d.Be, (sidx, self._plain[f"{prefix}0sT"][0], d.cat_D, d.cat_C)
-        if rows is None:
-            self.mlp_forward(M, x, ldx, w_in, fl, acts + [None], out, out_width, gather=gather)
-        else:
-            r0, r1 = rows
-            if gather is not None:
-                gather = (sidx[r0:r1],) + gather[1:]
-            self.mlp_forward(r1 - r0, x.view(M, ldx)[r0:r1], ldx, w_in, fl, [t[r0:r1] for t in acts] + [None],
-                             out[r0:r1], out_width, gather=gather)
+        self.mlp_forward(M, x, ldx, w_in, fl, acts + [None], out, out_width, gather=gather)
         return out, acts, layers
 
     def imagine(self, start_feat, N: int, Hm: int, noise, save: bool = True, tag: str = "", feat_tag: str = "",
-                split: bool = False, start_sidx: Optional[torch.Tensor] = None, rec_saves: bool = True,
+                start_sidx: Optional[torch.Tensor] = None, rec_saves: bool = True,
                 act_us: Optional[torch.Tensor] = None):
         """Imagination rollout.  save: keep what the actor update needs; rec_saves=False leaves out the recurrence saves
         (only the imagination backward reads them); act_us [Mi x 2A]: also keep the exact (u, std) of every action
@@ -1080,42 +1063,10 @@ class DreamerEngine:
                 a.sv_x, a.sv_gates = ptr(self.buf("isv_x", Mi, d.Be)), ptr(self.buf("isv_gates", Mi, 4 * d.Be))
                 a.sv_p = ptr(self.buf("isv_p", Mi, d.Hd))
             a.sv_act_us = ptr(act_us)
-        H1 = Hm // 2 if (split and Hm >= 2) else 0
         with self.span("imagine_fwd"):
-            if not H1:
-                cabi.check(lib.bd_imagine_forward_scan(C.byref(a), cabi.stream()))
-            else:
-                # two time segments: the frozen reward / value heads of the first can run under the second
-                # (_behaviour_phase).  Same kernel, same operands per step: bit-identical to one launch.
-                a.sv_actor_stride = Mi * d.Hd
-                a.Hm = H1
-                cabi.check(lib.bd_imagine_forward_scan(C.byref(a), cabi.stream()))
-                self._ev_img_half = torch.cuda.Event()
-                self._ev_img_half.record(torch.cuda.current_stream())
-                r0 = H1 * N
-                f4 = 4      # bytes per float
-                a.Hm = Hm - H1
-                a.start_feat = ptr(ifeat) + (r0 - N) * (d.Be + d.S) * f4
-                a.eps_action = ptr(noise["action"]) + r0 * d.A * f4
-                if noise.get("entropy") is not None:
-                    a.eps_entropy = ptr(noise["entropy"]) + r0 * d.n_entropy * d.A * f4
-                a.eps_prior = ptr(noise["img_prior"]) + r0 * d.S * f4
-                a.feat = ptr(ifeat) + r0 * (d.Be + d.S) * f4
-                a.prior_mean = a.prior_mean + r0 * d.S * f4
-                a.prior_std = a.prior_std + r0 * d.S * f4
-                a.entropy, a.action = ptr(ent) + r0 * f4, ptr(act) + r0 * d.A * f4
-                if save:
-                    a.sv_actor = a.sv_actor + r0 * d.Hd * f4
-                    a.sv_act_stats = a.sv_act_stats + r0 * self.act_stats_width * f4
-                    if rec_saves:
-                        a.sv_x, a.sv_gates = a.sv_x + r0 * d.Be * f4, a.sv_gates + r0 * 4 * d.Be * f4
-                        a.sv_p = a.sv_p + r0 * d.Hd * f4
-                    if act_us is not None:
-                        a.sv_act_us = a.sv_act_us + r0 * 2 * d.A * f4
-                cabi.check(lib.bd_imagine_forward_scan(C.byref(a), cabi.stream()))
+            cabi.check(lib.bd_imagine_forward_scan(C.byref(a), cabi.stream()))
         if save and not d.discrete_actions:     # the entropy estimate of all Hm x N rows: off the recurrence
             self._entropy_estimate(noise, ent, Hm, N)     # (bd_actor_entropy), outside the scan's span
-        self._img_split_rows = H1 * N
         return ifeat, ent, act
 
     @property
@@ -1624,9 +1575,8 @@ class DreamerEngine:
         dyn = mix is None or mix > 0
         start_sidx = self._buf[ptag + "sidx"] if d.categorical else None
         act_us = self.buf("act_us", Mi, 2 * d.A) if mix is not None and not d.discrete_actions else None
-        ifeat, ent, act = self.imagine(feat, N, Hm, noise, feat_tag=ptag, split=self.img_split, start_sidx=start_sidx,
-                                       rec_saves=dyn, act_us=act_us)
-        r0 = self._img_split_rows
+        ifeat, ent, act = self.imagine(feat, N, Hm, noise, feat_tag=ptag, start_sidx=start_sidx, rec_saves=dyn,
+                                       act_us=act_us)
         isidx = self._buf[ptag + "isidx"] if d.categorical else None
         inv_mi = self.dp.mean_grad_scale(Mi)
         wts = dret = None
@@ -1647,9 +1597,7 @@ class DreamerEngine:
                 dret = self.buf("dret_w", Mi)
                 torch.mul(wts, -mix * inv_mi, out=dret)
         # d returns does not depend on the rewards or values (bd_lambda_return_backward reads only dret / dconst), so
-        # with the fused heads their output gradients are known before the heads run.  A split rollout runs the fused
-        # heads once after its second segment: every row's result is independent of the launch it is in, so the split
-        # stays bit-identical to the single launch (test_pipelined_schedule_is_bit_identical_to_serial)
+        # with the fused heads their output gradients are known before the heads run
         fused = dyn and self.heads_fused
         if dyn:
             d_r, d_v = self.buf("d_ir_out", Mi), self.buf("d_iv_out", Mi)
@@ -1663,19 +1611,8 @@ class DreamerEngine:
                 self.img_heads_fused(Mi, ifeat, d_r, d_v, r_out, v_out, difeat)
         else:
             with self.span("img_heads_fwd"):
-                if not r0:
-                    r_out, r_acts, r_layers = self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1, sidx=isidx)
-                    v_out, v_acts, v_layers = self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1, sidx=isidx)
-                else:       # rows of the first time segment on a helper stream, under the second segment of the rollout
-                    with torch.cuda.stream(self._s_heads):
-                        self._s_heads.wait_event(self._ev_img_half)
-                        self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1, rows=(0, r0))
-                        self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1, rows=(0, r0))
-                    r_out, r_acts, r_layers = self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1,
-                                                                 rows=(r0, Mi))
-                    v_out, v_acts, v_layers = self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1,
-                                                                 rows=(r0, Mi))
-                    torch.cuda.current_stream().wait_stream(self._s_heads)
+                r_out, r_acts, r_layers = self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1, sidx=isidx)
+                v_out, v_acts, v_layers = self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1, sidx=isidx)
         returns = self.buf(ptag + "returns", Mi)
         cabi.check(lib.bd_lambda_return_forward(ptr(r_out), ptr(v_out), Hm, N, hp["discount"], hp["disclam"], ptr(returns), st))
         cabi.check(lib.bd_sum(ptr(returns), Mi, sc, SLOT_RET, ws, st))
@@ -1694,10 +1631,6 @@ class DreamerEngine:
                 self._critic_phase(ifeat, returns, Mi, F, inv_mi, self.red_ws_side, isidx, wts)
                 self._ev_cr_done[par] = torch.cuda.Event()
                 self._ev_cr_done[par].record(self._side)
-        elif self.overlap_critic:    # fork: critic phase on the side stream, actor backward continues here
-            self._side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._side):
-                self._critic_phase(ifeat, returns, Mi, F, inv_mi, self.red_ws_side, isidx, wts)
         dentropy = -hp["entropy_weight"] * inv_mi if hp["entropy_weight"] != -1 else 0.0
         d_apre, d_aout = self.buf("d_actor_pre", DENSE_LAYERS, Mi, d.Hd), self.buf("d_actor_out", Mi, d.actor_out)
         sv_actor = self._buf["sv_actor"]
@@ -1780,12 +1713,8 @@ class DreamerEngine:
             wa.run()
         self._optimizer_step_or_defer("opt_actor", "actor", SLOT_GN_ACTOR, hp["actor_learning_rate"], red_ws)
 
-        if par is not None:
-            pass
-        elif not self.overlap_critic:
+        if par is None:
             self._critic_phase(ifeat, returns, Mi, F, inv_mi, red_ws, isidx, wts)
-        else:
-            torch.cuda.current_stream().wait_stream(self._side)     # join before the next step reuses ifeat / returns
         self._counts = dict(N=N, Mi=Mi, S=(d.cat_D if d.categorical else d.S), sum_form=sum_form)
 
     def _critic_phase(self, ifeat, returns, Mi: int, F: int, inv_mi: float, red_ws: torch.Tensor, isidx=None, wts=None) -> None:

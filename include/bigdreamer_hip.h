@@ -262,15 +262,15 @@ int bd_observe_backward(const bd_observe_bwd_args* a, void* stream);
  * kernel's static + dynamic LDS would exceed the CU's 160 KiB. */
 int bd_observe_cluster_size(int B, int Be);   /* workgroups per 16-row tile; 0 = use bd_observe_forward/backward */
 /* Two cluster forms sit behind the same calls.  Round 3 (csrc/observe_ksplit.hip, the default where the cluster has one
- * member per 16-column belief block and Hd <= Be): EVERY layer of the step is split along K over the members with the
- * weight slices resident in registers -- gate partials reduce-scatter, posterior-hidden partials reduce-scatter, head
- * partials all-reduce: three hand-offs per step, nothing computed redundantly.  Round 1 (csrc/observe_cluster.hip, wide
- * batches with two belief blocks per member, or bd_observe_cluster_set_ksplit(0)): only the GRU is split, by output
- * columns, one all-gather per step, the small layers recomputed by every member.  Identical arguments and results. */
-int bd_observe_cluster_set_ksplit(int mode);  /* 3 = K-split, forward GRU split by output columns (two hand-offs per forward
-                                               * step; the default); 1 = K-split, GRU split along K in both directions;
-                                               * 2 = as 1 with granule hand-offs ("the data is the flag"); 0 = round-1 form;
-                                               * -1 = default (environment BD_OBS_KSPLIT, else 3) */
+ * member per 16-column belief block and Hd <= Be): the layers of the step are split over the members with the weight
+ * slices resident in registers -- forward: GRU split by output columns, posterior-hidden partials reduce-scatter, head
+ * partials all-reduce (two hand-offs per step); backward: every layer split along K (three hand-offs per step); nothing
+ * but the small embed layer computed redundantly.  Round 1 (csrc/observe_cluster.hip, wide batches with two belief
+ * blocks per member, or bd_observe_cluster_set_ksplit(0)): only the GRU is split, by output columns, one all-gather per
+ * step, the small layers recomputed by every member.  Identical arguments and results. */
+int bd_observe_cluster_set_ksplit(int mode);  /* -1 = the K-split form wherever the shapes allow it (the default);
+                                               * 0 = the round-1 form everywhere.  Any other value returns an error
+                                               * and leaves the setting unchanged. */
 size_t bd_observe_cluster_ws_floats(int B, int Be);
 int bd_observe_forward_cluster(const bd_observe_fwd_args* a, float* ws, size_t ws_floats, void* stream);
 int bd_observe_backward_cluster(const bd_observe_bwd_args* a, float* ws, size_t ws_floats, void* stream);

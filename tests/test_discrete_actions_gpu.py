@@ -279,9 +279,9 @@ def test_pipelined_schedule_is_bit_identical_to_serial(name, rho):
     d, seed, hp, _ = _CASES[name]
     P = synth.make_params(d, seed)
     engs = []
-    for pipe, split in ((True, False), (False, False), (True, True)):
+    for pipe in (True, False):
         eng = DreamerEngine(d, dict(hp, gradient_mixing=rho), "cuda", params=P)
-        eng.pipeline, eng.img_split = pipe, split
+        eng.pipeline = pipe
         engs.append(eng)
     steps = 4
     batches = [_dev(synth.make_batch(d, seed + 10 * i)) for i in range(steps)]

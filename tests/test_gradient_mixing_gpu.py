@@ -182,9 +182,9 @@ def test_pipelined_schedule_is_bit_identical_to_serial(name, rho):
     d, seed, hp, _ = _case(name)
     P = synth.make_params(d, seed)
     engs = []
-    for pipe, defer, split in ((True, False, False), (False, False, False), (True, True, False), (True, False, True)):
+    for pipe, defer in ((True, False), (False, False), (True, True)):
         eng = DreamerEngine(d, dict(hp, gradient_mixing=rho), "cuda", params=P)
-        eng.pipeline, eng.defer_opt, eng.img_split = pipe, defer, split
+        eng.pipeline, eng.defer_opt = pipe, defer
         engs.append(eng)
     steps = 4
     batches = [_dev(synth.make_batch(d, seed + 10 * i)) for i in range(steps)]

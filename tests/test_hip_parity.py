@@ -98,12 +98,6 @@ def test_forward_pieces_vs_oracle(name):
                                           ("tiny_freenats0", False), ("config2", False),
                                           # the round-1 cluster form (GRU columns split, one all-gather per step)
                                           ("small", "round1"), ("tiny_freenats0", "round1"), ("config2", "round1"),
-                                          # the K-split form with granule ("the data is the flag") hand-offs
-                                          ("small", "ksplit_gr"), ("tiny_freenats0", "ksplit_gr"), ("config1", "ksplit_gr"),
-                                          ("config2", "ksplit_gr"),
-                                          # the K-split form whose forward also splits the GRU along K (three hand-offs per step)
-                                          ("small", "ksplit_r1"), ("tiny_freenats0", "ksplit_r1"), ("config1", "ksplit_r1"),
-                                          ("config2", "ksplit_r1"),
                                           ("tiny_pixel", True), ("tiny_pixel_lin", True),
                                           ("tiny_pixel", "miopen"), ("tiny_pixel_lin", "miopen"),
                                           ("config3", True), ("tiny_discount", True), ("tiny_discount", False)])
@@ -115,11 +109,10 @@ def test_train_steps_vs_oracle_and_golden(name, cluster, monkeypatch):
     torch_convs = cluster == "miopen"
     if torch_convs:
         cluster = True
-    # cluster=True: the K-split cluster scan (csrc/observe_ksplit.hip; default form: forward GRU split by output columns, flag
-    # hand-offs); "ksplit_r1": forward GRU split along K as well; "ksplit_gr": that form with granule hand-offs; "round1":
-    # observe_cluster.hip's form; False: one workgroup per tile (observe.hip)
-    cabi.check(cabi.lib.bd_observe_cluster_set_ksplit({"round1": 0, "ksplit_r1": 1, "ksplit_gr": 2}.get(cluster, -1)))
-    if cluster in ("round1", "ksplit_r1", "ksplit_gr"):
+    # cluster=True: the K-split cluster scan (csrc/observe_ksplit.hip); "round1": observe_cluster.hip's form; False: one
+    # workgroup per tile (observe.hip)
+    cabi.check(cabi.lib.bd_observe_cluster_set_ksplit(0 if cluster == "round1" else -1))
+    if cluster == "round1":
         cluster = True
     d, seed, hp, full, g, P, batch, noise, eng = _setup(name, cluster)
     if d.pixel:
@@ -266,12 +259,10 @@ def test_pipelined_schedule_is_bit_identical_to_serial(name):
     d, seed, hp, _full = CASES[name]
     P = synth.make_params(d, seed)
     engs = []
-    for pipe, defer, split in ((True, False, False), (False, False, False), (True, True, False), (True, False, True),
-                               (False, False, True)):
+    for pipe, defer in ((True, False), (False, False), (True, True)):
         eng = DreamerEngine(d, hp, "cuda", params=P)
         eng.pipeline = pipe
         eng.defer_opt = defer        # the data-parallel order of the optimiser steps (engine._optimizer_step_or_defer)
-        eng.img_split = split        # imagination launched in two time segments, heads of the first under the second
         engs.append(eng)
     steps = 4
     batches = [_dev(synth.make_batch(d, seed + 10 * i)) for i in range(steps)]

@@ -94,10 +94,10 @@ def test_pipelined_schedule_stays_bit_identical_with_fused_heads():
     d, seed, hp, _ = CASES["small"]
     P = synth.make_params(d, seed)
     engs = []
-    for pipe, split in ((True, False), (False, False), (False, True)):
+    for pipe in (True, False):
         eng = DreamerEngine(d, hp, "cuda", params=P)
         assert eng.heads_fused
-        eng.pipeline, eng.img_split = pipe, split
+        eng.pipeline = pipe
         engs.append(eng)
     batches = [_dev(synth.make_batch(d, seed + 10 * i)) for i in range(3)]
     noises = [_dev(synth.make_noise(d, seed + 10 * i)) for i in range(3)]

@@ -32,6 +32,11 @@ def test_cabi_rejects_bad_arguments_without_gpu():
     assert _cabi.lib.bd_sum(None, 0, None, 0, None, None) != 0
     with pytest.raises(RuntimeError):
         _cabi.check(_cabi.lib.bd_lambda_return_forward(None, None, 0, 0, 0.99, 0.95, None, None))
+    # the cluster-form switch takes -1 (default) and 0 (round-1 form) only
+    for mode in (1, 2, 3, -2):
+        assert _cabi.lib.bd_observe_cluster_set_ksplit(mode) != 0, mode
+        assert b"bd_observe_cluster_set_ksplit" in _cabi.lib.bd_last_error()
+    assert _cabi.lib.bd_observe_cluster_set_ksplit(0) == 0 and _cabi.lib.bd_observe_cluster_set_ksplit(-1) == 0
 
 
 def test_replay_sample_indices_match_reference():

@@ -16,9 +16,9 @@ fn = _cabi.lib.bd_debug_kstamps; fn.restype = ctypes.c_int
 out = (ctypes.c_ulonglong * 64)()
 assert fn(out) == 0
 st = np.array(out[:12], dtype=np.int64)
-names = ["A state/action frags + prefetches (+barrier)", "F1 x_c (wave 0) (+barrier)", "F2 gate partials + sc1 stores + publish",
-         "wait_all #1", "F3 reduce + gates (+2 barriers)", "F4 q partials + publish", "wait_all #2", "F5 reduce + ELU (+2 barriers)",
-         "F6 head partials + publish", "wait_all #3", "F7 reduce + sample (+2 barriers)"]
+names = ["(no phase A: frags written by the step before)", "F1 x, all blocks (+barrier)", "F2 gate K-partials (+barrier)", "-",
+         "F3 reduce + gates + belief store (+barrier)", "F4 prefetches + q partials", "publish + wait_all #1",
+         "F5 reduce + belief gather + ELU (+barrier)", "F6 head partials", "publish + wait_all #2", "F7 reduce + sample (+2 barriers)"]
 tot = st[11] - st[0]
 print(f"K-split observe FORWARD step (member 0): {tot} cycles")
 for i, n in enumerate(names):
