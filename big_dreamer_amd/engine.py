@@ -954,7 +954,7 @@ class DreamerEngine:
         """Cluster scan only while its tiles*C one-per-CU members leave half the chip to the kernels the other pipeline
         streams run beside it (members claim a whole CU's LDS and advance in lock step: on a crowded chip they would
         queue for CUs behind unrelated workgroups); larger batches use the single-workgroup scan (observe.hip)."""
-        if not self.use_obs_cluster:
+        if not self.use_obs_cluster or self.d.S > 64:     # the cluster forward spreads the head over at most 64 state columns
             return False
         C_ = int(lib.bd_observe_cluster_size(B, self.d.Be))
         return C_ > 0 and ((B + 15) // 16) * C_ <= int(os.environ.get("BD_OBS_CLUSTER_MAX_WGS", "128"))
