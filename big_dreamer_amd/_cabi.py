@@ -167,6 +167,15 @@ class PlanArgs(C.Structure):
         ["init_belief", "init_state", "act_mean", "act_std", "eps_action", "eps_state", "actions", "returns", "feat"]))
 
 
+class PlanCatArgs(C.Structure):
+    _fields_ = ([(n, I32) for n in ("rows", "H", "cand", "Be", "D", "C", "A", "Hd")] + _ptr_fields(
+        ["w_embed_sT", "w_embed_a", "b_embed", "w_ir", "w_iz", "w_in", "w_hr", "w_hz", "w_hn", "b_ih", "b_hh", "w_p1",
+         "b_p1", "w_p2", "b_p2", "w_r0h", "w_r0sT"]) + [("w_r", P * 4), ("b_r", P * 5)] + _ptr_fields(
+        ["init_belief", "init_state", "act_mean", "act_std", "eps_action", "q_prior"]) + [
+        ("seed", C.c_ulonglong), ("step", C.c_ulonglong), ("stream_id", C.c_uint)] + _ptr_fields(
+        ["actions", "returns", "feat", "sidx"]))
+
+
 class ConvArgs(C.Structure):
     _fields_ = [("in_", P), ("out", P), ("w", P), ("bias", P),
                 ("imgs", I32), ("gh", I32), ("gw", I32), ("N", I32), ("K", I32),
@@ -225,6 +234,7 @@ _SIGS = {
     "bd_kl_categorical_backward": (I32, [P, P, I32, I32, I32, F32, F32, F32, F32, P, I32, P, P, P]),
     "bd_plan_rollout": (I32, [C.POINTER(PlanArgs), P]),
     "bd_cem_refit": (I32, [P, I32, P, I32, I32, I32, I32, I32, P, P, P]),
+    "bd_plan_rollout_cat": (I32, [C.POINTER(PlanCatArgs), P]),
     "bd_lambda_return_backward": (I32, [P, F32, I32, I32, F32, F32, P, P, P]),
     "bd_img_heads_supported": (I32, [I32, I32]),
     "bd_img_heads_fwd_bwd": (I32, [C.POINTER(ImgHeadsArgs), P]),

@@ -1011,6 +1011,14 @@ class DreamerEngine:
         self.mlp_forward(M, x, ldx, w_in, fl, acts + [None], out, out_width, gather=gather)
         return out, acts, layers
 
+    def _check_cat_start(self, state: torch.Tensor) -> None:
+        """A dense start state [rows x S] handed to a kernel that carries class indices: all-zero or one-hot per factor."""
+        d = self.d
+        st = state.reshape(state.shape[0], d.cat_D, d.cat_C)
+        if int(((st != 0).sum(-1) > 1).any()):
+            raise ValueError("Categorical latents: the start state must be all-zero or one-hot per factor "
+                             f"({d.cat_D} x {d.cat_C}); got a factor with more than one non-zero class")
+
     def imagine(self, start_feat, N: int, Hm: int, noise, save: bool = True, tag: str = "", feat_tag: str = "",
                 start_sidx: Optional[torch.Tensor] = None, rec_saves: bool = True,
                 act_us: Optional[torch.Tensor] = None):
@@ -1024,10 +1032,7 @@ class DreamerEngine:
                 # takes, per factor, the all-zero case (the collect loop's initial state, src/main.py:91-95: the actor and
                 # the embed layer see zeros, as in the reference) or the one non-zero class.  Anything denser cannot be
                 # carried as class indices: refuse it rather than silently treat it as one-hot.
-                st = start_feat[:, d.Be:].reshape(N, d.cat_D, d.cat_C)
-                if int(((st != 0).sum(-1) > 1).any()):
-                    raise ValueError("Categorical latents: the start state must be all-zero or one-hot per factor "
-                                     f"({d.cat_D} x {d.cat_C}); got a factor with more than one non-zero class")
+                self._check_cat_start(start_feat[:, d.Be:])
             return self._imagine_cat(start_feat, start_sidx, N, Hm, noise, save, tag, feat_tag, rec_saves, act_us)
         tm = lambda n: self.W("transition_model", n)
         ac = lambda n: self.W("actor", n)
@@ -1097,53 +1102,94 @@ class DreamerEngine:
 
     # ------------------------------------------------------------------------------------------ train step
     def plan(self, belief: torch.Tensor, state: torch.Tensor, horizon: int, iters: int, candidates: int, top: int,
-             eps_action: torch.Tensor, eps_state: torch.Tensor, trace: Optional[list] = None) -> torch.Tensor:
-        """MPCPlanner.forward (src/planner.py:28-90) on the current stream: `iters` x (bd_plan_rollout, bd_cem_refit).
-        belief (B,Be), state (B,S); eps_action (iters,H,B,candidates,A); eps_state (iters,H,B*candidates,S).
+             eps_action: torch.Tensor, eps_state: Optional[torch.Tensor], trace: Optional[list] = None) -> torch.Tensor:
+        """MPCPlanner.forward (src/planner.py:28-90) on the current stream: `iters` x (rollout, bd_cem_refit).
+        belief (B,Be), state (B,S); eps_action (iters,H,B,candidates,A); eps_state (iters,H,B*candidates,S): the
+        prior-state normals, or -- Categorical latents (bd_plan_rollout_cat) -- the sampler's Exp(1) draws, one per class;
+        there None = perf mode: the draws come from the Philox stream "plan_prior", generated inside the rollout kernel
+        (S % 4 == 0) or into ONE iteration's buffer by bd_rng_fill.
         Returns the action-belief mean of every planning step, (H,B,A); row 0 is the planner's answer."""
         d, pk = self.d, self.pk
         tm = lambda n: self.W("transition_model", n)
         B = belief.shape[0]
         rows = B * candidates
+        cat = d.categorical
         mean = self.buf("plan_mean", horizon, B, d.A)
         std = self.buf("plan_std", horizon, B, d.A)
         mean.zero_()                                    # q(a_t:t+H) ~ N(0, I), src/planner.py:41-46
         std.fill_(1.0)
         actions = self.buf("plan_actions", horizon, rows, d.A)
         returns = self.buf("plan_returns", rows)
-        a = cabi.PlanArgs()
-        a.rows, a.H, a.cand, a.Be, a.S, a.A, a.Hd = rows, horizon, candidates, d.Be, d.S, d.A, d.Hd
-        a.w_embed_s, a.w_embed_a, a.b_embed = ptr(pk["embed_s"]), ptr(pk["embed_a"]), ptr(tm("fc_embed_state_action.0.bias"))
+        if cat:
+            self._check_cat_start(state)
+            a = cabi.PlanCatArgs()
+            a.rows, a.H, a.cand, a.Be, a.D, a.C, a.A, a.Hd = rows, horizon, candidates, d.Be, d.cat_D, d.cat_C, d.A, d.Hd
+            a.w_embed_sT = ptr(self._plain["embed_sT"][0])
+            a.w_p2, a.b_p2 = ptr(pk["p2"]), ptr(tm("belief_prior.model.2.bias"))
+            a.w_r0h, a.w_r0sT = ptr(pk["rew0h"]), ptr(self._plain["rew0sT"][0])
+            for l in range(1, DENSE_LAYERS + 1):
+                a.w_r[l - 1] = ptr(pk[f"rew{l}"])
+            rollout = lib.bd_plan_rollout_cat
+        else:
+            a = cabi.PlanArgs()
+            a.rows, a.H, a.cand, a.Be, a.S, a.A, a.Hd = rows, horizon, candidates, d.Be, d.S, d.A, d.Hd
+            a.w_embed_s = ptr(pk["embed_s"])
+            a.w_p2m, a.w_p2s, a.b_p2 = ptr(pk["p2m"]), ptr(pk["p2s"]), ptr(tm("belief_prior.model.2.bias"))
+            for l in range(DENSE_LAYERS + 1):
+                a.w_r[l] = ptr(pk[f"rew{l}"])
+            a.min_std = self.hp["min_std_dev"]
+            rollout = lib.bd_plan_rollout
+        a.w_embed_a, a.b_embed = ptr(pk["embed_a"]), ptr(tm("fc_embed_state_action.0.bias"))
         a.w_ir, a.w_iz, a.w_in = ptr(pk["ir"]), ptr(pk["iz"]), ptr(pk["in"])
         a.w_hr, a.w_hz, a.w_hn = ptr(pk["hr"]), ptr(pk["hz"]), ptr(pk["hn"])
         a.b_ih, a.b_hh = ptr(tm("rnn.bias_ih")), ptr(tm("rnn.bias_hh"))
         a.w_p1, a.b_p1 = ptr(pk["p1"]), ptr(tm("belief_prior.model.0.bias"))
-        a.w_p2m, a.w_p2s, a.b_p2 = ptr(pk["p2m"]), ptr(pk["p2s"]), ptr(tm("belief_prior.model.2.bias"))
         for l in range(DENSE_LAYERS + 1):
-            a.w_r[l] = ptr(pk[f"rew{l}"])
             a.b_r[l] = ptr(self.W("reward_model", f"model.{2 * l}.bias"))
-        a.min_std = self.hp["min_std_dev"]
         a.init_belief, a.init_state = ptr(belief), ptr(state)
         a.act_mean, a.act_std, a.actions = ptr(mean), ptr(std), ptr(actions)
         # Reward model inside the rollout (one return per candidate leaves the CU) once the candidate tiles fill the
         # chip; below that the rollout is latency bound, so it writes [h'; s'] and the reward model runs as one dense
         # chain over all H x rows rows (measured at B=1: 0.98 -> see DESIGN.md; BD_PLAN_FUSE=0/1 forces either form).
+        # Categorical latents: the unfused form won at both measured sizes (1000 rows: 10.2 against 12.2 ms per plan,
+        # 10 000 rows: 34.0 against 35.5), so it is the default there at every row count.
         fuse_env = os.environ.get("BD_PLAN_FUSE", "")
-        fuse = (rows >= 16 * 256) if fuse_env == "" else fuse_env != "0"
+        fuse = (rows >= 16 * 256 and not cat) if fuse_env == "" else fuse_env != "0"
         F = d.Be + d.S
+        feat = sidx = None
         if fuse:
             a.returns, a.feat = ptr(returns), None
         else:
             feat = self.buf("plan_feat", horizon * rows, F)
             a.returns, a.feat = None, ptr(feat)
+            if cat:
+                sidx = self._buf_u8("plan_sidx", horizon * rows, d.cat_D)
+                a.sidx = ptr(sidx)
         st = cabi.stream()
         for it in range(iters):
-            a.eps_action, a.eps_state = ptr(eps_action[it]), ptr(eps_state[it])
-            cabi.check(lib.bd_plan_rollout(C.byref(a), st))
+            a.eps_action = ptr(eps_action[it])
+            if not cat:
+                a.eps_state = ptr(eps_state[it])
+            elif eps_state is not None:
+                a.q_prior = ptr(eps_state[it])
+            else:
+                # perf mode: a Philox step per CEM iteration of every plan call; at most ONE iteration's draws ever exist
+                a.seed, a.step, a.stream_id = self.rng_seed, self._rng_step.get("plan", 0), self.RNG_STREAMS["plan_prior"]
+                self._rng_step["plan"] = a.step + 1
+                if d.S % 4 == 0:
+                    a.q_prior = None
+                else:
+                    q = self.buf("plan_q", horizon, rows, d.S)
+                    r = cabi.RngFillArgs()
+                    r.n, r.seed, r.step = 1, a.seed, a.step
+                    r.t[0] = cabi.RngTensor(q.data_ptr(), q.numel(), cabi.BD_RNG_EXPONENTIAL, a.stream_id)
+                    cabi.check(lib.bd_rng_fill(C.byref(r), st))
+                    a.q_prior = ptr(q)
+            cabi.check(rollout(C.byref(a), st))
             if fuse:
                 ret, steps = returns, 1
             else:
-                ret, _, _ = self.dense_forward("reward_model", "rew", "plan_rew", feat, F, horizon * rows, 1)
+                ret, _, _ = self.dense_forward("reward_model", "rew", "plan_rew", feat, F, horizon * rows, 1, sidx=sidx)
                 steps = horizon
             if trace is not None:
                 trace.append(ret.view(steps, rows).sum(dim=0))
@@ -1163,7 +1209,7 @@ class DreamerEngine:
         self._rng_step = {"wm": 0, "bh": 0}
 
     # noise streams of the perf-mode generator (csrc/bd_rng.h: counter = (index, stream id, step))
-    RNG_STREAMS = {"obs_post": 1, "action": 2, "img_prior": 3, "entropy": 4, "obs_prior": 5}
+    RNG_STREAMS = {"obs_post": 1, "action": 2, "img_prior": 3, "entropy": 4, "obs_prior": 5, "plan_prior": 7}   # (6: pixel dequantisation)
 
     def make_noise(self, B: int, part: str = "all") -> Dict[str, torch.Tensor]:
         """Noise of one step in perf mode (parity tests pass explicit arrays): ONE bd_rng_fill launch per phase on the

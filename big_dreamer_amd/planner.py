@@ -4,6 +4,8 @@
 reward_model)`` and ``forward(belief, state) -> (B, A)`` are the reference's (src/planner.py:10-35).  Each CEM
 iteration is two launches: ``bd_plan_rollout`` (candidate actions, prior-only RSSM rollout and reward model fused
 per planning step, returns summed in LDS) and ``bd_cem_refit`` (top-k selection + mean / std refit).
+With ``latent_distribution="Categorical"`` the rollout is ``bd_plan_rollout_cat`` (csrc/planner_cat.hip): the state is
+carried as class indices and sampled per factor from the prior logits; the refit is the same.
 """
 from __future__ import annotations
 
@@ -41,7 +43,12 @@ class MPCPlanner(nn.Module):
         """belief (B, Be), state (B, S) -> first action mean (B, A)  (src/planner.py:28-90).
 
         ``_noise``: {"action": (iters, H, B, candidates, A), "state": (iters, H, B*candidates, S)} standard-normal
-        draws in the reference's order; drawn on the device when absent."""
+        draws in the reference's order; drawn on the device when absent.
+
+        Categorical latents (``bd_plan_rollout_cat``): ``state`` is all-zero or one-hot per factor, and
+        ``_noise["state"]`` holds the sampler's Exp(1) draws, one per class (sample = argmax(probs / q)).  Without
+        ``_noise`` only the action normals are drawn by torch; the sampler's draws come from the engine's Philox
+        stream, generated inside the rollout kernel (at most one CEM iteration's worth ever exists in memory)."""
         eng, d = self._eng, self._eng.d
         eng.join()                                   # order after queued pipeline work (engine.train_step)
         B = belief.shape[0]
@@ -49,7 +56,7 @@ class MPCPlanner(nn.Module):
         f = lambda t: t.to(eng.dev).contiguous().float()
         if _noise is None:
             eps_a = torch.randn(I, H, B, J, d.A, device=eng.dev)
-            eps_s = torch.randn(I, H, B * J, d.S, device=eng.dev)
+            eps_s = None if d.categorical else torch.randn(I, H, B * J, d.S, device=eng.dev)
         else:
             eps_a, eps_s = f(_noise["action"]), f(_noise["state"])
             assert tuple(eps_a.shape) == (I, H, B, J, d.A) and tuple(eps_s.shape) == (I, H, B * J, d.S)

@@ -275,14 +275,18 @@ def make_noise(d: Dims, seed: int = 0) -> Dict[str, np.ndarray]:
 
 def make_planner_noise(d: Dims, B: int, horizon: int, iters: int, candidates: int, seed: int = 0) -> Dict[str, np.ndarray]:
     """Noise of one MPCPlanner.forward in reference order (src/planner.py:53-65): per CEM iteration the action draws
-    (H,B,candidates,A), then one prior-state draw (B*candidates,S) per rollout step (src/models.py:256)."""
+    (H,B,candidates,A), then one prior-state draw (B*candidates,S) per rollout step (src/models.py:256).
+    Categorical latents: the state draws are the sampler's Exp(1) variates, drawn per factor as make_noise draws them."""
     ns = NoiseStream(seed)
+    rows = B * candidates
+    state_draw = (lambda: ns.exponential((rows * d.cat_D, d.cat_C)).reshape(rows, d.S)) if d.categorical else \
+        (lambda: ns.normal((rows, d.S)))
     act = np.empty((iters, horizon, B, candidates, d.A), np.float32)
-    st = np.empty((iters, horizon, B * candidates, d.S), np.float32)
+    st = np.empty((iters, horizon, rows, d.S), np.float32)
     for it in range(iters):
         act[it] = ns.normal((horizon, B, candidates, d.A))
         for t in range(horizon):
-            st[it, t] = ns.normal((B * candidates, d.S))
+            st[it, t] = state_draw()
     return {"action": act, "state": st}
 
 

@@ -640,6 +640,46 @@ int bd_plan_rollout(const bd_plan_args* a, void* stream);
 int bd_cem_refit(const float* returns, int ret_steps, const float* actions, int H, int B, int cand, int top, int A,
                  float* mean, float* stdev, void* stream);
 
+/* The rollout for latent_distribution="Categorical" (csrc/planner_cat.hip): same rows / candidates / actions / returns
+ * conventions as bd_plan_rollout, on TransitionModel.forward's Categorical branches with embeddings=None
+ * (src/models.py:226-228,241-260) and CategoricalBeliefModel (src/models.py:101-117).  The state is carried as D class
+ * indices: W_es s and the state columns of the reward model's first layer are gathers of rows of the plain transposes
+ * (`*_sT`, [S x out], as in bd_imagine_cat_fwd_args); the prior head gives S = D*C logits, per factor
+ * idx = argmax(softmax(logits) / q), q ~ Exp(1) (torch.multinomial's single-draw path, src/models.py:114-115), and the
+ * one-hot of idx is the state that continues.
+ * init_state: every factor all-zero (fed as zeros) or (scaled) one-hot, as bd_imagine_cat_forward with start_sidx = NULL.
+ * q_prior = NULL: the draws are generated in the kernel, element i of the [H x rows x S] tensor being what
+ * bd_rng_fill(kind = BD_RNG_EXPONENTIAL, seed, step, stream_id, count = H*rows*S) writes at i (needs S % 4 == 0).
+ * returns = NULL: the unfused form -- feat [H x rows x (Be+S)] = [h'; one-hot s'] and sidx [H x rows x D] are written
+ * and the caller runs the reward model (bd_mlp_forward with the one-hot segment).
+ * C <= 256; S <= 256, or 256 % C == 0 and S % 16 == 0; LDS as stated in csrc/planner_cat.hip (<= 160 KiB). */
+typedef struct {
+    int rows, H, cand, Be, D, C, A, Hd;
+    const float* w_embed_sT;                              /* plain [S x Be]: row k = W_e[:, k] */
+    const float* w_embed_a; const float* b_embed;         /* packed (Be, A), [Be] */
+    const float* w_ir; const float* w_iz; const float* w_in;
+    const float* w_hr; const float* w_hz; const float* w_hn;
+    const float* b_ih; const float* b_hh;
+    const float* w_p1; const float* b_p1;                 /* belief_prior.model.0 */
+    const float* w_p2; const float* b_p2;                 /* packed (S, Hd), [S]: prior logits */
+    const float* w_r0h;                                   /* reward_model.model.0, belief columns, packed (Hd, Be) */
+    const float* w_r0sT;                                  /* reward_model.model.0, state columns: plain [S x Hd] */
+    const float* w_r[4];                                  /* reward_model.model.{2,4,6,8}, packed */
+    const float* b_r[5];                                  /* reward_model.model.{0,2,4,6,8}.bias */
+    const float* init_belief;   /* [B x Be] */
+    const float* init_state;    /* [B x S]: zeros, or (scaled) one-hot per factor */
+    const float* act_mean;      /* [H x B x A] */
+    const float* act_std;       /* [H x B x A] */
+    const float* eps_action;    /* [H x rows x A] */
+    const float* q_prior;       /* [H x rows x S] Exp(1) draws, or NULL: generated from (seed, step, stream_id) */
+    unsigned long long seed; unsigned long long step; unsigned stream_id;
+    float* actions;             /* out [H x rows x A] */
+    float* returns;             /* out [rows]; NULL: skip the reward model and write feat and sidx instead */
+    float* feat;                /* out [H x rows x (Be+S)] or NULL */
+    unsigned char* sidx;        /* out [H x rows x D] sampled class per factor, or NULL */
+} bd_plan_cat_args;
+int bd_plan_rollout_cat(const bd_plan_cat_args* a, void* stream);
+
 /* ---- losses (src/planet.py:252-284, src/dreamer.py:110-146,342-383) ---------------------------
  * Reductions write RAW SUMS into a small device "scalar board" (float array); the host turns them
  * into the logged means after one D2H copy per step, and multi-GPU runs all-reduce the board's KL slot
