@@ -24,6 +24,7 @@ import torch
 
 from . import _cabi as cabi
 from .parallel import DataParallel
+from .params import ParamGroup, _adam_state_dict, _load_adam_state_dict
 from .synth import DENSE_LAYERS, MODEL_MODULES, Dims, model_modules, param_shapes
 
 lib = cabi.lib
@@ -69,96 +70,6 @@ def check_action_distribution(value) -> str:
     if value not in ACTION_DISTRIBUTIONS:
         raise ValueError(f"action_distribution must be one of {ACTION_DISTRIBUTIONS}, got {value!r}")
     return value
-
-
-class ParamGroup:
-    """Flat parameter / gradient / Adam-moment buffers of one optimiser, with named views.
-
-    With `conv_storage`, 4-D (convolution) tensors are STORED permuted (d0, d2, d3, d1) -- Conv2d (co, ky, kx, ci),
-    ConvTranspose2d (ci, ky, kx, co): the layout the hand-written conv kernels use as plain [N][K] matrices
-    (csrc/conv.hip) -- while `p` / `g` stay views with the reference's logical shape (state_dict, tests); `ps` / `gs`
-    are the contiguous storage views.  Clip, Adam and the all-reduce act on the flat buffers and do not care."""
-
-    def __init__(self, specs: List[Tuple[str, str, Tuple[int, ...]]], device, with_opt: bool = True,
-                 conv_storage: bool = False):
-        self.specs = specs
-        # every tensor starts on a 16-byte boundary of the flat buffers (pad floats stay zero: zero gradient, zero Adam
-        # update): 16-byte vector loads and LDS-DMA of a weight matrix as it lies in the buffer (csrc/gemm.hip)
-        al = lambda k: (k + 3) & ~3
-        n = sum(al(int(np.prod(s))) for _, _, s in specs)
-        self.numel = n
-        self.flat = torch.zeros(n, dtype=torch.float32, device=device)
-        self.grad = torch.zeros(n, dtype=torch.float32, device=device) if with_opt else None
-        self.m = torch.zeros(n, dtype=torch.float32, device=device) if with_opt else None
-        self.v = torch.zeros(n, dtype=torch.float32, device=device) if with_opt else None
-        self.step = 0
-        self.p: Dict[Tuple[str, str], torch.Tensor] = {}
-        self.g: Dict[Tuple[str, str], torch.Tensor] = {}
-        self.ps: Dict[Tuple[str, str], torch.Tensor] = {}
-        self.gs: Dict[Tuple[str, str], torch.Tensor] = {}
-        self._layout: Dict[Tuple[str, str], tuple] = {}
-        off = 0
-        for mod, name, shape in specs:
-            k = int(np.prod(shape))
-            perm = conv_storage and len(shape) == 4
-            sshape = (shape[0], shape[2], shape[3], shape[1]) if perm else shape
-            self._layout[(mod, name)] = (off, k, sshape, perm)
-
-            def views(buf):
-                st = buf[off:off + k].view(sshape)
-                return st, (st.permute(0, 3, 1, 2) if perm else st)
-
-            self.ps[(mod, name)], self.p[(mod, name)] = views(self.flat)
-            if with_opt:
-                self.gs[(mod, name)], self.g[(mod, name)] = views(self.grad)
-            off += al(k)
-
-    def logical(self, buf: torch.Tensor, mod: str, name: str) -> torch.Tensor:
-        """View of `buf` (a flat buffer laid out like `flat`: grad, m, v) with the reference's shape of (mod, name)."""
-        off, k, sshape, perm = self._layout[(mod, name)]
-        st = buf[off:off + k].view(sshape)
-        return st.permute(0, 3, 1, 2) if perm else st
-
-
-def _adam_state_dict(g: ParamGroup, lr: float, hp: dict, over: Optional[dict] = None) -> dict:
-    """The group's optimiser state in torch.optim.Adam's state_dict layout (parameter index = reference parameter
-    order, moments in the reference's logical shapes), so that the reference's ``model_optimizer.load_state_dict``
-    accepts it (src/planet.py:114)."""
-    state = {}
-    for i, (mod, name, _shape) in enumerate(g.specs):
-        state[i] = {"step": torch.tensor(float(g.step)), "exp_avg": g.logical(g.m, mod, name).detach().cpu().clone().contiguous(),
-                    "exp_avg_sq": g.logical(g.v, mod, name).detach().cpu().clone().contiguous()}
-    over = over or {}
-    group = {"lr": over.get("lr", lr), "betas": (0.9, 0.999), "eps": over.get("eps", hp["adam_epsilon"]),
-             "weight_decay": over.get("weight_decay", hp["weight_decay"]), "amsgrad": False,
-             "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-             "params": list(range(len(g.specs)))}
-    return {"state": state, "param_groups": [group]}
-
-
-def _load_adam_state_dict(g: ParamGroup, sd: dict) -> Optional[dict]:
-    """Restore moments + step; returns the checkpoint's param_group hyper-parameters (lr, eps, weight_decay) -- torch's
-    ``Optimizer.load_state_dict`` adopts them (src/planet.py:114), so the caller does too."""
-    pg = (sd.get("param_groups") or [None])[0]
-    hyper = {k: float(pg[k]) for k in ("lr", "eps", "weight_decay") if pg and k in pg} or None
-    if pg and tuple(pg.get("betas", (0.9, 0.999))) != (0.9, 0.999):
-        raise NotImplementedError(f"Adam betas {pg['betas']} in the checkpoint: the kernels implement (0.9, 0.999), the "
-                                  "reference's only setting (src/dreamer.py:56-67)")
-    st = sd["state"]
-    if not st:                      # a freshly built optimiser: nothing to restore
-        g.m.zero_(); g.v.zero_(); g.step = 0
-        return hyper
-    assert len(st) == len(g.specs), f"optimizer state has {len(st)} parameters, this group {len(g.specs)}"
-    steps = set()
-    for i, (mod, name, shape) in enumerate(g.specs):
-        e = st[i] if i in st else st[str(i)]
-        assert tuple(e["exp_avg"].shape) == tuple(shape), (mod, name, tuple(e["exp_avg"].shape), shape)
-        g.logical(g.m, mod, name).copy_(e["exp_avg"].to(torch.float32))
-        g.logical(g.v, mod, name).copy_(e["exp_avg_sq"].to(torch.float32))
-        steps.add(int(float(e["step"])))
-    assert len(steps) == 1, f"per-parameter Adam step counts differ: {steps}"
-    g.step = steps.pop()
-    return hyper
 
 
 class _LogRecord:
@@ -802,85 +713,84 @@ class DreamerEngine:
         from . import conv as _conv
         return _conv.to_nchw(self.conv.decode(feat.contiguous().float(), tag="api_"))
 
+    def _bind_rssm(self, a) -> None:
+        """Embed (action half, bias) and GRU weights of a forward scan's arguments: observe, imagine and plan, both latent
+        families.  The state half of the embed layer differs by family and stays with the caller."""
+        pk = self.pk
+        tm = lambda n: self.W("transition_model", n)
+        a.w_embed_a, a.b_embed = ptr(pk["embed_a"]), ptr(tm("fc_embed_state_action.0.bias"))
+        a.w_ir, a.w_iz, a.w_in = ptr(pk["ir"]), ptr(pk["iz"]), ptr(pk["in"])
+        a.w_hr, a.w_hz, a.w_hn = ptr(pk["hr"]), ptr(pk["hz"]), ptr(pk["hn"])
+        a.b_ih, a.b_hh = ptr(tm("rnn.bias_ih")), ptr(tm("rnn.bias_hh"))
+
+    def _bind_rssm_t(self, b) -> None:
+        """The transposed embed (state half) and GRU weights of a backward scan's arguments, both latent families."""
+        pk = self.pk
+        b.wt_embed_s = ptr(pk["embed_s.T"])
+        b.wt_ir, b.wt_iz, b.wt_in = ptr(pk["ir.T"]), ptr(pk["iz.T"]), ptr(pk["in.T"])
+        b.wt_hr, b.wt_hz, b.wt_hn = ptr(pk["hr.T"]), ptr(pk["hz.T"]), ptr(pk["hn.T"])
+
     def observe(self, actions, nonterm, pre_emb, eps_post, init_belief, init_state, T: int, B: int, save: bool = True,
                 tag: str = "", prior_only: bool = False, feat_tag: str = ""):
         """TransitionModel.forward recurrence.  Returns feat [T*B x (Be+S)], mean, std of the fed-back state:
         the posterior (embeddings given) or, with prior_only=True (embeddings=None, src/models.py:241,296-297), the
-        prior -- the same kernel run with the prior head's weights and a zero embedding projection."""
+        prior -- the same kernel run with the prior head's weights and a zero embedding projection.
+        Categorical latents (bd_observe_cat_forward; eps_post = the sampler's Exp(1) draws): feat is [h; one-hot s], the
+        logits of the fed-back state come twice (the mean / std slots), and the class indices are left in
+        buf(tag + feat_tag + "sidx")."""
         d, pk = self.d, self.pk
-        if d.categorical:
-            return self._observe_cat(actions, nonterm, pre_emb, eps_post, init_belief, init_state, T, B, save, tag,
-                                     prior_only, feat_tag)
         tm = lambda n: self.W("transition_model", n)
         M = T * B
-        a = cabi.ObserveFwdArgs()
-        a.T, a.B, a.Be, a.S, a.A, a.Hd = T, B, d.Be, d.S, d.A, d.Hd
-        a.w_embed_s, a.w_embed_a, a.b_embed = ptr(pk["embed_s"]), ptr(pk["embed_a"]), ptr(tm("fc_embed_state_action.0.bias"))
-        a.w_ir, a.w_iz, a.w_in = ptr(pk["ir"]), ptr(pk["iz"]), ptr(pk["in"])
-        a.w_hr, a.w_hz, a.w_hn = ptr(pk["hr"]), ptr(pk["hz"]), ptr(pk["hn"])
-        a.b_ih, a.b_hh = ptr(tm("rnn.bias_ih")), ptr(tm("rnn.bias_hh"))
+        # the head that produces the fed-back state: both have the posterior's shapes once the embedding projection is zero
+        head, w1, w2 = ("belief_prior", "p1", "p2") if prior_only else ("belief_posterior", "q1h", "q2")
         if prior_only:
-            a.w_q1h, a.b_q1 = ptr(pk["p1"]), ptr(tm("belief_prior.model.0.bias"))
-            a.w_q2m, a.w_q2s, a.b_q2 = ptr(pk["p2m"]), ptr(pk["p2s"]), ptr(tm("belief_prior.model.2.bias"))
             pre_emb = self.buf(tag + "zero_pre_emb", M, d.Hd)       # stays zero: nothing ever writes it
-        else:
-            a.w_q1h, a.b_q1 = ptr(pk["q1h"]), ptr(tm("belief_posterior.model.0.bias"))
-            a.w_q2m, a.w_q2s, a.b_q2 = ptr(pk["q2m"]), ptr(pk["q2s"]), ptr(tm("belief_posterior.model.2.bias"))
-        a.init_belief, a.init_state, a.actions = ptr(init_belief), ptr(init_state), ptr(actions)
-        a.nonterm, a.pre_emb, a.eps_post = ptr(nonterm), ptr(pre_emb), ptr(eps_post)
-        a.min_std = self.hp["min_std_dev"]
         feat = self.buf(tag + feat_tag + "feat", M, d.Be + d.S)
-        qm, qs = self.buf(tag + "post_mean", M, d.S), self.buf(tag + "post_std", M, d.S)
-        a.feat, a.post_mean, a.post_std = ptr(feat), ptr(qm), ptr(qs)
+        if d.categorical:
+            a = cabi.ObserveCatFwdArgs()
+            a.D, a.C = d.cat_D, d.cat_C
+            a.w_embed_sT, a.w_q2 = ptr(self._plain["embed_sT"][0]), ptr(pk[w2])
+            a.q_post = ptr(eps_post)
+            qm = qs = self.buf(tag + "post_logits", M, d.S)
+            a.post_logits = ptr(qm)
+            a.sidx = ptr(self._buf_u8(tag + feat_tag + "sidx", M, d.cat_D))
+            scan, scan_cluster = lib.bd_observe_cat_forward, lib.bd_observe_cat_forward_cluster
+        else:
+            a = cabi.ObserveFwdArgs()
+            a.S = d.S
+            a.w_embed_s, a.w_q2m, a.w_q2s = ptr(pk["embed_s"]), ptr(pk[w2 + "m"]), ptr(pk[w2 + "s"])
+            a.eps_post, a.min_std = ptr(eps_post), self.hp["min_std_dev"]
+            qm, qs = self.buf(tag + "post_mean", M, d.S), self.buf(tag + "post_std", M, d.S)
+            a.post_mean, a.post_std = ptr(qm), ptr(qs)
+            scan, scan_cluster = lib.bd_observe_forward, lib.bd_observe_forward_cluster
+        a.T, a.B, a.Be, a.A, a.Hd = T, B, d.Be, d.A, d.Hd
+        self._bind_rssm(a)
+        a.w_q1h, a.b_q1, a.b_q2 = ptr(pk[w1]), ptr(tm(head + ".model.0.bias")), ptr(tm(head + ".model.2.bias"))
+        a.init_belief, a.init_state, a.actions = ptr(init_belief), ptr(init_state), ptr(actions)
+        a.nonterm, a.pre_emb, a.feat = ptr(nonterm), ptr(pre_emb), ptr(feat)
         if save:
             a.sv_s, a.sv_x = ptr(self.buf("sv_s", M, d.S)), ptr(self.buf("sv_x", M, d.Be))
             a.sv_gates, a.sv_q = ptr(self.buf("sv_gates", M, 4 * d.Be)), ptr(self.buf("sv_q", M, d.Hd))
         with self.span("observe_fwd"):
-            if self._cluster_ok(B):
-                ws = self._cluster_ws(B)
-                cabi.check(lib.bd_observe_forward_cluster(C.byref(a), ptr(ws), ws.numel(), cabi.stream()))
-            else:
-                cabi.check(lib.bd_observe_forward(C.byref(a), cabi.stream()))
+            self._run_observe_scan(a, B, scan, scan_cluster)
         return feat, qm, qs
 
-    def _observe_cat(self, actions, nonterm, pre_emb, q_post, init_belief, init_state, T, B, save, tag, prior_only, feat_tag):
-        """Categorical latents: TransitionModel.forward recurrence on bd_observe_cat_forward.  Returns feat
-        [T*B x (Be+S)] ([h; one-hot s]), the logits of the fed-back state twice (the Gaussian signature's mean / std
-        slots), and leaves the class indices in buf(tag + feat_tag + "sidx")."""
-        d, pk = self.d, self.pk
-        tm = lambda n: self.W("transition_model", n)
-        M = T * B
-        a = cabi.ObserveCatFwdArgs()
-        a.T, a.B, a.Be, a.D, a.C, a.A, a.Hd = T, B, d.Be, d.cat_D, d.cat_C, d.A, d.Hd
-        a.w_embed_sT, a.w_embed_a = ptr(self._plain["embed_sT"][0]), ptr(pk["embed_a"])
-        a.b_embed = ptr(tm("fc_embed_state_action.0.bias"))
-        a.w_ir, a.w_iz, a.w_in = ptr(pk["ir"]), ptr(pk["iz"]), ptr(pk["in"])
-        a.w_hr, a.w_hz, a.w_hn = ptr(pk["hr"]), ptr(pk["hz"]), ptr(pk["hn"])
-        a.b_ih, a.b_hh = ptr(tm("rnn.bias_ih")), ptr(tm("rnn.bias_hh"))
-        if prior_only:
-            a.w_q1h, a.b_q1 = ptr(pk["p1"]), ptr(tm("belief_prior.model.0.bias"))
-            a.w_q2, a.b_q2 = ptr(pk["p2"]), ptr(tm("belief_prior.model.2.bias"))
-            pre_emb = self.buf(tag + "zero_pre_emb", M, d.Hd)
-        else:
-            a.w_q1h, a.b_q1 = ptr(pk["q1h"]), ptr(tm("belief_posterior.model.0.bias"))
-            a.w_q2, a.b_q2 = ptr(pk["q2"]), ptr(tm("belief_posterior.model.2.bias"))
-        a.init_belief, a.init_state, a.actions = ptr(init_belief), ptr(init_state), ptr(actions)
-        a.nonterm, a.pre_emb, a.q_post = ptr(nonterm), ptr(pre_emb), ptr(q_post)
-        feat = self.buf(tag + feat_tag + "feat", M, d.Be + d.S)
-        logits = self.buf(tag + "post_logits", M, d.S)
-        sidx = self._buf_u8(tag + feat_tag + "sidx", M, d.cat_D)
-        a.feat, a.post_logits, a.sidx = ptr(feat), ptr(logits), ptr(sidx)
-        if save:
-            a.sv_s, a.sv_x = ptr(self.buf("sv_s", M, d.S)), ptr(self.buf("sv_x", M, d.Be))
-            a.sv_gates, a.sv_q = ptr(self.buf("sv_gates", M, 4 * d.Be)), ptr(self.buf("sv_q", M, d.Hd))
-        with self.span("observe_fwd"):
+    def _run_observe_scan(self, a, B: int, scan, scan_cluster) -> None:
+        """Launch an observe scan, forward or backward: its cluster form (several CUs per 16-row tile) where
+        _cat_cluster / _cluster_ok allow it, else the one-workgroup-per-tile kernel."""
+        d, st = self.d, cabi.stream()
+        if d.categorical:
             Cm = self._cat_cluster(B)
             if Cm:
-                ws = self._cat_cluster_ws(B, Cm)
-                cabi.check(lib.bd_observe_cat_forward_cluster(C.byref(a), Cm, ptr(ws), ws.numel(), cabi.stream()))
+                ws = self._cluster_ws(B, int(lib.bd_observe_cat_cluster_ws_floats(B, d.Be, d.Hd, d.cat_D, Cm)))
+                cabi.check(scan_cluster(C.byref(a), Cm, ptr(ws), ws.numel(), st))
             else:
-                cabi.check(lib.bd_observe_cat_forward(C.byref(a), cabi.stream()))
-        return feat, logits, logits
+                cabi.check(scan(C.byref(a), st))
+        elif self._cluster_ok(B):
+            ws = self._cluster_ws(B, int(lib.bd_observe_cluster_ws_floats(B, d.Be)))
+            cabi.check(scan_cluster(C.byref(a), ptr(ws), ws.numel(), st))
+        else:
+            cabi.check(scan(C.byref(a), st))
 
     def _cat_cluster(self, B: int) -> int:
         """Members per 16-row tile of the Categorical cluster observe scan (csrc/observe_cat_cluster.hip), 0 = use the
@@ -891,9 +801,17 @@ class DreamerEngine:
         d = self.d
         return int(lib.bd_observe_cat_cluster_size(B, d.Be, d.cat_D, d.cat_C, int(os.environ.get("BD_OBS_CLUSTER_MAX_WGS", "128"))))
 
-    def _cat_cluster_ws(self, B: int, Cm: int) -> torch.Tensor:
-        d = self.d
-        need = int(lib.bd_observe_cat_cluster_ws_floats(B, d.Be, d.Hd, d.cat_D, Cm))
+    def _cluster_ok(self, B: int) -> bool:
+        """Cluster scan only while its tiles*C one-per-CU members leave half the chip to the kernels the other pipeline
+        streams run beside it (members claim a whole CU's LDS and advance in lock step: on a crowded chip they would
+        queue for CUs behind unrelated workgroups); larger batches use the single-workgroup scan (observe.hip)."""
+        if not self.use_obs_cluster or self.d.S > 64:     # the cluster forward spreads the head over at most 64 state columns
+            return False
+        C_ = int(lib.bd_observe_cluster_size(B, self.d.Be))
+        return C_ > 0 and ((B + 15) // 16) * C_ <= int(os.environ.get("BD_OBS_CLUSTER_MAX_WGS", "128"))
+
+    def _cluster_ws(self, B: int, need: int) -> torch.Tensor:
+        """Workspace of the cluster scans (`need` floats: bd_observe_cluster_ws_floats / bd_observe_cat_cluster_ws_floats)."""
         off = int(lib.bd_observe_cluster_err_offset(B))
         if self._obs_ws is None or self._obs_ws.numel() < need or self._obs_err_off != off:
             self._obs_ws = torch.zeros(need, dtype=torch.float32, device=self.dev)     # zero: flags AND the sticky error word
@@ -906,66 +824,6 @@ class DreamerEngine:
             t = torch.zeros(*shape, dtype=torch.uint8, device=self.dev)
             self._buf[name] = t
         return t
-
-    def _imagine_cat(self, start_feat, start_sidx, N: int, Hm: int, noise, save: bool, tag: str, feat_tag: str,
-                     rec_saves: bool = True, act_us: Optional[torch.Tensor] = None):
-        d, pk = self.d, self.pk
-        tm = lambda n: self.W("transition_model", n)
-        ac = lambda n: self.W("actor", n)
-        Mi = Hm * N
-        a = cabi.ImagineCatFwdArgs()
-        a.N, a.Hm, a.Be, a.D, a.C, a.A, a.Hd, a.n_samples = N, Hm, d.Be, d.cat_D, d.cat_C, d.A, d.Hd, d.n_entropy
-        a.w_embed_sT, a.w_embed_a = ptr(self._plain["embed_sT"][0]), ptr(pk["embed_a"])
-        a.b_embed = ptr(tm("fc_embed_state_action.0.bias"))
-        a.w_ir, a.w_iz, a.w_in = ptr(pk["ir"]), ptr(pk["iz"]), ptr(pk["in"])
-        a.w_hr, a.w_hz, a.w_hn = ptr(pk["hr"]), ptr(pk["hz"]), ptr(pk["hn"])
-        a.b_ih, a.b_hh = ptr(tm("rnn.bias_ih")), ptr(tm("rnn.bias_hh"))
-        a.w_p1, a.b_p1 = ptr(pk["p1"]), ptr(tm("belief_prior.model.0.bias"))
-        a.w_p2, a.b_p2 = ptr(pk["p2"]), ptr(tm("belief_prior.model.2.bias"))
-        a.w_a0h, a.w_a0sT = ptr(pk["a0h"]), ptr(self._plain["a0sT"][0])
-        for l in range(1, DENSE_LAYERS):
-            a.w_a[l - 1] = ptr(pk[f"a{l}"])
-        for l in range(DENSE_LAYERS):
-            a.b_a[l] = ptr(ac(f"model.{2 * l}.bias"))
-        self._actor_head_args(a)
-        a.start_feat, a.start_sidx = ptr(start_feat), ptr(start_sidx)
-        a.eps_action, a.eps_entropy, a.q_prior = ptr(noise["action"]), ptr(noise.get("entropy")), ptr(noise["img_prior"])
-        a.act_raw_init_std, a.act_min_std, a.act_mean_scale = ACT_RAW_INIT_STD, ACT_MIN_STD, ACT_MEAN_SCALE
-        ifeat = self.buf(tag + feat_tag + "ifeat", Mi, d.Be + d.S)
-        a.feat = ptr(ifeat)
-        a.sidx = ptr(self._buf_u8(tag + feat_tag + "isidx", Mi, d.cat_D))      # read by the critic update: double-buffered like ifeat
-        a.prior_logits = ptr(self.buf(tag + "iprior_logits", Mi, d.S))
-        ent, act = self.buf(tag + "entropy", Mi), self.buf(tag + "action", Mi, d.A)
-        a.entropy, a.action = ptr(ent), ptr(act)
-        if save:
-            a.sv_actor = ptr(self.buf("sv_actor", DENSE_LAYERS, Mi, d.Hd))
-            a.sv_act_stats = ptr(self.buf("sv_act_stats", Mi, self.act_stats_width))
-            if rec_saves:
-                a.sv_x, a.sv_gates = ptr(self.buf("isv_x", Mi, d.Be)), ptr(self.buf("isv_gates", Mi, 4 * d.Be))
-                a.sv_p = ptr(self.buf("isv_p", Mi, d.Hd))
-            a.sv_act_us = ptr(act_us)
-        with self.span("imagine_fwd"):
-            cabi.check(lib.bd_imagine_cat_forward(C.byref(a), cabi.stream()))
-        if save and noise.get("entropy") is None and not d.discrete_actions:   # perf mode: the estimator draws in-kernel
-            self._entropy_estimate(noise, ent, Hm, N)
-        return ifeat, ent, act
-
-    def _cluster_ok(self, B: int) -> bool:
-        """Cluster scan only while its tiles*C one-per-CU members leave half the chip to the kernels the other pipeline
-        streams run beside it (members claim a whole CU's LDS and advance in lock step: on a crowded chip they would
-        queue for CUs behind unrelated workgroups); larger batches use the single-workgroup scan (observe.hip)."""
-        if not self.use_obs_cluster or self.d.S > 64:     # the cluster forward spreads the head over at most 64 state columns
-            return False
-        C_ = int(lib.bd_observe_cluster_size(B, self.d.Be))
-        return C_ > 0 and ((B + 15) // 16) * C_ <= int(os.environ.get("BD_OBS_CLUSTER_MAX_WGS", "128"))
-
-    def _cluster_ws(self, B: int) -> torch.Tensor:
-        need = int(lib.bd_observe_cluster_ws_floats(B, self.d.Be))
-        off = int(lib.bd_observe_cluster_err_offset(B))
-        if self._obs_ws is None or self._obs_ws.numel() < need or self._obs_err_off != off:
-            self._obs_ws = torch.zeros(need, dtype=torch.float32, device=self.dev)     # zero: flags AND the sticky error word
-            self._obs_err_off = off
-        return self._obs_ws
 
     def cluster_status(self, B: int) -> None:
         """Raise if a member of ANY cluster launch since the last check timed out waiting for its peers (synchronises;
@@ -1026,6 +884,8 @@ class DreamerEngine:
         (only the imagination backward reads them); act_us [Mi x 2A]: also keep the exact (u, std) of every action
         (bd_actor_reinforce)."""
         d, pk = self.d, self.pk
+        Mi = Hm * N
+        ifeat = self.buf(tag + feat_tag + "ifeat", Mi, d.Be + d.S)
         if d.categorical:
             if start_sidx is None:
                 # API callers (Dreamer.get_action / imagine_ahead / update_belief_and_act) hand a DENSE state: the kernel
@@ -1033,34 +893,34 @@ class DreamerEngine:
                 # the embed layer see zeros, as in the reference) or the one non-zero class.  Anything denser cannot be
                 # carried as class indices: refuse it rather than silently treat it as one-hot.
                 self._check_cat_start(start_feat[:, d.Be:])
-            return self._imagine_cat(start_feat, start_sidx, N, Hm, noise, save, tag, feat_tag, rec_saves, act_us)
-        tm = lambda n: self.W("transition_model", n)
-        ac = lambda n: self.W("actor", n)
-        Mi = Hm * N
-        a = cabi.ImagineFwdArgs()
-        a.N, a.Hm, a.Be, a.S, a.A, a.Hd, a.n_samples = N, Hm, d.Be, d.S, d.A, d.Hd, d.n_entropy
-        a.w_embed_s, a.w_embed_a, a.b_embed = ptr(pk["embed_s"]), ptr(pk["embed_a"]), ptr(tm("fc_embed_state_action.0.bias"))
-        a.w_ir, a.w_iz, a.w_in = ptr(pk["ir"]), ptr(pk["iz"]), ptr(pk["in"])
-        a.w_hr, a.w_hz, a.w_hn = ptr(pk["hr"]), ptr(pk["hz"]), ptr(pk["hn"])
-        a.b_ih, a.b_hh = ptr(tm("rnn.bias_ih")), ptr(tm("rnn.bias_hh"))
-        a.w_p1, a.b_p1 = ptr(pk["p1"]), ptr(tm("belief_prior.model.0.bias"))
-        a.w_p2m, a.w_p2s, a.b_p2 = ptr(pk["p2m"]), ptr(pk["p2s"]), ptr(tm("belief_prior.model.2.bias"))
-        a.w_a0h, a.w_a0s = ptr(pk["a0h"]), ptr(pk["a0s"])
-        for l in range(1, DENSE_LAYERS):
-            a.w_a[l - 1] = ptr(pk[f"a{l}"])
-        for l in range(DENSE_LAYERS):
-            a.b_a[l] = ptr(ac(f"model.{2 * l}.bias"))
+            a = cabi.ImagineCatFwdArgs()
+            a.D, a.C = d.cat_D, d.cat_C
+            a.w_embed_sT, a.w_p2, a.w_a0sT = ptr(self._plain["embed_sT"][0]), ptr(pk["p2"]), ptr(self._plain["a0sT"][0])
+            a.start_sidx, a.q_prior = ptr(start_sidx), ptr(noise["img_prior"])
+            a.sidx = ptr(self._buf_u8(tag + feat_tag + "isidx", Mi, d.cat_D))      # read by the critic update: double-buffered like ifeat
+            a.prior_logits = ptr(self.buf(tag + "iprior_logits", Mi, d.S))
+            scan = lib.bd_imagine_cat_forward
+            # this scan estimates the entropy itself from explicit draws; perf mode: the estimator draws in-kernel
+            entropy_after = noise.get("entropy") is None
+        else:
+            a = cabi.ImagineFwdArgs()
+            a.S = d.S
+            a.w_embed_s, a.w_p2m, a.w_p2s, a.w_a0s = ptr(pk["embed_s"]), ptr(pk["p2m"]), ptr(pk["p2s"]), ptr(pk["a0s"])
+            a.eps_prior, a.min_std = ptr(noise["img_prior"]), self.hp["min_std_dev"]
+            a.prior_mean = ptr(self.buf(tag + "iprior_mean", Mi, d.S))
+            a.prior_std = ptr(self.buf(tag + "iprior_std", Mi, d.S))
+            scan = lib.bd_imagine_forward_scan
+            entropy_after = True        # the entropy estimate of all Hm x N rows: off the recurrence (bd_actor_entropy)
+        a.N, a.Hm, a.Be, a.A, a.Hd, a.n_samples = N, Hm, d.Be, d.A, d.Hd, d.n_entropy
+        self._bind_rssm(a)
+        a.w_p1, a.b_p1 = ptr(pk["p1"]), ptr(self.W("transition_model", "belief_prior.model.0.bias"))
+        a.b_p2 = ptr(self.W("transition_model", "belief_prior.model.2.bias"))
         self._actor_head_args(a)
         a.start_feat = ptr(start_feat)
-        a.eps_action, a.eps_entropy, a.eps_prior = ptr(noise["action"]), ptr(noise.get("entropy")), ptr(noise["img_prior"])
-        a.min_std, a.act_raw_init_std = self.hp["min_std_dev"], ACT_RAW_INIT_STD
-        a.act_min_std, a.act_mean_scale = ACT_MIN_STD, ACT_MEAN_SCALE
-        ifeat = self.buf(tag + feat_tag + "ifeat", Mi, d.Be + d.S)
-        a.feat = ptr(ifeat)
-        a.prior_mean = ptr(self.buf(tag + "iprior_mean", Mi, d.S))
-        a.prior_std = ptr(self.buf(tag + "iprior_std", Mi, d.S))
+        a.eps_action, a.eps_entropy = ptr(noise["action"]), ptr(noise.get("entropy"))
+        a.act_raw_init_std, a.act_min_std, a.act_mean_scale = ACT_RAW_INIT_STD, ACT_MIN_STD, ACT_MEAN_SCALE
         ent, act = self.buf(tag + "entropy", Mi), self.buf(tag + "action", Mi, d.A)
-        a.entropy, a.action = ptr(ent), ptr(act)
+        a.feat, a.entropy, a.action = ptr(ifeat), ptr(ent), ptr(act)
         if save:
             a.sv_actor = ptr(self.buf("sv_actor", DENSE_LAYERS, Mi, d.Hd))
             a.sv_act_stats = ptr(self.buf("sv_act_stats", Mi, self.act_stats_width))
@@ -1069,9 +929,9 @@ class DreamerEngine:
                 a.sv_p = ptr(self.buf("isv_p", Mi, d.Hd))
             a.sv_act_us = ptr(act_us)
         with self.span("imagine_fwd"):
-            cabi.check(lib.bd_imagine_forward_scan(C.byref(a), cabi.stream()))
-        if save and not d.discrete_actions:     # the entropy estimate of all Hm x N rows: off the recurrence
-            self._entropy_estimate(noise, ent, Hm, N)     # (bd_actor_entropy), outside the scan's span
+            cabi.check(scan(C.byref(a), cabi.stream()))
+        if save and entropy_after and not d.discrete_actions:
+            self._entropy_estimate(noise, ent, Hm, N)     # outside the scan's span
         return ifeat, ent, act
 
     @property
@@ -1081,8 +941,14 @@ class DreamerEngine:
         return self.d.A if self.d.discrete_actions else 4 * self.d.A
 
     def _actor_head_args(self, a) -> None:
-        """The actor output layer of an imagination forward's arguments (bd_imagine_fwd_args / _cat_)."""
+        """The actor of an imagination forward's arguments (bd_imagine_fwd_args / _cat_): belief half of layer 0, hidden
+        layers, output layer.  The state half of layer 0 (w_a0s, or w_a0sT for the gather) stays with the caller."""
         pk = self.pk
+        a.w_a0h = ptr(pk["a0h"])
+        for l in range(1, DENSE_LAYERS):
+            a.w_a[l - 1] = ptr(pk[f"a{l}"])
+        for l in range(DENSE_LAYERS):
+            a.b_a[l] = ptr(self.W("actor", f"model.{2 * l}.bias"))
         a.b_a4 = ptr(self.W("actor", f"model.{2 * DENSE_LAYERS}.bias"))
         if self.d.discrete_actions:
             a.w_a4m, a.w_a4s, a.discrete_actions = ptr(pk["a4"]), None, 1
@@ -1139,10 +1005,7 @@ class DreamerEngine:
                 a.w_r[l] = ptr(pk[f"rew{l}"])
             a.min_std = self.hp["min_std_dev"]
             rollout = lib.bd_plan_rollout
-        a.w_embed_a, a.b_embed = ptr(pk["embed_a"]), ptr(tm("fc_embed_state_action.0.bias"))
-        a.w_ir, a.w_iz, a.w_in = ptr(pk["ir"]), ptr(pk["iz"]), ptr(pk["in"])
-        a.w_hr, a.w_hz, a.w_hn = ptr(pk["hr"]), ptr(pk["hz"]), ptr(pk["hn"])
-        a.b_ih, a.b_hh = ptr(tm("rnn.bias_ih")), ptr(tm("rnn.bias_hh"))
+        self._bind_rssm(a)
         a.w_p1, a.b_p1 = ptr(pk["p1"]), ptr(tm("belief_prior.model.0.bias"))
         for l in range(DENSE_LAYERS + 1):
             a.b_r[l] = ptr(self.W("reward_model", f"model.{2 * l}.bias"))
@@ -1390,6 +1253,7 @@ class DreamerEngine:
         feat, qm, qs = self.observe(actions[:-1], nonterm[:-1], pre_emb, noise["obs_post"], init_belief, init_state, T, B,
                                     feat_tag=feat_tag)
         cat = d.categorical
+        sidx = self._buf[feat_tag + "sidx"] if cat else None      # the posterior's class indices (observe left them there)
         with self.span("wm_heads_fwd"):
             _, pm, ps = self.prior_head(feat, N, None if cat else noise.get("obs_prior"))
             if self.pixel:
@@ -1397,15 +1261,13 @@ class DreamerEngine:
                 obs_t = self.conv.acts_enc[0].view(N, d.O)      # the same images in the NHWC order of the prediction
             else:
                 om_out, om_acts, om_layers = self.dense_forward("observation_model", "obs", "om", feat, F, N, d.O,
-                                                                sidx=self._buf[feat_tag + "sidx"] if cat else None)
-            rw_out, rw_acts, rw_layers = self.dense_forward("reward_model", "rew", "rw", feat, F, N, 1,
-                                                            sidx=self._buf[feat_tag + "sidx"] if cat else None)
+                                                                sidx=sidx)
+            rw_out, rw_acts, rw_layers = self.dense_forward("reward_model", "rew", "rw", feat, F, N, 1, sidx=sidx)
 
         inv_rows = self.dp.mean_grad_scale(N)
         dc_state = None
         if d.use_discount:      # _discount_loss (src/dreamer.py:239-251): Bernoulli(logits).log_prob(nonterminal), weight 5
-            dc_out, dc_acts, dc_layers = self.dense_forward("discount_model", "dsc", "dc", feat, F, N, 1,
-                                                            sidx=self._buf[feat_tag + "sidx"] if cat else None)
+            dc_out, dc_acts, dc_layers = self.dense_forward("discount_model", "dsc", "dc", feat, F, N, 1, sidx=sidx)
             d_dc = self.buf("d_dc_out", N, 1)
             cabi.check(lib.bd_bernoulli_nll(ptr(dc_out), ptr(nonterm[:-1]), N, hp["discount_weight"] * inv_rows, ptr(d_dc), sc,
                                             SLOT_DISC, ws, st))
@@ -1428,7 +1290,6 @@ class DreamerEngine:
         kl_w = hp["kl_loss_weight"] * (1.0 / W if sum_form else 1.0)
         if cat:
             dqm, dpm = self.buf("dql", N, d.S), self.buf("dpl", N, d.S)
-            dqs = dps = None
             cabi.check(lib.bd_kl_categorical_backward(ptr(qm), ptr(pm), N, d.cat_D, d.cat_C, hp["free_nats"], hp["kl_balance"],
                                                       kl_w, kl_inv, sc, SLOT_KL, ptr(dqm), ptr(dpm), st))
         else:
@@ -1470,62 +1331,45 @@ class DreamerEngine:
         else:
             d_p_out = self.buf("d_p_out", N, HO)
             cabi.check(lib.bd_gauss_head_backward(ptr(p_out), None, None, ptr(dpm), ptr(dps), N, d.S, ptr(d_p_out), st))
-        tm = lambda n: self.W("transition_model", n)
         p_layers = [("p1", None, d.Hd, d.Be, cabi.ACT_ELU), ("p2", None, HO, d.Hd, cabi.ACT_NONE)]
         self.mlp_backward(N, d_p_out, HO, p_layers, [p_hid, None], [d_p_hid, None], din0=dfeat, ld0=F, w0=d.Be,
                           accumulate=True)
-        # recurrence
-        d_e, d_gi, d_gh = self.buf("d_embed_pre", N, d.Be), self.buf("d_gi", N, 3 * d.Be), self.buf("d_gh", N, 3 * d.Be)
-        d_q1, d_q2 = self.buf("d_q1_pre", N, d.Hd), self.buf("d_q2_out", N, HO)
-        pk = self.pk
-        if cat:
-            b = cabi.ObserveCatBwdArgs()
-            b.T, b.B, b.Be, b.D, b.C, b.A, b.Hd = T, B, d.Be, d.cat_D, d.cat_C, d.A, d.Hd
-            b.wt_embed_s = ptr(pk["embed_s.T"])
-            b.wt_ir, b.wt_iz, b.wt_in = ptr(pk["ir.T"]), ptr(pk["iz.T"]), ptr(pk["in.T"])
-            b.wt_hr, b.wt_hz, b.wt_hn = ptr(pk["hr.T"]), ptr(pk["hz.T"]), ptr(pk["hn.T"])
-            b.wt_q1h, b.wt_q2 = ptr(pk["q1h.T"]), ptr(pk["q2.T"])
-            b.init_belief, b.nonterm = ptr(init_belief), ptr(nonterm[:-1])
-            b.feat, b.post_logits = ptr(feat), ptr(qm)
-            b.sv_x, b.sv_gates, b.sv_q = ptr(self._buf["sv_x"]), ptr(self._buf["sv_gates"]), ptr(self._buf["sv_q"])
-            b.dfeat, b.dpost_logits = ptr(dfeat), ptr(dqm)
-            b.d_embed_pre, b.d_gi, b.d_gh, b.d_q1_pre, b.d_q2_out = ptr(d_e), ptr(d_gi), ptr(d_gh), ptr(d_q1), ptr(d_q2)
-            with self.span("observe_bwd"):
-                Cm = self._cat_cluster(B)
-                if Cm:
-                    ws_c = self._cat_cluster_ws(B, Cm)
-                    cabi.check(lib.bd_observe_cat_backward_cluster(C.byref(b), Cm, ptr(ws_c), ws_c.numel(), st))
-                else:
-                    cabi.check(lib.bd_observe_cat_backward(C.byref(b), st))
-        else:
-            self._observe_backward_gaussian(T, B, init_belief, nonterm, noise, feat, qs, dfeat, dqm, dqs, d_e, d_gi, d_gh,
-                                            d_q1, d_q2, st)
+        d_e, d_gi, d_gh, d_q1, d_q2 = self._observe_backward(T, B, nonterm[:-1], noise["obs_post"], feat)
         self._dynamics_tail(batch, emb, obs_t, feat, init_belief, actions, d_e, d_gi, d_gh, d_q1, d_q2, d_p_hid, d_p_out,
                             p_hid, rw_dpre, rw_acts, om_dpre if (not self.pixel) else None,
                             om_acts if (not self.pixel) else None, N, B, F)
         return feat
 
-    def _observe_backward_gaussian(self, T, B, init_belief, nonterm, noise, feat, qs, dfeat, dqm, dqs, d_e, d_gi, d_gh, d_q1,
-                                   d_q2, st) -> None:
-        d, hp, pk = self.d, self.hp, self.pk
-        b = cabi.ObserveBwdArgs()
-        b.T, b.B, b.Be, b.S, b.A, b.Hd = T, B, d.Be, d.S, d.A, d.Hd
-        b.wt_embed_s = ptr(pk["embed_s.T"])
-        b.wt_ir, b.wt_iz, b.wt_in = ptr(pk["ir.T"]), ptr(pk["iz.T"]), ptr(pk["in.T"])
-        b.wt_hr, b.wt_hz, b.wt_hn = ptr(pk["hr.T"]), ptr(pk["hz.T"]), ptr(pk["hn.T"])
-        b.wt_q1h, b.wt_q2m, b.wt_q2s = ptr(pk["q1h.T"]), ptr(pk["q2m.T"]), ptr(pk["q2s.T"])
-        b.init_belief, b.nonterm, b.eps_post = ptr(init_belief), ptr(nonterm[:-1]), ptr(noise["obs_post"])
-        b.feat, b.post_std = ptr(feat), ptr(qs)
-        b.sv_x, b.sv_gates, b.sv_q = ptr(self._buf["sv_x"]), ptr(self._buf["sv_gates"]), ptr(self._buf["sv_q"])
-        b.dfeat, b.dpost_mean, b.dpost_std = ptr(dfeat), ptr(dqm), ptr(dqs)
-        b.min_std = hp["min_std_dev"]
+    def _observe_backward(self, T: int, B: int, nonterm, eps_post, feat):
+        """Backward of the observe scan, both latent families: from dfeat and the KL gradient w.r.t. the posterior (buffers
+        the dynamics phase has just filled) to the pre-activation gradients of the recurrence, which it returns:
+        d_embed_pre, d_gi, d_gh, d_q1_pre, d_q2_out."""
+        d, pk, buf = self.d, self.pk, self._buf
+        N = T * B
+        if d.categorical:
+            b = cabi.ObserveCatBwdArgs()
+            b.D, b.C = d.cat_D, d.cat_C
+            b.wt_q2 = ptr(pk["q2.T"])
+            b.post_logits, b.dpost_logits = ptr(buf["post_logits"]), ptr(buf["dql"])
+            scan, scan_cluster = lib.bd_observe_cat_backward, lib.bd_observe_cat_backward_cluster
+        else:
+            b = cabi.ObserveBwdArgs()
+            b.S = d.S
+            b.wt_q2m, b.wt_q2s = ptr(pk["q2m.T"]), ptr(pk["q2s.T"])
+            b.eps_post, b.post_std, b.min_std = ptr(eps_post), ptr(buf["post_std"]), self.hp["min_std_dev"]
+            b.dpost_mean, b.dpost_std = ptr(buf["dqm"]), ptr(buf["dqs"])
+            scan, scan_cluster = lib.bd_observe_backward, lib.bd_observe_backward_cluster
+        b.T, b.B, b.Be, b.A, b.Hd = T, B, d.Be, d.A, d.Hd
+        self._bind_rssm_t(b)
+        b.wt_q1h = ptr(pk["q1h.T"])
+        b.init_belief, b.nonterm, b.feat, b.dfeat = ptr(buf["init_belief"]), ptr(nonterm), ptr(feat), ptr(buf["dfeat"])
+        b.sv_x, b.sv_gates, b.sv_q = ptr(buf["sv_x"]), ptr(buf["sv_gates"]), ptr(buf["sv_q"])
+        d_e, d_gi, d_gh = self.buf("d_embed_pre", N, d.Be), self.buf("d_gi", N, 3 * d.Be), self.buf("d_gh", N, 3 * d.Be)
+        d_q1, d_q2 = self.buf("d_q1_pre", N, d.Hd), self.buf("d_q2_out", N, d.head_out)
         b.d_embed_pre, b.d_gi, b.d_gh, b.d_q1_pre, b.d_q2_out = ptr(d_e), ptr(d_gi), ptr(d_gh), ptr(d_q1), ptr(d_q2)
         with self.span("observe_bwd"):
-            if self._cluster_ok(B):
-                ws_c = self._cluster_ws(B)
-                cabi.check(lib.bd_observe_backward_cluster(C.byref(b), ptr(ws_c), ws_c.numel(), st))
-            else:
-                cabi.check(lib.bd_observe_backward(C.byref(b), st))
+            self._run_observe_scan(b, B, scan, scan_cluster)
+        return d_e, d_gi, d_gh, d_q1, d_q2
 
     def _dynamics_tail(self, batch, emb, obs_t, feat, init_belief, actions, d_e, d_gi, d_gh, d_q1, d_q2, d_p_hid, d_p_out,
                        p_hid, rw_dpre, rw_acts, om_dpre, om_acts, N, B, F) -> None:
@@ -1703,10 +1547,8 @@ class DreamerEngine:
                 c.N, c.Hm, c.Be, c.S, c.A, c.Hd = N, Hm, d.Be, d.S, d.A, d.Hd
                 c.wt_p2m, c.wt_p2s = ptr(pk["p2m.T"]), ptr(pk["p2s.T"])
                 c.prior_std, c.eps_prior, c.min_std = ptr(self._buf["iprior_std"]), ptr(noise["img_prior"]), hp["min_std_dev"]
-            c.wt_embed_s, c.wt_embed_a = ptr(pk["embed_s.T"]), ptr(pk["embed_a.T"])
-            c.wt_ir, c.wt_iz, c.wt_in = ptr(pk["ir.T"]), ptr(pk["iz.T"]), ptr(pk["in.T"])
-            c.wt_hr, c.wt_hz, c.wt_hn = ptr(pk["hr.T"]), ptr(pk["hz.T"]), ptr(pk["hn.T"])
-            c.wt_p1 = ptr(pk["p1.T"])
+            self._bind_rssm_t(c)
+            c.wt_embed_a, c.wt_p1 = ptr(pk["embed_a.T"]), ptr(pk["p1.T"])
             for l in range(1, DENSE_LAYERS):
                 c.wt_a[l - 1] = ptr(pk[f"a{l}.T"])
             if d.discrete_actions:
