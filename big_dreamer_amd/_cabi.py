@@ -23,6 +23,10 @@ lib = C.CDLL(LIB_PATH)
 
 BD_MAX_LAYERS = 6
 ACT_NONE, ACT_ELU, ACT_ELU_GRAD = 0, 1, 2
+ACT_RELU, ACT_RELU_GRAD, ACT_TANH, ACT_TANH_GRAD = 3, 4, 5, 6
+# cnn_activation_function (the torch.nn class names the reference resolves) -> (forward code, "times f' of the saved output")
+CNN_ACTS = {"ELU": (ACT_ELU, ACT_ELU_GRAD), "ReLU": (ACT_RELU, ACT_RELU_GRAD), "Tanh": (ACT_TANH, ACT_TANH_GRAD)}
+GRAD_ACTS = (ACT_ELU_GRAD, ACT_RELU_GRAD, ACT_TANH_GRAD)
 P = C.c_void_p
 F32 = C.c_float
 I32 = C.c_int
@@ -256,6 +260,7 @@ _SIGS = {
     "bd_conv_thin_forward": (I32, [P, I32, I32, I32, I32, I32, P, I32, P, I32, P, P, P]),
     "bd_conv_pack_class": (I32, [P, P, I32, I32, I32, I32, I32, I32, I32, P]),
     "bd_conv_pack_fused": (I32, [P, P, I32, I32, I32, P]),
+    "bd_act_backward": (I32, [P, P, C.c_size_t, I32, P]),
     "bd_elu_backward": (I32, [P, P, C.c_size_t, P]),
     "bd_image_layout": (I32, [P, P, I32, I32, I32, I32, P]),
     "bd_colsum_ws_floats": (C.c_size_t, [I32]),

@@ -1,8 +1,9 @@
 """Conv encoder / decoder of the pixel configurations on the hand-written gather-GEMM kernels (csrc/conv.hip).
 
-CnnImageEncoder (src/models.py:527-564): 4 x (Conv2d k4 s2 + ELU), Flatten, Identity | Linear(1024, E).
-ObservationModel (src/models.py:319-362): Linear(Be+S, E), ConvT(E,128,k5,s2)+ELU on a 1x1 image (= a Linear to
-(5,5,128)), ConvT(128,64,k5)+ELU, ConvT(64,32,k6)+ELU, ConvT(32,3,k6).
+CnnImageEncoder (src/models.py:527-564): 4 x (Conv2d k4 s2 + act), Flatten, Identity | Linear(1024, E).
+ObservationModel (src/models.py:319-362): Linear(Be+S, E), ConvT(E,128,k5,s2)+act on a 1x1 image (= a Linear to
+(5,5,128)), ConvT(128,64,k5)+act, ConvT(64,32,k6)+act, ConvT(32,3,k6).  act = cnn_activation_function (Dims.cnn_act):
+ELU, ReLU or Tanh, an epilogue code of the same kernels.
 
 Activations are NHWC; conv weights are stored (d0, ky, kx, d1) (engine.ParamGroup).  Forward, dgrad and the weight
 gradients of every layer are kernels of this library (bd_conv_gemm patterns F / T, bd_mlp_forward / backward for
@@ -24,8 +25,9 @@ import os
 lib = cabi.lib
 ptr = cabi.ptr
 THIN = os.environ.get("BD_CONV_THIN", "1") != "0"      # "0": the 3-channel-image layers on the row-tile gather kernels (A/B)
-# "1": the ELU backward as the epilogue of the dgrad kernels (BD_ACT_ELU_GRAD; parity-tested).  Off: measured 13.2 vs 13.1 ms
-# per step at configs[2] -- the scattered loads of the saved outputs cost the gather kernels more than the separate pass
+# "1": the activation backward (whichever cnn_activation_function is in force) as the epilogue of the dgrad kernels
+# (BD_ACT_*_GRAD; parity-tested).  Off: measured 13.2 vs 13.1 ms per step at configs[2] with ELU -- the scattered loads of the
+# saved outputs cost the gather kernels more than the separate pass
 FUSE_ELU = os.environ.get("BD_CONV_FUSE_ELU", "0") != "0"
 
 ENC = [(3, 32, 4), (32, 64, 4), (64, 128, 4), (128, 256, 4)]          # (ci, co, k); input 64 -> 31 -> 14 -> 6 -> 2
@@ -42,6 +44,8 @@ class ConvStacks:
         dev = eng.dev
         self.E = d.E
         self.lin_tail = d.E != 1024
+        # cnn_activation_function: the forward epilogue code and its "times f'(saved output)" twin, used at every site below
+        self.act, self.act_grad = cabi.CNN_ACTS[d.cnn_act]
         z = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
         # ---- packed weight copies (rebuilt by pack() after every model optimiser step) ----
         self.pk_enc_f = [z(cabi.packed_floats(co, k * k * ci)) for ci, co, k in ENC]
@@ -110,10 +114,10 @@ class ConvStacks:
             y = e.buf(tag + f"cv_a{i + 1}", M, sz, sz, co)
             if i == 0 and THIN:         # the 3-channel image: wave-private band pipelines (bd_conv_thin_forward)
                 conv.thin_f(self.acts_enc[-1], y, e.Ws("encoder", "model.0.weight").view(co, k * k * ci),
-                            e.W("encoder", "model.0.bias"), M, ENC_SIZES[0], ENC_SIZES[0], ci, k, cabi.ACT_ELU)
+                            e.W("encoder", "model.0.bias"), M, ENC_SIZES[0], ENC_SIZES[0], ci, k, self.act)
             else:
                 conv.pattern_f(self.acts_enc[-1], y, self.pk_enc_f[i], e.W("encoder", f"model.{2 * i}.bias"), M, ENC_SIZES[i],
-                               ENC_SIZES[i], ci, k, co, cabi.ACT_ELU)
+                               ENC_SIZES[i], ci, k, co, self.act)
             self.acts_enc.append(y)
         flat = e.buf(tag + "cv_flat", M, 1024)                 # the reference's Flatten order (c, h, w)
         cabi.check(lib.bd_image_layout(ptr(self.acts_enc[-1]), ptr(flat), M, 256, 4, 0, cabi.stream()))
@@ -132,14 +136,14 @@ class ConvStacks:
         e.mlp_forward(M, feat, F, F, [(self.pk_dec0, e.W("observation_model", "decoder.0.bias"), self.E, F, cabi.ACT_NONE)],
                       None, l0, self.E, raw_packs=True)
         d1 = e.buf(tag + "cv_d1", M, 5, 5, 128)
-        e.mlp_forward(M, l0, self.E, self.E, [(self.pk_dec1, self.bias_dec1, 25 * 128, self.E, cabi.ACT_ELU)], None, d1,
+        e.mlp_forward(M, l0, self.E, self.E, [(self.pk_dec1, self.bias_dec1, 25 * 128, self.E, self.act)], None, d1,
                       25 * 128, raw_packs=True)
         self.acts_dec = [l0, d1]
         for j, (ci, co, k) in enumerate(DEC):
             sz = DEC_SIZES[j + 1]
             y = e.buf(tag + f"cv_d{j + 2}", M, sz, sz, co)
             conv.pattern_t_fused(self.acts_dec[-1], y, self.pk_dec_t[j], e.W("observation_model", f"decoder.{DEC_IDX[j]}.bias"),
-                                 M, DEC_SIZES[j], DEC_SIZES[j], ci, k, co, sz, sz, cabi.ACT_ELU if j < 2 else cabi.ACT_NONE)
+                                 M, DEC_SIZES[j], DEC_SIZES[j], ci, k, co, sz, sz, self.act if j < 2 else cabi.ACT_NONE)
             self.acts_dec.append(y)
         return self.acts_dec[-1]
 
@@ -158,23 +162,23 @@ class ConvStacks:
         for j in (2, 1, 0):
             ci, co, k = DEC[j]
             isz, osz = DEC_SIZES[j], DEC_SIZES[j + 1]
-            a_in = self.acts_dec[j + 1]                         # this layer's input (post-ELU output of the layer below)
+            a_in = self.acts_dec[j + 1]                         # this layer's input (post-activation output of the layer below)
             name = f"decoder.{DEC_IDX[j]}"
             # dW (ci, ky, kx, co) = sum over input pixels of in[m][ci] * window(g)(m, (ky, kx, co));  db = column sums of g
             wb.add(a_in, ci, g, 0, M * isz * isz, ci, k * k * co, G(name + ".weight"), k * k * co, None,
                    gather=(k, k * co, isz, isz, osz, osz, co))
             self._colsum(wb, g, M * osz * osz, co, G(name + ".bias"))
-            # d input = strided conv of g with the stored matrix [ci][(ky, kx, co)], then through the ELU of the layer below
-            # (the ELU backward is the dgrad kernels' epilogue: BD_ACT_ELU_GRAD with the saved outputs a_in)
+            # d input = strided conv of g with the stored matrix [ci][(ky, kx, co)], then through the activation of the layer
+            # below (fused: the dgrad kernels' epilogue, BD_ACT_*_GRAD with the saved outputs a_in; else bd_act_backward)
             gi = e.buf(f"cv_gd{j + 1}", M, isz, isz, ci)
             if j == 2 and THIN:         # dgrad of ConvT(32 -> 3): a k6 convolution of the 3-channel image gradient
                 conv.thin_f(g, gi, e.Ws("observation_model", f"decoder.{DEC_IDX[j]}.weight").view(ci, k * k * co), None, M, osz,
-                            osz, co, k, cabi.ACT_ELU_GRAD if FUSE_ELU else cabi.ACT_NONE, a_in if FUSE_ELU else None)
+                            osz, co, k, self.act_grad if FUSE_ELU else cabi.ACT_NONE, a_in if FUSE_ELU else None)
             else:
                 conv.pattern_f(g, gi, self.pk_dec_f[j], None, M, osz, osz, co, k, ci,
-                               cabi.ACT_ELU_GRAD if FUSE_ELU else cabi.ACT_NONE, a_in if FUSE_ELU else None)
+                               self.act_grad if FUSE_ELU else cabi.ACT_NONE, a_in if FUSE_ELU else None)
             if not FUSE_ELU:
-                cabi.check(lib.bd_elu_backward(ptr(gi), ptr(a_in), gi.numel(), cabi.stream()))
+                cabi.check(lib.bd_act_backward(ptr(gi), ptr(a_in), gi.numel(), self.act, cabi.stream()))
             g = gi
         # the 1x1 -> 5x5 layer as a Linear: dW[ci][(ky,kx,co)] = sum_m l0[m][ci] * g[m][(ky,kx,co)]
         l0 = self.acts_dec[0]
@@ -210,11 +214,11 @@ class ConvStacks:
             ci, co, k = ENC[i]
             isz, osz = ENC_SIZES[i], ENC_SIZES[i + 1]
             if i == 3 or not FUSE_ELU:  # d pre-activation (below the top layer it is the epilogue of the dgrad that produced g)
-                cabi.check(lib.bd_elu_backward(ptr(g), ptr(self.acts_enc[i + 1]), g.numel(), cabi.stream()))
+                cabi.check(lib.bd_act_backward(ptr(g), ptr(self.acts_enc[i + 1]), g.numel(), self.act, cabi.stream()))
             wb.add(g, co, self.acts_enc[i], 0, M * osz * osz, co, k * k * ci, G(f"model.{2 * i}.weight"), k * k * ci,
                    G(f"model.{2 * i}.bias"), gather=(k, k * ci, osz, osz, isz, isz, ci))
             if i > 0:
                 gi = e.buf(f"cv_ga{i}", M, isz, isz, ci)
                 conv.pattern_t_fused(g, gi, self.pk_enc_t[i], None, M, osz, osz, co, k, ci, isz, isz,
-                                     cabi.ACT_ELU_GRAD if FUSE_ELU else cabi.ACT_NONE, self.acts_enc[i] if FUSE_ELU else None)
+                                     self.act_grad if FUSE_ELU else cabi.ACT_NONE, self.acts_enc[i] if FUSE_ELU else None)
                 g = gi

@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/bigdreamer_hip.h"   // BD_ACT_*
+
 namespace bd {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -102,7 +104,65 @@ __device__ __forceinline__ float one_minus_exp_neg(float x) { return 1.f - __exp
 #endif
 // derivative of ELU expressed through its output y (y<=0 <=> x<=0): 1 or exp(x) = y+1
 __device__ __forceinline__ float elu_grad_from_out(float y) { return y > 0.f ? 1.f : y + 1.f; }
-__device__ __forceinline__ float act_apply(int act, float x) { return act ? elu(x) : x; }
+// derivative of tanh through its output: 1 - y^2 as ONE fused multiply-add, so that every kernel that forms it (fused
+// epilogues, the standalone pass) rounds it the same way whatever the compiler would contract
+__device__ __forceinline__ float tanh_grad_from_out(float y) { return __builtin_fmaf(-y, y, 1.f); }
+// BD_ACT_* (bigdreamer_hip.h): odd codes are forward activations, the even code above each is "multiply by f' taken from
+// the SAVED output" (y <= 0 <=> x <= 0 for ELU and ReLU; tanh' = 1 - y^2), so no pre-activation is ever kept.  `act` is
+// uniform over a launch: with a compile-time constant only the named case remains.
+__device__ __forceinline__ float act_apply(int act, float x) {
+    if (act == BD_ACT_ELU) return elu(x);
+    if (act == BD_ACT_RELU) return x > 0.f ? x : 0.f;
+    if (act == BD_ACT_TANH) return tanh_act(x);
+    return x;
+}
+// f'(x) from the saved output y = f(x); `act` is the forward code or its _GRAD code (BD_ACT_NONE: 1)
+__device__ __forceinline__ float act_grad_from_out(int act, float y) {
+    const int fwd = (act - 1) | 1;
+    if (fwd == BD_ACT_ELU) return elu_grad_from_out(y);
+    if (fwd == BD_ACT_RELU) return y > 0.f ? 1.f : 0.f;
+    if (fwd == BD_ACT_TANH) return tanh_grad_from_out(y);
+    return 1.f;
+}
+__host__ __device__ inline bool act_is_forward(int act) { return act == BD_ACT_ELU || act == BD_ACT_RELU || act == BD_ACT_TANH; }
+__host__ __device__ inline bool act_is_grad(int act) {
+    return act == BD_ACT_ELU_GRAD || act == BD_ACT_RELU_GRAD || act == BD_ACT_TANH_GRAD;
+}
+// A lane's four epilogue elements at once: one uniform branch per activation around four straight-line evaluations, so
+// that the ELU case keeps the instruction sequence it had when ELU was the only activation.
+__device__ __forceinline__ floatx4 act_apply4(int act, floatx4 x) {
+    floatx4 v = x;
+    if (act == BD_ACT_ELU) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = elu(x[r]);
+    } else if (act == BD_ACT_RELU) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = x[r] > 0.f ? x[r] : 0.f;
+    } else if (act == BD_ACT_TANH) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = tanh_act(x[r]);
+    }
+    return v;
+}
+__device__ __forceinline__ floatx4 act_grad4(int act, floatx4 y) {
+    const int fwd = (act - 1) | 1;
+    floatx4 m = floatx4{1.f, 1.f, 1.f, 1.f};
+    if (fwd == BD_ACT_ELU) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m[r] = elu_grad_from_out(y[r]);
+    } else if (fwd == BD_ACT_RELU) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m[r] = y[r] > 0.f ? 1.f : 0.f;
+    } else if (fwd == BD_ACT_TANH) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m[r] = tanh_grad_from_out(y[r]);
+    }
+    return m;
+}
+// epilogue of a conv kernel: a forward code applies f; BD_ACT_NONE / a _GRAD code multiply by `mul` (1 / f' of the saved output)
+__device__ __forceinline__ floatx4 act_epilogue4(int act, floatx4 acc, floatx4 mul) {
+    return act_is_forward(act) ? act_apply4(act, acc) : acc * mul;
+}
 
 // ---- reductions ------------------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

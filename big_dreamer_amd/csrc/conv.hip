@@ -2,7 +2,7 @@
 // ObservationModel src/models.py:319-362) as gather-GEMMs on the fp32 MFMA tile machinery of this library.
 //
 // Activations are NHWC fp32 images.  Every stride-2 layer of the two stacks, forward and backward, is one of two
-// gather patterns in front of the same contraction out[m][n] = sum_k A(m, k) W[n][k] (+ bias, ELU):
+// gather patterns in front of the same contraction out[m][n] = sum_k A(m, k) W[n][k] (+ bias, activation):
 //   F  rows = output pixels of a stride-2 VALID convolution; A(m, .) = the k x k x C window, read as k segments of
 //      k*C contiguous floats (NHWC makes (kx, ci) contiguous).  Conv2d forward; ConvTranspose2d dgrad.
 //   T  rows = one parity class (oy%2, ox%2) of the output pixels of a stride-2 transposed convolution (sub-pixel
@@ -29,7 +29,7 @@ struct ConvFrag {
 };
 
 // One segment: column block nb, row tiles rt0 .. rt0+RTC-1 of the LDS tile X[rt][Kb] (fragment order).
-// `pre(rt, nb)` returns the epilogue's per-element multipliers (BD_ACT_ELU_GRAD: ELU' from the saved output; 1 otherwise):
+// `pre(rt, nb)` returns the epilogue's per-element multipliers (BD_ACT_*_GRAD: f' from the saved output; 1 otherwise):
 // requested BEFORE the contraction, consumed after it.
 template <int RTC, class Epi, class Pre>
 __device__ __forceinline__ void conv_segment(const float* __restrict__ X, int Kb, const float* __restrict__ Wp,
@@ -72,7 +72,9 @@ __device__ __forceinline__ void conv_segment(const float* __restrict__ X, int Kb
     for (int r = 0; r < RTC; ++r) epi(rt0 + r, nb, acc[r] + acc2[r], mul[r]);
 }
 
-template <int RT>
+// Every conv kernel exists twice (ANY, as in mlp.hip): ANY = false serves BD_ACT_NONE / _ELU / _ELU_GRAD with ELU written into
+// the epilogue, the code of the default cnn_activation_function; ANY = true takes the ReLU / Tanh codes at run time.
+template <int RT, bool ANY>
 __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(bd_conv_args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Kb = cdiv(a.K, 16), Nb = cdiv(a.N, 16);
@@ -158,27 +160,35 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(bd_conv_args a) {
         }
         return col < a.N;
     };
-    auto pre = [&](int rt, int nb) {          // BD_ACT_ELU_GRAD: ELU'(saved output) of this lane's four elements
+    auto pre = [&](int rt, int nb) {          // BD_ACT_*_GRAD: f'(saved output) of this lane's four elements
         floatx4 m = floatx4{1.f, 1.f, 1.f, 1.f};
         int coff, need;
-        if (a.act != BD_ACT_ELU_GRAD || !outpos(nb, coff, need)) return m;
+        if (!(ANY ? act_is_grad(a.act) : a.act == BD_ACT_ELU_GRAD) || !outpos(nb, coff, need)) return m;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = rt * 16 + 4 * (lane >> 4) + r;
             const int off = rowoff[row];
-            if (off >= 0 && (rowflag[row] & need) == need) m[r] = elu_grad_from_out(a.aux[(size_t)off + coff]);
+            if (off >= 0 && (rowflag[row] & need) == need) {
+                if constexpr (ANY) m[r] = a.aux[(size_t)off + coff];
+                else m[r] = elu_grad_from_out(a.aux[(size_t)off + coff]);
+            }
         }
+        if constexpr (ANY) m = act_grad4(a.act, m);      // (elements left at 1 are never stored)
         return m;
     };
     auto epi = [&](int rt, int nb, floatx4 acc, floatx4 mul) {
         int coff, need;
         if (!outpos(nb, coff, need)) return;
+        floatx4 v;
+        if constexpr (ANY) v = act_epilogue4(a.act, acc, mul);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = rt * 16 + 4 * (lane >> 4) + r;
             const int off = rowoff[row];
-            if (off >= 0 && (rowflag[row] & need) == need)
-                a.out[(size_t)off + coff] = a.act == BD_ACT_ELU ? elu(acc[r]) : acc[r] * mul[r];
+            if (off >= 0 && (rowflag[row] & need) == need) {
+                if constexpr (ANY) a.out[(size_t)off + coff] = v[r];
+                else a.out[(size_t)off + coff] = a.act == BD_ACT_ELU ? elu(acc[r]) : acc[r] * mul[r];
+            }
         }
     };
     int u = u0;
@@ -256,15 +266,16 @@ __global__ __launch_bounds__(256) void conv_pack_fused_kernel(const float* __res
     }
 }
 
-// g <- g * ELU'(y) from the saved ELU outputs (in place): the pre-activation gradient of a conv layer
-__global__ __launch_bounds__(256) void elu_backward_kernel(float* __restrict__ g, const float* __restrict__ y, size_t n4) {
+// g <- g * f'(y) from the saved outputs of activation `act` (in place): the pre-activation gradient of a conv layer
+__global__ __launch_bounds__(256) void act_backward_kernel(float* __restrict__ g, const float* __restrict__ y, size_t n4,
+                                                           int act) {
     floatx4* __restrict__ g4 = reinterpret_cast<floatx4*>(g);
     const floatx4* __restrict__ y4 = reinterpret_cast<const floatx4*>(y);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         floatx4 gv = g4[i];
         const floatx4 yv = y4[i];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) gv[j] *= elu_grad_from_out(yv[j]);
+        for (int j = 0; j < 4; ++j) gv[j] *= act_grad_from_out(act, yv[j]);
         g4[i] = gv;
     }
 }
@@ -375,7 +386,7 @@ __device__ __forceinline__ void patch_segment(const float* __restrict__ Pt, cons
     for (int r = 0; r < RTC; ++r) epi(rt0 + r, nb, acc[r] + acc2[r], mul[r]);
 }
 
-template <int RT>
+template <int RT, bool ANY>
 __global__ __launch_bounds__(kThreads) void conv_patch_kernel(bd_conv_args a, int tiles_y, int tiles_x, int PH, int PW) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Kb = a.K >> 4, Nb = cdiv(a.N, 16);
@@ -435,27 +446,35 @@ __global__ __launch_bounds__(kThreads) void conv_patch_kernel(bd_conv_args a, in
         }
         return col < a.N;
     };
-    auto pre = [&](int rt, int nb) {          // BD_ACT_ELU_GRAD: ELU'(saved output) of this lane's four elements
+    auto pre = [&](int rt, int nb) {          // BD_ACT_*_GRAD: f'(saved output) of this lane's four elements
         floatx4 m = floatx4{1.f, 1.f, 1.f, 1.f};
         int coff, need;
-        if (a.act != BD_ACT_ELU_GRAD || !outpos(nb, coff, need)) return m;
+        if (!(ANY ? act_is_grad(a.act) : a.act == BD_ACT_ELU_GRAD) || !outpos(nb, coff, need)) return m;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = rt * 16 + 4 * (lane >> 4) + r;
             const int off = rowoff[row];
-            if (off >= 0 && (rowflag[row] & need) == need) m[r] = elu_grad_from_out(a.aux[(size_t)off + coff]);
+            if (off >= 0 && (rowflag[row] & need) == need) {
+                if constexpr (ANY) m[r] = a.aux[(size_t)off + coff];
+                else m[r] = elu_grad_from_out(a.aux[(size_t)off + coff]);
+            }
         }
+        if constexpr (ANY) m = act_grad4(a.act, m);      // (elements left at 1 are never stored)
         return m;
     };
     auto epi = [&](int rt, int nb, floatx4 acc, floatx4 mul) {
         int coff, need;
         if (!outpos(nb, coff, need)) return;
+        floatx4 v;
+        if constexpr (ANY) v = act_epilogue4(a.act, acc, mul);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = rt * 16 + 4 * (lane >> 4) + r;
             const int off = rowoff[row];
-            if (off >= 0 && (rowflag[row] & need) == need)
-                a.out[(size_t)off + coff] = a.act == BD_ACT_ELU ? elu(acc[r]) : acc[r] * mul[r];
+            if (off >= 0 && (rowflag[row] & need) == need) {
+                if constexpr (ANY) a.out[(size_t)off + coff] = v[r];
+                else a.out[(size_t)off + coff] = a.act == BD_ACT_ELU ? elu(acc[r]) : acc[r] * mul[r];
+            }
         }
     };
     int u = u0;
@@ -468,8 +487,8 @@ __global__ __launch_bounds__(kThreads) void conv_patch_kernel(bd_conv_args a, in
     }
 }
 
-template <int RT>
-static int launch_patch(const bd_conv_args& a, hipStream_t s) {
+template <int RT, bool ANY>
+static int launch_patch_any(const bd_conv_args& a, hipStream_t s) {
     const int span_y = a.ss < 0 ? a.nseg - 1 : a.nseg - a.sy;              // extra patch rows beyond RT*sy
     const int nseg_b = a.seglen / a.C;
     const int span_x = nseg_b - a.sx;
@@ -477,24 +496,36 @@ static int launch_patch(const bd_conv_args& a, hipStream_t s) {
     const int Kb = a.K >> 4;
     const size_t lds = ((size_t)PH * PW * (a.C + 4) + Kb + RT + 32 * RT) * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_conv_gemm(patch): needs %zu B of LDS", lds);
-    if (lds > 64 * 1024 && allow_big_lds(conv_patch_kernel<RT>)) return -1;
+    if (lds > 64 * 1024 && allow_big_lds(conv_patch_kernel<RT, ANY>)) return -1;
     const int tiles_y = cdiv(a.gh, RT), tiles_x = cdiv(a.gw, 16);
-    hipLaunchKernelGGL(conv_patch_kernel<RT>, dim3((unsigned)(a.imgs * tiles_y * tiles_x)), dim3(kThreads), lds, s, a, tiles_y,
+    hipLaunchKernelGGL((conv_patch_kernel<RT, ANY>), dim3((unsigned)(a.imgs * tiles_y * tiles_x)), dim3(kThreads), lds, s, a, tiles_y,
                        tiles_x, PH, PW);
     BD_CHECK_LAUNCH("bd_conv_gemm(patch)");
     return 0;
 }
 
+static bool act_is_default(int act) { return act == BD_ACT_NONE || act == BD_ACT_ELU || act == BD_ACT_ELU_GRAD; }
+
 template <int RT>
-static int launch_conv(const bd_conv_args& a, hipStream_t s) {
+static int launch_patch(const bd_conv_args& a, hipStream_t s) {
+    return act_is_default(a.act) ? launch_patch_any<RT, false>(a, s) : launch_patch_any<RT, true>(a, s);
+}
+
+template <int RT, bool ANY>
+static int launch_conv_any(const bd_conv_args& a, hipStream_t s) {
     const int Kb = cdiv(a.K, 16);
     const size_t lds = ((size_t)RT * Kb * kFragFloats + 32 * RT) * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_conv_gemm: K=%d needs %zu B of LDS at %d rows per workgroup", a.K, lds, 16 * RT);
-    if (lds > 64 * 1024 && allow_big_lds(conv_gemm_kernel<RT>)) return -1;
+    if (lds > 64 * 1024 && allow_big_lds(conv_gemm_kernel<RT, ANY>)) return -1;
     const long M = (long)a.imgs * a.gh * a.gw;
-    hipLaunchKernelGGL(conv_gemm_kernel<RT>, dim3((unsigned)cdiv((int)M, 16 * RT)), dim3(kThreads), lds, s, a);
+    hipLaunchKernelGGL((conv_gemm_kernel<RT, ANY>), dim3((unsigned)cdiv((int)M, 16 * RT)), dim3(kThreads), lds, s, a);
     BD_CHECK_LAUNCH("bd_conv_gemm");
     return 0;
+}
+
+template <int RT>
+static int launch_conv(const bd_conv_args& a, hipStream_t s) {
+    return act_is_default(a.act) ? launch_conv_any<RT, false>(a, s) : launch_conv_any<RT, true>(a, s);
 }
 
 
@@ -510,7 +541,7 @@ static int launch_conv(const bd_conv_args& a, hipStream_t s) {
 constexpr int kThinSteps = 27;            // K <= 108
 __host__ __device__ inline int thin_band_al(int k, int roww) { return (k * roww + 64 + 255) & ~255; }
 
-template <int KS>
+template <int KS, bool ANY>
 __global__ __launch_bounds__(kThreads) void conv_thin_f_kernel(const float* __restrict__ in, int imgs, int IH, int IW, int C,
                                                                int kk, const float* __restrict__ W, int ldw, int K,
                                                                const float* __restrict__ bias, int act,
@@ -559,6 +590,7 @@ __global__ __launch_bounds__(kThreads) void conv_thin_f_kernel(const float* __re
         }
     };
     const int nrt = cdiv(gw, 16);
+    const bool any_grad = act_is_grad(act);
     int it = wave, b = 0;
     if (it < items) issue(it, mine);
     for (; it < items; it += kWaves, b ^= 1) {
@@ -566,7 +598,7 @@ __global__ __launch_bounds__(kThreads) void conv_thin_f_kernel(const float* __re
         //  waits below also cover them -- a few hundred cycles per item that the other wave of the SIMD fills)
         const int img = img0 + it / gh, y = it - (it / gh) * gh;
         const size_t obase = ((size_t)img * gh + y) * gw * 32;
-        // BD_ACT_ELU_GRAD: the multipliers of this grid row, requested BEFORE the next band's DMA (vmcnt retires in order: a
+        // BD_ACT_*_GRAD: the multipliers of this grid row, requested BEFORE the next band's DMA (vmcnt retires in order: a
         // load issued after the DMA could only be waited for together with it)
         float mul0[2][4], mul1[2][4];
 #pragma unroll
@@ -575,9 +607,14 @@ __global__ __launch_bounds__(kThreads) void conv_thin_f_kernel(const float* __re
             for (int r = 0; r < 4; ++r) {
                 mul0[rt][r] = mul1[rt][r] = 1.f;
                 const int x = rt * 16 + 4 * kq + r;
-                if (act == BD_ACT_ELU_GRAD && x < gw) {
-                    mul0[rt][r] = elu_grad_from_out(aux[obase + x * 32 + n]);
-                    mul1[rt][r] = elu_grad_from_out(aux[obase + x * 32 + 16 + n]);
+                if ((ANY ? any_grad : act == BD_ACT_ELU_GRAD) && x < gw) {
+                    if constexpr (ANY) {
+                        mul0[rt][r] = act_grad_from_out(act, aux[obase + x * 32 + n]);
+                        mul1[rt][r] = act_grad_from_out(act, aux[obase + x * 32 + 16 + n]);
+                    } else {
+                        mul0[rt][r] = elu_grad_from_out(aux[obase + x * 32 + n]);
+                        mul1[rt][r] = elu_grad_from_out(aux[obase + x * 32 + 16 + n]);
+                    }
                 }
             }
         if (it + kWaves < items) {
@@ -599,12 +636,22 @@ __global__ __launch_bounds__(kThreads) void conv_thin_f_kernel(const float* __re
                 acc0 = mfma16(a, w0[s], acc0);
                 acc1 = mfma16(a, w1[s], acc1);
             }
+            floatx4 v0, v1;
+            if constexpr (ANY) {
+                v0 = act_epilogue4(act, acc0, floatx4{mul0[rt][0], mul0[rt][1], mul0[rt][2], mul0[rt][3]});
+                v1 = act_epilogue4(act, acc1, floatx4{mul1[rt][0], mul1[rt][1], mul1[rt][2], mul1[rt][3]});
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int x = rt * 16 + 4 * kq + r;
                 if (x < gw) {
-                    orow[x * 32 + n] = act == BD_ACT_ELU ? elu(acc0[r]) : acc0[r] * mul0[rt][r];
-                    orow[x * 32 + 16 + n] = act == BD_ACT_ELU ? elu(acc1[r]) : acc1[r] * mul1[rt][r];
+                    if constexpr (ANY) {
+                        orow[x * 32 + n] = v0[r];
+                        orow[x * 32 + 16 + n] = v1[r];
+                    } else {
+                        orow[x * 32 + n] = act == BD_ACT_ELU ? elu(acc0[r]) : acc0[r] * mul0[rt][r];
+                        orow[x * 32 + 16 + n] = act == BD_ACT_ELU ? elu(acc1[r]) : acc1[r] * mul1[rt][r];
+                    }
                 }
             }
         }
@@ -625,7 +672,9 @@ int bd_conv_gemm(const bd_conv_args* a, void* stream) {
     BD_REQUIRE((long)a->imgs * a->gh * a->gw < (1L << 31) && (long)a->imgs * a->OH * a->OW * a->ldo < (1L << 31),
                "bd_conv_gemm: image batch too large for 32-bit element offsets");
     BD_REQUIRE(!a->mask || (a->vec4 && (1 << a->cshift) == a->C), "bd_conv_gemm: masked gathers need C a power of two >= 4");
-    BD_REQUIRE(a->act != BD_ACT_ELU_GRAD || a->aux, "bd_conv_gemm: BD_ACT_ELU_GRAD needs the saved outputs (aux)");
+    BD_REQUIRE(a->act == BD_ACT_NONE || act_is_forward(a->act) || act_is_grad(a->act), "bd_conv_gemm: unknown activation code %d",
+               a->act);
+    BD_REQUIRE(!act_is_grad(a->act) || a->aux, "bd_conv_gemm: a BD_ACT_*_GRAD code needs the saved outputs (aux)");
     BD_REQUIRE(a->fuse_cq == 0 || (a->mask && a->N == 4 * a->fuse_cq && a->osy == 2 && a->osx == 2 && a->oy0 == 0 && a->ox0 == 0),
                "bd_conv_gemm: fused classes need pattern T with N = 4*fuse_cq");
     BD_REQUIRE(!a->vec4 || (a->C % 4 == 0 && a->seglen % 4 == 0), "bd_conv_gemm: vec4 gathers need C, seglen multiples of 4");
@@ -681,14 +730,17 @@ int bd_conv_pack_fused(const float* src, float* dst, int Couter, int Cinner, int
     return 0;
 }
 
-int bd_elu_backward(float* g, const float* y, size_t n, void* stream) {
-    BD_REQUIRE(g && y && n > 0 && (n & 3) == 0, "bd_elu_backward: bad arguments (n must be a multiple of 4)");
+int bd_act_backward(float* g, const float* y, size_t n, int act, void* stream) {
+    BD_REQUIRE(g && y && n > 0 && (n & 3) == 0, "bd_act_backward: bad arguments (n must be a multiple of 4)");
+    BD_REQUIRE(act_is_forward(act) || act_is_grad(act), "bd_act_backward: unknown activation code %d", act);
     const size_t n4 = n >> 2;
     const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    hipLaunchKernelGGL(elu_backward_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, y, n4);
-    BD_CHECK_LAUNCH("bd_elu_backward");
+    hipLaunchKernelGGL(act_backward_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, y, n4, act);
+    BD_CHECK_LAUNCH("bd_act_backward");
     return 0;
 }
+
+int bd_elu_backward(float* g, const float* y, size_t n, void* stream) { return bd_act_backward(g, y, n, BD_ACT_ELU, stream); }
 
 size_t bd_colsum_ws_floats(int N) { return (size_t)bd::kColsumBlocks * (size_t)N; }
 
@@ -718,7 +770,8 @@ int bd_conv_thin_forward(const float* in, int imgs, int IH, int IW, int C, int k
     using namespace bd;
     BD_REQUIRE(in && W && out && imgs > 0 && IH > 0 && IW > 0 && C >= 1 && C <= 4 && k >= 2 && IH >= k && IW >= k,
                "bd_conv_thin_forward: bad arguments");
-    BD_REQUIRE(act != BD_ACT_ELU_GRAD || aux, "bd_conv_thin_forward: BD_ACT_ELU_GRAD needs the saved outputs (aux)");
+    BD_REQUIRE(act == BD_ACT_NONE || act_is_forward(act) || act_is_grad(act), "bd_conv_thin_forward: unknown activation code %d", act);
+    BD_REQUIRE(!act_is_grad(act) || aux, "bd_conv_thin_forward: a BD_ACT_*_GRAD code needs the saved outputs (aux)");
     const int K = k * k * C, gh = (IH - k) / 2 + 1, gw = (IW - k) / 2 + 1, roww = IW * C;
     BD_REQUIRE(K <= 4 * kThinSteps && ldw >= K && gw <= 32, "bd_conv_thin_forward: K = %d (<= %d), output width %d (<= 32)", K,
                4 * kThinSteps, gw);
@@ -728,14 +781,17 @@ int bd_conv_thin_forward(const float* in, int imgs, int IH, int IW, int C, int k
     const int ipw = cdiv(imgs, 512);                      // two workgroups per CU (<= 80 KB of LDS each)
     const int grid = cdiv(imgs, ipw);
     hipStream_t s = (hipStream_t)stream;
+    auto launch = [&](auto kernel) {
+        if (lds > 64 * 1024 && allow_big_lds(kernel)) return -1;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, s, in, imgs, IH, IW, C, k, W, ldw, K, bias, act, aux, out, gh, gw,
+                           ipw);
+        return 0;
+    };
+    const bool any = !act_is_default(act);
     if (K <= 48) {
-        if (lds > 64 * 1024 && allow_big_lds(conv_thin_f_kernel<12>)) return -1;
-        hipLaunchKernelGGL(conv_thin_f_kernel<12>, dim3(grid), dim3(kThreads), lds, s, in, imgs, IH, IW, C, k, W, ldw, K, bias, act, aux,
-                           out, gh, gw, ipw);
+        if (any ? launch(conv_thin_f_kernel<12, true>) : launch(conv_thin_f_kernel<12, false>)) return -1;
     } else {
-        if (lds > 64 * 1024 && allow_big_lds(conv_thin_f_kernel<kThinSteps>)) return -1;
-        hipLaunchKernelGGL(conv_thin_f_kernel<kThinSteps>, dim3(grid), dim3(kThreads), lds, s, in, imgs, IH, IW, C, k, W, ldw, K, bias,
-                           act, aux, out, gh, gw, ipw);
+        if (any ? launch(conv_thin_f_kernel<kThinSteps, true>) : launch(conv_thin_f_kernel<kThinSteps, false>)) return -1;
     }
     BD_CHECK_LAUNCH("bd_conv_thin_forward");
     return 0;

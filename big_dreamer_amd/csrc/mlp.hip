@@ -7,8 +7,28 @@
 
 namespace bd {
 
+// Every kernel below exists twice.  ANY = false serves chains whose layers are all BD_ACT_NONE / BD_ACT_ELU -- every chain of
+// the state path -- with ELU written into the epilogue, the code these kernels had when ELU was the only activation.
+// ANY = true takes the other forward codes (the pixel decoder's 1x1 -> 5x5 layer under cnn_activation_function) through
+// the runtime helpers of bd_device.h.
+template <bool ANY>
+__device__ __forceinline__ floatx4 chain_act4(int act, floatx4 x) {
+    if constexpr (ANY) return act_apply4(act, x);
+    floatx4 v = x;
+    if (act) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = elu(x[r]);
+    }
+    return v;
+}
+template <bool ANY>
+__device__ __forceinline__ float chain_grad(int act, float y) {
+    if constexpr (ANY) return act_grad_from_out(act, y);
+    return elu_grad_from_out(y);
+}
+
 // ---- forward --------------------------------------------------------------------------------------
-template <int RT>
+template <int RT, bool ANY>
 __global__ __launch_bounds__(kThreads) void mlp_fwd_kernel(bd_mlp_fwd_args a, int KbA, int KbB) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int row0 = blockIdx.x * 16 * RT;
@@ -55,11 +75,7 @@ __global__ __launch_bounds__(kThreads) void mlp_fwd_kernel(bd_mlp_fwd_args a, in
             const int ln = bd_tid() & 63, m = ln & 15, col0 = nb * 16 + 4 * (ln >> 4);
             const int grow = row0 + rt * 16 + m;
             if (gather0 && col0 < L.N) acc += *reinterpret_cast<const floatx4*>(xs + (rt * 16 + m) * L.N + col0);   // N0 % 4 == 0
-            floatx4 v = acc;
-            if (L.act) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = elu(acc[r]);
-            }
+            const floatx4 v = chain_act4<ANY>(L.act, acc);
             if (!last) *reinterpret_cast<floatx4*>(nxt + ((rt * Nb + nb) * 64 + ln) * 4) = v;
             if (grow < a.M && col0 < L.N) {
                 if (vec) {
@@ -81,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void mlp_fwd_kernel(bd_mlp_fwd_args a, in
 }
 
 // ---- backward (dgrad chain) -------------------------------------------------------------------------
-template <int RT>
+template <int RT, bool ANY>
 __global__ __launch_bounds__(kThreads) void mlp_bwd_kernel(bd_mlp_bwd_args a, int KbA, int KbB) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int row0 = blockIdx.x * 16 * RT;
@@ -98,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_kernel(bd_mlp_bwd_args a, in
             float v = 0.f;
             if (grow < a.M && k < L.N) {
                 v = a.dout[(size_t)grow * a.lddo + k] * a.dout_scale;
-                if (L.act) v *= elu_grad_from_out(L.saved[(size_t)grow * L.N + k]);
+                if (L.act) v *= chain_grad<ANY>(L.act, L.saved[(size_t)grow * L.N + k]);
                 if (L.dpre) L.dpre[(size_t)grow * L.N + k] = v;
             }
             cur[(r >> 4) * Kb * kFragFloats + frag_idx(r & 15, k)] = v;
@@ -136,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_kernel(bd_mlp_bwd_args a, in
                 if (grow < a.M && col0 < P.N) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (col0 + r < P.N) v[r] = P.act ? acc[r] * elu_grad_from_out(p.v[r]) : acc[r];
+                        if (col0 + r < P.N) v[r] = P.act ? acc[r] * chain_grad<ANY>(P.act, p.v[r]) : acc[r];
                     if (P.dpre) {
                         if (vec) *reinterpret_cast<floatx4*>(P.dpre + (size_t)grow * P.N + col0) = v;
                         else {
@@ -185,13 +201,13 @@ __device__ unsigned long long g_tallstamps[64];
 // For chains over tens of thousands of rows (the reward / value heads over every imagined transition).  Per layer:
 // sweep (accumulators stay in registers) -> barrier -> epilogue overwrites the image -> barrier.
 // The sweeps run in the transposed-accumulator form (bd_device.h, linear_sweep<TR>): a lane holds four consecutive
-// columns of one row, so a pair's epilogue is 4 x ELU, one ds_write_b128 into the (in-place) fragment image and one
+// columns of one row, so a pair's epilogue is 4 x the activation, one ds_write_b128 into the (in-place) fragment image and one
 // 16-byte global store, under one row/column predicate per lane.  With the row-per-register accumulator layout the same
 // epilogue was 4 conflicting ds_write_b32 + 4 dword stores + per-value predicates: 10k cycles per 200-wide layer and wave
 // against 20k for its sweep (s_memtime stamps, tools/tall_stamps.py) -- and on gfx950 a wave's VALU / memory instructions
 // do NOT overlap the fp32 MFMAs of the other waves of its SIMD (tools/probes/issue_probe.hip), so every epilogue cycle is
 // a matrix-pipe cycle lost.  Element offsets are 32-bit (host-checked), widths are multiples of 4 floats.
-template <int RT>
+template <int RT, bool ANY>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))) void mlp_fwd_tall_kernel(bd_mlp_fwd_args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int row0 = blockIdx.x * 16 * RT;
@@ -247,12 +263,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
         }
         tall_foreach<RT>(L.N, t, [&](int rt, int nb, floatx4 acc) {
             if (gather0 && nb * 16 + 4 * g < L.N) acc += *reinterpret_cast<const floatx4*>(img + ((rt * Nb + nb) * 64 + lane) * 4);
-            floatx4 v = acc;
-            if (L.act) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = elu(acc[r]);
-            }
-            if (!last) {      // (columns >= N of the last block are ELU(0 + 0) = 0: bias and packed weights are zero there)
+            const floatx4 v = chain_act4<ANY>(L.act, acc);
+            if (!last) {      // (columns >= N of the last block are f(0 + 0) = 0: bias and packed weights are zero there)
                 *reinterpret_cast<floatx4*>(img + ((rt * Nb + nb) * 64 + lane) * 4) = v;
                 if (L.save && row0 + rt * 16 + m < a.M && nb * 16 + 4 * g < L.N)
                     *reinterpret_cast<floatx4*>(L.save + (g_lane + (unsigned)(rt * 16) * N + (unsigned)(nb * 16))) = v;
@@ -273,7 +285,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
     }
 }
 
-template <int RT>
+template <int RT, bool ANY>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))) void mlp_bwd_tall_kernel(bd_mlp_bwd_args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int row0 = blockIdx.x * 16 * RT;
@@ -287,7 +299,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
             float v = 0.f;
             if (grow < a.M && k < L.N) {
                 v = a.dout[(size_t)grow * a.lddo + k] * a.dout_scale;
-                if (L.act) v *= elu_grad_from_out(L.saved[(size_t)grow * L.N + k]);
+                if (L.act) v *= chain_grad<ANY>(L.act, L.saved[(size_t)grow * L.N + k]);
                 if (L.dpre) L.dpre[(size_t)grow * L.N + k] = v;
             }
             img[(r >> 4) * Kb * kFragFloats + frag_idx(r & 15, k)] = v;
@@ -317,8 +329,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
             const bool in = row0 + rt * 16 + m < a.M && nb * 16 + 4 * g < P.N;
             floatx4 v = floatx4{0.f, 0.f, 0.f, 0.f};
             if (in) {
+                if constexpr (ANY) {
+                    v = acc * act_grad4(P.act, p);          // (BD_ACT_NONE: times 1)
+                } else {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = P.act ? acc[r] * elu_grad_from_out(p[r]) : acc[r];
+                    for (int r = 0; r < 4; ++r) v[r] = P.act ? acc[r] * elu_grad_from_out(p[r]) : acc[r];
+                }
                 if (P.dpre) *reinterpret_cast<floatx4*>(P.dpre + (g_lane + (unsigned)(rt * 16) * N + (unsigned)(nb * 16))) = v;
             }
             *reinterpret_cast<floatx4*>(img + ((rt * Nb + nb) * 64 + lane) * 4) = v;
@@ -421,9 +437,12 @@ int bd_mlp_forward(const bd_mlp_fwd_args* a, void* stream) {
     BD_REQUIRE(a->w1 == 0 || (a->in1 && a->ld1 >= a->w1), "bd_mlp_forward: bad input 1");
     BD_REQUIRE(a->out && a->ldo >= a->layer[a->n_layers - 1].N, "bd_mlp_forward: bad output");
     int KbA = 0, KbB = 0, k = a->w0 + a->w1;
+    bool any = false;              // a layer with an activation other than ELU: the ANY = true kernels
     for (int l = 0; l < a->n_layers; ++l) {
         const bd_layer& L = a->layer[l];
+        any = any || (L.act != BD_ACT_NONE && L.act != BD_ACT_ELU);
         BD_REQUIRE(L.w && L.N > 0 && L.K == k, "bd_mlp_forward: layer %d has K=%d, expected %d", l, L.K, k);
+        BD_REQUIRE(L.act == BD_ACT_NONE || act_is_forward(L.act), "bd_mlp_forward: layer %d has unknown activation code %d", l, L.act);
         int& kb = (l & 1) ? KbB : KbA;
         kb = cdiv(L.K, 16) > kb ? cdiv(L.K, 16) : kb;
         k = L.N;
@@ -442,14 +461,21 @@ int bd_mlp_forward(const bd_mlp_fwd_args* a, void* stream) {
             widest = (size_t)L.N > widest ? (size_t)L.N : widest;
         }
         ok = ok && (size_t)a->M * widest < ((size_t)1 << 31);
-        if (ok) return launch_tall(mlp_fwd_tall_kernel<kTallRT>, "bd_mlp_forward(tall)", a->M, KbA > KbB ? KbA : KbB,
+        if (ok && any) return launch_tall(mlp_fwd_tall_kernel<kTallRT, true>, "bd_mlp_forward(tall)", a->M, KbA > KbB ? KbA : KbB,
+                                          (hipStream_t)stream, *a);
+        if (ok) return launch_tall(mlp_fwd_tall_kernel<kTallRT, false>, "bd_mlp_forward(tall)", a->M, KbA > KbB ? KbA : KbB,
                                    (hipStream_t)stream, *a);
     }
     const size_t xs = a->gD > 0 ? (size_t)16 * a->layer[0].N : 0;
     const int rt = pick_rt(a->M, KbA, KbB, xs);
+    if (any) {
+        if (rt == 2)
+            return launch_chain(mlp_fwd_kernel<2, true>, "bd_mlp_forward", a->M, 2, KbA, KbB, (hipStream_t)stream, *a, 2 * xs);
+        return launch_chain(mlp_fwd_kernel<1, true>, "bd_mlp_forward", a->M, 1, KbA, KbB, (hipStream_t)stream, *a, xs);
+    }
     if (rt == 2)
-        return launch_chain(mlp_fwd_kernel<2>, "bd_mlp_forward", a->M, 2, KbA, KbB, (hipStream_t)stream, *a, 2 * xs);
-    return launch_chain(mlp_fwd_kernel<1>, "bd_mlp_forward", a->M, 1, KbA, KbB, (hipStream_t)stream, *a, xs);
+        return launch_chain(mlp_fwd_kernel<2, false>, "bd_mlp_forward", a->M, 2, KbA, KbB, (hipStream_t)stream, *a, 2 * xs);
+    return launch_chain(mlp_fwd_kernel<1, false>, "bd_mlp_forward", a->M, 1, KbA, KbB, (hipStream_t)stream, *a, xs);
 }
 
 int bd_mlp_backward(const bd_mlp_bwd_args* a, void* stream) {
@@ -459,9 +485,12 @@ int bd_mlp_backward(const bd_mlp_bwd_args* a, void* stream) {
     const bool want_din = a->din0 || a->din1;
     // buffer A holds d(out) of layers L-1, L-3, ...; buffer B the others
     int KbA = 0, KbB = 0;
+    bool any = false;              // as in bd_mlp_forward
     for (int l = a->n_layers - 1, j = 0; l >= 0; --l, ++j) {
         const bd_layer_bwd& L = a->layer[l];
+        any = any || (L.act != BD_ACT_NONE && L.act != BD_ACT_ELU);
         BD_REQUIRE(L.N > 0 && L.K > 0, "bd_mlp_backward: layer %d has bad dims", l);
+        BD_REQUIRE(L.act == BD_ACT_NONE || act_is_forward(L.act), "bd_mlp_backward: layer %d has unknown activation code %d", l, L.act);
         BD_REQUIRE(!L.act || L.saved, "bd_mlp_backward: layer %d needs its saved output", l);
         BD_REQUIRE(l == 0 ? (!want_din || L.wt) : (L.wt != nullptr), "bd_mlp_backward: layer %d needs packed W^T", l);
         BD_REQUIRE(l == 0 || a->layer[l - 1].N == L.K, "bd_mlp_backward: layer %d K mismatch", l);
@@ -481,11 +510,16 @@ int bd_mlp_backward(const bd_mlp_bwd_args* a, void* stream) {
         ok = ok && (size_t)a->M * widest < ((size_t)1 << 31);
         int kb = KbA > KbB ? KbA : KbB;
         if (want_din) kb = cdiv(a->layer[0].N, 16) > kb ? cdiv(a->layer[0].N, 16) : kb;
-        if (ok) return launch_tall(mlp_bwd_tall_kernel<kTallRT>, "bd_mlp_backward(tall)", a->M, kb, (hipStream_t)stream, *a);
+        if (ok && any) return launch_tall(mlp_bwd_tall_kernel<kTallRT, true>, "bd_mlp_backward(tall)", a->M, kb, (hipStream_t)stream, *a);
+        if (ok) return launch_tall(mlp_bwd_tall_kernel<kTallRT, false>, "bd_mlp_backward(tall)", a->M, kb, (hipStream_t)stream, *a);
     }
     const int rt = pick_rt(a->M, KbA, KbB);
-    if (rt == 2) return launch_chain(mlp_bwd_kernel<2>, "bd_mlp_backward", a->M, 2, KbA, KbB, (hipStream_t)stream, *a);
-    return launch_chain(mlp_bwd_kernel<1>, "bd_mlp_backward", a->M, 1, KbA, KbB, (hipStream_t)stream, *a);
+    if (any) {
+        if (rt == 2) return launch_chain(mlp_bwd_kernel<2, true>, "bd_mlp_backward", a->M, 2, KbA, KbB, (hipStream_t)stream, *a);
+        return launch_chain(mlp_bwd_kernel<1, true>, "bd_mlp_backward", a->M, 1, KbA, KbB, (hipStream_t)stream, *a);
+    }
+    if (rt == 2) return launch_chain(mlp_bwd_kernel<2, false>, "bd_mlp_backward", a->M, 2, KbA, KbB, (hipStream_t)stream, *a);
+    return launch_chain(mlp_bwd_kernel<1, false>, "bd_mlp_backward", a->M, 1, KbA, KbB, (hipStream_t)stream, *a);
 }
 
 }  // extern "C"

@@ -14,7 +14,8 @@ import torch
 from torch import Tensor
 
 from . import _cabi as cabi
-from .engine import DreamerEngine, check_action_distribution, check_gradient_mixing
+from .engine import (DreamerEngine, check_action_distribution, check_cnn_activation, check_dense_activation,
+                     check_gradient_mixing)
 from .memory import ExperienceReplay
 from .models import ActorModel, CnnImageEncoder, DenseModel, ObservationModel, TransitionModel, encoder_for
 from .synth import Dims
@@ -43,6 +44,10 @@ class Dreamer:
         # -1: the reference's dynamics-backprop actor gradient; rho in [0, 1]: DreamerV2's REINFORCE / dynamics mix
         # (the reference raises for anything but -1, src/dreamer.py:336-339)
         check_gradient_mixing(params["ActorCritic"].get("gradient_mixing", -1))
+        # the pixel conv stacks take ELU / ReLU / Tanh (no effect on state observations, as in the reference); the dense
+        # chains and scans are ELU only, and say so instead of ignoring the key
+        self.cnn_activation_function = check_cnn_activation(params.get("cnn_activation_function", "ELU"))
+        check_dense_activation(params.get("dense_activation_function", "ELU"))
         self.action_distribution = check_action_distribution(params.get("action_distribution", "Gaussian"))
         if self.action_distribution == "Categorical" and params.get("algorithm") == "planet":
             raise ValueError("action_distribution=Categorical: PlaNet's CEM planner searches a continuous action space")
@@ -70,7 +75,8 @@ class Dreamer:
         self.dims = Dims(B=self.batch_size, L=self.seq_len, H=self.planning_horizon, Be=self.belief_size,
                          S=self.state_size, Hd=self.hidden_size, E=self.embedding_size, A=self.action_size,
                          O=obs_size, pixel=self.pixel_observation, cat_D=cat_D, cat_C=cat_C,
-                         use_discount=self.use_discount, discrete_actions=self.action_distribution == "Categorical")
+                         use_discount=self.use_discount, discrete_actions=self.action_distribution == "Categorical",
+                         cnn_act=self.cnn_activation_function)
         self.engine = DreamerEngine(self.dims, _hp_from_params(params), self.device, world_size=world_size,
                                     process_group=process_group)
         e = self.engine
@@ -99,8 +105,9 @@ class Dreamer:
                                                 discrete_latent_dimensions=cat_D or 32, discrete_latent_classes=cat_C or 32,
                                                 engine=e)
         if px:
-            self.observation_model = ObservationModel(self.belief_size, self.state_size, E, engine=e)
-            self.encoder = CnnImageEncoder(E, engine=e)
+            self.observation_model = ObservationModel(self.belief_size, self.state_size, E,
+                                                      activation=self.cnn_activation_function, engine=e)
+            self.encoder = CnnImageEncoder(E, activation=self.cnn_activation_function, engine=e)
         else:
             self.observation_model = DenseModel(feat, self.hidden_size, env.observation_size, engine=e,
                                                 module="observation_model", prefix="obs")

@@ -25,7 +25,7 @@ import torch
 from . import _cabi as cabi
 from .parallel import DataParallel
 from .params import ParamGroup, _adam_state_dict, _load_adam_state_dict
-from .synth import DENSE_LAYERS, MODEL_MODULES, Dims, model_modules, param_shapes
+from .synth import CNN_ACTIVATIONS, DENSE_LAYERS, MODEL_MODULES, Dims, model_modules, param_shapes
 
 lib = cabi.lib
 ptr = cabi.ptr
@@ -59,6 +59,21 @@ def check_gradient_mixing(value) -> float:
     if not (rho == -1 or 0.0 <= rho <= 1.0):
         raise ValueError(f"gradient_mixing must be -1 or a number in [0, 1], got {value!r}")
     return rho
+
+
+def check_cnn_activation(value) -> str:
+    """cnn_activation_function: the activation of CnnImageEncoder / ObservationModel, a torch.nn class name as in the
+    reference (src/planet.py:186-192): "ELU" (default), "ReLU" or "Tanh" (epilogue codes of csrc/conv.hip)."""
+    if value not in CNN_ACTIVATIONS:
+        raise ValueError(f"cnn_activation_function must be one of {CNN_ACTIVATIONS}, got {value!r}")
+    return value
+
+
+def check_dense_activation(value) -> str:
+    """dense_activation_function: ELU is written into the epilogues of the scan, head and planner kernels."""
+    if value != "ELU":
+        raise NotImplementedError("the HIP path implements the reference default activation (ELU)")
+    return value
 
 
 ACTION_DISTRIBUTIONS = ("Gaussian", "Categorical")

@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from .engine import DreamerEngine
+from .engine import DreamerEngine, check_cnn_activation
 from .synth import DENSE_LAYERS
 
 
@@ -222,15 +222,25 @@ class ActorModel(_EngineBacked):
         return mean.view(*lead, -1), std.view(*lead, -1)
 
 
+def _cnn_act_module(activation: str, engine: DreamerEngine):
+    """The torch.nn class of `activation` (src/models.py resolves it with getattr(nn, name)); the kernels apply the engine's
+    ``Dims.cnn_act``, so the two must agree."""
+    check_cnn_activation(activation)
+    assert activation == engine.d.cnn_act, (f"activation={activation!r}, but the engine was built with "
+                                            f"cnn_act={engine.d.cnn_act!r}")
+    return getattr(nn, activation)
+
+
 class CnnImageEncoder(_EngineBacked):
-    """src/models.py:527-564: 4 x (Conv2d k4 s2 + ELU), Flatten, Identity | Linear(1024, E) -- ``model.{0,2,4,6[,9]}``.
-    The convolutions run on this library's gather-GEMM kernels (csrc/conv.hip through conv_stack.ConvStacks)."""
+    """src/models.py:527-564: 4 x (Conv2d k4 s2 + activation), Flatten, Identity | Linear(1024, E) --
+    ``model.{0,2,4,6[,9]}``.  The convolutions run on this library's gather-GEMM kernels (csrc/conv.hip through
+    conv_stack.ConvStacks), whose activation is the engine's ``Dims.cnn_act``: `activation` must name the same one."""
 
     def __init__(self, embedding_size: int, activation: str = "ELU", *, engine: DreamerEngine):
         super().__init__()
-        assert activation == "ELU"
-        self.model = nn.Sequential(nn.Conv2d(3, 32, 4, 2), nn.ELU(), nn.Conv2d(32, 64, 4, 2), nn.ELU(),
-                                   nn.Conv2d(64, 128, 4, 2), nn.ELU(), nn.Conv2d(128, 256, 4, 2), nn.ELU(), nn.Flatten(),
+        act = _cnn_act_module(activation, engine)
+        self.model = nn.Sequential(nn.Conv2d(3, 32, 4, 2), act(), nn.Conv2d(32, 64, 4, 2), act(),
+                                   nn.Conv2d(64, 128, 4, 2), act(), nn.Conv2d(128, 256, 4, 2), act(), nn.Flatten(),
                                    nn.Identity() if embedding_size == 1024 else nn.Linear(1024, embedding_size))
         self._bind(engine, "encoder", "model")
 
@@ -248,11 +258,11 @@ class ObservationModel(_EngineBacked):
     def __init__(self, belief_size: int, state_size: int, embedding_size: int, activation: str = "ELU", *,
                  engine: DreamerEngine):
         super().__init__()
-        assert activation == "ELU"
+        act = _cnn_act_module(activation, engine)
         self.output_shape = (3, 64, 64)
         self.decoder = nn.Sequential(nn.Linear(belief_size + state_size, embedding_size), nn.Identity(),
-                                     nn.ConvTranspose2d(embedding_size, 128, 5, 2), nn.ELU(),
-                                     nn.ConvTranspose2d(128, 64, 5, 2), nn.ELU(), nn.ConvTranspose2d(64, 32, 6, 2), nn.ELU(),
+                                     nn.ConvTranspose2d(embedding_size, 128, 5, 2), act(),
+                                     nn.ConvTranspose2d(128, 64, 5, 2), act(), nn.ConvTranspose2d(64, 32, 6, 2), act(),
                                      nn.ConvTranspose2d(32, 3, 6, 2))
         self._bind(engine, "observation_model", "model")
 

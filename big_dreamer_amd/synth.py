@@ -17,6 +17,9 @@ from typing import Dict, List, Tuple
 import numpy as np
 
 
+CNN_ACTIVATIONS = ("ELU", "ReLU", "Tanh")     # torch.nn class names, as the reference resolves them (getattr(nn, name))
+
+
 @dataclasses.dataclass(frozen=True)
 class Dims:
     """Problem dimensions (names as in SURVEY.md section 8)."""
@@ -36,8 +39,11 @@ class Dims:
     cat_C: int = 0        #                                    discrete_latent_classes; S must equal cat_D * cat_C (src/planet.py:56-57)
     use_discount: bool = False   # discount_model head + Bernoulli loss + discounted actor objective (src/dreamer.py:80-86,239-251,346-351)
     discrete_actions: bool = False   # action_distribution="Categorical": one-hot actions over A classes ("Discrete actions")
+    cnn_act: str = "ELU"  # cnn_activation_function: activation of the pixel conv stacks, "ELU" | "ReLU" | "Tanh" (src/planet.py:186-192)
 
     def __post_init__(self):
+        if self.cnn_act not in CNN_ACTIVATIONS:
+            raise ValueError(f"cnn_activation_function must be one of {CNN_ACTIVATIONS}, got {self.cnn_act!r}")
         assert (self.cat_D == 0) == (self.cat_C == 0) and (self.cat_D == 0 or self.S == self.cat_D * self.cat_C), \
             "Categorical latents: state_size = discrete_latent_dimensions * discrete_latent_classes"
 

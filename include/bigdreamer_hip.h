@@ -37,6 +37,14 @@ extern "C" {
 #define BD_ACT_ELU 1
 #define BD_ACT_ELU_GRAD 2   /* conv entry points only: out = value * ELU'(aux), aux = the SAVED ELU output at the same
                             * index as out (the dgrad of a layer and the ELU backward of the layer below in one pass) */
+/* cnn_activation_function of the pixel stacks: the conv entry points, bd_act_backward and the dense chains (bd_layer.act /
+ * bd_layer_bwd.act, forward codes only) take these too; the scans, heads and planners are ELU throughout.  A _GRAD code is
+ * its forward code + 1 and takes f' from the saved OUTPUT y:  ELU' = y > 0 ? 1 : y + 1,  ReLU' = y > 0 ? 1 : 0,
+ * Tanh' = 1 - y^2.  Any other value is rejected by every entry point. */
+#define BD_ACT_RELU 3
+#define BD_ACT_RELU_GRAD 4
+#define BD_ACT_TANH 5
+#define BD_ACT_TANH_GRAD 6
 
 const char* bd_last_error(void);
 int bd_version(void);
@@ -161,7 +169,7 @@ typedef struct {
     int fuse_cq;          /* pattern T with its four parity classes fused: N = 4*fuse_cq columns, column n = cls*fuse_cq
                            * + c goes to pixel (2y + (cls>>1), 2x + (cls&1)), channel c (osy = osx = 2, oy0 = ox0 = 0;
                            * gh x gw = the class-(0,0) grid; bias indexed by c); 0 = one class per call                */
-    const float* aux;     /* BD_ACT_ELU_GRAD: saved outputs, same layout as `out`; else unused                         */
+    const float* aux;     /* BD_ACT_*_GRAD: saved outputs, same layout as `out`; else unused                           */
 } bd_conv_args;
 int bd_conv_gemm(const bd_conv_args* a, void* stream);
 /* Stride-2 VALID convolution of a THIN image (C <= 4 channels) into 32 channels, NHWC: out (imgs, OH, OW, 32) =
@@ -169,14 +177,17 @@ int bd_conv_gemm(const bd_conv_args* a, void* stream);
  * as it lies in the buffer; bias may be NULL).  Conv2d(3 -> 32, k4) forward (src/models.py:538) and the dgrad of
  * ConvTranspose2d(32 -> 3, k6) (src/models.py:347).  k*k*C <= 108, OW <= 32. */
 int bd_conv_thin_forward(const float* in, int imgs, int IH, int IW, int C, int k, const float* W, int ldw, const float* bias,
-                         int act, const float* aux, float* out, void* stream);   /* aux: BD_ACT_ELU_GRAD only (else NULL) */
+                         int act, const float* aux, float* out, void* stream);   /* aux: BD_ACT_*_GRAD only (else NULL) */
 /* dst (packed) [n = inner][k = (a, b', outer)] = src[outer][py+2a][px+2(Tb-1-b')][inner], src stored (outer, ky, kx, inner) */
 int bd_conv_pack_class(const float* src, float* dst, int Couter, int Cinner, int ksz, int py, int px, int Ta, int Tb,
                        void* stream);
 /* all four parity classes at once (bd_conv_args.fuse_cq): dst [n = cls*Cinner + c][k = (a, b', outer)], T x T taps with
  * T = (ksz+1)/2, zero where the tap falls outside the kernel (odd ksz, parity 1) */
 int bd_conv_pack_fused(const float* src, float* dst, int Couter, int Cinner, int ksz, void* stream);
-/* g *= ELU'(y) in place from saved ELU outputs (n a multiple of 4) */
+/* g *= f'(y) in place from the saved outputs y of activation `act` (a forward code BD_ACT_ELU / _RELU / _TANH or its
+ * _GRAD code; n a multiple of 4): the standalone form of the _GRAD epilogues */
+int bd_act_backward(float* g, const float* y, size_t n, int act, void* stream);
+/* bd_act_backward(g, y, n, BD_ACT_ELU, stream) */
 int bd_elu_backward(float* g, const float* y, size_t n, void* stream);
 /* out[n] = sum_m rows[m][n] of an [M x N] row-major matrix, N <= 256 (bias gradient of a transposed-conv layer);
  * ws: bd_colsum_ws_floats(N) floats; fixed summation order */
