@@ -913,7 +913,10 @@ static size_t cat_grid(K kernel, int tiles, size_t lds, int* grid) {
         return 0;
     }
     const size_t room = (size_t)kMaxLds > at.sharedSizeBytes ? (size_t)kMaxLds - at.sharedSizeBytes : 0;
-    return room > lds ? room : lds;
+    // the whole-CU request is above 64 KiB whatever the shape needs: a narrow model (lds <= 64 KiB) has not opted in above
+    const size_t want = room > lds ? room : lds;
+    if (want > 64 * 1024 && lds <= 64 * 1024 && allow_big_lds(kernel)) return 0;
+    return want;
 }
 
 }  // namespace bd

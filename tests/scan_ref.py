@@ -313,38 +313,45 @@ def img_fwd_tensors(d: Dims):
     return t
 
 
+def actor_layers(d, W, x, I, K, t, AL=HW):
+    """The tanh-Normal actor of one imagination step from its input x = [h; s] through `action` (shared with
+    scan_cat_ref.py: the Categorical scan runs the same actor on [h; one-hot s])."""
+    init, amin, scale = f32(ACT_RAW_INIT_STD), f32(ACT_MIN_STD), f32(ACT_MEAN_SCALE)
+    A = d.A
+    for l in range(4):
+        pre, S = lin(x, W["W_a0"] if l == 0 else W["W_a"][l - 1], W["b_a"][l])
+        yield f"sv_actor{l}", t, ALL, elu64(pre), S, AL.act
+        x = K[f"sv_actor{l}"][t]
+    out, So = lin(x, W["W_a4"], W["b_a4"])
+    th = torch.tanh(out[:, :A] / scale)
+    yield "sv_act_stats", t, slice(0, A), th, (1 - th * th) * (So[:, :A] + out[:, :A].abs()) / scale + th.abs(), AL.tanh
+    pre, Sp = out[:, A:] + init, So[:, A:] + abs(init) + (out[:, A:] + init).abs()
+    sg = torch.sigmoid(pre)
+    yield "sv_act_stats", t, slice(A, 2 * A), sg, sg * (1 - sg) * Sp + sg, AL.sigmoid
+    st = K["sv_act_stats"][t]
+    mean = scale * st[:, :A]
+    yield "sv_act_stats", t, slice(2 * A, 3 * A), mean, mean.abs(), 0.0
+    sd = F.softplus(pre, beta=1, threshold=20) + amin
+    yield "sv_act_stats", t, slice(3 * A, 4 * A), sd, sg * Sp + sd, AL.softplus
+    mk, sk, eps = st[:, 2 * A:3 * A], st[:, 3 * A:], I["eps_action"][t]
+    u = mk + sk * eps
+    Su = mk.abs() + (sk * eps).abs() + u.abs()
+    if K.get("sv_act_us") is not None:
+        yield "sv_act_us", t, slice(0, A), u, Su, 0.0
+        yield "sv_act_us", t, slice(A, 2 * A), sk, 0.0 * sk, 0.0       # the same bits as slot 3
+        u, Su = K["sv_act_us"][t][:, :A], 0.0 * u
+    a = torch.tanh(u)
+    yield "action", t, ALL, a, (1 - a * a) * Su + a.abs(), AL.tanh
+
+
 def imagine_fwd_layers(d: Dims, W, I, K, min_std, AL=HW):
     """bd_imagine_forward_scan with sv_act_stats given, tanh-Normal actor.  K may lack prior_mean / sv_act_us (NULL)."""
-    ms, init, amin, scale = f32(min_std), f32(ACT_RAW_INIT_STD), f32(ACT_MIN_STD), f32(ACT_MEAN_SCALE)
-    Be, A = d.Be, d.A
+    ms = f32(min_std)
+    Be = d.Be
     for t in range(d.T):
         fp = K["feat"][t - 1] if t else I["start_feat"]
         h_prev, s_prev = fp[:, :Be], fp[:, Be:]
-        x = fp
-        for l in range(4):
-            pre, S = lin(x, W["W_a0"] if l == 0 else W["W_a"][l - 1], W["b_a"][l])
-            yield f"sv_actor{l}", t, ALL, elu64(pre), S, AL.act
-            x = K[f"sv_actor{l}"][t]
-        out, So = lin(x, W["W_a4"], W["b_a4"])
-        th = torch.tanh(out[:, :A] / scale)
-        yield "sv_act_stats", t, slice(0, A), th, (1 - th * th) * (So[:, :A] + out[:, :A].abs()) / scale + th.abs(), AL.tanh
-        pre, Sp = out[:, A:] + init, So[:, A:] + abs(init) + (out[:, A:] + init).abs()
-        sg = torch.sigmoid(pre)
-        yield "sv_act_stats", t, slice(A, 2 * A), sg, sg * (1 - sg) * Sp + sg, AL.sigmoid
-        st = K["sv_act_stats"][t]
-        mean = scale * st[:, :A]
-        yield "sv_act_stats", t, slice(2 * A, 3 * A), mean, mean.abs(), 0.0
-        sd = F.softplus(pre, beta=1, threshold=20) + amin
-        yield "sv_act_stats", t, slice(3 * A, 4 * A), sd, sg * Sp + sd, AL.softplus
-        mk, sk, eps = st[:, 2 * A:3 * A], st[:, 3 * A:], I["eps_action"][t]
-        u = mk + sk * eps
-        Su = mk.abs() + (sk * eps).abs() + u.abs()
-        if K.get("sv_act_us") is not None:
-            yield "sv_act_us", t, slice(0, A), u, Su, 0.0
-            yield "sv_act_us", t, slice(A, 2 * A), sk, 0.0 * sk, 0.0       # the same bits as slot 3
-            u, Su = K["sv_act_us"][t][:, :A], 0.0 * u
-        a = torch.tanh(u)
-        yield "action", t, ALL, a, (1 - a * a) * Su + a.abs(), AL.tanh
+        yield from actor_layers(d, W, fp, I, K, t, AL)
         pre, S = lin(torch.cat([s_prev, K["action"][t]], 1), W["W_e"], W["b_e"])
         yield "sv_x", t, ALL, elu64(pre), S, AL.act
         yield from gru_layers(W, K["sv_x"][t], h_prev, K, t, AL, Be)
@@ -359,25 +366,39 @@ def _mm(v, S, A, W):
     return v @ W, S @ W.abs() + v.abs() @ W.abs(), A @ W.abs()
 
 
-def imagine_bwd_layers(d: Dims, W, I, K, G, dentropy, min_std, AL=HW, actor_pre=True):
-    """I: forward inputs and tensors (start_feat, feat, prior_std, action, eps_*, sv_actor0..3, sv_act_stats with the
+def gauss_head_carry(W, I, min_std, AL):
+    """The Gaussian prior head of the imagination backward: (t, d state triple) -> the (value, S, A) triple of
+    d loss / d sv_p before ELU'."""
+    ms = f32(min_std)
+
+    def head(t, dm, Sdm, Adm):
+        eps = I["eps_prior"][t]
+        sig, Sx = sigmoid_recovery(I["prior_std"][t], ms)
+        dr = dm * eps * sig
+        Sdr = Sdm * eps.abs() * sig + (dm * eps).abs() * Sx + 2 * dr.abs()
+        Adr = Adm * eps.abs() * sig + AL.softplus * (dm * eps).abs()
+        return _mm(torch.cat([dm, dr], 1), torch.cat([Sdm, Sdr], 1), torch.cat([Adm, Adr], 1), W["W_2"])
+    return head
+
+
+def imagine_bwd_layers(d: Dims, W, I, K, G, dentropy, min_std, AL=HW, actor_pre=True, head=None, actor_tail=None):
+    """`head`: the prior head's backward (default: the Gaussian one; scan_cat_ref.py passes the Categorical one).
+    `actor_tail(t, dA)`: the layers from the d loss / d action triple on (default: the tanh-Normal actor below).
+    I: forward inputs and tensors (start_feat, feat, prior_std, action, eps_*, sv_actor0..3, sv_act_stats with the
     caller's slots 2, 3, sv_x, sv_gates, sv_p), float64; G: dfeat, ent_weight (or None); K: d_actor_out and, with
     actor_pre, d_actor_pre0..3 (written by the scan or by the caller's bd_mlp_backward: the same contract)."""
-    ms, dent0 = f32(min_std), f32(dentropy)
+    dent0 = f32(dentropy)
+    head = head or gauss_head_carry(W, I, min_std, AL)
     Be, S_, A = d.Be, d.S, d.A
     dev = W["W_e"].device
     zb, zs = torch.zeros(d.B, Be, dtype=D64, device=dev), torch.zeros(d.B, S_, dtype=D64, device=dev)
     dhc, dsc = (zb, zb, zb), (zs, zs, zs)
     Wes, Wea = W["W_e"][:, :S_], W["W_e"][:, S_:]
     for t in reversed(range(d.T)):
-        dfs, dfh, eps = G["dfeat"][t][:, Be:], G["dfeat"][t][:, :Be], I["eps_prior"][t]
+        dfs, dfh = G["dfeat"][t][:, Be:], G["dfeat"][t][:, :Be]
         dm = dsc[0] + dfs
         Sdm, Adm = dsc[1] + dfs.abs() + dm.abs(), dsc[2]
-        sig, Sx = sigmoid_recovery(I["prior_std"][t], ms)
-        dr = dm * eps * sig
-        Sdr = Sdm * eps.abs() * sig + (dm * eps).abs() * Sx + 2 * dr.abs()
-        Adr = Adm * eps.abs() * sig + AL.softplus * (dm * eps).abs()
-        acc = _mm(torch.cat([dm, dr], 1), torch.cat([Sdm, Sdr], 1), torch.cat([Adm, Adr], 1), W["W_2"])
+        acc = head(t, dm, Sdm, Adm)
         f = elu_grad_from_out64(I["sv_p"][t])
         dP = (acc[0] * f, acc[1] * f + (acc[0] * f).abs(), acc[2] * f + AL.act * acc[0].abs())
         m = _mm(*dP, W["W_1"])
@@ -395,6 +416,9 @@ def imagine_bwd_layers(d: Dims, W, I, K, G, dentropy, min_std, AL=HW, actor_pre=
         dE = (mx[0] * f, mx[1] * f + (mx[0] * f).abs(), mx[2] * f + AL.act * mx[0].abs())
         dsc = _mm(*dE, Wes)
         dA = _mm(*dE, Wea)
+        if actor_tail is not None:
+            yield from actor_tail(t, dA)
+            continue
         act, epa, st = I["action"][t], I["eps_action"][t], I["sv_act_stats"][t]
         th, sg, s2, s3 = st[:, :A], st[:, A:2 * A], st[:, 2 * A:3 * A], st[:, 3 * A:]
         fa = 1 - act * act
