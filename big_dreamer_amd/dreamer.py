@@ -4,6 +4,8 @@ Kept surface: ``Dreamer(params, env)``, ``train_step() ->
 ``imagine_ahead``, ``get_action``, ``update_critic``, ``update_belief_and_act``, ``buffer.append/sample``,
 ``eval()/train()``, ``observation_model(h, s)``, module attributes with reference ``state_dict`` names, ``load``
 of the reference's checkpoint dict (src/planet.py:103-114), and the module function ``lambda_return``.
+Added: ``act_step`` -- the decision of ``update_belief_and_act`` (src/planet.py:370-403, src/dreamer.py:429-444) without the
+environment, one kernel launch (bd_act_step).
 """
 from __future__ import annotations
 
@@ -285,11 +287,47 @@ class Dreamer:
         _, ent, act = e.imagine(start, N, 1, noise, save=False, tag="act_")   # one step: actor + sample (+ unused prior)
         return act.view(N, d.A).clone(), ent.view(N).clone()
 
+    @property
+    def act_fused(self) -> bool:
+        """Whether update_belief_and_act goes through act_step: the configuration is one bd_act_step takes and the switch
+        BD_ACT_FUSED (default 1, README) is not 0."""
+        return os.environ.get("BD_ACT_FUSED", "1") != "0" and self.engine.act_step_supported
+
+    @torch.no_grad()
+    def act_step(self, belief: Tensor, posterior_state: Tensor, action: Tensor, observation: Tensor, explore: bool = False,
+                 _noise: Optional[Dict[str, Tensor]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """The decision of update_belief_and_act (src/planet.py:370-403 with get_action, src/dreamer.py:429-444) without
+        the environment, in one kernel launch (bd_act_step): (belief, posterior state, previous action, observation) ->
+        (belief, posterior state, action), all on the device.  Pixel observations go through the conv encoder first.
+        `_noise`: the composed path's keys "post" (B,S), "action" (B,A) and, with explore, "explore" (B,A); "prior" and
+        "entropy" are accepted and ignored (their draws feed nothing that is returned).  Without it the draws come from
+        the engine's Philox streams.  The results are engine buffers, valid until the call after the next one."""
+        e = self.engine
+        if not e.act_step_supported:
+            raise NotImplementedError(
+                "act_step: the fused acting kernel takes Gaussian latents and the tanh-Normal actor at sizes "
+                f"bd_act_step_supported accepts (latent_distribution={self.latent_distribution}, action_distribution="
+                f"{self.action_distribution}, dims {self.dims.Be}/{self.dims.S}/{self.dims.A}/{self.dims.Hd}/{self.dims.E}); "
+                "use update_belief_and_act, which composes the step from the scan kernels")
+        obs = observation.to(self.device)
+        emb = None
+        if self.pixel_observation:
+            emb, obs = self.encoder(obs), None
+        return e.act_step(belief, posterior_state, action, obs=obs, embedding=emb, explore=bool(explore),
+                          action_noise=self.action_noise, noise=_noise)
+
     @torch.no_grad()
     def update_belief_and_act(self, env, belief, posterior_state, action, observation, explore=False,
                               _noise: Optional[Dict[str, Tensor]] = None):
         """src/planet.py:370-403.  (Data-parallel runs: issues any held-back actor update first -- a collective, call on
-        every rank, as the collect loop does.)"""
+        every rank, as the collect loop does.)  Where act_fused holds the decision is one launch (act_step); the code below
+        composes it from the encoder chain, a one-step observe scan and a one-step imagination otherwise."""
+        if self.act_fused:
+            belief, posterior_state, action = self.act_step(belief, posterior_state, action, observation, explore=explore,
+                                                            _noise=_noise)
+            batched = hasattr(env, "n") and hasattr(env, "envs")          # EnvBatcher (src/env.py:343)
+            next_observation, reward, done = env.step(action.cpu() if batched else action[0].cpu())
+            return belief, posterior_state, action, next_observation, reward, done
         self.engine.flush_optimizers()
         # `_noise` (parity tests): the reference's draws in its RNG order -- "prior" (B,S), "post" (B,S), "action" (B,A),
         # "entropy" (100,B,A), and with explore "explore" (B,A)

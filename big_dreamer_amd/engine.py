@@ -329,6 +329,7 @@ class DreamerEngine:
         self._rng_seed: Optional[int] = None
         self._rng_step = {"wm": 0, "bh": 0}
         self._rng_entropy_step = 0
+        self._act_parity = 0                 # act_step: which of its two output buffer sets the next call writes
         self._log_ring: List[_LogRecord] = []
         self._log_i = 0
         self._cur_rec: Optional[_LogRecord] = None
@@ -981,6 +982,71 @@ class DreamerEngine:
             cabi.check(lib.bd_actor_entropy_rng(self.rng_seed, self._rng_entropy_step, self.RNG_STREAMS["entropy"],
                                                 ptr(self._buf["sv_act_stats"]), ptr(ent), Hm, N, d.A, d.n_entropy, cabi.stream()))
 
+    # ------------------------------------------------------------------------------------------ acting
+    @property
+    def act_step_supported(self) -> bool:
+        """Whether act_step runs this configuration: Gaussian latents, the tanh-Normal actor, and sizes bd_act_step takes
+        (bd_act_step_supported; pixel observations use its embedding form, O = 0)."""
+        d = self.d
+        return (not d.categorical and not d.discrete_actions
+                and bool(lib.bd_act_step_supported(d.Be, d.S, d.A, d.Hd, d.E, 0 if self.pixel else d.O)))
+
+    def act_step(self, belief: torch.Tensor, state: torch.Tensor, action: torch.Tensor, obs: Optional[torch.Tensor] = None,
+                 embedding: Optional[torch.Tensor] = None, explore: bool = False, action_noise: float = 0.0,
+                 noise: Optional[Dict[str, torch.Tensor]] = None):
+        """One decision for B environments in one launch (bd_act_step; Planet.update_belief_and_act, src/planet.py:370-403):
+        (belief (B,Be), state (B,S), previous action (B,A), obs (B,O) | embedding (B,E)) -> (belief', state', action').
+        noise: {"post" (B,S), "action" (B,A), "explore" (B,A)} (parity), or None: the kernel draws from the Philox streams
+        act_post / act_action / act_explore, one counter step per decision.
+        Ordered behind queued train steps and packed-weight refreshes like every API call (flush_optimizers, join).
+        The results live in two alternating sets of engine buffers: a call never writes what it reads, and what it returns
+        stays valid until the call after the next one (clone to keep it longer)."""
+        d, pk = self.d, self.pk
+        tm = lambda n: self.W("transition_model", n)
+        self.flush_optimizers()
+        self.join()
+        f = lambda t: t.to(self.dev).float().contiguous()
+        belief, state, action = f(belief), f(state), f(action)
+        B = belief.shape[0]
+        a = cabi.ActArgs()
+        a.B, a.Be, a.S, a.A, a.Hd, a.E = B, d.Be, d.S, d.A, d.Hd, d.E
+        if embedding is None:
+            a.O, a.obs = d.O, ptr(f(obs).view(B, d.O))
+            for l in range(DENSE_LAYERS + 1):
+                a.w_enc[l], a.b_enc[l] = ptr(pk[f"enc{l}"]), ptr(self.W("encoder", f"model.{2 * l}.bias"))
+        else:
+            a.embedding = ptr(f(embedding).view(B, d.E))
+        self._bind_rssm(a)
+        self._actor_head_args(a)
+        a.w_embed_s, a.w_a0s = ptr(pk["embed_s"]), ptr(pk["a0s"])
+        a.w_q1h, a.w_q1e, a.b_q1 = ptr(pk["q1h"]), ptr(pk["q1e"]), ptr(tm("belief_posterior.model.0.bias"))
+        a.w_q2m, a.w_q2s, a.b_q2 = ptr(pk["q2m"]), ptr(pk["q2s"]), ptr(tm("belief_posterior.model.2.bias"))
+        a.belief, a.state, a.action = ptr(belief), ptr(state), ptr(action)
+        if noise is not None:
+            a.eps_post, a.eps_action = ptr(f(noise["post"]).view(B, d.S)), ptr(f(noise["action"]).view(B, d.A))
+            a.eps_explore = ptr(f(noise["explore"]).view(B, d.A)) if explore else None
+        else:
+            a.seed, a.step = self.rng_seed, self._rng_step.get("act", 0)
+            self._rng_step["act"] = a.step + 1
+        a.stream_post, a.stream_action, a.stream_explore = (self.RNG_STREAMS[k] for k in ("act_post", "act_action", "act_explore"))
+        a.min_std = self.hp["min_std_dev"]
+        a.act_raw_init_std, a.act_min_std, a.act_mean_scale = ACT_RAW_INIT_STD, ACT_MIN_STD, ACT_MEAN_SCALE
+        a.action_noise, a.explore = float(action_noise), int(bool(explore))
+        # the output set: the one none of the inputs lives in (a caller feeding results back alternates by itself)
+        ins = {belief.data_ptr(), state.data_ptr(), action.data_ptr()}
+        for p in (self._act_parity, 1 - self._act_parity):
+            out = (self.buf(f"act{p}_belief", B, d.Be), self.buf(f"act{p}_state", B, d.S), self.buf(f"act{p}_action", B, d.A))
+            if not ins & {t.data_ptr() for t in out}:
+                break
+        else:       # inputs taken from both sets
+            belief, state, action = belief.clone(), state.clone(), action.clone()
+            a.belief, a.state, a.action = ptr(belief), ptr(state), ptr(action)
+        self._act_parity = 1 - p
+        a.belief_out, a.state_out, a.action_out = (ptr(t) for t in out)
+        with self.span("act_step"):
+            cabi.check(lib.bd_act_step(C.byref(a), cabi.stream()))
+        return out
+
     # ------------------------------------------------------------------------------------------ train step
     def plan(self, belief: torch.Tensor, state: torch.Tensor, horizon: int, iters: int, candidates: int, top: int,
              eps_action: torch.Tensor, eps_state: Optional[torch.Tensor], trace: Optional[list] = None) -> torch.Tensor:
@@ -1087,7 +1153,8 @@ class DreamerEngine:
         self._rng_step = {"wm": 0, "bh": 0}
 
     # noise streams of the perf-mode generator (csrc/bd_rng.h: counter = (index, stream id, step))
-    RNG_STREAMS = {"obs_post": 1, "action": 2, "img_prior": 3, "entropy": 4, "obs_prior": 5, "plan_prior": 7}   # (6: pixel dequantisation)
+    RNG_STREAMS = {"obs_post": 1, "action": 2, "img_prior": 3, "entropy": 4, "obs_prior": 5, "plan_prior": 7,   # (6: pixel dequantisation)
+                   "act_post": 8, "act_action": 9, "act_explore": 10}     # bd_act_step: counter step = decision index
 
     def make_noise(self, B: int, part: str = "all") -> Dict[str, torch.Tensor]:
         """Noise of one step in perf mode (parity tests pass explicit arrays): ONE bd_rng_fill launch per phase on the

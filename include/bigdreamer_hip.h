@@ -691,6 +691,49 @@ typedef struct {
 } bd_plan_cat_args;
 int bd_plan_rollout_cat(const bd_plan_cat_args* a, void* stream);
 
+/* ---- acting: one decision of the collect / evaluation loop in ONE launch (csrc/act.hip) -------------------------
+ * Planet.update_belief_and_act (src/planet.py:370-403) with Dreamer.get_action (src/dreamer.py:429-444) for B
+ * environments, Gaussian latents and the tanh-Normal actor: encoder chain (or a ready embedding), embed layer + GRU cell
+ * (one step of bd_observe_forward, same weights), posterior head on [h'; embedding], s' = mean + std * eps_post, actor
+ * chain on [h'; s'], action = tanh(mean + std * eps_action) (mean scaling / init_std / min_std as bd_imagine_forward),
+ * and with explore != 0 action = clamp(action + action_noise * eps_explore, -1, 1).  The prior head, get_action's prior
+ * sample and the entropy estimate feed none of the three outputs and are not evaluated.
+ * Observation: obs [B x O] with the encoder DenseModel's five layers (w_enc packed, model.{0,2,4,6,8}), or -- obs = NULL --
+ * embedding [B x E] (pixel observations: the conv stack has already run; O and the encoder fields are then ignored).
+ * Noise: eps_post [B x S], eps_action [B x A], eps_explore [B x A] (may be NULL when explore = 0) as explicit buffers, or
+ * ALL NULL: standard normals drawn in the kernel, element i of each tensor being what bd_rng_fill(BD_RNG_NORMAL, seed,
+ * step, stream_post / stream_action / stream_explore) writes at i.
+ * The kernel never writes its inputs: belief_out / state_out / action_out must be other buffers than belief / state /
+ * action (the host ping-pongs).  One workgroup per 16 rows.  S, A <= 64; LDS as csrc/act.hip states (<= 160 KiB):
+ * bd_act_step_supported tells without raising an error (O = 0: the embedding form). */
+typedef struct {
+    int B, Be, S, A, Hd, E, O;
+    const float* w_enc[5]; const float* b_enc[5];         /* encoder.model.{0,2,4,6,8} (obs form only) */
+    const float* w_embed_s; const float* w_embed_a; const float* b_embed;
+    const float* w_ir; const float* w_iz; const float* w_in;
+    const float* w_hr; const float* w_hz; const float* w_hn;
+    const float* b_ih; const float* b_hh;
+    const float* w_q1h; const float* w_q1e; const float* b_q1;   /* belief_posterior.model.0[:, :Be] / [:, Be:] */
+    const float* w_q2m; const float* w_q2s; const float* b_q2;   /* belief_posterior.model.2 rows [:S] / [S:]   */
+    const float* w_a0h; const float* w_a0s; const float* w_a[3]; const float* b_a[4];   /* as bd_imagine_fwd_args */
+    const float* w_a4m; const float* w_a4s; const float* b_a4;
+    const float* belief;       /* [B x Be] */
+    const float* state;        /* [B x S]  */
+    const float* action;       /* [B x A]  previous action */
+    const float* obs;          /* [B x O] or NULL */
+    const float* embedding;    /* [B x E] or NULL (exactly one of obs / embedding) */
+    const float* eps_post; const float* eps_action; const float* eps_explore;
+    unsigned long long seed; unsigned long long step;     /* in-kernel noise: Philox key and decision counter */
+    unsigned stream_post, stream_action, stream_explore;  /* distinct Philox stream ids */
+    float min_std, act_raw_init_std, act_min_std, act_mean_scale, action_noise;
+    int explore;
+    float* belief_out;         /* [B x Be] */
+    float* state_out;          /* [B x S]  */
+    float* action_out;         /* [B x A]  */
+} bd_act_args;
+int bd_act_step_supported(int Be, int S, int A, int Hd, int E, int O);
+int bd_act_step(const bd_act_args* a, void* stream);
+
 /* ---- losses (src/planet.py:252-284, src/dreamer.py:110-146,342-383) ---------------------------
  * Reductions write RAW SUMS into a small device "scalar board" (float array); the host turns them
  * into the logged means after one D2H copy per step, and multi-GPU runs all-reduce the board's KL slot
