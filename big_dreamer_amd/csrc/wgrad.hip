@@ -699,9 +699,14 @@ __global__ __launch_bounds__(kWThreads) void wgrad_wide_kernel(const bd_wgrad_de
         else if (hk <= 3) BD_WN_BODY(WN, 3); \
         else BD_WN_BODY(WN, 4);            \
     } while (0)
-        if (hk > 4) {
-            // deep K tile (wgrad_tiles_k: up to 36 blocks, 9 per wave column): 16-row stages with a 592-float act row
-            // (37 blocks, == 16 mod 32); operands must take the 16-byte DMA form (conv layers with C % 4 == 0 do)
+        if (kb_cnt > 15) {
+            // deep K tile (wgrad_tiles_k: 16 .. 36 blocks, up to 9 per wave column): 16-row stages with a 592-float act row
+            // (37 blocks, == 16 mod 32); operands must take the 16-byte DMA form (conv layers with C % 4 == 0 do).
+            // A 16-block tile (K + bias in 241 .. 256; it exists only when wgrad_act16 holds, otherwise tiles_k splits at
+            // 12) belongs here too, on the <., 8> bodies: its 256 columns do not fit the 240-float act row of the bodies
+            // below (columns 240 .. 255 of a row landed on columns 0 .. 15 of the next one).  A 15-block tile fills that
+            // row exactly: wave column 3 of the <., 4> body then also multiplies columns 0 .. 15 of the NEXT LDS row as its
+            // 16th block -- inside the kernel's LDS request, and never stored (j < my_kb).
 #define BD_WDEEP(WN, WK) wgrad_wide_body<WN, WK, kWRows, kWLdNarrow, kWLdDeep>(d, ws, wlds, hb, Kext, z, n0, k0, nb_cnt, kb_cnt)
             if (hn <= 1) { if (hk <= 8) BD_WDEEP(1, 8); else BD_WDEEP(1, 9); }
             else { if (hk <= 8) BD_WDEEP(2, 8); else BD_WDEEP(2, 9); }

@@ -216,7 +216,7 @@ def wgrad_body(N: int, K: int, bias: bool, act16: bool, dense_ok: bool, mid: boo
             if nb == 13 and kb >= 4 and dense_ok:
                 out.add("dense")
             elif nb <= 4:
-                out.add("deep" if hk > 4 else "narrow")
+                out.add("deep" if kb > 15 else "narrow")
             elif nb <= 8 and mid:
                 out.add("mid")
             else:

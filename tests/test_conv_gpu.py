@@ -145,7 +145,9 @@ def test_gathered_wgrad_matches_conv_weight_gradients(Cin, Cout, k, size):
                                        (50, 33, 45, True), (100, 130, 48, False), (200, 64, 16, True), (45, 64, 80, False)])
 def test_plain_gemm_nt_matches_cpu_fp32(M, N, K, acc):
     """bd_gemm_nt (csrc/gemm.hip): C (+)= A B^T -- the decoder's K = 3200 dgrad GEMM (first case: configs[2] sizes, 256
-    workgroups of 160 x 64) and ragged shapes / every rows-per-workgroup variant, against a CPU fp32 matmul."""
+    workgroups of 160 x 64, RTM = 10) and seven small ragged shapes, against a CPU fp32 matmul.  Every grid of at most 256
+    workgroups picks RTM = 4, so these shapes run gemm_nt_kernel<10> once and <4> seven times; RTM = 6 and 8 and both load
+    forms of every RTM are in tests/test_conv_kernels_gpu.py::test_gemm_nt."""
     from big_dreamer_amd import _cabi as cabi
     g = torch.Generator().manual_seed(M + N)
     A = torch.randn(M, K + 4, generator=g)[:, :K]              # lda > K
