@@ -69,7 +69,7 @@ class ImgHeadsArgs(C.Structure):
 
 
 BD_RNG_MAX_TENSORS = 6
-BD_RNG_NORMAL, BD_RNG_EXPONENTIAL = 0, 1
+BD_RNG_NORMAL, BD_RNG_EXPONENTIAL, BD_RNG_UNIFORM = 0, 1, 2
 
 
 class RngTensor(C.Structure):
@@ -192,6 +192,20 @@ class ActArgs(C.Structure):
         ["belief_out", "state_out", "action_out"]))
 
 
+class ActCatArgs(C.Structure):
+    _fields_ = ([(n, I32) for n in ("B", "Be", "D", "C", "S", "A", "Hd", "E", "O", "latent_cat", "actor_cat")] + [
+        ("w_enc", P * 5), ("b_enc", P * 5)] + _ptr_fields(
+        ["w_embed_s", "w_embed_sT", "w_embed_a", "b_embed", "w_ir", "w_iz", "w_in", "w_hr", "w_hz", "w_hn", "b_ih", "b_hh",
+         "w_q1h", "w_q1e", "b_q1", "w_q2m", "w_q2s", "w_q2", "b_q2", "w_a0h", "w_a0s", "w_a0sT"]) + [
+        ("w_a", P * 3), ("b_a", P * 4)] + _ptr_fields(
+        ["w_a4m", "w_a4s", "b_a4", "belief", "state", "action", "obs", "embedding", "eps_post", "eps_action",
+         "eps_explore"]) + [("seed", C.c_ulonglong), ("step", C.c_ulonglong), ("stream_post", C.c_uint),
+                            ("stream_action", C.c_uint), ("stream_explore", C.c_uint),
+                            ("min_std", F32), ("act_raw_init_std", F32), ("act_min_std", F32), ("act_mean_scale", F32),
+                            ("action_noise", F32), ("explore", I32)] + _ptr_fields(
+        ["belief_out", "state_out", "action_out"]))
+
+
 class ConvArgs(C.Structure):
     _fields_ = [("in_", P), ("out", P), ("w", P), ("bias", P),
                 ("imgs", I32), ("gh", I32), ("gw", I32), ("N", I32), ("K", I32),
@@ -253,6 +267,8 @@ _SIGS = {
     "bd_plan_rollout_cat": (I32, [C.POINTER(PlanCatArgs), P]),
     "bd_act_step_supported": (I32, [I32, I32, I32, I32, I32, I32]),
     "bd_act_step": (I32, [C.POINTER(ActArgs), P]),
+    "bd_act_step_cat_supported": (I32, [I32] * 10),
+    "bd_act_step_cat": (I32, [C.POINTER(ActCatArgs), P]),
     "bd_lambda_return_backward": (I32, [P, F32, I32, I32, F32, F32, P, P, P]),
     "bd_img_heads_supported": (I32, [I32, I32]),
     "bd_img_heads_fwd_bwd": (I32, [C.POINTER(ImgHeadsArgs), P]),

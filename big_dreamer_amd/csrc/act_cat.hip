@@ -1,0 +1,376 @@
+// act_cat.hip -- one decision of the collect / evaluation loop in ONE launch for the DreamerV2 configurations:
+// Planet.update_belief_and_act (src/planet.py:370-403) with Dreamer.get_action (src/dreamer.py:429-444) on
+// latent_distribution="Categorical" (TransitionModel.forward's Categorical branches, src/models.py:226-228,258-260,269-271;
+// CategoricalBeliefModel, src/models.py:101-117) and / or action_distribution="Categorical" (src/models.py:518-522).
+//
+//   bd_act_step_cat: the ownership of bd_act_step (act.hip) -- a workgroup owns 16 environments, every activation of the
+//     step stays in LDS in MFMA fragment order, the weights stream once from L2.  One kernel body, templated on the latent
+//     kind LC and the actor kind AC; (LC, AC) = (1, 0), (1, 1), (0, 1) are instantiated, (0, 0) is bd_act_step.  Per tile:
+//       e  = encoder(obs), or a ready embedding                                    as act.hip step 1
+//       x  = ELU(W_ea a + W_es s + b_e);  h' = GRUCell(x, h)                       (src/models.py:251-252)
+//            LC: the incoming state [B x S] (per factor all-zero or one-hot) becomes class indices (state_to_indices) and
+//            W_es s a gather of D rows of the plain transpose embed_sT (bd_categorical.h), as in the scans
+//       q  = ELU(W_q1 [h'; e] + b)
+//            LC: all D*C logits into the swizzled CatFull image, one thread per (row, factor) takes argmax(probs / q),
+//            first maximum winning: cat_sample_reg / cat_sample_any, the operation order of the scans; s' = the one-hot
+//            !LC: s' = mean_q + std_q * eps_post                                   as act.hip step 3
+//       actor: 4 x (Linear+ELU) on [h'; s'] (LC: the state columns of layer 0 are a gather of a0sT rows), then
+//            !AC: a' = tanh(mean + std * eps_action), explore: clamp(a' + action_noise * eps_explore, -1, 1)   (act.hip 5)
+//            AC:  norm = out - logsumexp(out), p = softmax(norm), k = argmax(p / eps_action) (bd_discrete.h, one lane per
+//                 class), a' = (onehot(k) + p) - p in that order; explore: epsilon-greedy -- with (u, v) the row's two
+//                 uniforms, u < action_noise replaces a' by the exact one-hot of class min(floor(v A), A - 1)
+//     Left out because nothing returned reads it (as in act.hip): the prior head and its sample (src/models.py:256),
+//     get_action's prior sample, and the actor entropy (src/planet.py:386 drops it).  The three outputs are the composed
+//     path's.
+//   Noise: explicit buffers, or (all NULL) Philox4x32-10 draws with the element layout of bd_rng_fill: Exp(1) where a
+//     Categorical sampler consumes them, uniforms for epsilon-greedy, normals otherwise.
+//
+// LDS budget (floats; Kb_x = ceil(x / 16), 256 floats per fragment block, 8 waves):
+//     t0, t1, t2                 3 * max(Kb_h, Kb_hd) * 256     as act.hip; t0 / t2 also hold the two gathers' [16][out] sums
+//     ef | logits image          max(max(Kb_e, Kb_o) * 256, LC ? 16 * (ceil(S / 16) * 16 + 8) : 0)
+//                                the embedding is dead once the posterior's first layer has read it: the image takes its place
+//     state                      LC: 2 * 16 * D (class indices, weights)     !LC: Kb_s * 256 (fragment tile)
+//     action fragments           Kb_a * 256
+//     split-K scratch            kSplitScratchFloats = 10240    (its plain area also holds the actor's [16][A] logits)
+//   Be = Hd = 200, E = 1024, 32 x 32, A = 18:  9984 + 16512 + 1024 + 512 + 10240 = 38272 floats = 153 088 B of the 160 KiB a
+//   workgroup may use on gfx950 (with the embedding tile and the image side by side: 218 624 B).  A = 17, tanh-Normal: the same.
+#include "bd_device.h"
+#include "bd_host.h"
+#include "bd_scan.h"
+#include "bd_categorical.h"
+#include "bd_discrete.h"
+#include "bd_rng.h"
+
+namespace bd {
+
+struct ActCatDims {
+    int Kb_h, Kb_s, Kb_a, Kb_hd, Kb_e, Kb_o, Kb_g, Kb_io;
+    int n_ef, n_state;       // floats of the embedding | image region and of the state region
+    __host__ __device__ ActCatDims(int Be, int D, int C, int S, int A, int Hd, int E, int O, bool lc)
+        : Kb_h(cdiv(Be, 16)), Kb_s(cdiv(S, 16)), Kb_a(cdiv(A, 16)), Kb_hd(cdiv(Hd, 16)), Kb_e(cdiv(E, 16)), Kb_o(cdiv(O, 16)),
+          Kb_g(Kb_h > Kb_hd ? Kb_h : Kb_hd), Kb_io(Kb_e > Kb_o ? Kb_e : Kb_o) {
+        const int img = lc ? CatFull(D, C).image_floats() : 0;
+        n_ef = Kb_io * kFragFloats > img ? Kb_io * kFragFloats : img;
+        n_state = lc ? 2 * 16 * D : Kb_s * kFragFloats;
+    }
+    __host__ __device__ size_t lds_floats() const {
+        return (size_t)(3 * Kb_g + Kb_a) * kFragFloats + (size_t)n_ef + (size_t)n_state + kSplitScratchFloats;
+    }
+};
+
+struct ActCatEps {
+    float sample, explore;
+};
+
+enum { kDrawNormal = 0, kDrawExp = 1, kDrawUniform = 2 };      // the kinds of bd_rng_fill
+
+template <bool LC, bool AC>
+__global__ __launch_bounds__(kThreads) void act_step_cat_kernel(bd_act_cat_args a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const ActCatDims d(a.Be, a.D, a.C, a.S, a.A, a.Hd, a.E, a.O, LC);
+    const int row0 = blockIdx.x * 16;
+    const int rows_valid = a.B - row0 < 16 ? a.B - row0 : 16;
+    const int ng = d.Kb_g * kFragFloats;
+    float* t0 = smem;                             // encoder pong, embed gather, h' (kept to the end: the actor reads it)
+    float* t1 = t0 + ng;                          // h, posterior hidden, actor ping
+    float* t2 = t1 + ng;                          // encoder ping, x, actor gather, actor pong
+    float* ef = t2 + ng;                          // obs -> embedding -> (LC) the logits image
+    float* sf = ef + d.n_ef;                      // !LC: s, then s' (fragment tile)
+    float* sw_l = sf;                             // LC: [16][D] weights, [16][D] class indices
+    int* sidx_l = reinterpret_cast<int*>(sw_l + 16 * a.D);
+    float* af = sf + d.n_state;
+    float* scratch = af + d.Kb_a * kFragFloats;   // split-K partials (kSplitScratchFloats), 16-byte aligned
+    const int lane = bd_tid() & 63;
+    const CatGeo g(LC ? a.D : 1, LC ? a.C : 1);
+    // element e of a noise tensor: the caller's buffer, or what bd_rng_fill writes there for `kind`
+    auto draw_at = [&](const float* __restrict__ eps, unsigned stream, int kind, size_t e) -> float {
+        if (eps != nullptr) return eps[e];
+        const Rng r{(uint32_t)a.seed, (uint32_t)(a.seed >> 32), stream, (uint32_t)a.step};
+        float v[4];
+        if (kind == kDrawExp) rng_exp4(r, e >> 2, v);
+        else if (kind == kDrawUniform) rng_uniform4(r, e >> 2, v);
+        else rng_normal4(r, e >> 2, v);
+        const int j = (int)(e & 3);
+        return j == 0 ? v[0] : (j == 1 ? v[1] : (j == 2 ? v[2] : v[3]));
+    };
+    auto draw = [&](const float* __restrict__ eps, unsigned stream, int kind, int width, int row, int col) -> float {
+        return row0 + row < a.B ? draw_at(eps, stream, kind, (size_t)(row0 + row) * width + col) : 0.f;
+    };
+    auto hidden_epi = [&](float* dst, int width) { return HiddenEpiTR{dst, nullptr, 0, width, a.B, row0, lane}; };
+    // hidden layer whose state columns were gathered into xs [16][width]: ELU(acc + xs) -> fragment tile
+    auto gather_epi = [&](float* dst, const float* xs, int width) {
+        return [dst, xs, width, lane, rok_rows = a.B - row0](int nb, floatx4 acc) {
+            const int row = lane & 15, col0 = nb * 16 + 4 * (lane >> 4);
+            const bool rok = row < rok_rows;
+            floatx4 v;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = (rok && col0 + r < width) ? elu(acc[r] + xs[row * width + col0 + r]) : 0.f;
+            reinterpret_cast<floatx4*>(dst)[nb * 64 + lane] = v;
+        };
+    };
+
+    load_tile_concat<1>(t1, d.Kb_h, row0, a.B, a.belief, a.Be, a.Be, nullptr, 0, 0);
+    if constexpr (LC) state_to_indices(g, a.state, (size_t)a.S, row0, a.B, sidx_l, sw_l);
+    else load_tile_concat<1>(sf, d.Kb_s, row0, a.B, a.state, a.S, a.S, nullptr, 0, 0);
+    load_tile_concat<1>(af, d.Kb_a, row0, a.B, a.action, a.A, a.A, nullptr, 0, 0);
+    if (a.obs != nullptr) load_tile_concat<1>(ef, d.Kb_o, row0, a.B, a.obs, a.O, a.O, nullptr, 0, 0);
+    else load_tile_concat<1>(ef, d.Kb_e, row0, a.B, a.embedding, a.E, a.E, nullptr, 0, 0);
+    lds_barrier();
+
+    // ---- 1: encoder (state observations) ----
+    if (a.obs != nullptr) {
+        {
+            const Seg segs[1] = {{ef, a.w_enc[0], d.Kb_o}};
+            tile_linear_seg_tr<1>(segs, a.b_enc[0], a.Hd, hidden_epi(t2, a.Hd));
+        }
+        lds_barrier();
+        float* src = t2;
+        float* dst = t0;
+        for (int l = 1; l < 4; ++l) {
+            const Seg segs[1] = {{src, a.w_enc[l], d.Kb_hd}};
+            tile_linear_seg_tr<1>(segs, a.b_enc[l], a.Hd, hidden_epi(dst, a.Hd));
+            lds_barrier();
+            float* tmp = src; src = dst; dst = tmp;
+        }
+        // three swaps: layer 3's activations are in t0; the output layer is linear
+        const Seg segs[1] = {{t0, a.w_enc[4], d.Kb_hd}};
+        tile_linear_seg_tr<1>(segs, a.b_enc[4], a.E, [&](int nb, floatx4 acc) {
+            const int col0 = nb * 16 + 4 * (lane >> 4);
+            const bool rok = row0 + (lane & 15) < a.B;
+            floatx4 v;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = (rok && col0 + r < a.E) ? acc[r] : 0.f;
+            reinterpret_cast<floatx4*>(ef)[nb * 64 + lane] = v;
+        });
+        lds_barrier();
+    }
+    // ---- 2: x = ELU(W_e [s; a] + b_e);  h' = GRUCell(x, h) ----
+    if constexpr (LC) {
+        state_gather(g, a.w_embed_sT, a.Be, sidx_l, sw_l, nullptr, t0);      // t0 is free until the GRU's epilogue
+        lds_barrier();
+        const Seg segs[1] = {{af, a.w_embed_a, d.Kb_a}};
+        tile_linear_seg_tr<1>(segs, a.b_embed, a.Be, gather_epi(t2, t0, a.Be));
+    } else {
+        const Seg segs[2] = {{sf, a.w_embed_s, d.Kb_s}, {af, a.w_embed_a, d.Kb_a}};
+        tile_linear_seg_tr<2>(segs, a.b_embed, a.Be, hidden_epi(t2, a.Be));
+    }
+    lds_barrier();
+    {
+        const GruW gw{a.w_ir, a.w_iz, a.w_in, a.w_hr, a.w_hz, a.w_hn, a.b_ih, a.b_hh};
+        gru_tile(t2, t1, d.Kb_h, a.Be, gw, [&](int nb, floatx4 R, floatx4 Z, floatx4 NI, floatx4 NH) {
+            const int col = nb * 16 + (lane & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int grow = row0 + 4 * (lane >> 4) + r;
+                const int off = acc_frag_off(nb, lane, r);
+                const float rr = sigmoidf(R[r]), zz = sigmoidf(Z[r]);
+                const float nn = tanh_act(NI[r] + rr * NH[r]);
+                const float hn = (1.f - zz) * nn + zz * t1[off];
+                const bool ok = grow < a.B && col < a.Be;
+                t0[off] = ok ? hn : 0.f;
+                if (ok) a.belief_out[(size_t)grow * a.Be + col] = hn;
+            }
+        }, scratch);
+    }
+    lds_barrier();
+    // ---- 3: posterior on [h'; e]; the prior head is not evaluated ----
+    {
+        const Seg segs[2] = {{t0, a.w_q1h, d.Kb_h}, {ef, a.w_q1e, d.Kb_e}};
+        tile_linear_seg_tr<2>(segs, a.b_q1, a.Hd, hidden_epi(t1, a.Hd));
+    }
+    lds_barrier();
+    if constexpr (LC) {
+        const CatFull gf(a.D, a.C);
+        float* lg = ef;                           // the embedding is dead: its storage holds the logits image
+        const Seg seg[1] = {{t1, a.w_q2, d.Kb_hd}};
+        tile_linear_g<1, 1>(seg, a.b_q2, a.S, [&](int, int nb, floatx4 acc) {
+            const int col = nb * 16 + (lane & 15);
+            if (col >= a.S) return;
+            const int f = col / a.C, c = col - f * a.C;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lg[gf.addr(4 * (lane >> 4) + r, f, c)] = acc[r];
+        });
+        lds_barrier();
+        const Rng rng{(uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.stream_post, (uint32_t)a.step};
+        for (int i = bd_tid(); i < 16 * a.D; i += blockDim.x) {
+            const int row = i / a.D, f = i - row * a.D;
+            int arg = 0;
+            if (row < rows_valid) {
+                const size_t e0 = (size_t)(row0 + row) * a.S + f * a.C;      // first class of this factor in [B x S]
+                if (a.eps_post) {
+                    const float* qrow = a.eps_post + e0;
+                    arg = a.C == 32 ? cat_sample_reg<32>(gf, lg, qrow, row, f) : cat_sample_any(gf, lg, qrow, row, f);
+                } else {
+                    arg = a.C == 32 ? cat_sample_reg_rng<32>(gf, lg, rng, e0, row, f) : cat_sample_any_rng(gf, lg, rng, e0, row, f);
+                }
+            }
+            sidx_l[i] = arg;
+            sw_l[i] = row < rows_valid ? 1.f : 0.f;      // a sampled state is one-hot whatever the incoming state's weights were
+        }
+        lds_barrier();
+        write_onehot(g, sidx_l, sw_l, nullptr, a.state_out + (size_t)row0 * a.S, (size_t)a.S, rows_valid);
+    } else {
+        const Seg2 segs[1] = {{t1, a.w_q2m, a.w_q2s, d.Kb_hd}};
+        tile_dual_head_elem<1>(
+            segs, a.b_q2, a.b_q2 + a.S, a.S, scratch,
+            [&](int row, int col) { return draw(a.eps_post, a.stream_post, kDrawNormal, a.S, row, col); },
+            [&](int row, int col, float Mn, float Rw, float eps) {
+                const int grow = row0 + row;
+                float st = 0.f;
+                if (grow < a.B) {
+                    st = Mn + (softplusf(Rw) + a.min_std) * eps;
+                    a.state_out[(size_t)grow * a.S + col] = st;
+                }
+                sf[frag_idx(row, col)] = st;
+            });
+        lds_barrier();
+    }
+    // ---- 4: actor on [h'; s'] ----
+    if constexpr (LC) {
+        state_gather(g, a.w_a0sT, a.Hd, sidx_l, sw_l, nullptr, t2);         // x is dead since the GRU
+        lds_barrier();
+        const Seg segs[1] = {{t0, a.w_a0h, d.Kb_h}};
+        tile_linear_seg_tr<1>(segs, a.b_a[0], a.Hd, gather_epi(t1, t2, a.Hd));
+    } else {
+        const Seg segs[2] = {{t0, a.w_a0h, d.Kb_h}, {sf, a.w_a0s, d.Kb_s}};
+        tile_linear_seg_tr<2>(segs, a.b_a[0], a.Hd, hidden_epi(t1, a.Hd));
+    }
+    lds_barrier();
+    {
+        float* src = t1;
+        float* dst = t2;
+        for (int l = 1; l < 4; ++l) {
+            const Seg segs[1] = {{src, a.w_a[l - 1], d.Kb_hd}};
+            tile_linear_seg_tr<1>(segs, a.b_a[l], a.Hd, hidden_epi(dst, a.Hd));
+            lds_barrier();
+            float* tmp = src; src = dst; dst = tmp;
+        }
+        // three swaps: layer 3's activations are in t2
+    }
+    // ---- 5: the action sample and exploration ----
+    if constexpr (AC) {
+        // A logits -> the plain area behind the split-K partials, [16][A]; then one wave per row, one lane per class
+        float* out_s = scratch + kSplitPartialFloats;
+        const Seg segs[1] = {{t2, a.w_a4m, d.Kb_hd}};
+        tile_linear_seg<1>(segs, a.b_a4, a.A, [&](int nb, floatx4 acc) {
+            const int col = nb * 16 + (lane & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (col < a.A) out_s[(4 * (lane >> 4) + r) * a.A + col] = acc[r];
+        }, scratch);
+        lds_barrier();
+        const int wave = bd_wave(bd_tid());
+        for (int row = wave; row < rows_valid; row += kWaves) {        // wave-uniform: the butterflies see the whole wave
+            const int grow = row0 + row;
+            const bool valid = lane < a.A;
+            const float q = valid ? draw_at(a.eps_action, a.stream_action, kDrawExp, (size_t)grow * a.A + lane) : 1.f;
+            const float norm = disc_norm(valid ? out_s[row * a.A + lane] : 0.f, valid);
+            const float p = disc_probs(norm, valid);
+            const int k = disc_sample(p, q, valid, lane);
+            float act = disc_action_value(p, lane == k);
+            if (a.explore) {      // epsilon-greedy: (u, v) = the row's two uniforms
+                const float u = draw_at(a.eps_explore, a.stream_explore, kDrawUniform, (size_t)grow * 2);
+                const float v = draw_at(a.eps_explore, a.stream_explore, kDrawUniform, (size_t)grow * 2 + 1);
+                int kr = (int)floorf(v * (float)a.A);
+                kr = kr < a.A - 1 ? kr : a.A - 1;
+                if (u < a.action_noise) act = lane == kr ? 1.f : 0.f;
+            }
+            if (valid) a.action_out[(size_t)grow * a.A + lane] = act;
+        }
+    } else {
+        const Seg2 segs[1] = {{t2, a.w_a4m, a.w_a4s, d.Kb_hd}};
+        tile_dual_head_elem<1>(
+            segs, a.b_a4, a.b_a4 + a.A, a.A, scratch,
+            [&](int row, int col) {
+                // ONE call site of the normal generator for both draws: with two, hipcc stops inlining the library's
+                // sincosf, and the call's stack frame is the kernel's only scratch (act.hip: 544 B per lane)
+                float ev[2] = {0.f, 0.f};
+#pragma unroll 1
+                for (int t = 0; t < (a.explore ? 2 : 1); ++t)
+                    ev[t] = draw(t ? a.eps_explore : a.eps_action, t ? a.stream_explore : a.stream_action, kDrawNormal, a.A, row, col);
+                return ActCatEps{ev[0], ev[1]};
+            },
+            [&](int row, int col, float Mn, float Rw, ActCatEps eps) {
+                const int grow = row0 + row;
+                if (grow >= a.B) return;
+                const float mean = a.act_mean_scale * tanh_act(Mn / a.act_mean_scale);
+                const float sd = softplusf(Rw + a.act_raw_init_std) + a.act_min_std;
+                float act = tanh_act(mean + sd * eps.sample);
+                if (a.explore) act = fminf(fmaxf(act + a.action_noise * eps.explore, -1.f), 1.f);
+                a.action_out[(size_t)grow * a.A + col] = act;
+            });
+    }
+}
+
+// nullptr = dims the kernel takes (LDS aside); otherwise the reason
+static const char* act_cat_dims_error(int Be, int D, int C, int S, int A, int Hd, int E, int O, bool lc, bool ac) {
+    if (!lc && !ac) return "Gaussian latents with the tanh-Normal actor: that configuration is bd_act_step";
+    if (Be <= 0 || S <= 0 || A <= 0 || Hd <= 0 || E <= 0 || O < 0) return "bad dims";
+    // (bounds first: the tile counts of the LDS figure must not overflow)
+    if (Be > (1 << 20) || Hd > (1 << 20) || E > (1 << 20) || O > (1 << 20) || S > (1 << 20)) return "layer width above 2^20";
+    if (A > kHeadMaxN) return "action width above 64 (one lane per class; the widest Gaussian head)";
+    if (lc) {
+        if (D <= 0 || C <= 0 || D > (1 << 20) || C > 256 || (long long)D * C != S || !CatGeo(D, C).ok())
+            return "latents unsupported (S = D*C; C <= 256; S <= 256, or 256 % C == 0 and S % 16 == 0)";
+    } else if (S > kHeadMaxN) {
+        return "state width above 64";
+    }
+    return nullptr;
+}
+
+template <bool LC, bool AC>
+static int act_cat_launch(const bd_act_cat_args& k, size_t lds, hipStream_t stream) {
+    if (lds > 64 * 1024 && allow_big_lds(act_step_cat_kernel<LC, AC>)) return -1;
+    hipLaunchKernelGGL((act_step_cat_kernel<LC, AC>), dim3(cdiv(k.B, 16)), dim3(kThreads), lds, stream, k);
+    BD_CHECK_LAUNCH("bd_act_step_cat");
+    return 0;
+}
+
+}  // namespace bd
+
+extern "C" {
+using namespace bd;
+
+int bd_act_step_cat_supported(int Be, int D, int C, int S, int A, int Hd, int E, int O, int latent_cat, int actor_cat) {
+    const bool lc = latent_cat != 0, ac = actor_cat != 0;
+    if (act_cat_dims_error(Be, D, C, S, A, Hd, E, O, lc, ac) != nullptr) return 0;
+    return ActCatDims(Be, D, C, S, A, Hd, E, O, lc).lds_floats() * sizeof(float) <= (size_t)kMaxLds ? 1 : 0;
+}
+
+int bd_act_step_cat(const bd_act_cat_args* a, void* stream) {
+    BD_REQUIRE(a, "bd_act_step_cat: null argument block");
+    BD_REQUIRE(a->B > 0, "bd_act_step_cat: bad dims");
+    const bool lc = a->latent_cat != 0, ac = a->actor_cat != 0;
+    BD_REQUIRE((a->obs != nullptr) != (a->embedding != nullptr),
+               "bd_act_step_cat: give the observation (state observations) or the embedding (pixels), not both");
+    const int O = a->obs ? a->O : 0;
+    const char* why = act_cat_dims_error(a->Be, a->D, a->C, a->S, a->A, a->Hd, a->E, O, lc, ac);
+    BD_REQUIRE(why == nullptr, "bd_act_step_cat: %s (Be %d, %d x %d, S %d, A %d, Hd %d, E %d, O %d)", why, a->Be, a->D, a->C, a->S,
+               a->A, a->Hd, a->E, O);
+    const size_t lds = ActCatDims(a->Be, a->D, a->C, a->S, a->A, a->Hd, a->E, O, lc).lds_floats() * sizeof(float);
+    BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_act_step_cat: needs %zu B of LDS (limit %d)", lds, kMaxLds);
+    if (a->obs != nullptr) {
+        BD_REQUIRE(a->O > 0, "bd_act_step_cat: obs given with O = 0");
+        for (int l = 0; l < 5; ++l)
+            BD_REQUIRE(a->w_enc[l] && a->b_enc[l], "bd_act_step_cat: missing encoder weights (layer %d)", l);
+    }
+    BD_REQUIRE(a->w_embed_a && a->b_embed && a->w_ir && a->w_iz && a->w_in && a->w_hr && a->w_hz && a->w_hn && a->b_ih && a->b_hh &&
+                   a->w_q1h && a->w_q1e && a->b_q1 && a->b_q2 &&
+                   (lc ? (a->w_embed_sT && a->w_q2) : (a->w_embed_s && a->w_q2m && a->w_q2s)),
+               "bd_act_step_cat: missing transition weights");
+    BD_REQUIRE(a->w_a0h && (lc ? a->w_a0sT : a->w_a0s) && a->w_a[0] && a->w_a[1] && a->w_a[2] && a->b_a[0] && a->b_a[1] &&
+                   a->b_a[2] && a->b_a[3] && a->w_a4m && (ac || a->w_a4s) && a->b_a4, "bd_act_step_cat: missing actor weights");
+    BD_REQUIRE(a->belief && a->state && a->action, "bd_act_step_cat: missing inputs");
+    BD_REQUIRE(a->belief_out && a->state_out && a->action_out, "bd_act_step_cat: missing outputs");
+    BD_REQUIRE(a->belief_out != a->belief && a->state_out != a->state && a->action_out != a->action,
+               "bd_act_step_cat: an output aliases its input");
+    const bool all_null = !a->eps_post && !a->eps_action && !a->eps_explore;
+    BD_REQUIRE(all_null || (a->eps_post && a->eps_action && (a->eps_explore || !a->explore)),
+               "bd_act_step_cat: noise buffers: eps_post, eps_action (and eps_explore when explore) or all NULL");
+    bd_act_cat_args k = *a;
+    k.O = O;
+    if (lc) return ac ? act_cat_launch<true, true>(k, lds, (hipStream_t)stream) : act_cat_launch<true, false>(k, lds, (hipStream_t)stream);
+    return act_cat_launch<false, true>(k, lds, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 // gradients) are staged through an image of the same shape with coalesced loads.
 #pragma once
 #include "bd_device.h"
+#include "bd_rng.h"
 
 namespace bd {
 
@@ -335,6 +336,47 @@ __device__ __forceinline__ int cat_sample_any(const CatFull& g, const float* __r
     int arg = 0;
     for (int c = 0; c < g.C; ++c) {
         const float r = (expf((lg[g.addr(row, f, c)] - lse) - m2) / s2) / qrow[c];
+        if (r > best) { best = r; arg = c; }
+    }
+    return arg;
+}
+
+// cat_sample_reg with the C draws of this (row, factor) generated in registers: e0 = global element index of its first
+// class in the draw tensor (planner: [H x rows x S]; acting step: [B x S]) (a multiple of 4: S % 4 == 0 and CC % 4 == 0).  Same operations as the
+// explicit-buffer path from there on.
+template <int CC>
+__device__ __forceinline__ int cat_sample_reg_rng(const CatFull& g, const float* __restrict__ lg, const Rng& rng, uint64_t e0,
+                                                  int row, int f) {
+    __attribute__((aligned(16))) float q[CC];
+#pragma unroll
+    for (int c = 0; c < CC; c += 4) {
+        float t[4];
+        rng_exp4(rng, (e0 >> 2) + (c >> 2), t);
+        q[c] = t[0]; q[c + 1] = t[1]; q[c + 2] = t[2]; q[c + 3] = t[3];
+    }
+    return cat_sample_reg<CC>(g, lg, q, row, f);
+}
+
+// cat_sample_any with generated draws: any C, any alignment of e0 (a group of four draws may straddle two factors)
+__device__ __forceinline__ int cat_sample_any_rng(const CatFull& g, const float* __restrict__ lg, const Rng& rng, uint64_t e0,
+                                                  int row, int f) {
+    float m = -INFINITY;
+    for (int c = 0; c < g.C; ++c) m = fmaxf(m, lg[g.addr(row, f, c)]);
+    float s = 0.f;
+    for (int c = 0; c < g.C; ++c) s += expf(lg[g.addr(row, f, c)] - m);
+    const float lse = m + logf(s);
+    const float m2 = m - lse;
+    float s2 = 0.f;
+    for (int c = 0; c < g.C; ++c) s2 += expf((lg[g.addr(row, f, c)] - lse) - m2);
+    float best = -INFINITY;
+    int arg = 0;
+    float t[4] = {1.f, 1.f, 1.f, 1.f};
+    for (int c = 0; c < g.C; ++c) {
+        const uint64_t e = e0 + c;
+        const int j = (int)(e & 3);
+        if (c == 0 || j == 0) rng_exp4(rng, e >> 2, t);
+        const float q = j == 0 ? t[0] : (j == 1 ? t[1] : (j == 2 ? t[2] : t[3]));
+        const float r = (expf((lg[g.addr(row, f, c)] - lse) - m2) / s2) / q;
         if (r > best) { best = r; arg = c; }
     }
     return arg;

@@ -7,7 +7,7 @@
 //     key     = (seed lo, seed hi)                       -- per process: torch.initial_seed()
 //     counter = (index lo, index hi, stream id, step)    -- index: which group of 4 values; stream id: which noise tensor
 //                                                            (observe / action / prior / entropy ...); step: train step
-// One call yields four 32-bit words = four uniforms = four normals (two Box-Muller pairs) or four Exp(1) variates.
+// One call yields four 32-bit words = four normals (two Box-Muller pairs), four Exp(1) variates or four uniforms in [0, 1).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,6 +59,14 @@ __device__ __forceinline__ void rng_exp4(const Rng& g, uint64_t idx, float (&out
     const Philox4 p = philox4x32_10((uint32_t)idx, (uint32_t)(idx >> 32), g.stream, g.step, g.k0, g.k1);
 #pragma unroll
     for (int h = 0; h < 4; ++h) out[h] = -logf(u01(p.x[h]));
+}
+
+// four uniforms in [0, 1): 24 random bits each, u = (word >> 8) * 2^-24 (0 included: the epsilon-greedy draws compare and
+// floor them, nothing takes their logarithm)
+__device__ __forceinline__ void rng_uniform4(const Rng& g, uint64_t idx, float (&out)[4]) {
+    const Philox4 p = philox4x32_10((uint32_t)idx, (uint32_t)(idx >> 32), g.stream, g.step, g.k0, g.k1);
+#pragma unroll
+    for (int h = 0; h < 4; ++h) out[h] = (float)(p.x[h] >> 8) * (1.0f / 16777216.0f);
 }
 
 }  // namespace bd

@@ -23,6 +23,7 @@ __global__ __launch_bounds__(256) void rng_fill_kernel(bd_rng_fill_args a) {
     const Rng g{(uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.t[t].stream_id, (uint32_t)a.step};
     float v[4];
     if (a.t[t].kind == BD_RNG_EXPONENTIAL) rng_exp4(g, i4, v);
+    else if (a.t[t].kind == BD_RNG_UNIFORM) rng_uniform4(g, i4, v);
     else rng_normal4(g, i4, v);
     float* p = a.t[t].p + i;
     if (i + 4 <= a.t[t].count && ((uintptr_t)p & 15) == 0) {
@@ -49,7 +50,7 @@ int bd_rng_fill(const bd_rng_fill_args* a, void* stream) {
     BD_REQUIRE(a && a->n > 0 && a->n <= BD_RNG_MAX_TENSORS, "bd_rng_fill: 1..%d tensors", BD_RNG_MAX_TENSORS);
     size_t blocks = 0;
     for (int t = 0; t < a->n; ++t) {
-        BD_REQUIRE(a->t[t].p && a->t[t].count > 0 && (a->t[t].kind == BD_RNG_NORMAL || a->t[t].kind == BD_RNG_EXPONENTIAL),
+        BD_REQUIRE(a->t[t].p && a->t[t].count > 0 && (a->t[t].kind == BD_RNG_NORMAL || a->t[t].kind == BD_RNG_EXPONENTIAL || a->t[t].kind == BD_RNG_UNIFORM),
                    "bd_rng_fill: tensor %d: bad descriptor", t);
         blocks += (a->t[t].count + 1023) / 1024;
     }

@@ -316,15 +316,53 @@ class Dreamer:
         return e.act_step(belief, posterior_state, action, obs=obs, embedding=emb, explore=bool(explore),
                           action_noise=self.action_noise, noise=_noise)
 
+    @property
+    def act_fused_cat(self) -> bool:
+        """Whether update_belief_and_act goes through act_step_cat: Categorical latents and / or the Categorical actor at
+        sizes bd_act_step_cat takes, and the switch BD_ACT_FUSED_CAT (default 0, README; read at every call) is 1."""
+        return os.environ.get("BD_ACT_FUSED_CAT", "0") == "1" and self.engine.act_step_cat_supported
+
+    @torch.no_grad()
+    def act_step_cat(self, belief: Tensor, posterior_state: Tensor, action: Tensor, observation: Tensor, explore: bool = False,
+                     _noise: Optional[Dict[str, Tensor]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """act_step for latent_distribution=Categorical and / or action_distribution=Categorical (bd_act_step_cat): the
+        decision of update_belief_and_act without the environment, in one kernel launch.  Pixel observations go through the
+        conv encoder first.  `_noise`: the composed path's keys "post" (B,S), "action" (B,A) and, with explore, "explore"
+        (B,A) (tanh-Normal actor) or "explore_u" (B,) uniforms and "explore_k" (B,) classes (Categorical actor; the kernel
+        gets v = (k + 0.5) / A, whose class is k); "prior" and "entropy" are accepted and ignored.  Without it the draws come
+        from the engine's Philox streams.  The results are engine buffers, valid until the call after the next one."""
+        e, d = self.engine, self.dims
+        if not e.act_step_cat_supported:
+            raise NotImplementedError(
+                "act_step_cat: the fused acting kernel takes Categorical latents and / or the Categorical actor at sizes "
+                f"bd_act_step_cat_supported accepts (latent_distribution={self.latent_distribution}, action_distribution="
+                f"{self.action_distribution}, dims {d.Be}/{d.S}/{d.A}/{d.Hd}/{d.E}); Gaussian latents with the tanh-Normal "
+                "actor use act_step, everything else update_belief_and_act, which composes the step from the scan kernels")
+        obs = observation.to(self.device)
+        emb = None
+        if self.pixel_observation:
+            emb, obs = self.encoder(obs), None
+        nz = _noise
+        if nz is not None:
+            nz = {k: nz[k] for k in ("post", "action")}
+            if explore and d.discrete_actions:
+                u, k = _noise["explore_u"].to(self.device).float(), _noise["explore_k"].to(self.device).float()
+                nz["explore"] = torch.stack([u, (k + 0.5) / d.A], dim=1)
+            elif explore:
+                nz["explore"] = _noise["explore"]
+        return e.act_step_cat(belief, posterior_state, action, obs=obs, embedding=emb, explore=bool(explore),
+                              action_noise=self.action_noise, noise=nz)
+
     @torch.no_grad()
     def update_belief_and_act(self, env, belief, posterior_state, action, observation, explore=False,
                               _noise: Optional[Dict[str, Tensor]] = None):
         """src/planet.py:370-403.  (Data-parallel runs: issues any held-back actor update first -- a collective, call on
-        every rank, as the collect loop does.)  Where act_fused holds the decision is one launch (act_step); the code below
-        composes it from the encoder chain, a one-step observe scan and a one-step imagination otherwise."""
-        if self.act_fused:
-            belief, posterior_state, action = self.act_step(belief, posterior_state, action, observation, explore=explore,
-                                                            _noise=_noise)
+        every rank, as the collect loop does.)  Where act_fused holds the decision is one launch (act_step), and so it is
+        where act_fused_cat holds (act_step_cat; BD_ACT_FUSED_CAT=1, off by default); the code below composes it from the
+        encoder chain, a one-step observe scan and a one-step imagination otherwise."""
+        if self.act_fused or self.act_fused_cat:
+            step = self.act_step if self.act_fused else self.act_step_cat
+            belief, posterior_state, action = step(belief, posterior_state, action, observation, explore=explore, _noise=_noise)
             batched = hasattr(env, "n") and hasattr(env, "envs")          # EnvBatcher (src/env.py:343)
             next_observation, reward, done = env.step(action.cpu() if batched else action[0].cpu())
             return belief, posterior_state, action, next_observation, reward, done

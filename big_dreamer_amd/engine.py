@@ -1047,6 +1047,79 @@ class DreamerEngine:
             cabi.check(lib.bd_act_step(C.byref(a), cabi.stream()))
         return out
 
+    @property
+    def act_step_cat_supported(self) -> bool:
+        """Whether act_step_cat runs this configuration: Categorical latents and / or the Categorical actor at sizes
+        bd_act_step_cat takes (bd_act_step_cat_supported; pixel observations use its embedding form, O = 0).  Gaussian
+        latents with the tanh-Normal actor are act_step's."""
+        d = self.d
+        return ((d.categorical or d.discrete_actions)
+                and bool(lib.bd_act_step_cat_supported(d.Be, d.cat_D, d.cat_C, d.S, d.A, d.Hd, d.E, 0 if self.pixel else d.O,
+                                                       int(d.categorical), int(d.discrete_actions))))
+
+    def act_step_cat(self, belief: torch.Tensor, state: torch.Tensor, action: torch.Tensor, obs: Optional[torch.Tensor] = None,
+                     embedding: Optional[torch.Tensor] = None, explore: bool = False, action_noise: float = 0.0,
+                     noise: Optional[Dict[str, torch.Tensor]] = None):
+        """act_step for Categorical latents and / or the Categorical actor (bd_act_step_cat): one decision for B
+        environments in one launch, same arguments, ordering (flush_optimizers, join) and alternating output sets.
+        noise: {"post" (B,S), "action" (B,A), "explore"}: Exp(1) draws where a Categorical sampler consumes them, standard
+        normals otherwise; "explore" is (B,A) normals for the tanh-Normal actor and (B,2) uniforms (u, v) for the
+        Categorical one (epsilon-greedy: u < action_noise picks class min(floor(v A), A - 1)).  None: the kernel draws
+        from the Philox streams act_post / act_action / act_explore, one counter step per decision (shared with act_step).
+        A Categorical state must be all-zero or one-hot per factor, as for imagine() from a caller's state."""
+        d, pk = self.d, self.pk
+        tm = lambda n: self.W("transition_model", n)
+        self.flush_optimizers()
+        self.join()
+        f = lambda t: t.to(self.dev).float().contiguous()
+        belief, state, action = f(belief), f(state), f(action)
+        B = belief.shape[0]
+        a = cabi.ActCatArgs()
+        a.B, a.Be, a.S, a.A, a.Hd, a.E = B, d.Be, d.S, d.A, d.Hd, d.E
+        a.latent_cat, a.actor_cat = int(d.categorical), int(d.discrete_actions)
+        if embedding is None:
+            a.O, a.obs = d.O, ptr(f(obs).view(B, d.O))
+            for l in range(DENSE_LAYERS + 1):
+                a.w_enc[l], a.b_enc[l] = ptr(pk[f"enc{l}"]), ptr(self.W("encoder", f"model.{2 * l}.bias"))
+        else:
+            a.embedding = ptr(f(embedding).view(B, d.E))
+        self._bind_rssm(a)
+        self._actor_head_args(a)
+        a.w_q1h, a.w_q1e, a.b_q1 = ptr(pk["q1h"]), ptr(pk["q1e"]), ptr(tm("belief_posterior.model.0.bias"))
+        a.b_q2 = ptr(tm("belief_posterior.model.2.bias"))
+        if d.categorical:
+            self._check_cat_start(state.view(B, d.S))
+            a.D, a.C = d.cat_D, d.cat_C
+            a.w_embed_sT, a.w_a0sT, a.w_q2 = ptr(self._plain["embed_sT"][0]), ptr(self._plain["a0sT"][0]), ptr(pk["q2"])
+        else:
+            a.w_embed_s, a.w_a0s = ptr(pk["embed_s"]), ptr(pk["a0s"])
+            a.w_q2m, a.w_q2s = ptr(pk["q2m"]), ptr(pk["q2s"])
+        a.belief, a.state, a.action = ptr(belief), ptr(state), ptr(action)
+        if noise is not None:
+            a.eps_post, a.eps_action = ptr(f(noise["post"]).view(B, d.S)), ptr(f(noise["action"]).view(B, d.A))
+            a.eps_explore = ptr(f(noise["explore"]).view(B, 2 if d.discrete_actions else d.A)) if explore else None
+        else:
+            a.seed, a.step = self.rng_seed, self._rng_step.get("act", 0)
+            self._rng_step["act"] = a.step + 1
+        a.stream_post, a.stream_action, a.stream_explore = (self.RNG_STREAMS[k] for k in ("act_post", "act_action", "act_explore"))
+        a.min_std = self.hp["min_std_dev"]
+        a.act_raw_init_std, a.act_min_std, a.act_mean_scale = ACT_RAW_INIT_STD, ACT_MIN_STD, ACT_MEAN_SCALE
+        a.action_noise, a.explore = float(action_noise), int(bool(explore))
+        # the output set: the one none of the inputs lives in (as act_step; the two share the sets)
+        ins = {belief.data_ptr(), state.data_ptr(), action.data_ptr()}
+        for p in (self._act_parity, 1 - self._act_parity):
+            out = (self.buf(f"act{p}_belief", B, d.Be), self.buf(f"act{p}_state", B, d.S), self.buf(f"act{p}_action", B, d.A))
+            if not ins & {t.data_ptr() for t in out}:
+                break
+        else:       # inputs taken from both sets
+            belief, state, action = belief.clone(), state.clone(), action.clone()
+            a.belief, a.state, a.action = ptr(belief), ptr(state), ptr(action)
+        self._act_parity = 1 - p
+        a.belief_out, a.state_out, a.action_out = (ptr(t) for t in out)
+        with self.span("act_step_cat"):
+            cabi.check(lib.bd_act_step_cat(C.byref(a), cabi.stream()))
+        return out
+
     # ------------------------------------------------------------------------------------------ train step
     def plan(self, belief: torch.Tensor, state: torch.Tensor, horizon: int, iters: int, candidates: int, top: int,
              eps_action: torch.Tensor, eps_state: Optional[torch.Tensor], trace: Optional[list] = None) -> torch.Tensor:

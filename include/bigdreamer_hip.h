@@ -452,6 +452,7 @@ int bd_actor_reinforce_cat(const float* action, const float* act_stats, const fl
 #define BD_RNG_MAX_TENSORS 6
 #define BD_RNG_NORMAL 0
 #define BD_RNG_EXPONENTIAL 1
+#define BD_RNG_UNIFORM 2          /* u = (word >> 8) * 2^-24 in [0, 1): torch.rand of the epsilon-greedy exploration */
 typedef struct {
     int n;
     unsigned long long seed;
@@ -459,7 +460,7 @@ typedef struct {
     struct {
         float* p;
         size_t count;
-        int kind;                 /* BD_RNG_NORMAL | BD_RNG_EXPONENTIAL */
+        int kind;                 /* BD_RNG_NORMAL | BD_RNG_EXPONENTIAL | BD_RNG_UNIFORM */
         unsigned stream_id;       /* distinct per tensor */
     } t[BD_RNG_MAX_TENSORS];
 } bd_rng_fill_args;
@@ -733,6 +734,68 @@ typedef struct {
 } bd_act_args;
 int bd_act_step_supported(int Be, int S, int A, int Hd, int E, int O);
 int bd_act_step(const bd_act_args* a, void* stream);
+
+/* The same decision for the DreamerV2 configurations (csrc/act_cat.hip): latent_distribution="Categorical"
+ * (TransitionModel.forward's Categorical branches, src/models.py:226-228,258-260,269-271, CategoricalBeliefModel
+ * src/models.py:101-117) and / or action_distribution="Categorical" (src/models.py:518-522), one launch, same ownership
+ * as bd_act_step.  latent_cat / actor_cat select one of three instantiations; both 0 is rejected (that is bd_act_step).
+ *   latent_cat: the incoming state [B x S], S = D*C, is all-zero or (scaled) one-hot per factor and is carried as class
+ *     indices (the rule of bd_imagine_cat_forward with start_sidx = NULL); W_es s and the state columns of the actor's first
+ *     layer are gathers of rows of w_embed_sT / w_a0sT (plain [S x out]); the posterior head w_q2 (packed (S, Hd)) gives
+ *     D*C logits, per factor idx = argmax(softmax(logits) / q) with q = eps_post ~ Exp(1), first maximum winning;
+ *     state_out is the one-hot.  latent_cat = 0: Gaussian latents exactly as bd_act_step (w_embed_s, w_q2m / w_q2s, w_a0s,
+ *     eps_post standard normal; D, C ignored).
+ *   actor_cat: the head w_a4m / b_a4 has A <= 64 outputs (w_a4s unused), norm = out - logsumexp(out), p = softmax(norm),
+ *     k = argmax(p / eps_action) with eps_action ~ Exp(1), action = (onehot(k) + p) - p in that order (what
+ *     bd_imagine_forward returns with discrete_actions = 1); explore != 0 is epsilon-greedy (the port's
+ *     update_belief_and_act): eps_explore is [B x 2] uniforms (u, v) in [0, 1), and where u < action_noise the action is
+ *     the exact one-hot of class min(floor(v * A), A - 1).  actor_cat = 0: the tanh-Normal tail of bd_act_step
+ *     (eps_action, eps_explore [B x A] standard normal).
+ * Not evaluated, as in bd_act_step: the prior head and its sample (src/models.py:256), get_action's prior sample and the
+ * actor entropy (src/planet.py:386 drops it) -- none feeds belief, state or action.
+ * Noise: explicit buffers or ALL NULL; in-kernel draws have the element layout of bd_rng_fill on stream_post /
+ * stream_action / stream_explore with the kinds above (BD_RNG_EXPONENTIAL for a Categorical sampler, BD_RNG_UNIFORM for
+ * epsilon-greedy, BD_RNG_NORMAL otherwise).
+ * The host must have checked the incoming one-hot state (a factor with two non-zero classes cannot be carried as an
+ * index; the kernel would take the larger).  LDS as csrc/act_cat.hip states: bd_act_step_cat_supported answers from the
+ * launcher's own arithmetic (O = 0: the embedding form). */
+typedef struct {
+    int B, Be, D, C, S, A, Hd, E, O;
+    int latent_cat, actor_cat;
+    const float* w_enc[5]; const float* b_enc[5];         /* encoder.model.{0,2,4,6,8} (obs form only) */
+    const float* w_embed_s;                               /* Gaussian latents: packed (Be, S) */
+    const float* w_embed_sT;                              /* Categorical latents: plain [S x Be] */
+    const float* w_embed_a; const float* b_embed;
+    const float* w_ir; const float* w_iz; const float* w_in;
+    const float* w_hr; const float* w_hz; const float* w_hn;
+    const float* b_ih; const float* b_hh;
+    const float* w_q1h; const float* w_q1e; const float* b_q1;
+    const float* w_q2m; const float* w_q2s;               /* Gaussian latents: belief_posterior.model.2 rows [:S] / [S:] */
+    const float* w_q2;                                    /* Categorical latents: packed (S, Hd) */
+    const float* b_q2;                                    /* [2*S] / [S] */
+    const float* w_a0h;
+    const float* w_a0s;                                   /* Gaussian latents: packed (Hd, S) */
+    const float* w_a0sT;                                  /* Categorical latents: plain [S x Hd] */
+    const float* w_a[3]; const float* b_a[4];
+    const float* w_a4m; const float* w_a4s; const float* b_a4;   /* as bd_imagine_fwd_args (discrete_actions = actor_cat) */
+    const float* belief;       /* [B x Be] */
+    const float* state;        /* [B x S]  */
+    const float* action;       /* [B x A]  previous action */
+    const float* obs;          /* [B x O] or NULL */
+    const float* embedding;    /* [B x E] or NULL (exactly one of obs / embedding) */
+    const float* eps_post;     /* [B x S] */
+    const float* eps_action;   /* [B x A] */
+    const float* eps_explore;  /* [B x A], or [B x 2] with actor_cat; may be NULL when explore = 0 */
+    unsigned long long seed; unsigned long long step;
+    unsigned stream_post, stream_action, stream_explore;
+    float min_std, act_raw_init_std, act_min_std, act_mean_scale, action_noise;
+    int explore;
+    float* belief_out;         /* [B x Be] */
+    float* state_out;          /* [B x S]  */
+    float* action_out;         /* [B x A]  */
+} bd_act_cat_args;
+int bd_act_step_cat_supported(int Be, int D, int C, int S, int A, int Hd, int E, int O, int latent_cat, int actor_cat);
+int bd_act_step_cat(const bd_act_cat_args* a, void* stream);
 
 /* ---- losses (src/planet.py:252-284, src/dreamer.py:110-146,342-383) ---------------------------
  * Reductions write RAW SUMS into a small device "scalar board" (float array); the host turns them
