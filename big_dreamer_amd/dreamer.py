@@ -5,7 +5,7 @@ Kept surface: ``Dreamer(params, env)``, ``train_step() ->
 ``eval()/train()``, ``observation_model(h, s)``, module attributes with reference ``state_dict`` names, ``load``
 of the reference's checkpoint dict (src/planet.py:103-114), and the module function ``lambda_return``.
 Added: ``act_step`` -- the decision of ``update_belief_and_act`` (src/planet.py:370-403, src/dreamer.py:429-444) without the
-environment, one kernel launch (bd_act_step).
+environment, one kernel launch (bd_act_step); ``evaluate`` -- the test loop of the reference's src/main.py:191-283.
 """
 from __future__ import annotations
 
@@ -392,6 +392,20 @@ class Dreamer:
         batched = hasattr(env, "n") and hasattr(env, "envs")          # EnvBatcher (src/env.py:343)
         next_observation, reward, done = env.step(action.cpu() if batched else action[0].cpu())
         return belief, posterior_state, action, next_observation, reward, done
+
+    # ---------------------------------------------------------------------------------------- evaluation
+    def evaluate(self, envs=None, episodes: Optional[int] = None, video: bool = False, _noise=None) -> Dict[str, Any]:
+        """The reference's test loop (src/main.py:191-283; evaluate.run_evaluation): `episodes` (default
+        ``test_episodes``) environments side by side for at most max_episode_length // action_repeat decisions without
+        exploration noise.  Returns Eval_{min,avg,max,std}_return, ``returns``, ``steps`` and ``video`` -- uint8 (steps, 3,
+        GH, GW) real-vs-predicted frames, pixel observations only, else None.  `envs`: an EnvBatcher to use instead of a
+        fresh one.  Data-parallel runs: update_belief_and_act carries collectives, so every rank calls this."""
+        from .env import Env, EnvBatcher
+        from .evaluate import run_evaluation
+        if envs is None:
+            envs = EnvBatcher(Env, self.params, int(episodes or self.params["test_episodes"]))
+        max_steps = int(self.params["max_episode_length"]) // int(self.action_repeat)
+        return run_evaluation(self, envs, max_steps, video=bool(video) and self.pixel_observation, _noise=_noise)
 
 
 class DreamerV2(Dreamer):

@@ -729,6 +729,25 @@ class DreamerEngine:
         from . import conv as _conv
         return _conv.to_nchw(self.conv.decode(feat.contiguous().float(), tag="api_"))
 
+    def eval_frame(self, obs4d: torch.Tensor, belief: torch.Tensor, state: torch.Tensor, video: torch.Tensor, t: int) -> None:
+        """Frame `t` of the evaluation video (src/main.py:237-253; evaluate.run_evaluation): the observations (n,3,64,64) a
+        decision consumed, already on the device, next to ObservationModel(belief, state), as bytes, in one launch
+        (bd_eval_frame) that reads the decoder's output in the conv stack's own NHWC buffer.  video: device uint8
+        (frames, 3, GH, GW), evaluate.frame_shape(n).  Like the modules' forward(): join(), no collectives."""
+        from .evaluate import frame_shape
+        if not self.pixel:
+            raise ValueError("eval_frame: the video pairs pixel observations with the decoder's images (pixel_observation)")
+        n = obs4d.shape[0]
+        if not (obs4d.is_cuda and obs4d.dtype == torch.float32 and tuple(obs4d.shape) == (n, 3, 64, 64)):
+            raise ValueError(f"eval_frame: observations must be device fp32 (n, 3, 64, 64), got {tuple(obs4d.shape)} {obs4d.dtype}")
+        if not (video.dtype == torch.uint8 and video.dim() == 4 and tuple(video.shape[1:]) == frame_shape(n)
+                and video.is_contiguous()):
+            raise ValueError(f"eval_frame: video must be contiguous uint8 (frames,) + {frame_shape(n)}, got {tuple(video.shape)}")
+        self.join()
+        feat = torch.cat([belief, state], dim=1).to(self.dev).float().contiguous()
+        dec = self.conv.decode(feat, tag="api_")
+        cabi.check(lib.bd_eval_frame(ptr(obs4d.contiguous()), ptr(dec), n, ptr(video), video.shape[0], int(t), cabi.stream()))
+
     def _bind_rssm(self, a) -> None:
         """Embed (action half, bias) and GRU weights of a forward scan's arguments: observe, imagine and plan, both latent
         families.  The state half of the embed layer differs by family and stays with the caller."""

@@ -1,6 +1,7 @@
 """Environment surface the agent needs (src/planet.py:36,91,147-158): ``action_size``, ``observation_size``,
 ``reset/step/sample_random_action/close``.  gym / mujoco are not installed in the build image, so the CLI
-falls back to a small synthetic control task with the same interface; any object with this interface works."""
+falls back to a small synthetic control task with the same interface; any object with this interface works.
+``EnvBatcher`` (src/env.py:343-394) steps several of them side by side for the evaluation loop."""
 from __future__ import annotations
 
 import numpy as np
@@ -130,3 +131,36 @@ def Env(params):
     return SyntheticEnv(int(params.get("synthetic_env_observation_size", 3)),
                         int(params.get("synthetic_env_action_size", 1)), int(params["max_episode_length"]),
                         int(params["action_repeat"]), int(params["seed"]))
+
+
+class EnvBatcher:
+    """`n` environments stepped side by side (src/env.py:343-394): what the evaluation loop hands to
+    ``update_belief_and_act`` in place of a single environment.  An environment that has finished stays finished; from the
+    call after the one it finished in, its observation and reward rows are zero."""
+
+    def __init__(self, env_class, env_params, n: int):
+        self.n = n
+        self.envs = [env_class(env_params) for _ in range(n)]
+        self.dones = [True] * n
+
+    def reset(self) -> torch.Tensor:
+        observations = [env.reset() for env in self.envs]
+        self.dones = [False] * self.n
+        return torch.cat(observations)
+
+    def step(self, actions):
+        """actions: one row per environment.  Every environment is stepped, finished ones included.  Returns
+        (observations concatenated along dim 0, rewards float32 (n,), dones uint8 (n,))."""
+        finished = list(self.dones)           # as they were BEFORE this call: the row that finishes now keeps its values
+        observations, rewards, dones = zip(*[env.step(action) for env, action in zip(self.envs, actions)])
+        self.dones = [bool(d) or prev for d, prev in zip(dones, finished)]
+        observations = torch.cat(observations)
+        rewards = torch.tensor(rewards, dtype=torch.float32)
+        blank = torch.tensor(finished, dtype=torch.bool)
+        observations[blank] = 0
+        rewards[blank] = 0
+        return observations, rewards, torch.tensor(self.dones, dtype=torch.uint8)
+
+    def close(self) -> None:
+        for env in self.envs:
+            env.close()

@@ -195,6 +195,17 @@ size_t bd_colsum_ws_floats(int N);
 int bd_colsum(const float* rows, size_t M, int N, float* out, float* ws, void* stream);
 /* (imgs, C, HW) -> (imgs, HW, C) when to_nhwc, the reverse otherwise */
 int bd_image_layout(const float* src, float* dst, int imgs, int C, int HW, int to_nhwc, void* stream);
+/* Evaluation video (src/main.py:237-253): frame t of `video`, a device uint8 buffer of `frames` frames (3, GH, GW), 4-byte
+ * aligned = make_grid(cat([obs, prediction], dim=3) + 0.5, nrow=5) as bytes, one launch.
+ *   obs (n, 3, 64, 64) NCHW fp32: the observations the decision consumed, as uploaded for the encoder;
+ *   dec (n, 64, 64, 3) NHWC fp32: the decoder's output where the conv stack leaves it (no layout pass in between).
+ * A tile is 3 x 64 x 128 (real in columns 0-63, predicted in 64-127).  n == 1: the frame is the tile (GH = 64, GW = 128).
+ * Otherwise xmaps = min(5, n), ymaps = ceil(n / xmaps), GH = 66 ymaps + 2, GW = 130 xmaps + 2, tile k starts at row
+ * (k / xmaps) 66 + 2, column (k % xmaps) 130 + 2, and every other byte is 0.  A pixel is
+ * uint8(clip(floor((v + 0.5) * 256), 0, 255)) in fp32 arithmetic (postprocess_observation(., 8), src/utils.py:320-337).
+ * Every byte of the frame is written, padding included (the buffer needs no clearing); no other frame is touched.
+ * n <= 4096, 0 <= t < frames. */
+int bd_eval_frame(const float* obs, const float* dec, int n, unsigned char* video, int frames, int t, void* stream);
 
 /* ---- RSSM observe scan: TransitionModel.forward with embeddings (src/models.py:191-299) ------
  * One persistent launch walks all T steps; a workgroup owns 16 batch rows (rows are independent, so

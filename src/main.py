@@ -4,6 +4,8 @@
 Collect-update loop: every ``environment_steps_per_update`` env steps run ``collect_interval`` train steps
 (src/main.py:103-108), critic-target update cadence as at src/main.py:110-112, one env step with exploration
 noise (src/main.py:129-143), append to the replay buffer (src/main.py:146), log every ``log_freq``.
+``evaluation=true``: every ``test_interval`` steps the test loop (src/main.py:191-283) runs ``test_episodes`` environments
+without exploration noise and prints ``Eval_{min,avg,max,std}_return``; ``test=true`` evaluates once and exits.
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N src/main.py ...``; each rank collects
 its own experience and the gradients are all-reduced over RCCL (big_dreamer_amd/engine.py).
 """
@@ -19,6 +21,21 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from big_dreamer_amd.config import load_config  # noqa: E402
+
+
+def evaluate(model, params, step, rank):
+    """The test half of the reference's loop (src/main.py:191-283).  update_belief_and_act carries collectives in
+    data-parallel runs, so every rank evaluates; rank 0 prints and saves."""
+    video = (bool(params["pixel_observation"]) and params["log_video_freq"] not in (-1, 0)
+             and step % params["log_video_freq"] == 0)
+    result = model.evaluate(episodes=params["test_episodes"], video=video)
+    if rank != 0:
+        return
+    for key in ("Eval_min_return", "Eval_avg_return", "Eval_max_return", "Eval_std_return"):
+        print(f"{key} : {result[key]}", flush=True)
+    if result["video"] is not None and params["eval_video_dir"]:
+        os.makedirs(params["eval_video_dir"], exist_ok=True)
+        np.save(os.path.join(params["eval_video_dir"], f"Eval_rollout_{step}.npy"), result["video"])
 
 
 def my_app(argv):
@@ -41,6 +58,10 @@ def my_app(argv):
     agent_cls = {"planet": Planet, "dreamer": Dreamer, "dreamerV2": DreamerV2}[params["algorithm"]]
     model = agent_cls(params, env, world_size=world)
     torch.manual_seed(params["seed"] + rank)
+    if params["test"]:                                # evaluate the agent as built (models= loads a checkpoint) and stop
+        evaluate(model, params, 0, rank)
+        env.close()
+        return
     env_steps, num_episodes = model.randomly_initialize_replay_buffer()
     if rank == 0:
         print(f"Initialized with {num_episodes} episodes and {env_steps} steps")
@@ -73,6 +94,8 @@ def my_app(argv):
             logs["env_update_per_sec"] = params["log_freq"] / max(time.time() - past, 1e-9)
             past = time.time()
             print(step, {k: (round(v, 5) if isinstance(v, float) else v) for k, v in logs.items()}, flush=True)
+        if params["evaluation"] and step % params["test_interval"] == 0:
+            evaluate(model, params, step, rank)
     env.close()
 
 
