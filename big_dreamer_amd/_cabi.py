@@ -215,6 +215,12 @@ class ConvArgs(C.Structure):
                 ("act", I32), ("fuse_cq", I32), ("aux", P)]
 
 
+class ReplayAppendArgs(C.Structure):
+    _fields_ = [("n", I32), ("size", I32), ("rows", P), ("obs", P), ("obs_width", I32), ("bit_depth", I32),
+                ("dst_obs", P), ("act", P), ("A", I32), ("dst_act", P), ("reward", P), ("nonterminal", P),
+                ("dst_reward", P), ("dst_nonterminal", P)]
+
+
 # every symbol include/bigdreamer_hip.h declares, with its signature
 _SIGS = {
     "bd_last_error": (C.c_char_p, []),
@@ -285,6 +291,7 @@ _SIGS = {
     "bd_replay_gather": (I32, [P, P, I32, I32, P, P]),
     "bd_replay_gather_pixels": (I32, [P, P, I32, I32, I32, P, P, P]),
     "bd_replay_gather_pixels_rng": (I32, [P, P, I32, I32, I32, C.c_ulonglong, C.c_ulonglong, P, P]),
+    "bd_replay_append": (I32, [C.POINTER(ReplayAppendArgs), P]),
     "bd_reduce_ws_floats": (C.c_size_t, []),
     "bd_conv_gemm": (I32, [C.POINTER(ConvArgs), P]),
     "bd_conv_thin_forward": (I32, [P, I32, I32, I32, I32, I32, P, I32, P, I32, P, P, P]),

@@ -16,6 +16,7 @@ import torch
 from torch import Tensor
 
 from . import _cabi as cabi
+from .collect import check_collect_envs
 from .engine import (DreamerEngine, check_action_distribution, check_cnn_activation, check_dense_activation,
                      check_gradient_mixing)
 from .memory import ExperienceReplay
@@ -54,6 +55,7 @@ class Dreamer:
         if self.action_distribution == "Categorical" and params.get("algorithm") == "planet":
             raise ValueError("action_distribution=Categorical: PlaNet's CEM planner searches a continuous action space")
         self.use_discount = bool(params.get("use_discount", False))
+        self.collect_envs = check_collect_envs(params)     # replay lanes (collect.py); 1: the reference's single ring
         if params.get("disable_cuda", False) or not torch.cuda.is_available():
             raise RuntimeError("big_dreamer_amd runs on MI355X only: there is no CPU path (disable_cuda=True is the "
                                "reference's own CPU mode)")
@@ -122,7 +124,7 @@ class Dreamer:
         if self.use_discount:       # src/dreamer.py:80-85
             self.discount_model = DenseModel(feat, self.hidden_size, 1, engine=e, module="discount_model", prefix="dsc")
         self.buffer = ExperienceReplay(params["experience_size"], env.action_size, params["bit_depth"], px,
-                                       env.observation_size, self.device)
+                                       env.observation_size, self.device, lanes=self.collect_envs)
         self.load(params)
 
     # ---------------------------------------------------------------------------------------- checkpoints

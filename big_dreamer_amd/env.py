@@ -1,7 +1,8 @@
 """Environment surface the agent needs (src/planet.py:36,91,147-158): ``action_size``, ``observation_size``,
 ``reset/step/sample_random_action/close``.  gym / mujoco are not installed in the build image, so the CLI
 falls back to a small synthetic control task with the same interface; any object with this interface works.
-``EnvBatcher`` (src/env.py:343-394) steps several of them side by side for the evaluation loop."""
+``EnvBatcher`` (src/env.py:343-394) steps several of them side by side for the evaluation loop, ``VecEnv`` for the collect
+loop (auto-reset)."""
 from __future__ import annotations
 
 import numpy as np
@@ -160,6 +161,40 @@ class EnvBatcher:
         observations[blank] = 0
         rewards[blank] = 0
         return observations, rewards, torch.tensor(self.dones, dtype=torch.uint8)
+
+    def close(self) -> None:
+        for env in self.envs:
+            env.close()
+
+
+class VecEnv:
+    """`n` environments stepped side by side for COLLECTING (``collect_envs``): unlike EnvBatcher, an environment that
+    finishes is reset in the same call, so every row always carries a live episode.  Environment e is built from
+    ``dict(env_params, seed=env_params["seed"] + e)``, so that the synthetic tasks do not run in unison.
+    ``update_belief_and_act`` recognises it as a batched environment by ``n`` and ``envs``."""
+
+    def __init__(self, env_class, env_params, n: int):
+        self.n = int(n)
+        self.envs = [env_class(dict(env_params, seed=env_params["seed"] + e)) for e in range(self.n)]
+        self.action_size, self.observation_size = self.envs[0].action_size, self.envs[0].observation_size
+
+    def reset(self) -> torch.Tensor:
+        return torch.cat([env.reset() for env in self.envs])
+
+    def sample_random_action(self) -> torch.Tensor:
+        return torch.stack([torch.as_tensor(env.sample_random_action()) for env in self.envs])
+
+    def step(self, actions):
+        """actions: one row per environment.  Returns (observations (n, ...), rewards float32 (n,), dones bool (n,)).
+        An environment that finishes in this call is reset in this call: its observation row is the reset observation (the
+        first of its next episode) and its `done` is True for this call only."""
+        observations, rewards, dones = [], [], []
+        for env, action in zip(self.envs, actions):
+            observation, reward, done = env.step(action)
+            observations.append(env.reset() if done else observation)
+            rewards.append(reward)
+            dones.append(bool(done))
+        return torch.cat(observations), torch.tensor(rewards, dtype=torch.float32), torch.tensor(dones, dtype=torch.bool)
 
     def close(self) -> None:
         for env in self.envs:

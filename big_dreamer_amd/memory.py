@@ -3,7 +3,11 @@ the storage mirrored in HBM and the batch gather done by a HIP kernel (bd_replay
 ``sample`` returns device tensors without a host-side gather or a bulk H2D copy.
 
 Pixel observations are kept as uint8 (5-bit quantised frames, as the reference stores them) and de-quantised on
-the device by bd_replay_gather_pixels; the dequantisation noise is drawn by torch's device generator."""
+the device by bd_replay_gather_pixels; the dequantisation noise is drawn by torch's device generator.
+
+``lanes=N`` splits the ring into N lanes for collecting from N environments at once: lane e owns rows
+[e * lane_size, (e + 1) * lane_size), ``append_batch`` writes one transition per lane (one bd_replay_append launch keeps
+the mirror in step) and ``_sample_idx`` draws every chunk inside one lane ("Laned replay")."""
 from __future__ import annotations
 
 import numpy as np
@@ -13,9 +17,13 @@ from . import _cabi as cabi
 
 
 class ExperienceReplay:
-    def __init__(self, size, action_size, bit_depth, pixel_observation, observation_size, device):
+    def __init__(self, size, action_size, bit_depth, pixel_observation, observation_size, device, lanes=1):
         self.device = torch.device(device)
         self.size = size
+        self.lanes = int(lanes)
+        if self.lanes < 1 or size // self.lanes < 1:
+            raise ValueError(f"ExperienceReplay: {size} rows cannot be split into {lanes} lanes")
+        self.lane_size = size // self.lanes     # lane e owns rows [e * lane_size, (e + 1) * lane_size); the rest is unused
         self.pixel_observation = pixel_observation
         self.bit_depth = bit_depth
         if pixel_observation:
@@ -35,9 +43,14 @@ class ExperienceReplay:
         self._pix_seed, self._pix_step = None, 0
         self._ring = []           # pinned staging buffers for the index upload (async H2D, no host stall)
         self._ring_i = 0
+        self._stage = []          # pinned staging buffers of append_batch: [rows | rewards | nonterminals | actions | obs]
+        self._stage_i = 0
 
     # -- reference semantics (src/memory.py:33-49) --
     def append(self, observation, action, reward, done):
+        if self.lanes > 1:
+            raise ValueError(f"ExperienceReplay.append: this buffer has {self.lanes} lanes, which advance in lock step; "
+                             "use append_batch with one transition per lane")
         to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
         if self.pixel_observation:
             # postprocess_observation (src/utils.py:320-337): [-0.5, 0.5] float -> quantised uint8
@@ -59,8 +72,109 @@ class ExperienceReplay:
         self.full = self.full or self.idx == 0
         self.steps, self.episodes = self.steps + 1, self.episodes + (1 if done else 0)
 
+    def append_batch(self, observations, actions, rewards, dones, *, observations_device=None, actions_device=None):
+        """One transition per lane: row e of the inputs -- ``(lanes, ...)`` host tensors or arrays, as the environments
+        return them -- goes to row ``e * lane_size + idx`` of the host arrays with the arithmetic of ``append``
+        (observations are taken as float32), then the shared head advances.
+
+        Where the device mirror exists and is clean, one pinned staging upload ([rows | rewards | nonterminals], plus the
+        action / observation rows that are not on the device yet) and ONE bd_replay_append launch write the same rows of the
+        mirror.  `observations_device` / `actions_device` are the copies that already sit on the device -- the batch
+        uploaded for the encoder (pixels: NCHW in [-0.5, 0.5], quantised by the kernel) and the action the acting step
+        returned; the caller vouches that they hold what `observations` / `actions` hold.  Either way the mirror and the host
+        arrays hold the same bits afterwards.  The upload and the kernel are enqueued on the current stream
+        (``_cabi.stream()``), the stream on which ``sample`` enqueues its gathers, so a later ``sample`` sees the rows in
+        order without a synchronisation."""
+        to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        n, ls = self.lanes, self.lane_size
+        o = np.asarray(to_np(observations), dtype=np.float32)
+        a = np.asarray(to_np(actions), dtype=np.float32)
+        r = np.asarray(to_np(rewards), dtype=np.float32).reshape(-1)
+        d = np.asarray(to_np(dones)).astype(bool).reshape(-1)
+        for name, v in (("observations", o), ("actions", a), ("rewards", r), ("dones", d)):
+            if v.ndim < 1 or v.shape[0] != n:
+                raise ValueError(f"ExperienceReplay.append_batch: {name} has {v.shape[0] if v.ndim else 0} rows, "
+                                 f"the buffer has {n} lanes")
+        o, a = o.reshape((n,) + self.observations.shape[1:]), a.reshape(n, self.actions.shape[1])
+        rows = np.arange(n, dtype=np.int64) * ls + self.idx
+        if self.pixel_observation:
+            self.observations[rows] = np.clip(np.floor((o + 0.5) * 2 ** self.bit_depth) * 2 ** (8 - self.bit_depth),
+                                              0, 2 ** 8 - 1).astype(np.uint8)
+        else:
+            self.observations[rows] = o
+        self.actions[rows] = a
+        self.rewards[rows] = r
+        self.nonterminals[rows, 0] = ~d
+        if self._dev is not None and not self._dirty:
+            self._append_device(rows, o, a, observations_device, actions_device)
+        self.idx = (self.idx + 1) % ls
+        self.full = self.full or self.idx == 0
+        self.steps, self.episodes = self.steps + n, self.episodes + int(d.sum())
+
+    def _device_source(self, t, numel, name):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == numel):
+            raise ValueError(f"ExperienceReplay.append_batch: {name} must be a CUDA float32 tensor of {numel} elements")
+        return t if t.is_contiguous() else t.contiguous()
+
+    def _append_device(self, rows, o, a, observations_device, actions_device):
+        n, A = self.lanes, self.actions.shape[1]
+        width = self.observations[0].size
+        act_at = 3 * n
+        obs_at = (act_at + n * A + 3) // 4 * 4            # 16-byte aligned: the pixel path loads four floats at once
+        words = obs_at + n * width
+        if not self._stage:
+            self._stage = [(torch.empty(words, dtype=torch.int32).pin_memory(),
+                            torch.empty(words, dtype=torch.int32, device=self.device),
+                            torch.cuda.Event()) for _ in range(4)]
+            self._stage_i = 0
+        pinned, dev, ev = self._stage[self._stage_i]
+        self._stage_i = (self._stage_i + 1) % len(self._stage)
+        ev.synchronize()                       # the copy that last used this pinned buffer has completed
+        host = pinned.numpy()
+        host[:n] = rows
+        fhost = host.view(np.float32)
+        fhost[n:2 * n] = self.rewards[rows]
+        fhost[2 * n:3 * n] = self.nonterminals[rows, 0]
+        used = 3 * n
+        obs_src = act_src = None
+        if actions_device is not None:
+            act_src = self._device_source(actions_device, n * A, "actions_device")
+        if observations_device is not None:
+            obs_src = self._device_source(observations_device, n * width, "observations_device")
+        if act_src is None or obs_src is None:             # (the action rows ride along with an observation upload)
+            fhost[act_at:act_at + n * A] = a.reshape(-1)
+            used = act_at + n * A
+        if obs_src is None:
+            fhost[obs_at:words] = o.reshape(-1)
+            used = words
+        dev[:used].copy_(pinned[:used], non_blocking=True)
+        ev.record()
+        base = dev.data_ptr()
+        args = cabi.ReplayAppendArgs()
+        args.n, args.size, args.rows = n, self.size, base
+        args.obs = obs_src.data_ptr() if obs_src is not None else base + 4 * obs_at
+        args.obs_width, args.bit_depth = width, (self.bit_depth if self.pixel_observation else 0)
+        args.dst_obs = self._dev["observations"].data_ptr()
+        args.act = act_src.data_ptr() if act_src is not None else base + 4 * act_at
+        args.A, args.dst_act = A, self._dev["actions"].data_ptr()
+        args.reward, args.nonterminal = base + 4 * n, base + 8 * n
+        args.dst_reward, args.dst_nonterminal = self._dev["rewards"].data_ptr(), self._dev["nonterminals"].data_ptr()
+        cabi.check(cabi.lib.bd_replay_append(args, cabi.stream()))
+
     def _sample_idx(self, L):
-        """src/memory.py:51-68: uniform start, rejected if the chunk crosses the write head."""
+        """src/memory.py:51-68: uniform start, rejected if the chunk crosses the write head.  With lanes the same rule
+        inside one uniformly drawn lane (lane-local head, wrap at lane_size)."""
+        if self.lanes > 1:
+            ls = self.lane_size
+            if not self.full and self.idx <= L:
+                raise ValueError(f"ExperienceReplay: each of the {self.lanes} lanes holds {self.idx} transitions, a chunk "
+                                 f"of {L} needs more (seed more steps, or collect from fewer environments)")
+            while True:
+                lane = np.random.randint(0, self.lanes)
+                start = np.random.randint(0, ls if self.full else self.idx - L)
+                local = np.arange(start, start + L) % ls
+                if not self.idx in local[1:]:
+                    return lane * ls + local
         valid_idx = False
         while not valid_idx:
             idx = np.random.randint(0, self.size if self.full else self.idx - L)

@@ -857,6 +857,35 @@ int bd_replay_gather_pixels(const unsigned char* src, const int64_t* idx, int n_
 int bd_replay_gather_pixels_rng(const unsigned char* src, const int64_t* idx, int n_idx, int pixels, int bit_depth,
                                 unsigned long long seed, unsigned long long step, float* dst, void* stream);
 
+/* ---- replay append: ExperienceReplay.append (src/memory.py:33-49) for n environments at once (csrc/replay.hip) ----
+ * ONE launch writes n transitions into the device mirror of the replay buffer: transition i goes to row rows[i] of the
+ * four arrays.  The sources are read where they already are on the device -- the observation batch uploaded for the
+ * encoder, the action the acting step returned.
+ *   bit_depth = 0: state observations, obs [n x obs_width] fp32 copied into dst_obs (float [size x obs_width]);
+ *   bit_depth = 1 .. 8: pixels, obs [n x obs_width] fp32 in [-0.5, 0.5] (NCHW, obs_width = 3*64*64), dst_obs unsigned
+ *     char [size x obs_width]; a byte is uint8(clip(floor((v + 0.5) * 2^bits) * 2^(8 - bits), 0, 255)), every operation
+ *     rounded to fp32 on its own (postprocess_observation, src/utils.py:320-337): bit for bit what the host path stores.
+ *     obs_width is a multiple of 4, obs 16-byte and dst_obs 4-byte aligned (four values per lane, one dword store).
+ * The caller guarantees distinct rows.  A row outside [0, size) writes nothing (a guard: there is no device-side error
+ * word).  Asynchronous on `stream`; never allocates, never synchronises.  1 <= n <= 4096. */
+typedef struct {
+    int n;                       /* transitions in this call */
+    int size;                    /* rows of the mirror */
+    const int32_t* rows;         /* [n] destination row of each transition */
+    const float* obs;            /* [n x obs_width] */
+    int obs_width;
+    int bit_depth;               /* 0: fp32 copy; 1 .. 8: quantise to bytes */
+    void* dst_obs;               /* float* (bit_depth = 0) or unsigned char* [size x obs_width] */
+    const float* act;            /* [n x A] */
+    int A;
+    float* dst_act;              /* [size x A] */
+    const float* reward;         /* [n] */
+    const float* nonterminal;    /* [n] */
+    float* dst_reward;           /* [size] */
+    float* dst_nonterminal;      /* [size] */
+} bd_replay_append_args;
+int bd_replay_append(const bd_replay_append_args* a, void* stream);
+
 size_t bd_reduce_ws_floats(void);
 
 #ifdef __cplusplus

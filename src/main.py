@@ -6,6 +6,8 @@ Collect-update loop: every ``environment_steps_per_update`` env steps run ``coll
 noise (src/main.py:129-143), append to the replay buffer (src/main.py:146), log every ``log_freq``.
 ``evaluation=true``: every ``test_interval`` steps the test loop (src/main.py:191-283) runs ``test_episodes`` environments
 without exploration noise and prints ``Eval_{min,avg,max,std}_return``; ``test=true`` evaluates once and exits.
+``collect_envs=n`` (n > 1) collects from n environments side by side (big_dreamer_amd/collect.py): one loop iteration is one
+decision for all of them = n environment steps, with the same update-to-data ratio.
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N src/main.py ...``; each rank collects
 its own experience and the gradients are all-reduced over RCCL (big_dreamer_amd/engine.py).
 """
@@ -38,6 +40,41 @@ def evaluate(model, params, step, rank):
         np.save(os.path.join(params["eval_video_dir"], f"Eval_rollout_{step}.npy"), result["video"])
 
 
+def collect_many(model, env, params, rank):
+    """The collect-update loop for ``collect_envs = n > 1``: one iteration is one Collector.step() = n environment steps
+    [step, step + n).  Every multiple of ``environment_steps_per_update`` in that range runs one burst of
+    ``collect_interval`` train steps, so the update-to-data ratio stays that of the reference; update_critic is called once
+    per iteration if any step of the range is not a multiple of ``slow_critic_update_interval`` (the reference's inverted
+    cadence, src/main.py:110-112); logging and evaluation fire when a multiple of log_freq / test_interval falls in it."""
+    from big_dreamer_amd.collect import Collector
+    n = env.n
+    collector = Collector(model, env)
+    env_steps, num_episodes = collector.seed(params["seed_steps"])
+    if rank == 0:
+        print(f"Initialized with {num_episodes} episodes and {env_steps} steps")
+    logs, past, logged = {}, time.time(), env_steps
+    slow = params["ActorCritic"]["slow_critic_update_interval"]
+    for step in range(env_steps, params["train_steps"], n):
+        steps = range(step, step + n)
+        for _ in range(sum(1 for s in steps if s % params["environment_steps_per_update"] == 0)):
+            t0 = time.time()
+            for _ in range(params["collect_interval"]):
+                logs = model.train_step()
+            logs["weight_update_per_sec"] = params["collect_interval"] / (time.time() - t0)
+        if params["algorithm"] != "planet" and any(s % slow for s in steps):
+            model.update_critic()
+        collector.step(explore=True)
+        if collector.finished_returns:
+            logs["episode_total_reward"] = collector.finished_returns[-1]
+        if any(s % params["log_freq"] == 0 for s in steps) and rank == 0:
+            logs["env_update_per_sec"] = (step + n - logged) / max(time.time() - past, 1e-9)
+            past, logged = time.time(), step + n
+            print(step, {k: (round(v, 5) if isinstance(v, float) else v) for k, v in logs.items()}, flush=True)
+        if params["evaluation"] and any(s % params["test_interval"] == 0 for s in steps):
+            evaluate(model, params, step, rank)
+    env.close()
+
+
 def my_app(argv):
     params = load_config(argv)
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -53,14 +90,18 @@ def my_app(argv):
     torch.cuda.set_stream(torch.cuda.Stream())        # stay off the legacy null stream
     from big_dreamer_amd.dreamer import Dreamer, DreamerV2
     from big_dreamer_amd.planet import Planet
-    from big_dreamer_amd.env import Env
-    env = Env(params)
+    from big_dreamer_amd.env import Env, VecEnv
+    n_envs = int(params["collect_envs"])
+    env = Env(params) if n_envs == 1 else VecEnv(Env, params, n_envs)
     agent_cls = {"planet": Planet, "dreamer": Dreamer, "dreamerV2": DreamerV2}[params["algorithm"]]
     model = agent_cls(params, env, world_size=world)
     torch.manual_seed(params["seed"] + rank)
     if params["test"]:                                # evaluate the agent as built (models= loads a checkpoint) and stop
         evaluate(model, params, 0, rank)
         env.close()
+        return
+    if n_envs > 1:
+        collect_many(model, env, params, rank)
         return
     env_steps, num_episodes = model.randomly_initialize_replay_buffer()
     if rank == 0:
