@@ -301,6 +301,8 @@ _SIGS = {
     "bd_elu_backward": (I32, [P, P, C.c_size_t, P]),
     "bd_image_layout": (I32, [P, P, I32, I32, I32, I32, P]),
     "bd_eval_frame": (I32, [P, P, I32, U8P, I32, I32, P]),
+    "bd_openl_video": (I32, [P, P, I32, I32, U8P, P]),
+    "bd_openl_error": (I32, [P, P, I32, I32, I32, I32, P, P]),
     "bd_colsum_ws_floats": (C.c_size_t, [I32]),
     "bd_colsum": (I32, [P, C.c_size_t, I32, P, P, P]),
 }

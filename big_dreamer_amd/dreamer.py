@@ -5,7 +5,8 @@ Kept surface: ``Dreamer(params, env)``, ``train_step() ->
 ``eval()/train()``, ``observation_model(h, s)``, module attributes with reference ``state_dict`` names, ``load``
 of the reference's checkpoint dict (src/planet.py:103-114), and the module function ``lambda_return``.
 Added: ``act_step`` -- the decision of ``update_belief_and_act`` (src/planet.py:370-403, src/dreamer.py:429-444) without the
-environment, one kernel launch (bd_act_step); ``evaluate`` -- the test loop of the reference's src/main.py:191-283.
+environment, one kernel launch (bd_act_step); ``evaluate`` -- the test loop of the reference's src/main.py:191-283; ``open_loop`` -- the
+open-loop prediction video and error curve of DreamerV1 / DreamerV2 (openloop.py).
 """
 from __future__ import annotations
 
@@ -408,6 +409,25 @@ class Dreamer:
             envs = EnvBatcher(Env, self.params, int(episodes or self.params["test_episodes"]))
         max_steps = int(self.params["max_episode_length"]) // int(self.action_repeat)
         return run_evaluation(self, envs, max_steps, video=bool(video) and self.pixel_observation, _noise=_noise)
+
+    # ---------------------------------------------------------------------------------------- open-loop prediction
+    def open_loop(self, batch=None, sequences: int = 6, context: int = 5, video: Optional[bool] = None,
+                  _noise=None) -> Dict[str, Any]:
+        """The open-loop prediction diagnostic (DreamerV1's image_summaries, DreamerV2's video_pred; openloop.run_open_loop):
+        `sequences` replay sequences of ``seq_len`` records are filtered on their first `context` steps, then the prior runs
+        on on the recorded actions alone, and every step is decoded.  Returns ``openl_obs_mse`` -- (T,) float32, T =
+        seq_len - 1: per step the mean of (model - truth)^2 --, ``openl_mse_context`` and ``openl_mse_open`` (floats, its
+        means over steps < context and >= context), ``context``, ``video`` -- uint8 (T, 3, 192, 64 sequences): truth over
+        model over error per sequence, pixel observations only (`video=None`: yes for those), else None -- and the decoded
+        ``beliefs`` / ``states`` (device tensors).  `batch`: a time-major batch as ``buffer.sample(n, L)`` returns it; None
+        draws ``buffer.sample(sequences, seq_len)``, which advances the replay's index RNG and the pixel dequantisation
+        counter as any sample does (a training run that calls this samples different batches afterwards than one that does
+        not).  No collectives: in a data-parallel run rank 0 alone may call it."""
+        from .openloop import check_open_loop, run_open_loop
+        if batch is None:
+            check_open_loop(int(self.seq_len), int(sequences), int(context))
+            batch = self.buffer.sample(int(sequences), int(self.seq_len))
+        return run_open_loop(self, batch, int(context), video=video, _noise=_noise)
 
 
 class DreamerV2(Dreamer):

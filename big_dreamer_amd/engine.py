@@ -748,6 +748,43 @@ class DreamerEngine:
         dec = self.conv.decode(feat, tag="api_")
         cabi.check(lib.bd_eval_frame(ptr(obs4d.contiguous()), ptr(dec), n, ptr(video), video.shape[0], int(t), cabi.stream()))
 
+    def openl_video(self, truth: torch.Tensor, feat: torch.Tensor, video: Optional[torch.Tensor]) -> torch.Tensor:
+        """Open-loop prediction (openloop.run_open_loop): ObservationModel on the T n rows of feat [T n x (Be+S)] in one
+        decoder pass, and -- `video` given -- the whole truth / model / error video in one launch (bd_openl_video) that reads
+        the decoder's output in the conv stack's own NHWC buffer.  truth: device fp32 (T, n, 3, 64, 64), the batch's obs[1:];
+        video: device uint8 openloop.video_shape(T, n), or None to decode only.  Returns the NHWC buffer (T n, 64, 64, 3),
+        valid until the next API decode, for openl_error.  Like the modules' forward(): join(), no collectives."""
+        from .openloop import video_shape
+        if not self.pixel:
+            raise ValueError("openl_video: the video shows pixel observations next to the decoder's images (pixel_observation)")
+        if not (truth.is_cuda and truth.dtype == torch.float32 and truth.dim() == 5 and tuple(truth.shape[2:]) == (3, 64, 64)):
+            raise ValueError(f"openl_video: truth must be device fp32 (T, n, 3, 64, 64), got {tuple(truth.shape)} {truth.dtype}")
+        T, n = truth.shape[0], truth.shape[1]
+        if tuple(feat.shape) != (T * n, self.d.Be + self.d.S):
+            raise ValueError(f"openl_video: feat must be ({T * n}, {self.d.Be + self.d.S}), got {tuple(feat.shape)}")
+        if video is not None and not (video.dtype == torch.uint8 and tuple(video.shape) == video_shape(T, n)
+                                      and video.is_cuda and video.is_contiguous()):
+            raise ValueError(f"openl_video: video must be contiguous device uint8 {video_shape(T, n)}, got {tuple(video.shape)}")
+        self.join()
+        dec = self.conv.decode(feat.to(self.dev).float().contiguous(), tag="api_")
+        if video is not None:
+            cabi.check(lib.bd_openl_video(ptr(truth.contiguous()), ptr(dec), T, n, ptr(video), cabi.stream()))
+        return dec
+
+    def openl_error(self, truth: torch.Tensor, model: torch.Tensor, T: int, n: int, width: int, nhwc: bool) -> torch.Tensor:
+        """The open-loop error curve (bd_openl_error): (T,) fp32, per step the mean of (model - truth)^2 over the n * width
+        elements, summed in a fixed order.  truth, model: device fp32 of T n width elements, row t n + k = step t of sequence
+        k; nhwc: `model` is openl_video's NHWC buffer against NCHW truth (width 12288), else element by element."""
+        for name, x in (("truth", truth), ("model", model)):
+            if not (x.is_cuda and x.dtype == torch.float32 and x.numel() == T * n * width):
+                raise ValueError(f"openl_error: {name} must be device fp32 of {T} x {n} x {width} elements, got "
+                                 f"{tuple(x.shape)} {x.dtype}")
+        self.join()
+        out = torch.empty(T, dtype=torch.float32, device=self.dev)
+        cabi.check(lib.bd_openl_error(ptr(truth.contiguous()), ptr(model.contiguous()), T, n, width, int(bool(nhwc)), ptr(out),
+                                      cabi.stream()))
+        return out
+
     def _bind_rssm(self, a) -> None:
         """Embed (action half, bias) and GRU weights of a forward scan's arguments: observe, imagine and plan, both latent
         families.  The state half of the embed layer differs by family and stays with the caller."""

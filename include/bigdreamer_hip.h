@@ -206,6 +206,21 @@ int bd_image_layout(const float* src, float* dst, int imgs, int C, int HW, int t
  * Every byte of the frame is written, padding included (the buffer needs no clearing); no other frame is touched.
  * n <= 4096, 0 <= t < frames. */
 int bd_eval_frame(const float* obs, const float* dec, int n, unsigned char* video, int frames, int t, void* stream);
+/* Open-loop prediction video (DreamerV1 image_summaries / DreamerV2 video_pred; Dreamer.open_loop): the whole device uint8
+ * video (T, 3, 192, 64 n), 4-byte aligned, in one launch.  Frame t, columns 64 k .. 64 k + 63 hold sequence k: rows 0-63 the
+ * truth, 64-127 the model's image, 128-191 their difference; no padding.
+ *   truth (T n, 3, 64, 64) NCHW fp32: the batch's observations obs[1:], as the replay gathered them;
+ *   model (T n, 64, 64, 3) NHWC fp32: the decoder's output where the conv stack leaves it; row t n + k is step t of sequence k.
+ * Truth and model bytes are bd_eval_frame's uint8(clip(floor((v + 0.5) * 256), 0, 255)); an error byte is
+ * uint8(clip(floor(e * 256), 0, 255)) with e = ((model - truth) + 1) * 0.5; every operation rounded to fp32 on its own.
+ * Every byte is written exactly once.  T, n >= 1, T n 9216 words must fit an int. */
+int bd_openl_video(const float* truth, const float* model, int T, int n, unsigned char* video, void* stream);
+/* Open-loop error curve: out[t] = mean over the n * width elements of step t of (model - truth)^2, fp32; truth and model are
+ * [T n x width] with row t n + k = step t of sequence k.  model_nhwc = 1 (width must be 12288): model is the decoder's NHWC
+ * buffer and its element (k, y, x, c) pairs with truth (k, c, y, x); 0: element by element (the state observations' dense
+ * decoder).  Deterministic: one workgroup per t, per-lane strided partial sums, then a fixed tree (no atomics); the longest
+ * chain of additions is ceil(n width / 256) + 8.  n * width < 2^30. */
+int bd_openl_error(const float* truth, const float* model, int T, int n, int width, int model_nhwc, float* out, void* stream);
 
 /* ---- RSSM observe scan: TransitionModel.forward with embeddings (src/models.py:191-299) ------
  * One persistent launch walks all T steps; a workgroup owns 16 batch rows (rows are independent, so

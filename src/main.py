@@ -6,6 +6,8 @@ Collect-update loop: every ``environment_steps_per_update`` env steps run ``coll
 noise (src/main.py:129-143), append to the replay buffer (src/main.py:146), log every ``log_freq``.
 ``evaluation=true``: every ``test_interval`` steps the test loop (src/main.py:191-283) runs ``test_episodes`` environments
 without exploration noise and prints ``Eval_{min,avg,max,std}_return``; ``test=true`` evaluates once and exits.
+``openl_freq=k`` (k > 0): every k steps rank 0 runs ``open_loop`` on ``openl_sequences`` replay sequences with ``openl_context``
+context steps, prints ``openl_mse_context`` / ``openl_mse_open`` and saves the video as ``Openl_<step>.npy`` in ``eval_video_dir``.
 ``collect_envs=n`` (n > 1) collects from n environments side by side (big_dreamer_amd/collect.py): one loop iteration is one
 decision for all of them = n environment steps, with the same update-to-data ratio.
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N src/main.py ...``; each rank collects
@@ -40,6 +42,17 @@ def evaluate(model, params, step, rank):
         np.save(os.path.join(params["eval_video_dir"], f"Eval_rollout_{step}.npy"), result["video"])
 
 
+def open_loop(model, params, step):
+    """Rank 0 only (Dreamer.open_loop issues no collectives): the open-loop prediction error of a fresh replay batch and,
+    for pixel observations, its truth / model / error video."""
+    result = model.open_loop(sequences=params["openl_sequences"], context=params["openl_context"])
+    for key in ("openl_mse_context", "openl_mse_open"):
+        print(f"{key} : {result[key]}", flush=True)
+    if result["video"] is not None and params["eval_video_dir"]:
+        os.makedirs(params["eval_video_dir"], exist_ok=True)
+        np.save(os.path.join(params["eval_video_dir"], f"Openl_{step}.npy"), result["video"])
+
+
 def collect_many(model, env, params, rank):
     """The collect-update loop for ``collect_envs = n > 1``: one iteration is one Collector.step() = n environment steps
     [step, step + n).  Every multiple of ``environment_steps_per_update`` in that range runs one burst of
@@ -72,6 +85,8 @@ def collect_many(model, env, params, rank):
             print(step, {k: (round(v, 5) if isinstance(v, float) else v) for k, v in logs.items()}, flush=True)
         if params["evaluation"] and any(s % params["test_interval"] == 0 for s in steps):
             evaluate(model, params, step, rank)
+        if params["openl_freq"] > 0 and rank == 0 and any(s % params["openl_freq"] == 0 for s in steps):
+            open_loop(model, params, step)
     env.close()
 
 
@@ -137,6 +152,8 @@ def my_app(argv):
             print(step, {k: (round(v, 5) if isinstance(v, float) else v) for k, v in logs.items()}, flush=True)
         if params["evaluation"] and step % params["test_interval"] == 0:
             evaluate(model, params, step, rank)
+        if params["openl_freq"] > 0 and rank == 0 and step % params["openl_freq"] == 0:
+            open_loop(model, params, step)
     env.close()
 
 
