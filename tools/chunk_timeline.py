@@ -1,0 +1,44 @@
+"""Per-chunk timeline of the behaviour chain from a kernel trace ("Chunked behaviour chain").
+
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 20 --warmup 10 --no-secondary --no-cpu-baseline
+    python3 tools/chunk_timeline.py DIR [steps-from-the-end, default 2]
+
+For the last steps of the run: every launch of the two imagination scans, the fused heads and the tall dense backward
+chains (actor hidden chain, critic) with its hardware queue, start and end (us from the step's first scan launch), and how
+much of each heads / chain launch ran while a scan launch was running.  A heads chunk that starts only after the scan's last
+chunk has ended shares a hardware queue with the scan (or the overlap stream is busy): the plan then buys nothing."""
+import csv
+import glob
+import os
+import sys
+
+src = sys.argv[1]
+last = int(sys.argv[2]) if len(sys.argv) > 2 else 2
+path = src if src.endswith(".csv") else glob.glob(os.path.join(src, "**", "*_kernel_trace.csv"), recursive=True)[0]
+KINDS = (("imagine_fwd_kernel", "scan_fwd"), ("imagine_bwd_kernel", "scan_bwd"), ("img_heads_kernel", "heads"),
+         ("mlp_bwd_tall_kernel", "chain_bwd"))
+rows = []
+for r in csv.DictReader(open(path)):
+    kind = next((k for pat, k in KINDS if pat in r["Kernel_Name"]), None)
+    if kind:
+        rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), kind, r.get("Queue_Id", "?")))
+rows.sort()
+# a step starts at a forward-scan launch that follows a launch of another kind
+starts = [i for i, r in enumerate(rows) if r[2] == "scan_fwd" and (i == 0 or rows[i - 1][2] not in ("scan_fwd", "heads"))]
+total = {"heads": [0.0, 0.0], "chain_bwd": [0.0, 0.0]}
+for s, e in list(zip(starts, starts[1:] + [len(rows)]))[-last - 1:-1]:
+    step = rows[s:e]
+    t0 = step[0][0]
+    print(f"step at {t0} ns: {len(step)} launches")
+    for a, b, kind, q in step:
+        over = ""
+        if kind in total:
+            scan = "scan_fwd" if kind == "heads" else "scan_bwd"
+            ov = sum(max(0, min(b, b2) - max(a, a2)) for a2, b2, k2, _ in step if k2 == scan)
+            total[kind][0] += ov / 1e3
+            total[kind][1] += (b - a) / 1e3
+            over = f"   {ov / 1e3:7.1f} us under {scan}"
+        print(f"  {kind:9s} queue {q:>3s}  {(a - t0) / 1e3:8.1f} .. {(b - t0) / 1e3:8.1f} us  ({(b - a) / 1e3:6.1f}){over}")
+for kind, (ov, dur) in total.items():
+    if dur:
+        print(f"{kind}: {ov:.1f} of {dur:.1f} us ({100 * ov / dur:.0f} %) ran under a scan launch (chain_bwd includes the critic's chains)")
