@@ -153,21 +153,47 @@ class Dreamer:
                 if key in d:
                     self.engine.load_optimizer_state_dict(group, d[key])
 
-    def save(self, path: str) -> None:
+    def save(self, path: str, extra: Optional[Dict[str, Any]] = None) -> None:
         """Checkpoint in the layout ``Planet.load`` reads (src/planet.py:109-114: transition_model, observation_model,
         reward_model, encoder, model_optimizer -- the reference can resume from it), plus actor / critic /
         critic_target, the discount head when ``use_discount`` is set (its parameters are the tail of the world-model
         optimiser, src/dreamer.py:167-169) and the actor / value optimisers (src/dreamer.py:56-67 names) so that this
         framework resumes exactly.
+        One more key, ``run_state``, holds what decides the NEXT draws (``load`` ignores it, ``load_run_state`` restores it):
+        the engine's noise state (engine.noise_state), the torch CPU and device, numpy and Python generator states
+        (checkpoint.capture_generators) and `extra`, a flat dict of ints, floats and strings that belongs to the caller (the
+        CLI keeps its step there).  The whole file loads with ``weights_only=True``, and it is written atomically.
+        The replay buffer is saved apart (``buffer.save``); the episode in flight -- environment, belief, state, previous
+        action -- is the caller's and is not saved: a resumed run starts fresh episodes.
+        Data-parallel runs: a COLLECTIVE (it issues the held-back optimiser steps): every rank calls it at the same point.
         The reference declares ``save`` (src/base_agent.py:29-34) but never implements it (src/main.py:274 TODO)."""
+        from .checkpoint import atomic_write, capture_generators, check_extra
         e = self.engine
+        extra = check_extra(extra)
+        # first: noise_state() issues the held-back optimiser steps and orders the pipeline streams before this one, so the
+        # weights copied below are those the saved moments and step counts belong to
+        noise = e.noise_state()
         d = {key: {k: v.detach().cpu().clone().contiguous() for k, v in getattr(self, key).state_dict().items()}
              for key in ("transition_model", "observation_model", "reward_model", "encoder", "actor", "critic",
                          "critic_target") + (("discount_model",) if self.use_discount else ())}
         d["model_optimizer"] = e.optimizer_state_dict("model")
         d["actor_optimizer"] = e.optimizer_state_dict("actor")
         d["value_optimizer"] = e.optimizer_state_dict("critic")
-        torch.save(d, path)
+        d["run_state"] = {"format": 1, "noise": noise, "generators": capture_generators(self.device),
+                          "extra": extra}
+        atomic_write(path, lambda fh: torch.save(d, fh))
+
+    def load_run_state(self, path: str) -> Dict[str, Any]:
+        """Restore the ``run_state`` of a checkpoint ``save`` wrote -- the four generators and the engine's noise state,
+        exactly as saved -- and return its ``extra``.  Weights and optimisers are ``load``'s (``models=<file>``), the replay
+        is ``buffer.load``'s; call this last, after everything that draws random numbers while the agent is set up.
+        ValueError for a checkpoint without ``run_state`` (the reference's files, and files older than this key).
+        Data-parallel runs: a COLLECTIVE, as ``save`` is."""
+        from .checkpoint import read_run_state, restore_generators
+        rs = read_run_state(path)
+        self.engine.load_noise_state(rs["noise"])
+        restore_generators(rs["generators"], self.device)
+        return dict(rs["extra"])
 
     def eval(self) -> None:      # no dropout / batch-norm anywhere on the path
         pass

@@ -1336,6 +1336,33 @@ class DreamerEngine:
         self._rng_seed = (int(seed) + 0x9E3779B97F4A7C15 * (self.dp.rank + 1)) & 0xFFFFFFFFFFFFFFFF
         self._rng_step = {"wm": 0, "bh": 0}
 
+    def noise_state(self) -> dict:
+        """The perf-mode noise generator as plain ints: ``seed`` -- the keyed ``_rng_seed`` as ``set_noise_seed`` stored
+        it (rank term included), or None while it is still unset --, ``step`` -- every counter of ``_rng_step``, "act" and
+        "plan" included once a decision or a plan has drawn from them -- and ``entropy_step``.  With the weights and the
+        optimisers this is all of the engine that decides a later value ("Checkpoint and resume").
+        Issues the held-back optimiser steps (flush_optimizers) and join(), as optimizer_state_dict does: in a
+        data-parallel run this is a COLLECTIVE, every rank calls it at the same point."""
+        self.flush_optimizers()
+        self.join()
+        return {"seed": None if self._rng_seed is None else int(self._rng_seed),
+                "step": {str(k): int(v) for k, v in self._rng_step.items()},
+                "entropy_step": int(self._rng_entropy_step)}
+
+    def load_noise_state(self, d: dict) -> None:
+        """Set what ``noise_state`` returned, exactly: the key is taken as stored and never derived again from
+        torch.initial_seed() or the rank (a state with ``seed`` None leaves it to the first draw, as on a fresh engine).
+        Issues the held-back optimiser steps and join() first: a COLLECTIVE in a data-parallel run, like noise_state."""
+        self.flush_optimizers()
+        self.join()
+        step = {str(k): int(v) for k, v in d["step"].items()}
+        if not {"wm", "bh"} <= set(step):
+            raise ValueError(f"load_noise_state: the step counters {sorted(step)} lack 'wm' or 'bh'")
+        seed = d["seed"]
+        self._rng_seed = None if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._rng_step = step
+        self._rng_entropy_step = int(d["entropy_step"])
+
     # noise streams of the perf-mode generator (csrc/bd_rng.h: counter = (index, stream id, step))
     RNG_STREAMS = {"obs_post": 1, "action": 2, "img_prior": 3, "entropy": 4, "obs_prior": 5, "plan_prior": 7,   # (6: pixel dequantisation)
                    "act_post": 8, "act_action": 9, "act_explore": 10}     # bd_act_step: counter step = decision index

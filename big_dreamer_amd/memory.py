@@ -7,13 +7,17 @@ the device by bd_replay_gather_pixels; the dequantisation noise is drawn by torc
 
 ``lanes=N`` splits the ring into N lanes for collecting from N environments at once: lane e owns rows
 [e * lane_size, (e + 1) * lane_size), ``append_batch`` writes one transition per lane (one bd_replay_append launch keeps
-the mirror in step) and ``_sample_idx`` draws every chunk inside one lane ("Laned replay")."""
+the mirror in step) and ``_sample_idx`` draws every chunk inside one lane ("Laned replay").
+
+``save`` / ``load`` write and read the filled rows, the counters and the pixel noise state as one uncompressed ``.npz`` of
+plain arrays ("Checkpoint and resume")."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from . import _cabi as cabi
+from .checkpoint import atomic_write
 
 
 class ExperienceReplay:
@@ -191,6 +195,67 @@ class ExperienceReplay:
     def mark_dirty(self):
         """Call after writing the numpy arrays directly (e.g. bulk synthetic fill)."""
         self._dirty = True
+
+    # -- checkpoints (DESIGN.md, "Checkpoint and resume") --
+    _ARRAYS = ("observations", "actions", "rewards", "nonterminals")
+
+    def _geometry(self) -> dict:
+        """What ``load`` requires to be equal on both sides."""
+        return {"size": int(self.size), "lanes": int(self.lanes), "lane_size": int(self.lane_size),
+                "bit_depth": int(self.bit_depth), "pixel_observation": int(bool(self.pixel_observation)),
+                "observation_width": int(self.observations[0].size), "action_width": int(self.actions.shape[1])}
+
+    def _filled(self, a: np.ndarray) -> np.ndarray:
+        """The rows of `a` that hold data: [0, size if full else idx), or per lane [0, lane_size if full else idx) as
+        (lanes, k, ...)."""
+        if self.lanes == 1:
+            return a[:self.size if self.full else self.idx]
+        k = self.lane_size if self.full else self.idx
+        return a[:self.lanes * self.lane_size].reshape((self.lanes, self.lane_size) + a.shape[1:])[:, :k]
+
+    def save(self, path: str) -> None:
+        """Write the buffer to `path` as one uncompressed ``.npz`` of plain arrays: the FILLED rows of the four arrays
+        (pixels stay uint8; the uninitialised rest is never written, so the file grows with what has been collected, not
+        with ``size``), ``idx`` / ``full`` / ``steps`` / ``episodes``, the geometry ``load`` checks, and the pixel gather's
+        noise key and counter.  The host arrays are the truth (the device mirror holds the same bits), so nothing is read
+        back from the device.  The write is atomic (checkpoint.atomic_write): `path` holds the old file or the new one."""
+        z = {k: np.ascontiguousarray(self._filled(getattr(self, k))) for k in self._ARRAYS}
+        z.update({k: np.asarray(v, dtype=np.int64) for k, v in self._geometry().items()})
+        z.update(format=np.asarray(1, dtype=np.int64), idx=np.asarray(self.idx, dtype=np.int64),
+                 full=np.asarray(bool(self.full)), steps=np.asarray(self.steps, dtype=np.int64),
+                 episodes=np.asarray(self.episodes, dtype=np.int64), pix_step=np.asarray(self._pix_step, dtype=np.int64),
+                 pix_seed_drawn=np.asarray(self._pix_seed is not None),      # False: keyed at the first pixel sample
+                 pix_seed=np.asarray(self._pix_seed or 0, dtype=np.uint64))
+        atomic_write(path, lambda fh: np.savez(fh, **z))
+
+    def load(self, path: str) -> None:
+        """Read a file ``save`` wrote into this buffer, which must have the same ``size``, ``lanes``, widths, ``bit_depth``
+        and observation kind (ValueError otherwise: loading into a buffer of another shape is not supported).  Restores the
+        rows, the counters and the pixel noise state and calls ``mark_dirty()``: the next ``sample`` uploads the mirror
+        again.  Read with ``allow_pickle=False``: nothing from the file is executed."""
+        with np.load(path, allow_pickle=False) as z:
+            mine = self._geometry()
+            theirs = {k: int(z[k]) for k in mine}
+            if theirs != mine:
+                diff = {k: (mine[k], theirs[k]) for k in mine if mine[k] != theirs[k]}
+                raise ValueError(f"ExperienceReplay.load: {path} was saved from a buffer of another shape "
+                                 f"(this buffer, file): {diff}")
+            idx, full = int(z["idx"]), bool(z["full"])
+            head = self.lane_size if self.lanes > 1 else self.size
+            if not 0 <= idx < head:
+                raise ValueError(f"ExperienceReplay.load: {path} has idx={idx}, this buffer's head runs in [0, {head})")
+            old, (self.idx, self.full) = (self.idx, self.full), (idx, full)
+            for k in self._ARRAYS:
+                dst, src = self._filled(getattr(self, k)), z[k]
+                if src.shape != dst.shape or src.dtype != dst.dtype:
+                    self.idx, self.full = old
+                    raise ValueError(f"ExperienceReplay.load: {path}: {k} is {src.dtype}{src.shape}, this buffer's filled "
+                                     f"rows are {dst.dtype}{dst.shape}")
+                dst[...] = src
+            self.steps, self.episodes = int(z["steps"]), int(z["episodes"])
+            self._pix_step = int(z["pix_step"])
+            self._pix_seed = int(z["pix_seed"]) if bool(z["pix_seed_drawn"]) else None
+        self.mark_dirty()
 
     def _upload_indices(self, vec: np.ndarray) -> torch.Tensor:
         """Async H2D of the gather indices through a ring of pinned buffers, so that the host can run

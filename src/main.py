@@ -10,6 +10,15 @@ without exploration noise and prints ``Eval_{min,avg,max,std}_return``; ``test=t
 context steps, prints ``openl_mse_context`` / ``openl_mse_open`` and saves the video as ``Openl_<step>.npy`` in ``eval_video_dir``.
 ``collect_envs=n`` (n > 1) collects from n environments side by side (big_dreamer_amd/collect.py): one loop iteration is one
 decision for all of them = n environment steps, with the same update-to-data ratio.
+``checkpoint_dir=<dir>``: at the end of every loop iteration whose step is a multiple of ``checkpoint_interval`` (with
+``collect_envs=n``: whose n steps hold one) every rank writes ``<dir>/models_<step>.pth`` and, with
+``checkpoint_experience=true``, ``<dir>/experience_<step>.npz`` (``_rank<r>`` before the extension in multi-GPU runs), <step>
+being the iteration's first step; ``checkpoint_keep=k`` keeps the newest k.  ``experience_replay=<file>`` loads the buffer
+instead of running the seed phase.  ``resume=true models=<file>`` continues that run at its saved step plus one iteration
+with the same weights, optimisers, noise counters and generator states.  The episode in flight is NOT restored -- an
+environment cannot be serialised in general --: the environments are reset and belief, state and action start at zero, so
+the first update burst after the resume point is bit-identical to the uninterrupted run's, and the run then goes on from
+the same weights, optimiser state, replay and noise position on fresh episodes.
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N src/main.py ...``; each rank collects
 its own experience and the gradients are all-reduced over RCCL (big_dreamer_amd/engine.py).
 """
@@ -53,7 +62,47 @@ def open_loop(model, params, step):
         np.save(os.path.join(params["eval_video_dir"], f"Openl_{step}.npy"), result["video"])
 
 
-def collect_many(model, env, params, rank):
+def checkpoint(model, params, step, rank, world, n_envs):
+    """models_<step> (always) and experience_<step> (checkpoint_experience) into checkpoint_dir.  Dreamer.save issues the
+    held-back optimiser steps of a data-parallel run, a collective: every rank is here at the same point of the loop, and
+    writes files of its own (replay contents and generator states differ per rank)."""
+    from big_dreamer_amd import checkpoint as ck
+    directory = params["checkpoint_dir"]
+    os.makedirs(directory, exist_ok=True)
+    model.save(ck.models_path(directory, step, rank, world), extra={"step": step, "collect_envs": n_envs})
+    if params["checkpoint_experience"]:
+        model.buffer.save(ck.experience_path(directory, step, rank, world))
+    ck.prune(directory, int(params["checkpoint_keep"]), rank=rank if world > 1 else None)
+
+
+def fill_replay(model, params, rank, seed_phase):
+    """The replay before the loop: experience_replay=<file> loads it, otherwise `seed_phase` collects seed_steps with
+    random actions.  Returns the environment steps the buffer stands for, where the loop starts."""
+    if params["experience_replay"]:
+        model.buffer.load(params["experience_replay"])
+        env_steps = model.buffer.steps * params["action_repeat"]       # as the seed phase counts them
+        if rank == 0:
+            print(f"Loaded {model.buffer.episodes} episodes and {env_steps} steps from {params['experience_replay']}")
+        return env_steps
+    env_steps, num_episodes = seed_phase()
+    if rank == 0:
+        print(f"Initialized with {num_episodes} episodes and {env_steps} steps")
+    return env_steps
+
+
+def resume(model, params, n_envs, first_step):
+    """The last thing before the loop: with resume=true restore the run state of models= (after it nothing may draw from a
+    generator but the loop itself) and return the step the loop continues at, the saved step plus one iteration; else
+    `first_step`."""
+    if not params["resume"]:
+        return first_step
+    extra = model.load_run_state(params["models"])
+    if "step" not in extra:
+        raise ValueError(f"resume=true: {params['models']} was not written by this command line (its run_state has no step)")
+    return int(extra["step"]) + n_envs
+
+
+def collect_many(model, env, params, rank, world):
     """The collect-update loop for ``collect_envs = n > 1``: one iteration is one Collector.step() = n environment steps
     [step, step + n).  Every multiple of ``environment_steps_per_update`` in that range runs one burst of
     ``collect_interval`` train steps, so the update-to-data ratio stays that of the reference; update_critic is called once
@@ -62,9 +111,8 @@ def collect_many(model, env, params, rank):
     from big_dreamer_amd.collect import Collector
     n = env.n
     collector = Collector(model, env)
-    env_steps, num_episodes = collector.seed(params["seed_steps"])
-    if rank == 0:
-        print(f"Initialized with {num_episodes} episodes and {env_steps} steps")
+    env_steps = fill_replay(model, params, rank, lambda: collector.seed(params["seed_steps"]))
+    env_steps = resume(model, params, n, env_steps)
     logs, past, logged = {}, time.time(), env_steps
     slow = params["ActorCritic"]["slow_critic_update_interval"]
     for step in range(env_steps, params["train_steps"], n):
@@ -87,6 +135,8 @@ def collect_many(model, env, params, rank):
             evaluate(model, params, step, rank)
         if params["openl_freq"] > 0 and rank == 0 and any(s % params["openl_freq"] == 0 for s in steps):
             open_loop(model, params, step)
+        if params["checkpoint_dir"] and any(s % params["checkpoint_interval"] == 0 for s in steps):
+            checkpoint(model, params, step, rank, world, n)
     env.close()
 
 
@@ -98,6 +148,16 @@ def my_app(argv):
     random.seed(params["seed"] + rank)
     if params["algorithm"] not in ("planet", "dreamer", "dreamerV2"):     # as src/main.py:73-81
         raise NotImplementedError(f'algorithm {params["algorithm"]} is not yet implemented.')
+    from big_dreamer_amd import checkpoint as ck
+    for key in ("models", "experience_replay"):                    # multi-GPU: every rank loads its own ..._rank<r> file
+        params[key] = ck.for_rank(params[key], rank, world)
+    if params["resume"]:
+        if not params["models"] or not os.path.exists(params["models"]):
+            raise ValueError(f"resume=true needs models=<checkpoint file> (models='{params['models']}')")
+        saved = ck.read_run_state(params["models"])["extra"].get("collect_envs", params["collect_envs"])
+        if int(saved) != int(params["collect_envs"]):
+            raise ValueError(f"resume=true: {params['models']} was saved by a run with collect_envs={saved}, this run has "
+                             f"collect_envs={params['collect_envs']}")
     local = int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
     if world > 1:      # (device_id: the communicator is built now, before the engine's streams -- DESIGN.md section 6)
@@ -116,11 +176,9 @@ def my_app(argv):
         env.close()
         return
     if n_envs > 1:
-        collect_many(model, env, params, rank)
+        collect_many(model, env, params, rank, world)
         return
-    env_steps, num_episodes = model.randomly_initialize_replay_buffer()
-    if rank == 0:
-        print(f"Initialized with {num_episodes} episodes and {env_steps} steps")
+    env_steps = fill_replay(model, params, rank, model.randomly_initialize_replay_buffer)
     dev = model.device
     observation = env.reset()
     belief = torch.zeros(1, params["belief_size"], device=dev)
@@ -129,6 +187,7 @@ def my_app(argv):
     posterior_state = torch.zeros(1, model.state_size, device=dev)
     action = torch.zeros(1, env.action_size, device=dev)
     logs, episode_reward, past = {}, 0.0, time.time()
+    env_steps = resume(model, params, 1, env_steps)
     for step in range(env_steps, params["train_steps"]):
         if step % params["environment_steps_per_update"] == 0:
             t0 = time.time()
@@ -154,6 +213,8 @@ def my_app(argv):
             evaluate(model, params, step, rank)
         if params["openl_freq"] > 0 and rank == 0 and step % params["openl_freq"] == 0:
             open_loop(model, params, step)
+        if params["checkpoint_dir"] and step % params["checkpoint_interval"] == 0:
+            checkpoint(model, params, step, rank, world, 1)
     env.close()
 
 
