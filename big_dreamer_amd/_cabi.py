@@ -182,18 +182,6 @@ class PlanCatArgs(C.Structure):
 
 
 class ActArgs(C.Structure):
-    _fields_ = ([(n, I32) for n in ("B", "Be", "S", "A", "Hd", "E", "O")] + [("w_enc", P * 5), ("b_enc", P * 5)] + _ptr_fields(
-        ["w_embed_s", "w_embed_a", "b_embed", "w_ir", "w_iz", "w_in", "w_hr", "w_hz", "w_hn", "b_ih", "b_hh", "w_q1h",
-         "w_q1e", "b_q1", "w_q2m", "w_q2s", "b_q2", "w_a0h", "w_a0s"]) + [("w_a", P * 3), ("b_a", P * 4)] + _ptr_fields(
-        ["w_a4m", "w_a4s", "b_a4", "belief", "state", "action", "obs", "embedding", "eps_post", "eps_action",
-         "eps_explore"]) + [("seed", C.c_ulonglong), ("step", C.c_ulonglong), ("stream_post", C.c_uint),
-                            ("stream_action", C.c_uint), ("stream_explore", C.c_uint),
-                            ("min_std", F32), ("act_raw_init_std", F32), ("act_min_std", F32), ("act_mean_scale", F32),
-                            ("action_noise", F32), ("explore", I32)] + _ptr_fields(
-        ["belief_out", "state_out", "action_out"]))
-
-
-class ActCatArgs(C.Structure):
     _fields_ = ([(n, I32) for n in ("B", "Be", "D", "C", "S", "A", "Hd", "E", "O", "latent_cat", "actor_cat")] + [
         ("w_enc", P * 5), ("b_enc", P * 5)] + _ptr_fields(
         ["w_embed_s", "w_embed_sT", "w_embed_a", "b_embed", "w_ir", "w_iz", "w_in", "w_hr", "w_hz", "w_hn", "b_ih", "b_hh",
@@ -205,6 +193,9 @@ class ActCatArgs(C.Structure):
                             ("min_std", F32), ("act_raw_init_std", F32), ("act_min_std", F32), ("act_mean_scale", F32),
                             ("action_noise", F32), ("explore", I32)] + _ptr_fields(
         ["belief_out", "state_out", "action_out"]))
+
+
+ActCatArgs = ActArgs       # bd_act_cat_args is a typedef of bd_act_args
 
 
 class ConvArgs(C.Structure):

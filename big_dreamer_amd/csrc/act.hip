@@ -1,38 +1,70 @@
 // act.hip -- one decision of the collect / evaluation loop in ONE launch: Planet.update_belief_and_act
-// (src/planet.py:370-403) with Dreamer.get_action (src/dreamer.py:429-444) on Gaussian latents and the tanh-Normal actor.
+// (src/planet.py:370-403) with Dreamer.get_action (src/dreamer.py:429-444), for the four configurations of
+// latent_distribution = Gaussian | Categorical (TransitionModel.forward's Categorical branches, src/models.py:226-228,258-260,
+// 269-271; CategoricalBeliefModel, src/models.py:101-117) and action_distribution = tanh-Normal | Categorical
+// (src/models.py:506-522).
 //
-//   bd_act_step: a workgroup owns 16 environments; every activation of the step stays in LDS in MFMA fragment order, the
-//     weights (3.9 MB at the reference's default sizes) stream once from L2.  Per tile:
+//   One kernel body, act_step_kernel<LC, AC>, templated on the latent kind LC and the actor kind AC; all four are
+//     instantiated.  bd_act_step launches (0, 0), bd_act_step_cat the other three.  A workgroup owns 16 environments; every
+//     activation of the step stays in LDS in MFMA fragment order, the weights (3.9 MB at the reference's default sizes)
+//     stream once from L2.  At B <= 16 the step is a single CU walking a chain of thirteen dependent layers.  Per tile:
 //       e  = encoder(obs)                    DenseModel 4 x (Linear+ELU) + Linear (src/models.py:365-408), or a ready
 //                                            embedding (pixel observations: the conv stack has run)
-//       x  = ELU(W_e [s; a] + b_e);  h' = GRUCell(x, h)                          (src/models.py:251-252)
-//       q  = ELU(W_q1 [h'; e] + b);  s' = mean_q + std_q * eps_post              (src/models.py:266-267, :70-73)
-//       actor: 4 x (Linear+ELU) on [h'; s'], mean = 5 tanh(m/5), std = softplus(r + c0) + 1e-4,
-//              a' = tanh(mean + std * eps_action)                                (src/models.py:506-517, src/dreamer.py:443)
-//       explore: a' = clamp(a' + action_noise * eps_explore, -1, 1)              (src/planet.py:388-392)
-//     What the composed path computes besides and nobody reads is left out: the prior head of the belief update
-//     (src/models.py:256: with an embedding the posterior sample is the state that continues), the prior sample of
-//     get_action's one imagination step and the 100-sample entropy estimate (src/planet.py:386 drops it).  None of them
-//     feeds belief, state or action, so the three outputs are exactly the composed path's.
-//   Noise: explicit buffers, or (all NULL) Philox4x32-10 draws made in the kernel with the element layout of bd_rng_fill,
-//     so a run with in-kernel noise equals, bit for bit, a run fed bd_rng_fill's buffers for the same (seed, step, stream).
-//   One workgroup per 16 rows: at B <= 16 the step is a single CU walking a chain of thirteen dependent layers.
+//       x  = ELU(W_es s + W_ea a + b_e);  h' = GRUCell(x, h)                       (src/models.py:251-252)
+//            LC: the incoming state [B x S] (per factor all-zero or one-hot) becomes class indices (state_to_indices) and
+//            W_es s a gather of D rows of the plain transpose embed_sT (bd_categorical.h), as in the scans
+//       q  = ELU(W_q1 [h'; e] + b)                                                 (src/models.py:266-267)
+//            !LC: s' = mean_q + std_q * eps_post                                   (src/models.py:70-73)
+//            LC: all D*C logits into the swizzled CatFull image, one thread per (row, factor) takes argmax(probs / q),
+//            first maximum winning: cat_sample_reg / cat_sample_any, the operation order of the scans; s' = the one-hot
+//       actor: 4 x (Linear+ELU) on [h'; s'] (LC: the state columns of layer 0 are a gather of a0sT rows), then
+//            !AC: mean = 5 tanh(m/5), std = softplus(r + c0) + 1e-4, a' = tanh(mean + std * eps_action)
+//                 (src/models.py:506-517, src/dreamer.py:443); explore: a' = clamp(a' + action_noise * eps_explore, -1, 1)
+//                 (src/planet.py:388-392)
+//            AC:  norm = out - logsumexp(out), p = softmax(norm), k = argmax(p / eps_action) (bd_discrete.h, one lane per
+//                 class), a' = (onehot(k) + p) - p in that order; explore: epsilon-greedy -- with (u, v) the row's two
+//                 uniforms, u < action_noise replaces a' by the exact one-hot of class min(floor(v A), A - 1)
+//     What the composed path computes besides and nobody reads is left out: the prior head of the belief update and its
+//     sample (src/models.py:256: with an embedding the posterior sample is the state that continues), the prior sample of
+//     get_action's one imagination step and the actor entropy (src/planet.py:386 drops it).  None of them feeds belief,
+//     state or action, so the three outputs are exactly the composed path's.
+//   Noise: explicit buffers, or (all NULL) Philox4x32-10 draws made in the kernel with the element layout of bd_rng_fill
+//     (Exp(1) where a Categorical sampler consumes them, uniforms for epsilon-greedy, normals otherwise), so a run with
+//     in-kernel noise equals, bit for bit, a run fed bd_rng_fill's buffers for the same (seed, step, stream).
+//
+// LDS budget (floats; Kb_x = ceil(x / 16), 256 floats per fragment block, 8 waves):
+//     t0, t1, t2                 3 * max(Kb_h, Kb_hd) * 256     a belief-wide or a hidden-wide vector each; with LC t0 / t2
+//                                also hold the two gathers' [16][out] sums
+//     ef | logits image          max(max(Kb_e, Kb_o) * 256, LC ? 16 * (ceil(S / 16) * 16 + 8) : 0)
+//                                observation (dead after the encoder's first layer), then the embedding; the embedding is
+//                                dead once the posterior's first layer has read it: the image takes its place
+//     state                      LC: 2 * 16 * D (class indices, weights)     !LC: Kb_s * 256 (fragment tile)
+//     action fragments           Kb_a * 256
+//     split-K scratch            kSplitScratchFloats = 10240    (its plain area also holds the actor's [16][A] logits)
+//   Gaussian, Be = Hd = 200, E = 1024, S = 30, A = 1:  9984 + 16384 + 512 + 256 + 10240 = 37376 floats = 149 504 B.
+//   Be = Hd = 200, E = 1024, 32 x 32, A = 18:  9984 + 16512 + 1024 + 512 + 10240 = 38272 floats = 153 088 B of the 160 KiB a
+//   workgroup may use on gfx950 (with the embedding tile and the image side by side: 218 624 B).  A = 17, tanh-Normal: the same.
 #include "bd_device.h"
 #include "bd_host.h"
 #include "bd_scan.h"
+#include "bd_categorical.h"
+#include "bd_discrete.h"
 #include "bd_rng.h"
 
 namespace bd {
 
 struct ActDims {
-    int Kb_h, Kb_s, Kb_a, Kb_hd, Kb_e, Kb_o;
-    int Kb_g;     // the three general tiles hold a belief-wide or a hidden-wide vector
-    int Kb_io;    // observation (dead after the encoder's first layer), then the embedding
-    __host__ __device__ ActDims(int Be, int S, int A, int Hd, int E, int O)
+    int Kb_h, Kb_s, Kb_a, Kb_hd, Kb_e, Kb_o, Kb_g, Kb_io;
+    int n_ef, n_state;       // floats of the embedding | image region and of the state region
+    __host__ __device__ ActDims(int Be, int D, int C, int S, int A, int Hd, int E, int O, bool lc)
         : Kb_h(cdiv(Be, 16)), Kb_s(cdiv(S, 16)), Kb_a(cdiv(A, 16)), Kb_hd(cdiv(Hd, 16)), Kb_e(cdiv(E, 16)), Kb_o(cdiv(O, 16)),
-          Kb_g(Kb_h > Kb_hd ? Kb_h : Kb_hd), Kb_io(Kb_e > Kb_o ? Kb_e : Kb_o) {}
+          Kb_g(Kb_h > Kb_hd ? Kb_h : Kb_hd), Kb_io(Kb_e > Kb_o ? Kb_e : Kb_o) {
+        const int img = lc ? CatFull(D, C).image_floats() : 0;
+        n_ef = Kb_io * kFragFloats > img ? Kb_io * kFragFloats : img;
+        n_state = lc ? 2 * 16 * D : Kb_s * kFragFloats;
+    }
     __host__ __device__ size_t lds_floats() const {
-        return (size_t)(3 * Kb_g + Kb_io + Kb_s + Kb_a) * kFragFloats + kSplitScratchFloats;
+        return (size_t)(3 * Kb_g + Kb_a) * kFragFloats + (size_t)n_ef + (size_t)n_state + kSplitScratchFloats;
     }
 };
 
@@ -40,35 +72,56 @@ struct ActEps {
     float sample, explore;
 };
 
+enum { kDrawNormal = 0, kDrawExp = 1, kDrawUniform = 2 };      // the kinds of bd_rng_fill
+
+template <bool LC, bool AC>
 __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const ActDims d(a.Be, a.S, a.A, a.Hd, a.E, a.O);
+    const ActDims d(a.Be, a.D, a.C, a.S, a.A, a.Hd, a.E, a.O, LC);
     const int row0 = blockIdx.x * 16;
+    const int rows_valid = a.B - row0 < 16 ? a.B - row0 : 16;
     const int ng = d.Kb_g * kFragFloats;
-    float* t0 = smem;                             // encoder pong, h', (kept to the end: the actor reads it)
+    float* t0 = smem;                             // encoder pong, embed gather, h' (kept to the end: the actor reads it)
     float* t1 = t0 + ng;                          // h, posterior hidden, actor ping
-    float* t2 = t1 + ng;                          // encoder ping, x, actor pong
-    float* ef = t2 + ng;                          // obs -> embedding
-    float* sf = ef + d.Kb_io * kFragFloats;       // s, then s'
-    float* af = sf + d.Kb_s * kFragFloats;
+    float* t2 = t1 + ng;                          // encoder ping, x, actor gather, actor pong
+    float* ef = t2 + ng;                          // obs -> embedding -> (LC) the logits image
+    float* sf = ef + d.n_ef;                      // !LC: s, then s' (fragment tile)
+    float* sw_l = sf;                             // LC: [16][D] weights, [16][D] class indices
+    int* sidx_l = reinterpret_cast<int*>(sw_l + 16 * a.D);
+    float* af = sf + d.n_state;
     float* scratch = af + d.Kb_a * kFragFloats;   // split-K partials (kSplitScratchFloats), 16-byte aligned
     const int lane = bd_tid() & 63;
-    const Rng key{(uint32_t)a.seed, (uint32_t)(a.seed >> 32), 0u, (uint32_t)a.step};
-    // element (row, col) of a [B x width] noise tensor: the caller's buffer, or what bd_rng_fill writes there
-    auto draw = [&](const float* __restrict__ eps, unsigned stream, int width, int row, int col) -> float {
-        const int grow = row0 + row;
-        if (grow >= a.B) return 0.f;
-        const size_t e = (size_t)grow * width + col;
+    const CatGeo g(LC ? a.D : 1, LC ? a.C : 1);
+    // element e of a noise tensor: the caller's buffer, or what bd_rng_fill writes there for `kind`
+    auto draw_at = [&](const float* __restrict__ eps, unsigned stream, int kind, size_t e) -> float {
         if (eps != nullptr) return eps[e];
+        const Rng r{(uint32_t)a.seed, (uint32_t)(a.seed >> 32), stream, (uint32_t)a.step};
         float v[4];
-        rng_normal4(Rng{key.k0, key.k1, stream, key.step}, e >> 2, v);
+        if (kind == kDrawExp) rng_exp4(r, e >> 2, v);
+        else if (kind == kDrawUniform) rng_uniform4(r, e >> 2, v);
+        else rng_normal4(r, e >> 2, v);
         const int j = (int)(e & 3);
         return j == 0 ? v[0] : (j == 1 ? v[1] : (j == 2 ? v[2] : v[3]));
     };
+    auto draw = [&](const float* __restrict__ eps, unsigned stream, int kind, int width, int row, int col) -> float {
+        return row0 + row < a.B ? draw_at(eps, stream, kind, (size_t)(row0 + row) * width + col) : 0.f;
+    };
     auto hidden_epi = [&](float* dst, int width) { return HiddenEpiTR{dst, nullptr, 0, width, a.B, row0, lane}; };
+    // hidden layer whose state columns were gathered into xs [16][width]: ELU(acc + xs) -> fragment tile
+    auto gather_epi = [&](float* dst, const float* xs, int width) {
+        return [dst, xs, width, lane, rok_rows = a.B - row0](int nb, floatx4 acc) {
+            const int row = lane & 15, col0 = nb * 16 + 4 * (lane >> 4);
+            const bool rok = row < rok_rows;
+            floatx4 v;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = (rok && col0 + r < width) ? elu(acc[r] + xs[row * width + col0 + r]) : 0.f;
+            reinterpret_cast<floatx4*>(dst)[nb * 64 + lane] = v;
+        };
+    };
 
     load_tile_concat<1>(t1, d.Kb_h, row0, a.B, a.belief, a.Be, a.Be, nullptr, 0, 0);
-    load_tile_concat<1>(sf, d.Kb_s, row0, a.B, a.state, a.S, a.S, nullptr, 0, 0);
+    if constexpr (LC) state_to_indices(g, a.state, (size_t)a.S, row0, a.B, sidx_l, sw_l);
+    else load_tile_concat<1>(sf, d.Kb_s, row0, a.B, a.state, a.S, a.S, nullptr, 0, 0);
     load_tile_concat<1>(af, d.Kb_a, row0, a.B, a.action, a.A, a.A, nullptr, 0, 0);
     if (a.obs != nullptr) load_tile_concat<1>(ef, d.Kb_o, row0, a.B, a.obs, a.O, a.O, nullptr, 0, 0);
     else load_tile_concat<1>(ef, d.Kb_e, row0, a.B, a.embedding, a.E, a.E, nullptr, 0, 0);
@@ -102,7 +155,12 @@ __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
         lds_barrier();
     }
     // ---- 2: x = ELU(W_e [s; a] + b_e);  h' = GRUCell(x, h) ----
-    {
+    if constexpr (LC) {
+        state_gather(g, a.w_embed_sT, a.Be, sidx_l, sw_l, nullptr, t0);      // t0 is free until the GRU's epilogue
+        lds_barrier();
+        const Seg segs[1] = {{af, a.w_embed_a, d.Kb_a}};
+        tile_linear_seg_tr<1>(segs, a.b_embed, a.Be, gather_epi(t2, t0, a.Be));
+    } else {
         const Seg segs[2] = {{sf, a.w_embed_s, d.Kb_s}, {af, a.w_embed_a, d.Kb_a}};
         tile_linear_seg_tr<2>(segs, a.b_embed, a.Be, hidden_epi(t2, a.Be));
     }
@@ -131,11 +189,41 @@ __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
         tile_linear_seg_tr<2>(segs, a.b_q1, a.Hd, hidden_epi(t1, a.Hd));
     }
     lds_barrier();
-    {
+    if constexpr (LC) {
+        const CatFull gf(a.D, a.C);
+        float* lg = ef;                           // the embedding is dead: its storage holds the logits image
+        const Seg seg[1] = {{t1, a.w_q2, d.Kb_hd}};
+        tile_linear_g<1, 1>(seg, a.b_q2, a.S, [&](int, int nb, floatx4 acc) {
+            const int col = nb * 16 + (lane & 15);
+            if (col >= a.S) return;
+            const int f = col / a.C, c = col - f * a.C;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lg[gf.addr(4 * (lane >> 4) + r, f, c)] = acc[r];
+        });
+        lds_barrier();
+        const Rng rng{(uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.stream_post, (uint32_t)a.step};
+        for (int i = bd_tid(); i < 16 * a.D; i += blockDim.x) {
+            const int row = i / a.D, f = i - row * a.D;
+            int arg = 0;
+            if (row < rows_valid) {
+                const size_t e0 = (size_t)(row0 + row) * a.S + f * a.C;      // first class of this factor in [B x S]
+                if (a.eps_post) {
+                    const float* qrow = a.eps_post + e0;
+                    arg = a.C == 32 ? cat_sample_reg<32>(gf, lg, qrow, row, f) : cat_sample_any(gf, lg, qrow, row, f);
+                } else {
+                    arg = a.C == 32 ? cat_sample_reg_rng<32>(gf, lg, rng, e0, row, f) : cat_sample_any_rng(gf, lg, rng, e0, row, f);
+                }
+            }
+            sidx_l[i] = arg;
+            sw_l[i] = row < rows_valid ? 1.f : 0.f;      // a sampled state is one-hot whatever the incoming state's weights were
+        }
+        lds_barrier();
+        write_onehot(g, sidx_l, sw_l, nullptr, a.state_out + (size_t)row0 * a.S, (size_t)a.S, rows_valid);
+    } else {
         const Seg2 segs[1] = {{t1, a.w_q2m, a.w_q2s, d.Kb_hd}};
         tile_dual_head_elem<1>(
             segs, a.b_q2, a.b_q2 + a.S, a.S, scratch,
-            [&](int row, int col) { return draw(a.eps_post, a.stream_post, a.S, row, col); },
+            [&](int row, int col) { return draw(a.eps_post, a.stream_post, kDrawNormal, a.S, row, col); },
             [&](int row, int col, float Mn, float Rw, float eps) {
                 const int grow = row0 + row;
                 float st = 0.f;
@@ -145,10 +233,15 @@ __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
                 }
                 sf[frag_idx(row, col)] = st;
             });
+        lds_barrier();
     }
-    lds_barrier();
     // ---- 4: actor on [h'; s'] ----
-    {
+    if constexpr (LC) {
+        state_gather(g, a.w_a0sT, a.Hd, sidx_l, sw_l, nullptr, t2);         // x is dead since the GRU
+        lds_barrier();
+        const Seg segs[1] = {{t0, a.w_a0h, d.Kb_h}};
+        tile_linear_seg_tr<1>(segs, a.b_a[0], a.Hd, gather_epi(t1, t2, a.Hd));
+    } else {
         const Seg segs[2] = {{t0, a.w_a0h, d.Kb_h}, {sf, a.w_a0s, d.Kb_s}};
         tile_linear_seg_tr<2>(segs, a.b_a[0], a.Hd, hidden_epi(t1, a.Hd));
     }
@@ -164,14 +257,49 @@ __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
         }
         // three swaps: layer 3's activations are in t2
     }
-    // ---- 5: tanh-Normal sample, exploration noise ----
-    {
+    // ---- 5: the action sample and exploration ----
+    if constexpr (AC) {
+        // A logits -> the plain area behind the split-K partials, [16][A]; then one wave per row, one lane per class
+        float* out_s = scratch + kSplitPartialFloats;
+        const Seg segs[1] = {{t2, a.w_a4m, d.Kb_hd}};
+        tile_linear_seg<1>(segs, a.b_a4, a.A, [&](int nb, floatx4 acc) {
+            const int col = nb * 16 + (lane & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (col < a.A) out_s[(4 * (lane >> 4) + r) * a.A + col] = acc[r];
+        }, scratch);
+        lds_barrier();
+        const int wave = bd_wave(bd_tid());
+        for (int row = wave; row < rows_valid; row += kWaves) {        // wave-uniform: the butterflies see the whole wave
+            const int grow = row0 + row;
+            const bool valid = lane < a.A;
+            const float q = valid ? draw_at(a.eps_action, a.stream_action, kDrawExp, (size_t)grow * a.A + lane) : 1.f;
+            const float norm = disc_norm(valid ? out_s[row * a.A + lane] : 0.f, valid);
+            const float p = disc_probs(norm, valid);
+            const int k = disc_sample(p, q, valid, lane);
+            float act = disc_action_value(p, lane == k);
+            if (a.explore) {      // epsilon-greedy: (u, v) = the row's two uniforms
+                const float u = draw_at(a.eps_explore, a.stream_explore, kDrawUniform, (size_t)grow * 2);
+                const float v = draw_at(a.eps_explore, a.stream_explore, kDrawUniform, (size_t)grow * 2 + 1);
+                int kr = (int)floorf(v * (float)a.A);
+                kr = kr < a.A - 1 ? kr : a.A - 1;
+                if (u < a.action_noise) act = lane == kr ? 1.f : 0.f;
+            }
+            if (valid) a.action_out[(size_t)grow * a.A + lane] = act;
+        }
+    } else {
         const Seg2 segs[1] = {{t2, a.w_a4m, a.w_a4s, d.Kb_hd}};
         tile_dual_head_elem<1>(
             segs, a.b_a4, a.b_a4 + a.A, a.A, scratch,
             [&](int row, int col) {
-                return ActEps{draw(a.eps_action, a.stream_action, a.A, row, col),
-                              a.explore ? draw(a.eps_explore, a.stream_explore, a.A, row, col) : 0.f};
+                // ONE call site of the normal generator for both draws: with two, hipcc stops inlining the library's
+                // sincosf, and the call's stack frame becomes the kernel's only scratch (544 B per lane, and 40 more VGPRs
+                // on the Gaussian instantiation when the two draws were written as two calls)
+                float ev[2] = {0.f, 0.f};
+#pragma unroll 1
+                for (int t = 0; t < (a.explore ? 2 : 1); ++t)
+                    ev[t] = draw(t ? a.eps_explore : a.eps_action, t ? a.stream_explore : a.stream_action, kDrawNormal, a.A, row, col);
+                return ActEps{ev[0], ev[1]};
             },
             [&](int row, int col, float Mn, float Rw, ActEps eps) {
                 const int grow = row0 + row;
@@ -185,12 +313,67 @@ __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
     }
 }
 
-static bool act_dims_ok(int Be, int S, int A, int Hd, int E, int O) {
-    if (Be <= 0 || S <= 0 || A <= 0 || Hd <= 0 || E <= 0 || O < 0) return false;
-    // (bounds first: the tile counts below must not overflow)
-    if (Be > (1 << 20) || Hd > (1 << 20) || E > (1 << 20) || O > (1 << 20)) return false;
-    if (S > kHeadMaxN || A > kHeadMaxN) return false;
-    return ActDims(Be, S, A, Hd, E, O).lds_floats() * sizeof(float) <= (size_t)kMaxLds;
+// nullptr = dims the kernel takes (LDS aside); otherwise the reason
+static const char* act_dims_error(int Be, int D, int C, int S, int A, int Hd, int E, int O, bool lc) {
+    if (Be <= 0 || S <= 0 || A <= 0 || Hd <= 0 || E <= 0 || O < 0) return "bad dims";
+    // (bounds first: the tile counts of the LDS figure must not overflow)
+    if (Be > (1 << 20) || Hd > (1 << 20) || E > (1 << 20) || O > (1 << 20) || S > (1 << 20)) return "layer width above 2^20";
+    if (A > kHeadMaxN) return "action width above 64 (one lane per class; the widest Gaussian head)";
+    if (lc) {
+        if (D <= 0 || C <= 0 || D > (1 << 20) || C > 256 || (long long)D * C != S || !CatGeo(D, C).ok())
+            return "latents unsupported (S = D*C; C <= 256; S <= 256, or 256 % C == 0 and S % 16 == 0)";
+    } else if (S > kHeadMaxN) {
+        return "state width above 64";
+    }
+    return nullptr;
+}
+
+static bool act_supported(int Be, int D, int C, int S, int A, int Hd, int E, int O, bool lc) {
+    return act_dims_error(Be, D, C, S, A, Hd, E, O, lc) == nullptr &&
+           ActDims(Be, D, C, S, A, Hd, E, O, lc).lds_floats() * sizeof(float) <= (size_t)kMaxLds;
+}
+
+template <bool LC, bool AC>
+static int act_launch(const char* who, const bd_act_args& k, size_t lds, hipStream_t stream) {
+    if (lds > 64 * 1024 && allow_big_lds(act_step_kernel<LC, AC>)) return -1;
+    hipLaunchKernelGGL((act_step_kernel<LC, AC>), dim3(cdiv(k.B, 16)), dim3(kThreads), lds, stream, k);
+    BD_CHECK_LAUNCH(who);
+    return 0;
+}
+
+// the checks of both entry points (`who` names the one that was called), then the launch of the (latent_cat, actor_cat) kernel
+static int act_step(const char* who, const bd_act_args* a, hipStream_t stream) {
+    BD_REQUIRE(a->B > 0, "%s: bad dims", who);
+    const bool lc = a->latent_cat != 0, ac = a->actor_cat != 0;
+    BD_REQUIRE((a->obs != nullptr) != (a->embedding != nullptr),
+               "%s: give the observation (state observations) or the embedding (pixels), not both", who);
+    const int O = a->obs ? a->O : 0;
+    const char* why = act_dims_error(a->Be, a->D, a->C, a->S, a->A, a->Hd, a->E, O, lc);
+    BD_REQUIRE(why == nullptr, "%s: %s (Be %d, %d x %d, S %d, A %d, Hd %d, E %d, O %d)", who, why, a->Be, a->D, a->C, a->S, a->A,
+               a->Hd, a->E, O);
+    const size_t lds = ActDims(a->Be, a->D, a->C, a->S, a->A, a->Hd, a->E, O, lc).lds_floats() * sizeof(float);
+    BD_REQUIRE(lds <= (size_t)kMaxLds, "%s: needs %zu B of LDS (limit %d)", who, lds, kMaxLds);
+    if (a->obs != nullptr) {
+        BD_REQUIRE(a->O > 0, "%s: obs given with O = 0", who);
+        for (int l = 0; l < 5; ++l) BD_REQUIRE(a->w_enc[l] && a->b_enc[l], "%s: missing encoder weights (layer %d)", who, l);
+    }
+    BD_REQUIRE(a->w_embed_a && a->b_embed && a->w_ir && a->w_iz && a->w_in && a->w_hr && a->w_hz && a->w_hn && a->b_ih && a->b_hh &&
+                   a->w_q1h && a->w_q1e && a->b_q1 && a->b_q2 &&
+                   (lc ? (a->w_embed_sT && a->w_q2) : (a->w_embed_s && a->w_q2m && a->w_q2s)),
+               "%s: missing transition weights", who);
+    BD_REQUIRE(a->w_a0h && (lc ? a->w_a0sT : a->w_a0s) && a->w_a[0] && a->w_a[1] && a->w_a[2] && a->b_a[0] && a->b_a[1] &&
+                   a->b_a[2] && a->b_a[3] && a->w_a4m && (ac || a->w_a4s) && a->b_a4, "%s: missing actor weights", who);
+    BD_REQUIRE(a->belief && a->state && a->action, "%s: missing inputs", who);
+    BD_REQUIRE(a->belief_out && a->state_out && a->action_out, "%s: missing outputs", who);
+    BD_REQUIRE(a->belief_out != a->belief && a->state_out != a->state && a->action_out != a->action,
+               "%s: an output aliases its input", who);
+    const bool all_null = !a->eps_post && !a->eps_action && !a->eps_explore;
+    BD_REQUIRE(all_null || (a->eps_post && a->eps_action && (a->eps_explore || !a->explore)),
+               "%s: noise buffers: eps_post, eps_action (and eps_explore when explore) or all NULL", who);
+    bd_act_args k = *a;
+    k.O = O;
+    if (lc) return ac ? act_launch<true, true>(who, k, lds, stream) : act_launch<true, false>(who, k, lds, stream);
+    return ac ? act_launch<false, true>(who, k, lds, stream) : act_launch<false, false>(who, k, lds, stream);
 }
 
 }  // namespace bd
@@ -198,41 +381,26 @@ static bool act_dims_ok(int Be, int S, int A, int Hd, int E, int O) {
 extern "C" {
 using namespace bd;
 
-int bd_act_step_supported(int Be, int S, int A, int Hd, int E, int O) { return act_dims_ok(Be, S, A, Hd, E, O) ? 1 : 0; }
+int bd_act_step_supported(int Be, int S, int A, int Hd, int E, int O) { return act_supported(Be, 0, 0, S, A, Hd, E, O, false) ? 1 : 0; }
+
+int bd_act_step_cat_supported(int Be, int D, int C, int S, int A, int Hd, int E, int O, int latent_cat, int actor_cat) {
+    if (!latent_cat && !actor_cat) return 0;      // that configuration is bd_act_step
+    return act_supported(Be, D, C, S, A, Hd, E, O, latent_cat != 0) ? 1 : 0;
+}
 
 int bd_act_step(const bd_act_args* a, void* stream) {
     BD_REQUIRE(a, "bd_act_step: null argument block");
-    BD_REQUIRE(a->B > 0 && a->Be > 0 && a->S > 0 && a->A > 0 && a->Hd > 0 && a->E > 0 && a->O >= 0, "bd_act_step: bad dims");
-    BD_REQUIRE(a->S <= kHeadMaxN && a->A <= kHeadMaxN, "bd_act_step: state / action width above %d", kHeadMaxN);
-    BD_REQUIRE(a->Be <= (1 << 20) && a->Hd <= (1 << 20) && a->E <= (1 << 20) && a->O <= (1 << 20),
-               "bd_act_step: layer width above 2^20");
-    BD_REQUIRE((a->obs != nullptr) != (a->embedding != nullptr),
-               "bd_act_step: give the observation (state observations) or the embedding (pixels), not both");
-    if (a->obs != nullptr) {
-        BD_REQUIRE(a->O > 0, "bd_act_step: obs given with O = 0");
-        for (int l = 0; l < 5; ++l) BD_REQUIRE(a->w_enc[l] && a->b_enc[l], "bd_act_step: missing encoder weights (layer %d)", l);
-    }
-    BD_REQUIRE(a->w_embed_s && a->w_embed_a && a->b_embed && a->w_ir && a->w_iz && a->w_in && a->w_hr && a->w_hz && a->w_hn &&
-                   a->b_ih && a->b_hh && a->w_q1h && a->w_q1e && a->b_q1 && a->w_q2m && a->w_q2s && a->b_q2,
-               "bd_act_step: missing transition weights");
-    BD_REQUIRE(a->w_a0h && a->w_a0s && a->w_a[0] && a->w_a[1] && a->w_a[2] && a->b_a[0] && a->b_a[1] && a->b_a[2] && a->b_a[3] &&
-                   a->w_a4m && a->w_a4s && a->b_a4, "bd_act_step: missing actor weights");
-    BD_REQUIRE(a->belief && a->state && a->action, "bd_act_step: missing inputs");
-    BD_REQUIRE(a->belief_out && a->state_out && a->action_out, "bd_act_step: missing outputs");
-    BD_REQUIRE(a->belief_out != a->belief && a->state_out != a->state && a->action_out != a->action,
-               "bd_act_step: an output aliases its input");
-    const bool all_null = !a->eps_post && !a->eps_action && !a->eps_explore;
-    BD_REQUIRE(all_null || (a->eps_post && a->eps_action && (a->eps_explore || !a->explore)),
-               "bd_act_step: noise buffers: eps_post, eps_action (and eps_explore when explore) or all NULL");
-    const ActDims d(a->Be, a->S, a->A, a->Hd, a->E, a->obs ? a->O : 0);
-    const size_t lds = d.lds_floats() * sizeof(float);
-    BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_act_step: needs %zu B of LDS", lds);
-    if (lds > 64 * 1024 && allow_big_lds(act_step_kernel)) return -1;
-    bd_act_args k = *a;
-    if (k.obs == nullptr) k.O = 0;
-    hipLaunchKernelGGL(act_step_kernel, dim3(cdiv(a->B, 16)), dim3(kThreads), lds, (hipStream_t)stream, k);
-    BD_CHECK_LAUNCH("bd_act_step");
-    return 0;
+    BD_REQUIRE(!a->latent_cat && !a->actor_cat,
+               "bd_act_step: takes latent_cat = 0 and actor_cat = 0 (Gaussian latents with the tanh-Normal actor); the other "
+               "configurations are bd_act_step_cat");
+    return act_step("bd_act_step", a, (hipStream_t)stream);
+}
+
+int bd_act_step_cat(const bd_act_args* a, void* stream) {
+    BD_REQUIRE(a, "bd_act_step_cat: null argument block");
+    BD_REQUIRE(a->latent_cat || a->actor_cat,
+               "bd_act_step_cat: Gaussian latents with the tanh-Normal actor: that configuration is bd_act_step");
+    return act_step("bd_act_step_cat", a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -331,19 +331,23 @@ class Dreamer:
         `_noise`: the composed path's keys "post" (B,S), "action" (B,A) and, with explore, "explore" (B,A); "prior" and
         "entropy" are accepted and ignored (their draws feed nothing that is returned).  Without it the draws come from
         the engine's Philox streams.  The results are engine buffers, valid until the call after the next one."""
-        e = self.engine
-        if not e.act_step_supported:
-            raise NotImplementedError(
-                "act_step: the fused acting kernel takes Gaussian latents and the tanh-Normal actor at sizes "
-                f"bd_act_step_supported accepts (latent_distribution={self.latent_distribution}, action_distribution="
-                f"{self.action_distribution}, dims {self.dims.Be}/{self.dims.S}/{self.dims.A}/{self.dims.Hd}/{self.dims.E}); "
-                "use update_belief_and_act, which composes the step from the scan kernels")
+        obs, emb = self._act_inputs(self.engine.act_step_supported, observation,
+                                    "act_step: the fused acting kernel takes Gaussian latents and the tanh-Normal actor at sizes "
+                                    "bd_act_step_supported accepts ({config}); use update_belief_and_act, which composes the "
+                                    "step from the scan kernels")
+        return self.engine.act_step(belief, posterior_state, action, obs=obs, embedding=emb, explore=bool(explore),
+                                    action_noise=self.action_noise, noise=_noise)
+
+    def _act_inputs(self, supported: bool, observation: Tensor, refusal: str):
+        """The preamble of act_step / act_step_cat: refuse an unsupported configuration (`refusal`, its {config} filled in
+        here), then the observation on the device as (obs, None), or -- pixels -- (None, its conv embedding)."""
+        if not supported:
+            d = self.dims
+            raise NotImplementedError(refusal.format(
+                config=f"latent_distribution={self.latent_distribution}, action_distribution={self.action_distribution}, "
+                       f"dims {d.Be}/{d.S}/{d.A}/{d.Hd}/{d.E}"))
         obs = observation.to(self.device)
-        emb = None
-        if self.pixel_observation:
-            emb, obs = self.encoder(obs), None
-        return e.act_step(belief, posterior_state, action, obs=obs, embedding=emb, explore=bool(explore),
-                          action_noise=self.action_noise, noise=_noise)
+        return (None, self.encoder(obs)) if self.pixel_observation else (obs, None)
 
     @property
     def act_fused_cat(self) -> bool:
@@ -360,17 +364,12 @@ class Dreamer:
         (B,A) (tanh-Normal actor) or "explore_u" (B,) uniforms and "explore_k" (B,) classes (Categorical actor; the kernel
         gets v = (k + 0.5) / A, whose class is k); "prior" and "entropy" are accepted and ignored.  Without it the draws come
         from the engine's Philox streams.  The results are engine buffers, valid until the call after the next one."""
-        e, d = self.engine, self.dims
-        if not e.act_step_cat_supported:
-            raise NotImplementedError(
-                "act_step_cat: the fused acting kernel takes Categorical latents and / or the Categorical actor at sizes "
-                f"bd_act_step_cat_supported accepts (latent_distribution={self.latent_distribution}, action_distribution="
-                f"{self.action_distribution}, dims {d.Be}/{d.S}/{d.A}/{d.Hd}/{d.E}); Gaussian latents with the tanh-Normal "
-                "actor use act_step, everything else update_belief_and_act, which composes the step from the scan kernels")
-        obs = observation.to(self.device)
-        emb = None
-        if self.pixel_observation:
-            emb, obs = self.encoder(obs), None
+        d = self.dims
+        obs, emb = self._act_inputs(self.engine.act_step_cat_supported, observation,
+                                    "act_step_cat: the fused acting kernel takes Categorical latents and / or the Categorical "
+                                    "actor at sizes bd_act_step_cat_supported accepts ({config}); Gaussian latents with the "
+                                    "tanh-Normal actor use act_step, everything else update_belief_and_act, which composes "
+                                    "the step from the scan kernels")
         nz = _noise
         if nz is not None:
             nz = {k: nz[k] for k in ("post", "action")}
@@ -379,8 +378,8 @@ class Dreamer:
                 nz["explore"] = torch.stack([u, (k + 0.5) / d.A], dim=1)
             elif explore:
                 nz["explore"] = _noise["explore"]
-        return e.act_step_cat(belief, posterior_state, action, obs=obs, embedding=emb, explore=bool(explore),
-                              action_noise=self.action_noise, noise=nz)
+        return self.engine.act_step_cat(belief, posterior_state, action, obs=obs, embedding=emb, explore=bool(explore),
+                                        action_noise=self.action_noise, noise=nz)
 
     @torch.no_grad()
     def update_belief_and_act(self, env, belief, posterior_state, action, observation, explore=False,

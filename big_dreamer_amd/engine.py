@@ -1112,51 +1112,7 @@ class DreamerEngine:
         Ordered behind queued train steps and packed-weight refreshes like every API call (flush_optimizers, join).
         The results live in two alternating sets of engine buffers: a call never writes what it reads, and what it returns
         stays valid until the call after the next one (clone to keep it longer)."""
-        d, pk = self.d, self.pk
-        tm = lambda n: self.W("transition_model", n)
-        self.flush_optimizers()
-        self.join()
-        f = lambda t: t.to(self.dev).float().contiguous()
-        belief, state, action = f(belief), f(state), f(action)
-        B = belief.shape[0]
-        a = cabi.ActArgs()
-        a.B, a.Be, a.S, a.A, a.Hd, a.E = B, d.Be, d.S, d.A, d.Hd, d.E
-        if embedding is None:
-            a.O, a.obs = d.O, ptr(f(obs).view(B, d.O))
-            for l in range(DENSE_LAYERS + 1):
-                a.w_enc[l], a.b_enc[l] = ptr(pk[f"enc{l}"]), ptr(self.W("encoder", f"model.{2 * l}.bias"))
-        else:
-            a.embedding = ptr(f(embedding).view(B, d.E))
-        self._bind_rssm(a)
-        self._actor_head_args(a)
-        a.w_embed_s, a.w_a0s = ptr(pk["embed_s"]), ptr(pk["a0s"])
-        a.w_q1h, a.w_q1e, a.b_q1 = ptr(pk["q1h"]), ptr(pk["q1e"]), ptr(tm("belief_posterior.model.0.bias"))
-        a.w_q2m, a.w_q2s, a.b_q2 = ptr(pk["q2m"]), ptr(pk["q2s"]), ptr(tm("belief_posterior.model.2.bias"))
-        a.belief, a.state, a.action = ptr(belief), ptr(state), ptr(action)
-        if noise is not None:
-            a.eps_post, a.eps_action = ptr(f(noise["post"]).view(B, d.S)), ptr(f(noise["action"]).view(B, d.A))
-            a.eps_explore = ptr(f(noise["explore"]).view(B, d.A)) if explore else None
-        else:
-            a.seed, a.step = self.rng_seed, self._rng_step.get("act", 0)
-            self._rng_step["act"] = a.step + 1
-        a.stream_post, a.stream_action, a.stream_explore = (self.RNG_STREAMS[k] for k in ("act_post", "act_action", "act_explore"))
-        a.min_std = self.hp["min_std_dev"]
-        a.act_raw_init_std, a.act_min_std, a.act_mean_scale = ACT_RAW_INIT_STD, ACT_MIN_STD, ACT_MEAN_SCALE
-        a.action_noise, a.explore = float(action_noise), int(bool(explore))
-        # the output set: the one none of the inputs lives in (a caller feeding results back alternates by itself)
-        ins = {belief.data_ptr(), state.data_ptr(), action.data_ptr()}
-        for p in (self._act_parity, 1 - self._act_parity):
-            out = (self.buf(f"act{p}_belief", B, d.Be), self.buf(f"act{p}_state", B, d.S), self.buf(f"act{p}_action", B, d.A))
-            if not ins & {t.data_ptr() for t in out}:
-                break
-        else:       # inputs taken from both sets
-            belief, state, action = belief.clone(), state.clone(), action.clone()
-            a.belief, a.state, a.action = ptr(belief), ptr(state), ptr(action)
-        self._act_parity = 1 - p
-        a.belief_out, a.state_out, a.action_out = (ptr(t) for t in out)
-        with self.span("act_step"):
-            cabi.check(lib.bd_act_step(C.byref(a), cabi.stream()))
-        return out
+        return self._act("act_step", belief, state, action, obs, embedding, explore, action_noise, noise)
 
     @property
     def act_step_cat_supported(self) -> bool:
@@ -1178,14 +1134,24 @@ class DreamerEngine:
         Categorical one (epsilon-greedy: u < action_noise picks class min(floor(v A), A - 1)).  None: the kernel draws
         from the Philox streams act_post / act_action / act_explore, one counter step per decision (shared with act_step).
         A Categorical state must be all-zero or one-hot per factor, as for imagine() from a caller's state."""
+        return self._act("act_step_cat", belief, state, action, obs, embedding, explore, action_noise, noise)
+
+    def _act(self, name: str, belief, state, action, obs, embedding, explore, action_noise, noise):
+        """The body of act_step / act_step_cat: binds the argument block for this engine's latent and actor kind, picks the
+        output set and launches the entry point bd_<name> under the span <name> (the entry point refuses a kind that is
+        not its own; so does the check below, before anything of the engine's state is touched)."""
         d, pk = self.d, self.pk
+        if (name == "act_step_cat") != bool(d.categorical or d.discrete_actions):
+            raise RuntimeError(f"{name}: not this engine's configuration (Categorical latents: {bool(d.categorical)}, "
+                               f"Categorical actor: {bool(d.discrete_actions)}); Gaussian latents with the tanh-Normal actor are "
+                               "act_step's, the other three act_step_cat's")
         tm = lambda n: self.W("transition_model", n)
         self.flush_optimizers()
         self.join()
         f = lambda t: t.to(self.dev).float().contiguous()
         belief, state, action = f(belief), f(state), f(action)
         B = belief.shape[0]
-        a = cabi.ActCatArgs()
+        a = cabi.ActArgs()
         a.B, a.Be, a.S, a.A, a.Hd, a.E = B, d.Be, d.S, d.A, d.Hd, d.E
         a.latent_cat, a.actor_cat = int(d.categorical), int(d.discrete_actions)
         if embedding is None:
@@ -1216,7 +1182,7 @@ class DreamerEngine:
         a.min_std = self.hp["min_std_dev"]
         a.act_raw_init_std, a.act_min_std, a.act_mean_scale = ACT_RAW_INIT_STD, ACT_MIN_STD, ACT_MEAN_SCALE
         a.action_noise, a.explore = float(action_noise), int(bool(explore))
-        # the output set: the one none of the inputs lives in (as act_step; the two share the sets)
+        # the output set: the one none of the inputs lives in (a caller feeding results back alternates by itself)
         ins = {belief.data_ptr(), state.data_ptr(), action.data_ptr()}
         for p in (self._act_parity, 1 - self._act_parity):
             out = (self.buf(f"act{p}_belief", B, d.Be), self.buf(f"act{p}_state", B, d.S), self.buf(f"act{p}_action", B, d.A))
@@ -1227,8 +1193,8 @@ class DreamerEngine:
             a.belief, a.state, a.action = ptr(belief), ptr(state), ptr(action)
         self._act_parity = 1 - p
         a.belief_out, a.state_out, a.action_out = (ptr(t) for t in out)
-        with self.span("act_step_cat"):
-            cabi.check(lib.bd_act_step_cat(C.byref(a), cabi.stream()))
+        with self.span(name):
+            cabi.check(getattr(lib, "bd_" + name)(C.byref(a), cabi.stream()))
         return out
 
     # ------------------------------------------------------------------------------------------ train step

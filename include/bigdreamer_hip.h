@@ -736,71 +736,39 @@ int bd_plan_rollout_cat(const bd_plan_cat_args* a, void* stream);
 
 /* ---- acting: one decision of the collect / evaluation loop in ONE launch (csrc/act.hip) -------------------------
  * Planet.update_belief_and_act (src/planet.py:370-403) with Dreamer.get_action (src/dreamer.py:429-444) for B
- * environments, Gaussian latents and the tanh-Normal actor: encoder chain (or a ready embedding), embed layer + GRU cell
- * (one step of bd_observe_forward, same weights), posterior head on [h'; embedding], s' = mean + std * eps_post, actor
- * chain on [h'; s'], action = tanh(mean + std * eps_action) (mean scaling / init_std / min_std as bd_imagine_forward),
- * and with explore != 0 action = clamp(action + action_noise * eps_explore, -1, 1).  The prior head, get_action's prior
- * sample and the entropy estimate feed none of the three outputs and are not evaluated.
+ * environments: encoder chain (or a ready embedding), embed layer + GRU cell (one step of bd_observe_forward, same weights),
+ * posterior head on [h'; embedding] and its sample s', actor chain on [h'; s'], the action sample and exploration.  The
+ * prior head and its sample (src/models.py:256), get_action's prior sample and the entropy estimate (src/planet.py:386
+ * drops it) feed none of the three outputs and are not evaluated.
+ * One argument block and one kernel body for the four configurations; latent_cat / actor_cat select the instantiation.
+ * bd_act_step takes latent_cat = actor_cat = 0 only (a zeroed block with the Gaussian fields filled in), bd_act_step_cat
+ * the other three and rejects both 0 (that is bd_act_step).
+ *   latent_cat = 0: Gaussian latents (w_embed_s, w_q2m / w_q2s, w_a0s; D, C ignored): s' = mean + std * eps_post with
+ *     eps_post standard normal, std = softplus(raw) + min_std.  S <= 64.
+ *   latent_cat: latent_distribution="Categorical" (TransitionModel.forward's Categorical branches, src/models.py:226-228,
+ *     258-260,269-271, CategoricalBeliefModel src/models.py:101-117): the incoming state [B x S], S = D*C, is all-zero or
+ *     (scaled) one-hot per factor and is carried as class indices (the rule of bd_imagine_cat_forward with start_sidx =
+ *     NULL); W_es s and the state columns of the actor's first layer are gathers of rows of w_embed_sT / w_a0sT (plain
+ *     [S x out]); the posterior head w_q2 (packed (S, Hd)) gives D*C logits, per factor idx = argmax(softmax(logits) / q)
+ *     with q = eps_post ~ Exp(1), first maximum winning; state_out is the one-hot.  The host must have checked the incoming
+ *     one-hot state (a factor with two non-zero classes cannot be carried as an index; the kernel would take the larger).
+ *   actor_cat = 0: the tanh-Normal actor: action = tanh(mean + std * eps_action) (mean scaling / init_std / min_std as
+ *     bd_imagine_forward), and with explore != 0 action = clamp(action + action_noise * eps_explore, -1, 1); eps_action,
+ *     eps_explore [B x A] standard normal.
+ *   actor_cat: action_distribution="Categorical" (src/models.py:518-522): the head w_a4m / b_a4 has A outputs (w_a4s
+ *     unused), norm = out - logsumexp(out), p = softmax(norm), k = argmax(p / eps_action) with eps_action ~ Exp(1), action =
+ *     (onehot(k) + p) - p in that order (what bd_imagine_forward returns with discrete_actions = 1); explore != 0 is
+ *     epsilon-greedy (the port's update_belief_and_act): eps_explore is [B x 2] uniforms (u, v) in [0, 1), and where
+ *     u < action_noise the action is the exact one-hot of class min(floor(v * A), A - 1).
  * Observation: obs [B x O] with the encoder DenseModel's five layers (w_enc packed, model.{0,2,4,6,8}), or -- obs = NULL --
  * embedding [B x E] (pixel observations: the conv stack has already run; O and the encoder fields are then ignored).
- * Noise: eps_post [B x S], eps_action [B x A], eps_explore [B x A] (may be NULL when explore = 0) as explicit buffers, or
- * ALL NULL: standard normals drawn in the kernel, element i of each tensor being what bd_rng_fill(BD_RNG_NORMAL, seed,
- * step, stream_post / stream_action / stream_explore) writes at i.
+ * Noise: explicit buffers (eps_explore may be NULL when explore = 0), or ALL NULL: drawn in the kernel, element i of each
+ * tensor being what bd_rng_fill(kind, seed, step, stream_post / stream_action / stream_explore) writes at i, with the kinds
+ * above (BD_RNG_EXPONENTIAL for a Categorical sampler, BD_RNG_UNIFORM for epsilon-greedy, BD_RNG_NORMAL otherwise).
  * The kernel never writes its inputs: belief_out / state_out / action_out must be other buffers than belief / state /
- * action (the host ping-pongs).  One workgroup per 16 rows.  S, A <= 64; LDS as csrc/act.hip states (<= 160 KiB):
- * bd_act_step_supported tells without raising an error (O = 0: the embedding form). */
-typedef struct {
-    int B, Be, S, A, Hd, E, O;
-    const float* w_enc[5]; const float* b_enc[5];         /* encoder.model.{0,2,4,6,8} (obs form only) */
-    const float* w_embed_s; const float* w_embed_a; const float* b_embed;
-    const float* w_ir; const float* w_iz; const float* w_in;
-    const float* w_hr; const float* w_hz; const float* w_hn;
-    const float* b_ih; const float* b_hh;
-    const float* w_q1h; const float* w_q1e; const float* b_q1;   /* belief_posterior.model.0[:, :Be] / [:, Be:] */
-    const float* w_q2m; const float* w_q2s; const float* b_q2;   /* belief_posterior.model.2 rows [:S] / [S:]   */
-    const float* w_a0h; const float* w_a0s; const float* w_a[3]; const float* b_a[4];   /* as bd_imagine_fwd_args */
-    const float* w_a4m; const float* w_a4s; const float* b_a4;
-    const float* belief;       /* [B x Be] */
-    const float* state;        /* [B x S]  */
-    const float* action;       /* [B x A]  previous action */
-    const float* obs;          /* [B x O] or NULL */
-    const float* embedding;    /* [B x E] or NULL (exactly one of obs / embedding) */
-    const float* eps_post; const float* eps_action; const float* eps_explore;
-    unsigned long long seed; unsigned long long step;     /* in-kernel noise: Philox key and decision counter */
-    unsigned stream_post, stream_action, stream_explore;  /* distinct Philox stream ids */
-    float min_std, act_raw_init_std, act_min_std, act_mean_scale, action_noise;
-    int explore;
-    float* belief_out;         /* [B x Be] */
-    float* state_out;          /* [B x S]  */
-    float* action_out;         /* [B x A]  */
-} bd_act_args;
-int bd_act_step_supported(int Be, int S, int A, int Hd, int E, int O);
-int bd_act_step(const bd_act_args* a, void* stream);
-
-/* The same decision for the DreamerV2 configurations (csrc/act_cat.hip): latent_distribution="Categorical"
- * (TransitionModel.forward's Categorical branches, src/models.py:226-228,258-260,269-271, CategoricalBeliefModel
- * src/models.py:101-117) and / or action_distribution="Categorical" (src/models.py:518-522), one launch, same ownership
- * as bd_act_step.  latent_cat / actor_cat select one of three instantiations; both 0 is rejected (that is bd_act_step).
- *   latent_cat: the incoming state [B x S], S = D*C, is all-zero or (scaled) one-hot per factor and is carried as class
- *     indices (the rule of bd_imagine_cat_forward with start_sidx = NULL); W_es s and the state columns of the actor's first
- *     layer are gathers of rows of w_embed_sT / w_a0sT (plain [S x out]); the posterior head w_q2 (packed (S, Hd)) gives
- *     D*C logits, per factor idx = argmax(softmax(logits) / q) with q = eps_post ~ Exp(1), first maximum winning;
- *     state_out is the one-hot.  latent_cat = 0: Gaussian latents exactly as bd_act_step (w_embed_s, w_q2m / w_q2s, w_a0s,
- *     eps_post standard normal; D, C ignored).
- *   actor_cat: the head w_a4m / b_a4 has A <= 64 outputs (w_a4s unused), norm = out - logsumexp(out), p = softmax(norm),
- *     k = argmax(p / eps_action) with eps_action ~ Exp(1), action = (onehot(k) + p) - p in that order (what
- *     bd_imagine_forward returns with discrete_actions = 1); explore != 0 is epsilon-greedy (the port's
- *     update_belief_and_act): eps_explore is [B x 2] uniforms (u, v) in [0, 1), and where u < action_noise the action is
- *     the exact one-hot of class min(floor(v * A), A - 1).  actor_cat = 0: the tanh-Normal tail of bd_act_step
- *     (eps_action, eps_explore [B x A] standard normal).
- * Not evaluated, as in bd_act_step: the prior head and its sample (src/models.py:256), get_action's prior sample and the
- * actor entropy (src/planet.py:386 drops it) -- none feeds belief, state or action.
- * Noise: explicit buffers or ALL NULL; in-kernel draws have the element layout of bd_rng_fill on stream_post /
- * stream_action / stream_explore with the kinds above (BD_RNG_EXPONENTIAL for a Categorical sampler, BD_RNG_UNIFORM for
- * epsilon-greedy, BD_RNG_NORMAL otherwise).
- * The host must have checked the incoming one-hot state (a factor with two non-zero classes cannot be carried as an
- * index; the kernel would take the larger).  LDS as csrc/act_cat.hip states: bd_act_step_cat_supported answers from the
- * launcher's own arithmetic (O = 0: the embedding form). */
+ * action (the host ping-pongs).  One workgroup per 16 rows.  A <= 64; LDS as csrc/act.hip states (<= 160 KiB):
+ * bd_act_step_supported / bd_act_step_cat_supported answer from the launcher's own arithmetic without raising an error
+ * (O = 0: the embedding form). */
 typedef struct {
     int B, Be, D, C, S, A, Hd, E, O;
     int latent_cat, actor_cat;
@@ -811,7 +779,7 @@ typedef struct {
     const float* w_ir; const float* w_iz; const float* w_in;
     const float* w_hr; const float* w_hz; const float* w_hn;
     const float* b_ih; const float* b_hh;
-    const float* w_q1h; const float* w_q1e; const float* b_q1;
+    const float* w_q1h; const float* w_q1e; const float* b_q1;   /* belief_posterior.model.0[:, :Be] / [:, Be:] */
     const float* w_q2m; const float* w_q2s;               /* Gaussian latents: belief_posterior.model.2 rows [:S] / [S:] */
     const float* w_q2;                                    /* Categorical latents: packed (S, Hd) */
     const float* b_q2;                                    /* [2*S] / [S] */
@@ -828,14 +796,17 @@ typedef struct {
     const float* eps_post;     /* [B x S] */
     const float* eps_action;   /* [B x A] */
     const float* eps_explore;  /* [B x A], or [B x 2] with actor_cat; may be NULL when explore = 0 */
-    unsigned long long seed; unsigned long long step;
-    unsigned stream_post, stream_action, stream_explore;
+    unsigned long long seed; unsigned long long step;     /* in-kernel noise: Philox key and decision counter */
+    unsigned stream_post, stream_action, stream_explore;  /* distinct Philox stream ids */
     float min_std, act_raw_init_std, act_min_std, act_mean_scale, action_noise;
     int explore;
     float* belief_out;         /* [B x Be] */
     float* state_out;          /* [B x S]  */
     float* action_out;         /* [B x A]  */
-} bd_act_cat_args;
+} bd_act_args;
+typedef bd_act_args bd_act_cat_args;
+int bd_act_step_supported(int Be, int S, int A, int Hd, int E, int O);
+int bd_act_step(const bd_act_args* a, void* stream);
 int bd_act_step_cat_supported(int Be, int D, int C, int S, int A, int Hd, int E, int O, int latent_cat, int actor_cat);
 int bd_act_step_cat(const bd_act_cat_args* a, void* stream);
 

@@ -1,5 +1,5 @@
 """float64 numpy restatement of one acting decision (Planet.update_belief_and_act, src/planet.py:370-403, with
-Dreamer.get_action, src/dreamer.py:429-444) for the three configurations of bd_act_step_cat (csrc/act_cat.hip):
+Dreamer.get_action, src/dreamer.py:429-444) for the three configurations of bd_act_step_cat (csrc/act.hip):
 Categorical latents with the tanh-Normal actor, Categorical latents with the Categorical actor, Gaussian latents with the
 Categorical actor.  The shared parts (dense chains, the cell, the tanh-Normal tail) are tests/act_ref.py's; the samplers
 are tests/scan_cat_ref.py's (`ratios64`, `first_max`, `one_hot_rows`).

@@ -1,4 +1,4 @@
-"""GPU: the fused acting step for Categorical latents and / or the Categorical actor (csrc/act_cat.hip: bd_act_step_cat;
+"""GPU: the fused acting step for Categorical latents and / or the Categorical actor (csrc/act.hip: bd_act_step_cat;
 Engine.act_step_cat, Dreamer.act_step_cat, the BD_ACT_FUSED_CAT route of Dreamer.update_belief_and_act) against the
 float64 restatement tests/act_cat_ref.py at widths and row counts that are no multiples of the 16 x 16 tile, against the
 composed path before and after a weight update, and the uniform kind of bd_rng_fill.
