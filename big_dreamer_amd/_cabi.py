@@ -166,19 +166,16 @@ class ImagineCatBwdArgs(C.Structure):
 
 
 class PlanArgs(C.Structure):
-    _fields_ = ([(n, I32) for n in ("rows", "H", "cand", "Be", "S", "A", "Hd")] + _ptr_fields(
-        ["w_embed_s", "w_embed_a", "b_embed", "w_ir", "w_iz", "w_in", "w_hr", "w_hz", "w_hn", "b_ih", "b_hh", "w_p1",
-         "b_p1", "w_p2m", "w_p2s", "b_p2"]) + [("w_r", P * 5), ("b_r", P * 5), ("min_std", F32)] + _ptr_fields(
-        ["init_belief", "init_state", "act_mean", "act_std", "eps_action", "eps_state", "actions", "returns", "feat"]))
-
-
-class PlanCatArgs(C.Structure):
-    _fields_ = ([(n, I32) for n in ("rows", "H", "cand", "Be", "D", "C", "A", "Hd")] + _ptr_fields(
-        ["w_embed_sT", "w_embed_a", "b_embed", "w_ir", "w_iz", "w_in", "w_hr", "w_hz", "w_hn", "b_ih", "b_hh", "w_p1",
-         "b_p1", "w_p2", "b_p2", "w_r0h", "w_r0sT"]) + [("w_r", P * 4), ("b_r", P * 5)] + _ptr_fields(
-        ["init_belief", "init_state", "act_mean", "act_std", "eps_action", "q_prior"]) + [
+    _fields_ = ([(n, I32) for n in ("rows", "H", "cand", "Be", "D", "C", "S", "A", "Hd", "latent_cat")] + _ptr_fields(
+        ["w_embed_s", "w_embed_sT", "w_embed_a", "b_embed", "w_ir", "w_iz", "w_in", "w_hr", "w_hz", "w_hn", "b_ih", "b_hh",
+         "w_p1", "b_p1", "w_p2m", "w_p2s", "w_p2", "b_p2"]) + [("w_r", P * 5)] + _ptr_fields(["w_r0h", "w_r0sT"]) + [
+        ("b_r", P * 5), ("min_std", F32)] + _ptr_fields(
+        ["init_belief", "init_state", "act_mean", "act_std", "eps_action", "eps_state"]) + [
         ("seed", C.c_ulonglong), ("step", C.c_ulonglong), ("stream_id", C.c_uint)] + _ptr_fields(
         ["actions", "returns", "feat", "sidx"]))
+
+
+PlanCatArgs = PlanArgs     # bd_plan_cat_args is a typedef of bd_plan_args
 
 
 class ActArgs(C.Structure):

@@ -1197,17 +1197,39 @@ class DreamerEngine:
             cabi.check(getattr(lib, "bd_" + name)(C.byref(a), cabi.stream()))
         return out
 
+    def _plan_args(self, rows: int, H: int, cand: int):
+        """bd_plan_args with the dims, latent_cat and every weight of the engine's latent kind; inputs, outputs and noise
+        are the caller's."""
+        d, pk = self.d, self.pk
+        tm = lambda n: self.W("transition_model", n)
+        a = cabi.PlanArgs()
+        a.rows, a.H, a.cand, a.Be, a.S, a.A, a.Hd, a.latent_cat = rows, H, cand, d.Be, d.S, d.A, d.Hd, int(d.categorical)
+        self._bind_rssm(a)
+        a.w_p1, a.b_p1, a.b_p2 = ptr(pk["p1"]), ptr(tm("belief_prior.model.0.bias")), ptr(tm("belief_prior.model.2.bias"))
+        for l in range(DENSE_LAYERS + 1):
+            a.b_r[l] = ptr(self.W("reward_model", f"model.{2 * l}.bias"))
+            if l > 0:
+                a.w_r[l] = ptr(pk[f"rew{l}"])
+        if d.categorical:
+            a.D, a.C = d.cat_D, d.cat_C
+            a.w_embed_sT, a.w_p2 = ptr(self._plain["embed_sT"][0]), ptr(pk["p2"])
+            a.w_r0h, a.w_r0sT = ptr(pk["rew0h"]), ptr(self._plain["rew0sT"][0])
+        else:
+            a.w_embed_s, a.w_p2m, a.w_p2s = ptr(pk["embed_s"]), ptr(pk["p2m"]), ptr(pk["p2s"])
+            a.w_r[0] = ptr(pk["rew0"])
+            a.min_std = self.hp["min_std_dev"]
+        return a
+
     # ------------------------------------------------------------------------------------------ train step
     def plan(self, belief: torch.Tensor, state: torch.Tensor, horizon: int, iters: int, candidates: int, top: int,
              eps_action: torch.Tensor, eps_state: Optional[torch.Tensor], trace: Optional[list] = None) -> torch.Tensor:
         """MPCPlanner.forward (src/planner.py:28-90) on the current stream: `iters` x (rollout, bd_cem_refit).
         belief (B,Be), state (B,S); eps_action (iters,H,B,candidates,A); eps_state (iters,H,B*candidates,S): the
-        prior-state normals, or -- Categorical latents (bd_plan_rollout_cat) -- the sampler's Exp(1) draws, one per class;
+        prior-state normals, or -- Categorical latents -- the sampler's Exp(1) draws, one per class;
         there None = perf mode: the draws come from the Philox stream "plan_prior", generated inside the rollout kernel
         (S % 4 == 0) or into ONE iteration's buffer by bd_rng_fill.
         Returns the action-belief mean of every planning step, (H,B,A); row 0 is the planner's answer."""
-        d, pk = self.d, self.pk
-        tm = lambda n: self.W("transition_model", n)
+        d = self.d
         B = belief.shape[0]
         rows = B * candidates
         cat = d.categorical
@@ -1219,27 +1241,8 @@ class DreamerEngine:
         returns = self.buf("plan_returns", rows)
         if cat:
             self._check_cat_start(state)
-            a = cabi.PlanCatArgs()
-            a.rows, a.H, a.cand, a.Be, a.D, a.C, a.A, a.Hd = rows, horizon, candidates, d.Be, d.cat_D, d.cat_C, d.A, d.Hd
-            a.w_embed_sT = ptr(self._plain["embed_sT"][0])
-            a.w_p2, a.b_p2 = ptr(pk["p2"]), ptr(tm("belief_prior.model.2.bias"))
-            a.w_r0h, a.w_r0sT = ptr(pk["rew0h"]), ptr(self._plain["rew0sT"][0])
-            for l in range(1, DENSE_LAYERS + 1):
-                a.w_r[l - 1] = ptr(pk[f"rew{l}"])
-            rollout = lib.bd_plan_rollout_cat
-        else:
-            a = cabi.PlanArgs()
-            a.rows, a.H, a.cand, a.Be, a.S, a.A, a.Hd = rows, horizon, candidates, d.Be, d.S, d.A, d.Hd
-            a.w_embed_s = ptr(pk["embed_s"])
-            a.w_p2m, a.w_p2s, a.b_p2 = ptr(pk["p2m"]), ptr(pk["p2s"]), ptr(tm("belief_prior.model.2.bias"))
-            for l in range(DENSE_LAYERS + 1):
-                a.w_r[l] = ptr(pk[f"rew{l}"])
-            a.min_std = self.hp["min_std_dev"]
-            rollout = lib.bd_plan_rollout
-        self._bind_rssm(a)
-        a.w_p1, a.b_p1 = ptr(pk["p1"]), ptr(tm("belief_prior.model.0.bias"))
-        for l in range(DENSE_LAYERS + 1):
-            a.b_r[l] = ptr(self.W("reward_model", f"model.{2 * l}.bias"))
+        a = self._plan_args(rows, horizon, candidates)
+        rollout = lib.bd_plan_rollout_cat if cat else lib.bd_plan_rollout
         a.init_belief, a.init_state = ptr(belief), ptr(state)
         a.act_mean, a.act_std, a.actions = ptr(mean), ptr(std), ptr(actions)
         # Reward model inside the rollout (one return per candidate leaves the CU) once the candidate tiles fill the
@@ -1262,23 +1265,21 @@ class DreamerEngine:
         st = cabi.stream()
         for it in range(iters):
             a.eps_action = ptr(eps_action[it])
-            if not cat:
+            if not cat or eps_state is not None:
                 a.eps_state = ptr(eps_state[it])
-            elif eps_state is not None:
-                a.q_prior = ptr(eps_state[it])
             else:
                 # perf mode: a Philox step per CEM iteration of every plan call; at most ONE iteration's draws ever exist
                 a.seed, a.step, a.stream_id = self.rng_seed, self._rng_step.get("plan", 0), self.RNG_STREAMS["plan_prior"]
                 self._rng_step["plan"] = a.step + 1
                 if d.S % 4 == 0:
-                    a.q_prior = None
+                    a.eps_state = None
                 else:
                     q = self.buf("plan_q", horizon, rows, d.S)
                     r = cabi.RngFillArgs()
                     r.n, r.seed, r.step = 1, a.seed, a.step
                     r.t[0] = cabi.RngTensor(q.data_ptr(), q.numel(), cabi.BD_RNG_EXPONENTIAL, a.stream_id)
                     cabi.check(lib.bd_rng_fill(C.byref(r), st))
-                    a.q_prior = ptr(q)
+                    a.eps_state = ptr(q)
             cabi.check(rollout(C.byref(a), st))
             if fuse:
                 ret, steps = returns, 1

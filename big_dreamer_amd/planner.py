@@ -4,7 +4,7 @@
 reward_model)`` and ``forward(belief, state) -> (B, A)`` are the reference's (src/planner.py:10-35).  Each CEM
 iteration is two launches: ``bd_plan_rollout`` (candidate actions, prior-only RSSM rollout and reward model fused
 per planning step, returns summed in LDS) and ``bd_cem_refit`` (top-k selection + mean / std refit).
-With ``latent_distribution="Categorical"`` the rollout is ``bd_plan_rollout_cat`` (csrc/planner_cat.hip): the state is
+With ``latent_distribution="Categorical"`` the rollout is ``bd_plan_rollout_cat`` (the same kernel body, csrc/planner.hip): the state is
 carried as class indices and sampled per factor from the prior logits; the refit is the same.
 """
 from __future__ import annotations

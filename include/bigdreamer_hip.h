@@ -661,78 +661,67 @@ typedef struct {
 } bd_imagine_cat_bwd_args;
 int bd_imagine_cat_backward(const bd_imagine_cat_bwd_args* a, void* stream);
 
-/* ---- CEM planner: MPCPlanner.forward (src/planner.py:28-90) -------------------------------------
- * One CEM iteration = bd_plan_rollout + bd_cem_refit.  rows = B * cand candidate action sequences (row = b * cand + c);
+/* ---- CEM planner: MPCPlanner.forward (src/planner.py:28-90), csrc/planner.hip ---------------------
+ * One CEM iteration = a rollout + bd_cem_refit.  rows = B * cand candidate action sequences (row = b * cand + c);
  * the rollout forms a_t = act_mean[t][b] + act_std[t][b] * eps_action[t][row] (src/planner.py:60-62), runs the
  * prior-only RSSM step (src/models.py:241-256, embeddings=None, nonterminals=None) and the reward model
  * (src/models.py:365-408) per step in LDS and writes the actions [H x rows x A] and the summed predicted reward per
- * candidate (src/planner.py:68-72).  w_r[0] is the reward model's first layer packed over K = Be+S. */
+ * candidate (src/planner.py:68-72).
+ * One argument block and one kernel body for both latent kinds; latent_cat selects the instantiation.  bd_plan_rollout
+ * takes latent_cat = 0 only (a zeroed block with the Gaussian fields filled in), bd_plan_rollout_cat latent_cat != 0 only.
+ *   latent_cat = 0: Gaussian latents (w_embed_s, w_p2m / w_p2s, w_r[0] packed over K = Be+S, min_std; D, C, seed, step,
+ *     stream_id, sidx ignored): s' = mean + (softplus(raw) + min_std) * eps_state, eps_state standard normal.  S <= 64.
+ *   latent_cat: latent_distribution="Categorical" (TransitionModel.forward's Categorical branches, src/models.py:226-228,
+ *     241-260; CategoricalBeliefModel, src/models.py:101-117), S = D*C.  The state is carried as D class indices: W_es s and
+ *     the state columns of the reward model's first layer are gathers of rows of the plain transposes (w_embed_sT, w_r0sT:
+ *     [S x out], as in bd_imagine_cat_fwd_args; w_r0h holds that layer's belief columns, w_r[0] is ignored); the prior head
+ *     w_p2 gives S logits, per factor idx = argmax(softmax(logits) / q) with q = eps_state ~ Exp(1), first maximum winning
+ *     (torch.multinomial's single-draw path, src/models.py:114-115), and the one-hot of idx is the state that continues.
+ *     init_state: every factor all-zero (fed as zeros) or (scaled) one-hot, as bd_imagine_cat_forward with start_sidx = NULL.
+ *     eps_state = NULL: the draws are generated in the kernel, element i of the [H x rows x S] tensor being what
+ *     bd_rng_fill(kind = BD_RNG_EXPONENTIAL, seed, step, stream_id, count = H*rows*S) writes at i (needs S % 4 == 0).
+ *     C <= 256; S <= 256, or 256 % C == 0 and S % 16 == 0.
+ * returns = NULL: the unfused form -- feat [H x rows x (Be+S)] = [h'; s'] (the one-hot s' with latent_cat, and then sidx
+ * [H x rows x D] too) is written and the caller runs the reward model (bd_mlp_forward, with the one-hot segment there);
+ * the reward weights may then be NULL.  LDS as csrc/planner.hip states (<= 160 KiB). */
 typedef struct {
-    int rows, H, cand, Be, S, A, Hd;
-    const float* w_embed_s; const float* w_embed_a; const float* b_embed;
+    int rows, H, cand, Be, D, C, S, A, Hd;
+    int latent_cat;
+    const float* w_embed_s;                               /* Gaussian latents: packed (Be, S) */
+    const float* w_embed_sT;                              /* Categorical latents: plain [S x Be]: row k = W_e[:, k] */
+    const float* w_embed_a; const float* b_embed;         /* packed (Be, A), [Be] */
     const float* w_ir; const float* w_iz; const float* w_in;
     const float* w_hr; const float* w_hz; const float* w_hn;
     const float* b_ih; const float* b_hh;
     const float* w_p1; const float* b_p1;                 /* belief_prior.model.0 */
-    const float* w_p2m; const float* w_p2s; const float* b_p2;   /* belief_prior.model.2 rows [:S] / [S:] */
-    const float* w_r[5]; const float* b_r[5];             /* reward_model.model.{0,2,4,6,8} */
+    const float* w_p2m; const float* w_p2s;               /* Gaussian latents: belief_prior.model.2 rows [:S] / [S:] */
+    const float* w_p2;                                    /* Categorical latents: packed (S, Hd): prior logits */
+    const float* b_p2;                                    /* [2*S] / [S] */
+    const float* w_r[5];                                  /* reward_model.model.{0,2,4,6,8}, packed; [0]: Gaussian latents only */
+    const float* w_r0h;                                   /* Categorical latents: model.0, belief columns, packed (Hd, Be) */
+    const float* w_r0sT;                                  /* Categorical latents: model.0, state columns: plain [S x Hd] */
+    const float* b_r[5];                                  /* reward_model.model.{0,2,4,6,8}.bias */
     float min_std;
     const float* init_belief;   /* [B x Be]  (every candidate of environment b starts from row b, src/planner.py:37) */
     const float* init_state;    /* [B x S]   */
     const float* act_mean;      /* [H x B x A] */
     const float* act_std;       /* [H x B x A] */
     const float* eps_action;    /* [H x rows x A]  the torch.randn draws of src/planner.py:53-59 */
-    const float* eps_state;     /* [H x rows x S]  the prior-state draws (src/models.py:72) */
+    const float* eps_state;     /* [H x rows x S]  the prior-state draws (src/models.py:72); with latent_cat NULL = in-kernel */
+    unsigned long long seed; unsigned long long step; unsigned stream_id;   /* in-kernel noise (latent_cat, eps_state = NULL) */
     float* actions;             /* out [H x rows x A] */
-    float* returns;             /* out [rows]; NULL: skip the reward model and write `feat` instead */
+    float* returns;             /* out [rows]; NULL: skip the reward model and write `feat` (and sidx) instead */
     float* feat;                /* out [H x rows x (Be+S)] ([h'; s'] per step) or NULL */
+    unsigned char* sidx;        /* out [H x rows x D] sampled class per factor (latent_cat), or NULL */
 } bd_plan_args;
+typedef bd_plan_args bd_plan_cat_args;
 int bd_plan_rollout(const bd_plan_args* a, void* stream);
+int bd_plan_rollout_cat(const bd_plan_cat_args* a, void* stream);
 /* Re-fit the action belief to the `top` best candidates of every environment (src/planner.py:74-87):
  * mean / stdev [H x B x A] <- mean and biased standard deviation over the selected action sequences.
  * returns is [ret_steps x B*cand]: ret_steps = 1 for summed returns, H for per-step reward predictions (summed here). */
 int bd_cem_refit(const float* returns, int ret_steps, const float* actions, int H, int B, int cand, int top, int A,
                  float* mean, float* stdev, void* stream);
-
-/* The rollout for latent_distribution="Categorical" (csrc/planner_cat.hip): same rows / candidates / actions / returns
- * conventions as bd_plan_rollout, on TransitionModel.forward's Categorical branches with embeddings=None
- * (src/models.py:226-228,241-260) and CategoricalBeliefModel (src/models.py:101-117).  The state is carried as D class
- * indices: W_es s and the state columns of the reward model's first layer are gathers of rows of the plain transposes
- * (`*_sT`, [S x out], as in bd_imagine_cat_fwd_args); the prior head gives S = D*C logits, per factor
- * idx = argmax(softmax(logits) / q), q ~ Exp(1) (torch.multinomial's single-draw path, src/models.py:114-115), and the
- * one-hot of idx is the state that continues.
- * init_state: every factor all-zero (fed as zeros) or (scaled) one-hot, as bd_imagine_cat_forward with start_sidx = NULL.
- * q_prior = NULL: the draws are generated in the kernel, element i of the [H x rows x S] tensor being what
- * bd_rng_fill(kind = BD_RNG_EXPONENTIAL, seed, step, stream_id, count = H*rows*S) writes at i (needs S % 4 == 0).
- * returns = NULL: the unfused form -- feat [H x rows x (Be+S)] = [h'; one-hot s'] and sidx [H x rows x D] are written
- * and the caller runs the reward model (bd_mlp_forward with the one-hot segment).
- * C <= 256; S <= 256, or 256 % C == 0 and S % 16 == 0; LDS as stated in csrc/planner_cat.hip (<= 160 KiB). */
-typedef struct {
-    int rows, H, cand, Be, D, C, A, Hd;
-    const float* w_embed_sT;                              /* plain [S x Be]: row k = W_e[:, k] */
-    const float* w_embed_a; const float* b_embed;         /* packed (Be, A), [Be] */
-    const float* w_ir; const float* w_iz; const float* w_in;
-    const float* w_hr; const float* w_hz; const float* w_hn;
-    const float* b_ih; const float* b_hh;
-    const float* w_p1; const float* b_p1;                 /* belief_prior.model.0 */
-    const float* w_p2; const float* b_p2;                 /* packed (S, Hd), [S]: prior logits */
-    const float* w_r0h;                                   /* reward_model.model.0, belief columns, packed (Hd, Be) */
-    const float* w_r0sT;                                  /* reward_model.model.0, state columns: plain [S x Hd] */
-    const float* w_r[4];                                  /* reward_model.model.{2,4,6,8}, packed */
-    const float* b_r[5];                                  /* reward_model.model.{0,2,4,6,8}.bias */
-    const float* init_belief;   /* [B x Be] */
-    const float* init_state;    /* [B x S]: zeros, or (scaled) one-hot per factor */
-    const float* act_mean;      /* [H x B x A] */
-    const float* act_std;       /* [H x B x A] */
-    const float* eps_action;    /* [H x rows x A] */
-    const float* q_prior;       /* [H x rows x S] Exp(1) draws, or NULL: generated from (seed, step, stream_id) */
-    unsigned long long seed; unsigned long long step; unsigned stream_id;
-    float* actions;             /* out [H x rows x A] */
-    float* returns;             /* out [rows]; NULL: skip the reward model and write feat and sidx instead */
-    float* feat;                /* out [H x rows x (Be+S)] or NULL */
-    unsigned char* sidx;        /* out [H x rows x D] sampled class per factor, or NULL */
-} bd_plan_cat_args;
-int bd_plan_rollout_cat(const bd_plan_cat_args* a, void* stream);
 
 /* ---- acting: one decision of the collect / evaluation loop in ONE launch (csrc/act.hip) -------------------------
  * Planet.update_belief_and_act (src/planet.py:370-403) with Dreamer.get_action (src/dreamer.py:429-444) for B

@@ -1,11 +1,13 @@
 """Shared helpers for the parity tests (golden loading, fingerprint checks, comparisons)."""
 import os
+import re
 
 import numpy as np
 
 from big_dreamer_amd import synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "big_dreamer_amd", "csrc")
 
 # name -> (Dims, seed, hyper-parameter overrides, stored in full?)
 CASES = {
@@ -86,3 +88,17 @@ PLANNER_CASES = {
     "planner_tiny": (synth.TINY, 2, 5, 4, 64, 8, 6, True),
     "planner_config2": (synth.CONFIG2, 1, 15, 10, 1000, 100, 7, False),
 }
+
+
+def split_scratch_floats():
+    """kSplitScratchFloats as bd_device.h defines it, at the waves per workgroup of the acting step and the planner
+    rollout (REC_WAVES of the Makefile)."""
+    with open(os.path.join(CSRC, "bd_device.h")) as fh:
+        hdr = fh.read()
+    with open(os.path.join(CSRC, "Makefile")) as fh:
+        waves = int(re.search(r"^REC_WAVES \?= (\d+)", fh.read(), re.M).group(1))
+    k = {n: int(re.search(rf"constexpr int {n} = (\d+);", hdr).group(1)) for n in ("kFragFloats", "kSplitPairs", "kHeadMaxN")}
+    assert re.search(r"kSplitPartialFloats = kWaves \* kSplitPairs \* 2 \* kFragFloats;", hdr)
+    assert re.search(r"kHeadPlainFloats = 2 \* 16 \* kHeadMaxN;", hdr)
+    assert re.search(r"kSplitScratchFloats = kSplitPartialFloats \+ kHeadPlainFloats;", hdr)
+    return waves * k["kSplitPairs"] * 2 * k["kFragFloats"] + 2 * 16 * k["kHeadMaxN"]

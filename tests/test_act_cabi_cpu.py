@@ -3,28 +3,14 @@ points over one argument block, one validator and one kernel body: the sizes eac
 (latent_cat, actor_cat) configurations each takes, and that a refusal names the entry point that was called."""
 import ctypes as C
 import itertools
-import os
-import re
 
 import pytest
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "big_dreamer_amd", "csrc")
+from tests.helpers import split_scratch_floats
+
 MAX_LDS = 160 * 1024
 GRID = list(itertools.product((24, 200), (6, 30, 64, 65), (0, 1, 2, 64, 65), (20, 200, 1 << 16, (1 << 20) + 1), (40, 1024),
                               (-1, 0, 3, 5)))        # Be, S, A, Hd, E, O
-
-
-def _split_scratch_floats():
-    """kSplitScratchFloats as bd_device.h defines it, at the acting step's waves per workgroup (REC_WAVES of the Makefile)."""
-    with open(os.path.join(CSRC, "bd_device.h")) as fh:
-        hdr = fh.read()
-    with open(os.path.join(CSRC, "Makefile")) as fh:
-        waves = int(re.search(r"^REC_WAVES \?= (\d+)", fh.read(), re.M).group(1))
-    k = {n: int(re.search(rf"constexpr int {n} = (\d+);", hdr).group(1)) for n in ("kFragFloats", "kSplitPairs", "kHeadMaxN")}
-    assert re.search(r"kSplitPartialFloats = kWaves \* kSplitPairs \* 2 \* kFragFloats;", hdr)
-    assert re.search(r"kHeadPlainFloats = 2 \* 16 \* kHeadMaxN;", hdr)
-    assert re.search(r"kSplitScratchFloats = kSplitPartialFloats \+ kHeadPlainFloats;", hdr)
-    return waves * k["kSplitPairs"] * 2 * k["kFragFloats"] + 2 * 16 * k["kHeadMaxN"]
 
 
 def _rule(Be, S, A, Hd, E, O, scratch):
@@ -39,7 +25,7 @@ def _rule(Be, S, A, Hd, E, O, scratch):
 def test_supported_sizes():
     from big_dreamer_amd import _cabi as cabi
     lib = cabi.lib
-    scratch = _split_scratch_floats()
+    scratch = split_scratch_floats()
     assert scratch == 10240
     assert (200, 30, 1, 200, 1024, 3) in GRID and _rule(200, 30, 1, 200, 1024, 3, scratch) == 1      # the reference's default
     got = {1: 0, 0: 0}

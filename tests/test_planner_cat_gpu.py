@@ -49,26 +49,8 @@ def _agent(d, seed, cls="dreamer", extra=()):
 
 
 def _args(eng, rows, H, cand):
-    """bd_plan_cat_args with the engine's weights; inputs / outputs are filled by the caller."""
-    from big_dreamer_amd import _cabi as cabi
-    from big_dreamer_amd._cabi import ptr
-    d, pk = eng.d, eng.pk
-    tm = lambda n: eng.W("transition_model", n)
-    a = cabi.PlanCatArgs()
-    a.rows, a.H, a.cand, a.Be, a.D, a.C, a.A, a.Hd = rows, H, cand, d.Be, d.cat_D, d.cat_C, d.A, d.Hd
-    a.w_embed_sT, a.w_embed_a = ptr(eng._plain["embed_sT"][0]), ptr(pk["embed_a"])
-    a.b_embed = ptr(tm("fc_embed_state_action.0.bias"))
-    a.w_ir, a.w_iz, a.w_in = ptr(pk["ir"]), ptr(pk["iz"]), ptr(pk["in"])
-    a.w_hr, a.w_hz, a.w_hn = ptr(pk["hr"]), ptr(pk["hz"]), ptr(pk["hn"])
-    a.b_ih, a.b_hh = ptr(tm("rnn.bias_ih")), ptr(tm("rnn.bias_hh"))
-    a.w_p1, a.b_p1 = ptr(pk["p1"]), ptr(tm("belief_prior.model.0.bias"))
-    a.w_p2, a.b_p2 = ptr(pk["p2"]), ptr(tm("belief_prior.model.2.bias"))
-    a.w_r0h, a.w_r0sT = ptr(pk["rew0h"]), ptr(eng._plain["rew0sT"][0])
-    for l in range(1, 5):
-        a.w_r[l - 1] = ptr(pk[f"rew{l}"])
-    for l in range(5):
-        a.b_r[l] = ptr(eng.W("reward_model", f"model.{2 * l}.bias"))
-    return a
+    """bd_plan_args with the engine's weights; inputs / outputs are filled by the caller."""
+    return eng._plan_args(rows, H, cand)
 
 
 class _Rollout:
@@ -91,9 +73,9 @@ class _Rollout:
         a.init_belief, a.init_state, a.act_mean, a.act_std, a.eps_action = (t.data_ptr() for t in keep)
         if q is not None:
             qd = q.contiguous().float().cuda()
-            a.q_prior = qd.data_ptr()
+            a.eps_state = qd.data_ptr()
         else:
-            a.q_prior = None
+            a.eps_state = None
             a.seed, a.step, a.stream_id = rng
         a.actions = self.actions.data_ptr()
         if fuse:
@@ -168,6 +150,35 @@ def test_rollout_vs_oracle_both_forms(name):
     fused = ro.run(belief, state, mean, std, eps_a, q, fuse=True)
     assert_close(f"{name} fused actions", fused[0], got[0], 0, 0)
     assert_close(f"{name} fused returns", fused[1], got[1], 2e-5, 2e-5)
+
+
+@pytest.mark.parametrize("name, in_kernel", [("cat_tiny", False), ("cat_32", True)])
+def test_rollout_ignores_the_gaussian_fields(name, in_kernel):
+    """C ABI level, Categorical entry point: bd_plan_args carries both latent kinds' fields; with latent_cat set the
+    Gaussian ones (w_embed_s, w_p2m, w_p2s, w_r[0], min_std) are never read: junk in them gives the same actions, returns
+    (fused form), feat and sidx (unfused form), bit for bit.  cat_tiny: 3 x 5 latents (the generic-C sampler), 42 rows
+    (last tile 10 rows), explicit draws; cat_32: the register sampler with in-kernel noise, 154 rows."""
+    d, B, cand, H, seed, _ = ROLLOUT_CASES[name]
+    agent, _, _ = _agent(d, seed)
+    belief, state, mean, std, eps_a, q = _rollout_inputs(d, B, cand, H, seed)
+    ro = _Rollout(agent.engine, B, H, cand)
+    got = {}
+    for junk in (False, True):
+        if junk:
+            ro.a.w_embed_s = ro.a.w_p2m = ro.a.w_p2s = 4096
+            ro.a.w_r[0], ro.a.min_std = 4096, 123.0
+        for fuse in (True, False):
+            for t in (ro.actions, ro.returns, ro.feat):
+                t.fill_(float("nan"))
+            ro.sidx.fill_(255)
+            ro.run(belief, state, mean, std, eps_a, None if in_kernel else q, fuse=fuse, rng=(0x51ed + seed, 2, 9))
+            outs = (ro.actions, ro.returns) if fuse else (ro.actions, ro.feat, ro.sidx)
+            assert all(bool(torch.isfinite(t.float()).all()) for t in outs) and (fuse or int(ro.sidx.max()) < d.cat_C)
+            got[junk, fuse] = [t.clone() for t in outs]
+    for fuse in (True, False):
+        for x, y in zip(got[True, fuse], got[False, fuse]):
+            assert torch.equal(x, y), (name, fuse)
+    assert torch.equal(got[False, True][0], got[False, False][0]) and float(got[False, True][1].abs().min()) > 0
 
 
 def test_start_states_and_refusals():
@@ -274,7 +285,7 @@ def test_planner_full_size_teacher_forced():
 
 
 def test_in_kernel_noise_matches_rng_fill():
-    """q_prior = NULL with (seed, step, stream_id) is bit-identical to a run fed the buffer bd_rng_fill writes for the same
+    """eps_state = NULL with (seed, step, stream_id) is bit-identical to a run fed the buffer bd_rng_fill writes for the same
     triple; another step gives other index paths; S % 4 != 0 (CAT_TINY) is refused by the kernel and served by the
     engine's fill path."""
     from big_dreamer_amd import _cabi as cabi

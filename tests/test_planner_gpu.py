@@ -118,6 +118,42 @@ def test_planner_rollout_matches_unfused_modules(fuse, monkeypatch):
     assert cabi.lib.bd_plan_rollout(C.byref(bad), cabi.stream()) != 0 and b"bad dims" in cabi.lib.bd_last_error()
 
 
+def test_rollout_ignores_the_categorical_fields():
+    """C ABI level, Gaussian entry point: bd_plan_args carries both latent kinds' fields; with latent_cat = 0 the
+    Categorical ones (D, C, the Philox triple, w_embed_sT, w_p2, w_r0h, w_r0sT, sidx) are never read: junk in them gives
+    the same actions, returns (fused form) and feat (unfused form), bit for bit.  No width is a multiple of 16 and the
+    150 rows are ten tiles, the last with 6 rows."""
+    from big_dreamer_amd import _cabi as cabi
+    d, seed, B, cand, H = synth.SMALL, 3, 3, 50, 6
+    rows = B * cand
+    agent, _, _ = _agent(d, seed)
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    rn = lambda *s: torch.randn(*s, device="cuda", generator=gen)
+    belief, state, mean, std = 0.5 * rn(B, d.Be), rn(B, d.S), 0.3 * rn(H, B, d.A), 0.2 + rn(H, B, d.A).abs()
+    eps_a, eps_s = rn(H, rows, d.A), rn(H, rows, d.S)
+    a = agent.engine._plan_args(rows, H, cand)
+    a.init_belief, a.init_state, a.act_mean, a.act_std = (t.data_ptr() for t in (belief, state, mean, std))
+    a.eps_action, a.eps_state = eps_a.data_ptr(), eps_s.data_ptr()
+    got = {}
+    for junk in (False, True):
+        if junk:
+            a.D, a.C, a.seed, a.step, a.stream_id = 7, 9, 0x123456789, 5, 3
+            a.w_embed_sT = a.w_p2 = a.w_r0h = a.w_r0sT = a.sidx = 4096
+        for form in ("returns", "feat"):
+            actions = torch.full((H, rows, d.A), float("nan"), device="cuda")
+            out = torch.full((rows,) if form == "returns" else (H * rows, d.Be + d.S), float("nan"), device="cuda")
+            a.actions = actions.data_ptr()
+            a.returns, a.feat = (out.data_ptr(), None) if form == "returns" else (None, out.data_ptr())
+            cabi.check(cabi.lib.bd_plan_rollout(C.byref(a), cabi.stream()))
+            torch.cuda.synchronize()
+            assert bool(torch.isfinite(actions).all()) and bool(torch.isfinite(out).all()), (junk, form)
+            got[junk, form] = (actions, out)
+    for form in ("returns", "feat"):
+        assert torch.equal(got[True, form][0], got[False, form][0]), f"{form}: actions"
+        assert torch.equal(got[True, form][1], got[False, form][1]), form
+    assert torch.equal(got[False, "returns"][0], got[False, "feat"][0]) and float(got[False, "returns"][1].abs().min()) > 0
+
+
 def test_planet_train_steps_vs_oracle_and_reference_golden():
     """Planet.train_step x2 (dynamics learning, summed free-nats KL): logs, clipped gradients, post-Adam weights."""
     from oracle import dreamer_oracle as O

@@ -62,8 +62,8 @@ def main():
 
     if cat:
         return categorical(B, d, H, iters, cand, top, agent, mpc, belief, state, spread)
-    fused = timed(lambda: mpc(belief, state), 20)
-    print(f"B={B}: fused HIP {fused:.2f} ms/plan", flush=True)
+    fused, lo, hi = spread(lambda: mpc(belief, state), 20)
+    print(f"B={B}: fused HIP {fused:.2f} ms/plan (range {lo:.2f}-{hi:.2f} over {REPS} x 20 plans)", flush=True)
 
     def unfused():
         xb = belief.unsqueeze(1).expand(B, cand, d.Be).reshape(-1, d.Be)
