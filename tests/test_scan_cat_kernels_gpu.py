@@ -254,8 +254,10 @@ class ImagineCase:
         return dict(feat=d.Be + d.S, prior_logits=d.S, action=d.A, sv_act_stats=4 * d.A, sv_x=d.Be, sv_gates=4 * d.Be, sv_p=d.Hd,
                     sv_act_us=2 * d.A, entropy=1)
 
-    def forward(self, with_us=True, start_sidx=None, start_feat=None, entropy=False):
-        """entropy: eps_entropy given (the call runs bd_actor_entropy itself); otherwise the scan alone."""
+    def forward(self, with_us=True, start_sidx=None, start_feat=None, entropy=False, eps_entropy=None, n_samples=N_SAMPLES,
+                stats=True):
+        """entropy: eps_entropy given (the call runs bd_actor_entropy itself); otherwise the scan alone.  eps_entropy
+        (a Placed [Hm * n_samples * N x A]) with stats = False: the in-scan estimate (test_entropy_kernels_gpu.py)."""
         c, d, pk, p = cabi(), self.d, self.pk, self.pin
         M = d.T * d.B
         out = {k: pout(M, w) for k, w in self.widths().items()}
@@ -263,8 +265,10 @@ class ImagineCase:
         out["sidx"] = PlacedBytes(M, d.D)
         if not with_us or self.discrete:
             out["sv_act_us"] = None
+        if not stats:
+            out["sv_act_stats"] = None
         a = c.ImagineCatFwdArgs()
-        a.N, a.Hm, a.Be, a.D, a.C, a.A, a.Hd, a.n_samples = d.B, d.T, d.Be, d.D, d.C, d.A, d.Hd, N_SAMPLES
+        a.N, a.Hm, a.Be, a.D, a.C, a.A, a.Hd, a.n_samples = d.B, d.T, d.Be, d.D, d.C, d.A, d.Hd, n_samples
         a.w_embed_sT, a.w_embed_a, a.b_embed = self.embed_sT.data_ptr(), pk["embed_a"].data_ptr(), self.W["b_e"].data_ptr()
         a.w_ir, a.w_iz, a.w_in = (pk[k].data_ptr() for k in ("ir", "iz", "in"))
         a.w_hr, a.w_hz, a.w_hn = (pk[k].data_ptr() for k in ("hr", "hz", "hn"))
@@ -282,7 +286,7 @@ class ImagineCase:
             sx.view.copy_(start_sidx)
         a.start_sidx = sx.ptr if start_sidx is not None else None
         a.eps_action, a.q_prior = p["eps_action"].ptr, p["q_prior"].ptr
-        a.eps_entropy = p["eps_entropy"].ptr if entropy else None
+        a.eps_entropy = eps_entropy.ptr if eps_entropy is not None else (p["eps_entropy"].ptr if entropy else None)
         a.act_raw_init_std, a.act_min_std, a.act_mean_scale = R.ACT_RAW_INIT_STD, R.ACT_MIN_STD, R.ACT_MEAN_SCALE
         for k, v in out.items():
             setattr(a, k, ptr(v))
@@ -291,7 +295,7 @@ class ImagineCase:
         sync()
         for k, v in out.items():
             assert v is None or v.outside_unchanged(), f"imagine forward: {k} written outside its rows"
-        if not entropy and not self.discrete:
+        if not entropy and not self.discrete and stats:
             assert bool((out["entropy"].buf == SENTINEL).all()), "the scan wrote an entropy although sv_act_stats was given"
         return out
 

@@ -218,8 +218,10 @@ class ImagineCase:
         return dict(feat=d.Be + d.S, prior_mean=d.S, prior_std=d.S, action=d.A, sv_act_stats=4 * d.A, sv_x=d.Be, sv_gates=4 * d.Be,
                     sv_p=d.Hd, sv_act_us=2 * d.A, entropy=1)
 
-    def forward(self, with_us=True, with_mean=True, split=0):
-        """One launch, or two time segments [0, split) and [split, Hm) through sv_actor_stride."""
+    def forward(self, with_us=True, with_mean=True, split=0, eps_entropy=None, n_samples=1, stats=True, wrapper=False):
+        """One launch, or two time segments [0, split) and [split, Hm) through sv_actor_stride.  eps_entropy (a Placed
+        [Hm * n_samples * N x A]) with stats = False: the in-scan entropy estimate; with wrapper = True:
+        bd_imagine_forward, which follows the scan with bd_actor_entropy (test_entropy_kernels_gpu.py)."""
         c, d, pk, p = cabi(), self.d, self.pk, self.pin
         M = d.T * d.B
         out = {k: pout(M, w) for k, w in self.widths().items()}
@@ -228,9 +230,11 @@ class ImagineCase:
             out["sv_act_us"] = None
         if not with_mean:
             out["prior_mean"] = None
+        if not stats:
+            out["sv_act_stats"] = None
         for t0, t1 in (((0, split), (split, d.T)) if split else ((0, d.T),)):
             a = c.ImagineFwdArgs()
-            a.N, a.Hm, a.Be, a.S, a.A, a.Hd, a.n_samples = d.B, t1 - t0, d.Be, d.S, d.A, d.Hd, 1
+            a.N, a.Hm, a.Be, a.S, a.A, a.Hd, a.n_samples = d.B, t1 - t0, d.Be, d.S, d.A, d.Hd, n_samples
             a.w_embed_s, a.w_embed_a, a.b_embed = pk["embed_s"].data_ptr(), pk["embed_a"].data_ptr(), self.W["b_e"].data_ptr()
             a.w_ir, a.w_iz, a.w_in = (pk[k].data_ptr() for k in ("ir", "iz", "in"))
             a.w_hr, a.w_hz, a.w_hn = (pk[k].data_ptr() for k in ("hr", "hz", "hn"))
@@ -245,17 +249,19 @@ class ImagineCase:
             a.w_a4m, a.w_a4s, a.b_a4 = pk["a4m"].data_ptr(), pk["a4s"].data_ptr(), self.W["b_a4"].data_ptr()
             shift = lambda pl, w: None if pl is None else pl.ptr + 4 * t0 * d.B * w
             a.start_feat = p["start_feat"].ptr if t0 == 0 else shift(out["feat"], d.Be + d.S) - 4 * d.B * (d.Be + d.S)
-            a.eps_action, a.eps_prior, a.eps_entropy = shift(p["eps_action"], d.A), shift(p["eps_prior"], d.S), None
+            a.eps_action, a.eps_prior = shift(p["eps_action"], d.A), shift(p["eps_prior"], d.S)
+            a.eps_entropy = shift(eps_entropy, n_samples * d.A)
             a.min_std, a.act_raw_init_std, a.act_min_std, a.act_mean_scale = self.min_std, R.ACT_RAW_INIT_STD, R.ACT_MIN_STD, R.ACT_MEAN_SCALE
             for k, w in self.widths().items():
                 setattr(a, k, shift(out[k], w))
             a.sv_actor, a.sv_actor_stride = shift(out["sv_actor"], d.Hd), M * d.Hd
             a.discrete_actions = 0
-            c.check(c.lib.bd_imagine_forward_scan(C.byref(a), c.stream()))
+            c.check((c.lib.bd_imagine_forward if wrapper else c.lib.bd_imagine_forward_scan)(C.byref(a), c.stream()))
             sync()
         for k, v in out.items():
             assert v is None or v.outside_unchanged(), f"imagine forward: {k} written outside its rows"
-        assert bool((out["entropy"].buf == SENTINEL).all()), "the scan wrote an entropy although sv_act_stats was given"
+        if stats and not (wrapper and eps_entropy is not None):
+            assert bool((out["entropy"].buf == SENTINEL).all()), "the scan wrote an entropy although sv_act_stats was given"
         return out
 
     def tensors64(self, out):
