@@ -308,6 +308,8 @@ __global__ __launch_bounds__(kThreads) void plan_rollout_kernel(bd_plan_args a_)
 // torch.topk orders it) with a bitonic sort of 64-bit keys in LDS -- (order-preserving image of the float) << 32 |
 // ~index -- padded to a power of two with keys below every real one; the first `top` entries are the selection, and
 // every (t, a) pair is reduced over them by one wave.
+// The image ranks +0 strictly above -0, the documented order does not: it holds because the caller's sum starts from 0.f
+// (0.f + -0.f = +0.f, IEEE addition, no fast-math), so x is never -0 (tests/test_plan_kernels_gpu.py, the "zeros" returns).
 __device__ __forceinline__ unsigned long long refit_key(float x, int i) {
     unsigned u = __float_as_uint(x);
     if (x != x) u = 0xFFFFFFFFu;

@@ -683,7 +683,9 @@ int bd_imagine_cat_backward(const bd_imagine_cat_bwd_args* a, void* stream);
  *     C <= 256; S <= 256, or 256 % C == 0 and S % 16 == 0.
  * returns = NULL: the unfused form -- feat [H x rows x (Be+S)] = [h'; s'] (the one-hot s' with latent_cat, and then sidx
  * [H x rows x D] too) is written and the caller runs the reward model (bd_mlp_forward, with the one-hot segment there);
- * the reward weights may then be NULL.  LDS as csrc/planner.hip states (<= 160 KiB). */
+ * the reward weights may then be NULL.  returns and feat (with latent_cat: and sidx) may also BOTH be given: one launch then
+ * writes all of them, each with the bits of the launch that asks for it alone (tests/test_plan_kernels_gpu.py).
+ * LDS as csrc/planner.hip states (<= 160 KiB). */
 typedef struct {
     int rows, H, cand, Be, D, C, S, A, Hd;
     int latent_cat;
