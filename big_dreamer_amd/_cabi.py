@@ -189,10 +189,15 @@ class ActArgs(C.Structure):
                             ("stream_action", C.c_uint), ("stream_explore", C.c_uint),
                             ("min_std", F32), ("act_raw_init_std", F32), ("act_min_std", F32), ("act_mean_scale", F32),
                             ("action_noise", F32), ("explore", I32)] + _ptr_fields(
-        ["belief_out", "state_out", "action_out"]))
+        ["belief_out", "state_out", "action_out"]) + [
+        # the evaluation policy: appended, a zeroed tail is the sampling step
+        ("action_mode", I32), ("latent_mean", I32), ("n_mode", I32), ("eps_mode", P), ("stream_mode", C.c_uint),
+        ("act_stats_out", P), ("mode_index_out", P)])
 
 
 ActCatArgs = ActArgs       # bd_act_cat_args is a typedef of bd_act_args
+BD_POLICY_SAMPLE, BD_POLICY_MODE, BD_POLICY_MEAN = 0, 1, 2
+ACTION_MODES = {"sample": BD_POLICY_SAMPLE, "mode": BD_POLICY_MODE, "mean": BD_POLICY_MEAN}
 
 
 class ConvArgs(C.Structure):
@@ -264,6 +269,7 @@ _SIGS = {
     "bd_act_step": (I32, [C.POINTER(ActArgs), P]),
     "bd_act_step_cat_supported": (I32, [I32] * 10),
     "bd_act_step_cat": (I32, [C.POINTER(ActCatArgs), P]),
+    "bd_tanh_normal_mode": (I32, [P, P, P, C.c_ulonglong, C.c_ulonglong, C.c_uint, I32, I32, I32, P, P, P]),
     "bd_lambda_return_backward": (I32, [P, F32, I32, I32, F32, F32, P, P, P]),
     "bd_img_heads_supported": (I32, [I32, I32]),
     "bd_img_heads_fwd_bwd": (I32, [C.POINTER(ImgHeadsArgs), P]),

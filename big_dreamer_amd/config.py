@@ -7,6 +7,8 @@ from typing import Any, Dict, List
 
 import yaml
 
+ACTION_MODES = ("sample", "mode", "mean")        # eval_action, and action_mode of the acting step
+
 DEFAULT_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "conf", "config.yaml")
 
 
@@ -42,4 +44,8 @@ def load_config(overrides: List[str] = (), path: str = DEFAULT_CONFIG) -> Dict[s
         if parts[-1] not in node:
             raise KeyError(f"unknown config key '{key}' (the reference's Hydra config rejects unknown keys too)")
         node[parts[-1]] = _parse_value(val)
+    if cfg.get("eval_action", "sample") not in ACTION_MODES:
+        raise ValueError(f"eval_action={cfg['eval_action']!r} is none of {ACTION_MODES}")
+    if not isinstance(cfg.get("eval_state_mean", False), bool):
+        raise ValueError(f"eval_state_mean={cfg['eval_state_mean']!r} is not a boolean")
     return cfg

@@ -28,6 +28,15 @@
 //     sample (src/models.py:256: with an embedding the posterior sample is the state that continues), the prior sample of
 //     get_action's one imagination step and the actor entropy (src/planet.py:386 drops it).  None of them feeds belief,
 //     state or action, so the three outputs are exactly the composed path's.
+//   The evaluation policy (the block's tail: action_mode, latent_mean; include/bigdreamer_hip.h) is a THIRD template
+//     parameter EV: act_step_kernel<LC, AC, false> are the four sampling kernels, which look at none of it; a block with
+//     anything of the tail set launches <LC, AC, true>, the same body with
+//       latent_mean            !LC: eps_post = 0 (s' = mean_q)      LC: q = 1 (per-factor argmax of the posterior logits)
+//       BD_POLICY_MEAN         !AC: a' = tanh(mean + std * 0)       AC: the exact one-hot of argmax p (q = 1)
+//       BD_POLICY_MODE         !AC: SampleDist.mode (src/models.py:708-723) -- the row's (mean, std) go to LDS (the head of
+//                              the split-K partials, dead by then), one wave per row picks among n_mode draws
+//                              (tanh_normal_mode_index, also behind bd_tanh_normal_mode)      AC: as BD_POLICY_MEAN
+//     and exploration on top as in the sampling step.
 //   Noise: explicit buffers, or (all NULL) Philox4x32-10 draws made in the kernel with the element layout of bd_rng_fill
 //     (Exp(1) where a Categorical sampler consumes them, uniforms for epsilon-greedy, normals otherwise), so a run with
 //     in-kernel noise equals, bit for bit, a run fed bd_rng_fill's buffers for the same (seed, step, stream).
@@ -74,7 +83,90 @@ struct ActEps {
 
 enum { kDrawNormal = 0, kDrawExp = 1, kDrawUniform = 2 };      // the kinds of bd_rng_fill
 
-template <bool LC, bool AC>
+// ---- the evaluation policy (bd_act_args' tail) ---------------------------------------------------------------------------
+// element e of a standard-normal tensor: the caller's buffer, or what bd_rng_fill(BD_RNG_NORMAL) writes there
+__device__ __forceinline__ float normal_at(const float* __restrict__ eps, const Rng& r, size_t e) {
+    if (eps != nullptr) return eps[e];
+    float v[4];
+    rng_normal4(r, e >> 2, v);
+    const int j = (int)(e & 3);
+    return j == 0 ? v[0] : (j == 1 ? v[1] : (j == 2 ? v[2] : v[3]));
+}
+
+// The n draws of one row, layout (n, rows, A): draw j, column c.
+struct ModeDraws {
+    const float* eps;
+    Rng rng;
+    size_t rows, row;
+    int A;
+    __device__ __forceinline__ float operator()(int j, int c) const { return normal_at(eps, rng, ((size_t)j * rows + row) * A + c); }
+};
+
+// SampleDist.mode (src/models.py:708-723), the selection: of the n draws y_j = tanh(mean + sd * e_j) of ONE row the index
+// of the largest tanh-Normal log-density summed over the A columns, the first maximum winning.  One wave: lane l takes
+// draws l, l + 64, ... (a later pass replaces the lane's best only when strictly larger), walks the A columns with
+// entropy_const / entropy_sample, then an xor butterfly in which the lower index wins a tie.  mean, sd: the row's A values
+// (LDS or global).  Every lane returns the same index; a row whose sums are all NaN returns 0.
+__device__ __forceinline__ int tanh_normal_mode_index(const float* mean, const float* sd, int A, int n, const ModeDraws& draws,
+                                                      int lane) {
+    float best = -INFINITY;
+    int arg = n;
+    for (int j = lane; j < n; j += 64) {
+        float sum = 0.f;
+        for (int c = 0; c < A; ++c) {
+            const EntConst ec = entropy_const(mean[c], sd[c]);
+            float lp, dm, ds;
+            entropy_sample(ec, draws(j, c), lp, dm, ds);
+            sum += lp;
+        }
+        if (sum > best) { best = sum; arg = j; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off, 64);
+        const int oa = __shfl_xor(arg, off, 64);
+        if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    }
+    return arg < n ? arg : 0;
+}
+
+// cat_sample_any with every draw q = 1 (the same operations in the same order; x / 1 is x): the first largest class
+__device__ __forceinline__ int cat_argmax_any(const CatFull& g, const float* __restrict__ lg, int row, int f) {
+    float m = -INFINITY;
+    for (int c = 0; c < g.C; ++c) m = fmaxf(m, lg[g.addr(row, f, c)]);
+    float s = 0.f;
+    for (int c = 0; c < g.C; ++c) s += expf(lg[g.addr(row, f, c)] - m);
+    const float lse = m + logf(s);
+    const float m2 = m - lse;
+    float s2 = 0.f;
+    for (int c = 0; c < g.C; ++c) s2 += expf((lg[g.addr(row, f, c)] - lse) - m2);
+    float best = -INFINITY;
+    int arg = 0;
+    for (int c = 0; c < g.C; ++c) {
+        const float r = (expf((lg[g.addr(row, f, c)] - lse) - m2) / s2) / 1.f;
+        if (r > best) { best = r; arg = c; }
+    }
+    return arg;
+}
+
+// bd_tanh_normal_mode: one wave per row, kWaves rows per workgroup
+__global__ __launch_bounds__(kThreads) void tanh_normal_mode_kernel(const float* __restrict__ mean, const float* __restrict__ sd,
+                                                                    const float* __restrict__ eps, Rng rng, int N, int A, int n,
+                                                                    float* __restrict__ action, int* __restrict__ index) {
+    const int lane = bd_tid() & 63;
+    const size_t row = (size_t)blockIdx.x * kWaves + bd_wave(bd_tid());
+    if (row >= (size_t)N) return;                 // wave-uniform
+    const float* mr = mean + row * A;
+    const float* sr = sd + row * A;
+    const ModeDraws draws{eps, rng, (size_t)N, row, A};
+    const int j = tanh_normal_mode_index(mr, sr, A, n, draws, lane);
+    if (lane < A) action[row * A + lane] = tanh_act(mr[lane] + sr[lane] * draws(j, lane));
+    if (lane == 0 && index != nullptr) index[row] = j;
+}
+
+// EV = false: the sampling step; the evaluation fields of the block are not looked at.  EV = true: the same body with
+// action_mode / latent_mean honoured (a second set of instantiations: the sampling kernels' registers stay as they were).
+template <bool LC, bool AC, bool EV>
 __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const ActDims d(a.Be, a.D, a.C, a.S, a.A, a.Hd, a.E, a.O, LC);
@@ -207,7 +299,16 @@ __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
             int arg = 0;
             if (row < rows_valid) {
                 const size_t e0 = (size_t)(row0 + row) * a.S + f * a.C;      // first class of this factor in [B x S]
-                if (a.eps_post) {
+                if (EV && a.latent_mean) {      // q = 1 for every class
+                    if (a.C == 32) {
+                        __attribute__((aligned(16))) float ones[32];
+#pragma unroll
+                        for (int c = 0; c < 32; ++c) ones[c] = 1.f;
+                        arg = cat_sample_reg<32>(gf, lg, ones, row, f);
+                    } else {
+                        arg = cat_argmax_any(gf, lg, row, f);
+                    }
+                } else if (a.eps_post) {
                     const float* qrow = a.eps_post + e0;
                     arg = a.C == 32 ? cat_sample_reg<32>(gf, lg, qrow, row, f) : cat_sample_any(gf, lg, qrow, row, f);
                 } else {
@@ -223,7 +324,10 @@ __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
         const Seg2 segs[1] = {{t1, a.w_q2m, a.w_q2s, d.Kb_hd}};
         tile_dual_head_elem<1>(
             segs, a.b_q2, a.b_q2 + a.S, a.S, scratch,
-            [&](int row, int col) { return draw(a.eps_post, a.stream_post, kDrawNormal, a.S, row, col); },
+            [&](int row, int col) {
+                if (EV && a.latent_mean) return 0.f;
+                return draw(a.eps_post, a.stream_post, kDrawNormal, a.S, row, col);
+            },
             [&](int row, int col, float Mn, float Rw, float eps) {
                 const int grow = row0 + row;
                 float st = 0.f;
@@ -273,11 +377,12 @@ __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
         for (int row = wave; row < rows_valid; row += kWaves) {        // wave-uniform: the butterflies see the whole wave
             const int grow = row0 + row;
             const bool valid = lane < a.A;
-            const float q = valid ? draw_at(a.eps_action, a.stream_action, kDrawExp, (size_t)grow * a.A + lane) : 1.f;
+            const bool greedy = EV && a.action_mode != BD_POLICY_SAMPLE;      // the mode and the mean: argmax p, q = 1
+            const float q = valid && !greedy ? draw_at(a.eps_action, a.stream_action, kDrawExp, (size_t)grow * a.A + lane) : 1.f;
             const float norm = disc_norm(valid ? out_s[row * a.A + lane] : 0.f, valid);
             const float p = disc_probs(norm, valid);
             const int k = disc_sample(p, q, valid, lane);
-            float act = disc_action_value(p, lane == k);
+            float act = greedy ? (lane == k ? 1.f : 0.f) : disc_action_value(p, lane == k);
             if (a.explore) {      // epsilon-greedy: (u, v) = the row's two uniforms
                 const float u = draw_at(a.eps_explore, a.stream_explore, kDrawUniform, (size_t)grow * 2);
                 const float v = draw_at(a.eps_explore, a.stream_explore, kDrawUniform, (size_t)grow * 2 + 1);
@@ -289,6 +394,48 @@ __global__ __launch_bounds__(kThreads) void act_step_kernel(bd_act_args a) {
         }
     } else {
         const Seg2 segs[1] = {{t2, a.w_a4m, a.w_a4s, d.Kb_hd}};
+        if (EV && a.action_mode != BD_POLICY_SAMPLE) {
+            // the row's (mean, std) -> LDS [2][16][A] at the head of the split-K partials (dead once the head's own barrier
+            // has passed) and act_stats_out; BD_POLICY_MEAN finishes here, BD_POLICY_MODE with one wave per row below
+            float* ms = scratch;
+            float* ss = scratch + 16 * a.A;
+            const Rng rng_x{(uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.stream_explore, (uint32_t)a.step};
+            auto explored = [&](float act, int grow, int col) {
+                if (!a.explore) return act;
+                return fminf(fmaxf(act + a.action_noise * normal_at(a.eps_explore, rng_x, (size_t)grow * a.A + col), -1.f), 1.f);
+            };
+            tile_dual_head_elem<1>(
+                segs, a.b_a4, a.b_a4 + a.A, a.A, scratch, [](int, int) { return 0.f; },
+                [&](int row, int col, float Mn, float Rw, float zero) {
+                    const int grow = row0 + row;
+                    const float mean = a.act_mean_scale * tanh_act(Mn / a.act_mean_scale);
+                    const float sd = softplusf(Rw + a.act_raw_init_std) + a.act_min_std;
+                    ms[row * a.A + col] = mean;
+                    ss[row * a.A + col] = sd;
+                    if (grow >= a.B) return;
+                    if (a.act_stats_out) {
+                        a.act_stats_out[(size_t)grow * 2 * a.A + col] = mean;
+                        a.act_stats_out[(size_t)grow * 2 * a.A + a.A + col] = sd;
+                    }
+                    if (a.action_mode == BD_POLICY_MEAN)      // the sampling step's expression at eps_action = 0
+                        a.action_out[(size_t)grow * a.A + col] = explored(tanh_act(mean + sd * zero), grow, col);
+                });
+            if (a.action_mode == BD_POLICY_MODE) {
+                lds_barrier();
+                const Rng rng_m{(uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.stream_mode, (uint32_t)a.step};
+                const int wave = bd_wave(bd_tid());
+                for (int row = wave; row < rows_valid; row += kWaves) {        // wave-uniform: the butterfly sees the whole wave
+                    const int grow = row0 + row;
+                    const ModeDraws draws{a.eps_mode, rng_m, (size_t)a.B, (size_t)grow, a.A};
+                    const int j = tanh_normal_mode_index(ms + row * a.A, ss + row * a.A, a.A, a.n_mode, draws, lane);
+                    if (lane < a.A)
+                        a.action_out[(size_t)grow * a.A + lane] =
+                            explored(tanh_act(ms[row * a.A + lane] + ss[row * a.A + lane] * draws(j, lane)), grow, lane);
+                    if (lane == 0 && a.mode_index_out) a.mode_index_out[grow] = j;
+                }
+            }
+            return;
+        }
         tile_dual_head_elem<1>(
             segs, a.b_a4, a.b_a4 + a.A, a.A, scratch,
             [&](int row, int col) {
@@ -333,12 +480,19 @@ static bool act_supported(int Be, int D, int C, int S, int A, int Hd, int E, int
            ActDims(Be, D, C, S, A, Hd, E, O, lc).lds_floats() * sizeof(float) <= (size_t)kMaxLds;
 }
 
-template <bool LC, bool AC>
-static int act_launch(const char* who, const bd_act_args& k, size_t lds, hipStream_t stream) {
-    if (lds > 64 * 1024 && allow_big_lds(act_step_kernel<LC, AC>)) return -1;
-    hipLaunchKernelGGL((act_step_kernel<LC, AC>), dim3(cdiv(k.B, 16)), dim3(kThreads), lds, stream, k);
+template <bool LC, bool AC, bool EV>
+static int act_launch_ev(const char* who, const bd_act_args& k, size_t lds, hipStream_t stream) {
+    if (lds > 64 * 1024 && allow_big_lds(act_step_kernel<LC, AC, EV>)) return -1;
+    hipLaunchKernelGGL((act_step_kernel<LC, AC, EV>), dim3(cdiv(k.B, 16)), dim3(kThreads), lds, stream, k);
     BD_CHECK_LAUNCH(who);
     return 0;
+}
+
+// a zeroed evaluation tail: the sampling kernel; anything set: the evaluation instantiation
+template <bool LC, bool AC>
+static int act_launch(const char* who, const bd_act_args& k, size_t lds, hipStream_t stream) {
+    if (k.action_mode != BD_POLICY_SAMPLE || k.latent_mean) return act_launch_ev<LC, AC, true>(who, k, lds, stream);
+    return act_launch_ev<LC, AC, false>(who, k, lds, stream);
 }
 
 // the checks of both entry points (`who` names the one that was called), then the launch of the (latent_cat, actor_cat) kernel
@@ -367,11 +521,19 @@ static int act_step(const char* who, const bd_act_args* a, hipStream_t stream) {
     BD_REQUIRE(a->belief_out && a->state_out && a->action_out, "%s: missing outputs", who);
     BD_REQUIRE(a->belief_out != a->belief && a->state_out != a->state && a->action_out != a->action,
                "%s: an output aliases its input", who);
-    const bool all_null = !a->eps_post && !a->eps_action && !a->eps_explore;
-    BD_REQUIRE(all_null || (a->eps_post && a->eps_action && (a->eps_explore || !a->explore)),
-               "%s: noise buffers: eps_post, eps_action (and eps_explore when explore) or all NULL", who);
+    BD_REQUIRE(a->action_mode == BD_POLICY_SAMPLE || a->action_mode == BD_POLICY_MODE || a->action_mode == BD_POLICY_MEAN,
+               "%s: action_mode %d (BD_POLICY_SAMPLE, BD_POLICY_MODE or BD_POLICY_MEAN)", who, a->action_mode);
+    // the draws this call consumes; eps_mode counts only where it is read (a sampling block may carry anything there)
+    const bool use_post = !a->latent_mean, use_action = a->action_mode == BD_POLICY_SAMPLE;
+    const bool use_mode = a->action_mode == BD_POLICY_MODE && !ac;
+    BD_REQUIRE(!use_mode || (a->n_mode >= 1 && a->n_mode <= (1 << 20)), "%s: n_mode %d (1 .. 2^20 draws of the mode)", who, a->n_mode);
+    const bool all_null = !a->eps_post && !a->eps_action && !a->eps_explore && !(use_mode && a->eps_mode);
+    BD_REQUIRE(all_null || ((a->eps_post || !use_post) && (a->eps_action || !use_action) && (a->eps_explore || !a->explore) &&
+                            (a->eps_mode || !use_mode)),
+               "%s: noise buffers: eps_post, eps_action (and eps_explore when explore, eps_mode for the mode) or all NULL", who);
     bd_act_args k = *a;
     k.O = O;
+    if (!use_mode) k.eps_mode = nullptr;
     if (lc) return ac ? act_launch<true, true>(who, k, lds, stream) : act_launch<true, false>(who, k, lds, stream);
     return ac ? act_launch<false, true>(who, k, lds, stream) : act_launch<false, false>(who, k, lds, stream);
 }
@@ -401,6 +563,20 @@ int bd_act_step_cat(const bd_act_args* a, void* stream) {
     BD_REQUIRE(a->latent_cat || a->actor_cat,
                "bd_act_step_cat: Gaussian latents with the tanh-Normal actor: that configuration is bd_act_step");
     return act_step("bd_act_step_cat", a, (hipStream_t)stream);
+}
+
+int bd_tanh_normal_mode(const float* mean, const float* std, const float* eps_mode, unsigned long long seed,
+                        unsigned long long step, unsigned stream_id, int N, int A, int n, float* action, int* index,
+                        void* stream) {
+    BD_REQUIRE(N >= 1 && A >= 1 && A <= 64 && n >= 1 && n <= (1 << 20),
+               "bd_tanh_normal_mode: bad dims (N %d >= 1, 1 <= A %d <= 64, 1 <= n %d <= 2^20)", N, A, n);
+    BD_REQUIRE(mean && std && action, "bd_tanh_normal_mode: missing mean, std or action");
+    BD_REQUIRE(action != mean && action != std, "bd_tanh_normal_mode: the action aliases an input");
+    const Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), stream_id, (uint32_t)step};
+    hipLaunchKernelGGL(tanh_normal_mode_kernel, dim3(cdiv(N, kWaves)), dim3(kThreads), 0, (hipStream_t)stream, mean, std, eps_mode,
+                       rng, N, A, n, action, index);
+    BD_CHECK_LAUNCH("bd_tanh_normal_mode");
+    return 0;
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@ from torch import Tensor
 
 from . import _cabi as cabi
 from .collect import check_collect_envs
+from .config import ACTION_MODES
 from .engine import (DreamerEngine, check_action_distribution, check_cnn_activation, check_dense_activation,
                      check_gradient_mixing)
 from .memory import ExperienceReplay
@@ -324,19 +325,24 @@ class Dreamer:
 
     @torch.no_grad()
     def act_step(self, belief: Tensor, posterior_state: Tensor, action: Tensor, observation: Tensor, explore: bool = False,
-                 _noise: Optional[Dict[str, Tensor]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+                 _noise: Optional[Dict[str, Tensor]] = None, action_mode: str = "sample",
+                 state_mean: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
         """The decision of update_belief_and_act (src/planet.py:370-403 with get_action, src/dreamer.py:429-444) without
         the environment, in one kernel launch (bd_act_step): (belief, posterior state, previous action, observation) ->
         (belief, posterior state, action), all on the device.  Pixel observations go through the conv encoder first.
         `_noise`: the composed path's keys "post" (B,S), "action" (B,A) and, with explore, "explore" (B,A); "prior" and
         "entropy" are accepted and ignored (their draws feed nothing that is returned).  Without it the draws come from
-        the engine's Philox streams.  The results are engine buffers, valid until the call after the next one."""
+        the engine's Philox streams.  The results are engine buffers, valid until the call after the next one.
+        `action_mode`, `state_mean`: the evaluation policy (update_belief_and_act); "mode" reads `_noise`'s "mode"
+        (n_entropy,B,A), the layout of get_action's."""
+        _check_action_mode(action_mode)
         obs, emb = self._act_inputs(self.engine.act_step_supported, observation,
                                     "act_step: the fused acting kernel takes Gaussian latents and the tanh-Normal actor at sizes "
                                     "bd_act_step_supported accepts ({config}); use update_belief_and_act, which composes the "
                                     "step from the scan kernels")
         return self.engine.act_step(belief, posterior_state, action, obs=obs, embedding=emb, explore=bool(explore),
-                                    action_noise=self.action_noise, noise=_noise)
+                                    action_noise=self.action_noise, noise=_noise, action_mode=action_mode,
+                                    state_mean=bool(state_mean))
 
     def _act_inputs(self, supported: bool, observation: Tensor, refusal: str):
         """The preamble of act_step / act_step_cat: refuse an unsupported configuration (`refusal`, its {config} filled in
@@ -357,13 +363,16 @@ class Dreamer:
 
     @torch.no_grad()
     def act_step_cat(self, belief: Tensor, posterior_state: Tensor, action: Tensor, observation: Tensor, explore: bool = False,
-                     _noise: Optional[Dict[str, Tensor]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+                     _noise: Optional[Dict[str, Tensor]] = None, action_mode: str = "sample",
+                     state_mean: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
         """act_step for latent_distribution=Categorical and / or action_distribution=Categorical (bd_act_step_cat): the
         decision of update_belief_and_act without the environment, in one kernel launch.  Pixel observations go through the
         conv encoder first.  `_noise`: the composed path's keys "post" (B,S), "action" (B,A) and, with explore, "explore"
         (B,A) (tanh-Normal actor) or "explore_u" (B,) uniforms and "explore_k" (B,) classes (Categorical actor; the kernel
         gets v = (k + 0.5) / A, whose class is k); "prior" and "entropy" are accepted and ignored.  Without it the draws come
-        from the engine's Philox streams.  The results are engine buffers, valid until the call after the next one."""
+        from the engine's Philox streams.  The results are engine buffers, valid until the call after the next one.
+        `action_mode`, `state_mean`: the evaluation policy, as act_step."""
+        _check_action_mode(action_mode)
         d = self.dims
         obs, emb = self._act_inputs(self.engine.act_step_cat_supported, observation,
                                     "act_step_cat: the fused acting kernel takes Categorical latents and / or the Categorical "
@@ -372,25 +381,36 @@ class Dreamer:
                                     "the step from the scan kernels")
         nz = _noise
         if nz is not None:
-            nz = {k: nz[k] for k in ("post", "action")}
+            nz = {k: nz[k] for k in ("post", "action", "mode") if k in nz}
             if explore and d.discrete_actions:
                 u, k = _noise["explore_u"].to(self.device).float(), _noise["explore_k"].to(self.device).float()
                 nz["explore"] = torch.stack([u, (k + 0.5) / d.A], dim=1)
             elif explore:
                 nz["explore"] = _noise["explore"]
         return self.engine.act_step_cat(belief, posterior_state, action, obs=obs, embedding=emb, explore=bool(explore),
-                                        action_noise=self.action_noise, noise=nz)
+                                        action_noise=self.action_noise, noise=nz, action_mode=action_mode,
+                                        state_mean=bool(state_mean))
 
     @torch.no_grad()
     def update_belief_and_act(self, env, belief, posterior_state, action, observation, explore=False,
-                              _noise: Optional[Dict[str, Tensor]] = None):
+                              _noise: Optional[Dict[str, Tensor]] = None, action_mode: str = "sample",
+                              state_mean: bool = False):
         """src/planet.py:370-403.  (Data-parallel runs: issues any held-back actor update first -- a collective, call on
         every rank, as the collect loop does.)  Where act_fused holds the decision is one launch (act_step), and so it is
         where act_fused_cat holds (act_step_cat; BD_ACT_FUSED_CAT=1, off by default); the code below composes it from the
-        encoder chain, a one-step observe scan and a one-step imagination otherwise."""
+        encoder chain, a one-step observe scan and a one-step imagination otherwise.
+        The evaluation policy (Dreamer v1 / v2 evaluate with the actor's mode, v2 optionally with the posterior mean):
+        `action_mode` "sample" (the reference's loop), "mode" -- tanh-Normal actor: SampleDist.mode, of n_entropy draws
+        (`_noise`'s "mode" (n_entropy,B,A)) the one with the largest log-density, the first maximum winning; Categorical
+        actor: the exact one-hot of argmax p -- or "mean" -- tanh(mean), no draw; Categorical actor: as "mode".
+        `state_mean`: the posterior's mean (Gaussian latents) or per-factor argmax (Categorical) instead of a sample.
+        Exploration, where asked for, is applied on top as before.  Every route honours them; another `action_mode` is a
+        ValueError."""
+        _check_action_mode(action_mode)
         if self.act_fused or self.act_fused_cat:
             step = self.act_step if self.act_fused else self.act_step_cat
-            belief, posterior_state, action = step(belief, posterior_state, action, observation, explore=explore, _noise=_noise)
+            belief, posterior_state, action = step(belief, posterior_state, action, observation, explore=explore, _noise=_noise,
+                                                   action_mode=action_mode, state_mean=state_mean)
             batched = hasattr(env, "n") and hasattr(env, "envs")          # EnvBatcher (src/env.py:343)
             next_observation, reward, done = env.step(action.cpu() if batched else action[0].cpu())
             return belief, posterior_state, action, next_observation, reward, done
@@ -399,13 +419,32 @@ class Dreamer:
         # "entropy" (100,B,A), and with explore "explore" (B,A)
         nz = _noise
         embedding = self.encoder(observation.to(self.device)).unsqueeze(dim=0)
+        B = belief.shape[0]
+        if state_mean:
+            # the mean of the posterior: its sample at zero normal noise, or -- Categorical -- at q = 1 for every class
+            fixed = (torch.ones if self.dims.categorical else torch.zeros)(1, B, self.state_size, device=self.device)
+            state_noise = (fixed if nz is None or "prior" not in nz else nz["prior"].unsqueeze(0), fixed)
+        else:
+            state_noise = None if nz is None else (nz["prior"].unsqueeze(0), nz["post"].unsqueeze(0))
         belief, _, _, posterior_state, _ = self.transition_model(
-            posterior_state, action.unsqueeze(dim=0), belief, embedding,
-            _noise=None if nz is None else (nz["prior"].unsqueeze(0), nz["post"].unsqueeze(0)))
+            posterior_state, action.unsqueeze(dim=0), belief, embedding, _noise=state_noise)
         belief, posterior_state = belief.squeeze(dim=0), posterior_state.squeeze(dim=0)
-        action, _ = self.get_action(belief, posterior_state, _noise=None if nz is None else dict(
-            {k: nz[k].unsqueeze(0).contiguous() for k in ("action", "entropy") if k in nz},
-            img_prior=torch.ones(1, belief.shape[0], self.state_size, device=self.device)))
+        if action_mode == "sample":
+            action, _ = self.get_action(belief, posterior_state, _noise=None if nz is None else dict(
+                {k: nz[k].unsqueeze(0).contiguous() for k in ("action", "entropy") if k in nz},
+                img_prior=torch.ones(1, B, self.state_size, device=self.device)))
+        elif self.dims.discrete_actions:
+            action, _ = self.get_action(belief, posterior_state, deterministic=True)      # the exact one-hot of argmax p
+        else:
+            mean, std = self.actor(belief, posterior_state)
+            if action_mode == "mode":
+                action, _ = self.engine.tanh_normal_mode(mean, std, None if nz is None else nz["mode"])
+            else:       # tanh(mean) as the sampling kernels form it: zero action noise (one draw for the unread entropy)
+                action, _ = self.get_action(belief, posterior_state, _noise={
+                    "action": torch.zeros(1, B, self.action_size, device=self.device),
+                    "entropy": torch.zeros(1, 1, B, self.action_size, device=self.device).expand(
+                        1, self.dims.n_entropy, B, self.action_size).contiguous(),
+                    "img_prior": torch.ones(1, B, self.state_size, device=self.device)})
         if explore and self.dims.discrete_actions:
             # epsilon-greedy: with probability action_noise a uniformly random one-hot (Gaussian noise would leave the
             # simplex); `_noise`: "explore_u" (B,) uniforms, "explore_k" (B,) classes
@@ -422,18 +461,26 @@ class Dreamer:
         return belief, posterior_state, action, next_observation, reward, done
 
     # ---------------------------------------------------------------------------------------- evaluation
-    def evaluate(self, envs=None, episodes: Optional[int] = None, video: bool = False, _noise=None) -> Dict[str, Any]:
+    def evaluate(self, envs=None, episodes: Optional[int] = None, video: bool = False, _noise=None,
+                 action_mode: Optional[str] = None, state_mean: Optional[bool] = None) -> Dict[str, Any]:
         """The reference's test loop (src/main.py:191-283; evaluate.run_evaluation): `episodes` (default
         ``test_episodes``) environments side by side for at most max_episode_length // action_repeat decisions without
         exploration noise.  Returns Eval_{min,avg,max,std}_return, ``returns``, ``steps`` and ``video`` -- uint8 (steps, 3,
         GH, GW) real-vs-predicted frames, pixel observations only, else None.  `envs`: an EnvBatcher to use instead of a
-        fresh one.  Data-parallel runs: update_belief_and_act carries collectives, so every rank calls this."""
+        fresh one.  Data-parallel runs: update_belief_and_act carries collectives, so every rank calls this.
+        `action_mode` / `state_mean`: the evaluation policy of update_belief_and_act; None takes the config's
+        ``eval_action`` ('sample') / ``eval_state_mean`` (false).  With "mean" (or a Categorical actor's "mode") and
+        state_mean the decisions draw nothing: two evaluations of one agent on the same environments return the same."""
         from .env import Env, EnvBatcher
         from .evaluate import run_evaluation
+        action_mode = self.params.get("eval_action", "sample") if action_mode is None else action_mode
+        state_mean = bool(self.params.get("eval_state_mean", False)) if state_mean is None else bool(state_mean)
+        _check_action_mode(action_mode)
         if envs is None:
             envs = EnvBatcher(Env, self.params, int(episodes or self.params["test_episodes"]))
         max_steps = int(self.params["max_episode_length"]) // int(self.action_repeat)
-        return run_evaluation(self, envs, max_steps, video=bool(video) and self.pixel_observation, _noise=_noise)
+        return run_evaluation(self, envs, max_steps, video=bool(video) and self.pixel_observation, _noise=_noise,
+                              action_mode=action_mode, state_mean=state_mean)
 
     # ---------------------------------------------------------------------------------------- open-loop prediction
     def open_loop(self, batch=None, sequences: int = 6, context: int = 5, video: Optional[bool] = None,
@@ -465,6 +512,11 @@ class DreamerV2(Dreamer):
             p["kl_loss_weight"] = 0.1
         super().__init__(p, env, **kw)
         self.kl_balance = p["kl_balance"]
+
+
+def _check_action_mode(action_mode) -> None:
+    if action_mode not in ACTION_MODES:
+        raise ValueError(f"action_mode {action_mode!r} is none of {ACTION_MODES}")
 
 
 def _tanh_normal_log_prob(y: Tensor, mean: Tensor, std: Tensor) -> Tensor:

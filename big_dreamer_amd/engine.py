@@ -357,6 +357,7 @@ class DreamerEngine:
         self._rng_step = {"wm": 0, "bh": 0}
         self._rng_entropy_step = 0
         self._act_parity = 0                 # act_step: which of its two output buffer sets the next call writes
+        self.last_act_stats = self.last_act_mode_index = None     # act_step with an evaluation policy: what it left
         self._log_ring: List[_LogRecord] = []
         self._log_i = 0
         self._cur_rec: Optional[_LogRecord] = None
@@ -1104,15 +1105,20 @@ class DreamerEngine:
 
     def act_step(self, belief: torch.Tensor, state: torch.Tensor, action: torch.Tensor, obs: Optional[torch.Tensor] = None,
                  embedding: Optional[torch.Tensor] = None, explore: bool = False, action_noise: float = 0.0,
-                 noise: Optional[Dict[str, torch.Tensor]] = None):
+                 noise: Optional[Dict[str, torch.Tensor]] = None, action_mode: str = "sample", state_mean: bool = False):
         """One decision for B environments in one launch (bd_act_step; Planet.update_belief_and_act, src/planet.py:370-403):
         (belief (B,Be), state (B,S), previous action (B,A), obs (B,O) | embedding (B,E)) -> (belief', state', action').
         noise: {"post" (B,S), "action" (B,A), "explore" (B,A)} (parity), or None: the kernel draws from the Philox streams
         act_post / act_action / act_explore, one counter step per decision.
         Ordered behind queued train steps and packed-weight refreshes like every API call (flush_optimizers, join).
         The results live in two alternating sets of engine buffers: a call never writes what it reads, and what it returns
-        stays valid until the call after the next one (clone to keep it longer)."""
-        return self._act("act_step", belief, state, action, obs, embedding, explore, action_noise, noise)
+        stays valid until the call after the next one (clone to keep it longer).
+        The evaluation policy: action_mode "mode" -- SampleDist.mode, of n_entropy draws noise["mode"] (n_entropy,B,A) (or the
+        Philox stream act_mode, same decision counter) the one with the largest log-density, first maximum winning --,
+        "mean" -- tanh(mean), no draw --; state_mean: s' = the posterior's mean.  A draw that is not consumed may be missing
+        from `noise`.  Such a call leaves the actor's (B,2A) mean | std in ``last_act_stats`` and, for "mode", the winning
+        draws' indices (B,) int32 in ``last_act_mode_index``."""
+        return self._act("act_step", belief, state, action, obs, embedding, explore, action_noise, noise, action_mode, state_mean)
 
     @property
     def act_step_cat_supported(self) -> bool:
@@ -1126,17 +1132,21 @@ class DreamerEngine:
 
     def act_step_cat(self, belief: torch.Tensor, state: torch.Tensor, action: torch.Tensor, obs: Optional[torch.Tensor] = None,
                      embedding: Optional[torch.Tensor] = None, explore: bool = False, action_noise: float = 0.0,
-                     noise: Optional[Dict[str, torch.Tensor]] = None):
+                     noise: Optional[Dict[str, torch.Tensor]] = None, action_mode: str = "sample", state_mean: bool = False):
         """act_step for Categorical latents and / or the Categorical actor (bd_act_step_cat): one decision for B
         environments in one launch, same arguments, ordering (flush_optimizers, join) and alternating output sets.
         noise: {"post" (B,S), "action" (B,A), "explore"}: Exp(1) draws where a Categorical sampler consumes them, standard
         normals otherwise; "explore" is (B,A) normals for the tanh-Normal actor and (B,2) uniforms (u, v) for the
         Categorical one (epsilon-greedy: u < action_noise picks class min(floor(v A), A - 1)).  None: the kernel draws
         from the Philox streams act_post / act_action / act_explore, one counter step per decision (shared with act_step).
-        A Categorical state must be all-zero or one-hot per factor, as for imagine() from a caller's state."""
-        return self._act("act_step_cat", belief, state, action, obs, embedding, explore, action_noise, noise)
+        A Categorical state must be all-zero or one-hot per factor, as for imagine() from a caller's state.
+        action_mode / state_mean as act_step; the Categorical actor's "mode" and "mean" are both the exact one-hot of
+        argmax p, and Categorical latents' state_mean the per-factor argmax of the posterior logits."""
+        return self._act("act_step_cat", belief, state, action, obs, embedding, explore, action_noise, noise, action_mode,
+                         state_mean)
 
-    def _act(self, name: str, belief, state, action, obs, embedding, explore, action_noise, noise):
+    def _act(self, name: str, belief, state, action, obs, embedding, explore, action_noise, noise, action_mode="sample",
+             state_mean=False):
         """The body of act_step / act_step_cat: binds the argument block for this engine's latent and actor kind, picks the
         output set and launches the entry point bd_<name> under the span <name> (the entry point refuses a kind that is
         not its own; so does the check below, before anything of the engine's state is touched)."""
@@ -1145,6 +1155,8 @@ class DreamerEngine:
             raise RuntimeError(f"{name}: not this engine's configuration (Categorical latents: {bool(d.categorical)}, "
                                f"Categorical actor: {bool(d.discrete_actions)}); Gaussian latents with the tanh-Normal actor are "
                                "act_step's, the other three act_step_cat's")
+        if action_mode not in cabi.ACTION_MODES:
+            raise ValueError(f"{name}: action_mode {action_mode!r} is none of {sorted(cabi.ACTION_MODES)}")
         tm = lambda n: self.W("transition_model", n)
         self.flush_optimizers()
         self.join()
@@ -1172,13 +1184,32 @@ class DreamerEngine:
             a.w_embed_s, a.w_a0s = ptr(pk["embed_s"]), ptr(pk["a0s"])
             a.w_q2m, a.w_q2s = ptr(pk["q2m"]), ptr(pk["q2s"])
         a.belief, a.state, a.action = ptr(belief), ptr(state), ptr(action)
+        a.action_mode, a.latent_mean = cabi.ACTION_MODES[action_mode], int(bool(state_mean))
+        draws_mode = a.action_mode == cabi.BD_POLICY_MODE and not d.discrete_actions
+        self.last_act_stats = self.last_act_mode_index = None
+        if a.action_mode != cabi.BD_POLICY_SAMPLE and not d.discrete_actions:
+            self.last_act_stats = self.buf("act_stats", B, 2 * d.A)
+            a.act_stats_out = ptr(self.last_act_stats)
+        if draws_mode:
+            a.n_mode = d.n_entropy
+            t = self._buf.get("act_mode_index")
+            if t is None or t.shape[0] != B:
+                t = self._buf["act_mode_index"] = torch.zeros(B, dtype=torch.int32, device=self.dev)
+            self.last_act_mode_index, a.mode_index_out = t, t.data_ptr()
         if noise is not None:
-            a.eps_post, a.eps_action = ptr(f(noise["post"]).view(B, d.S)), ptr(f(noise["action"]).view(B, d.A))
+            # a draw that this call does not consume may be missing
+            if not state_mean:
+                a.eps_post = ptr(f(noise["post"]).view(B, d.S))
+            if a.action_mode == cabi.BD_POLICY_SAMPLE:
+                a.eps_action = ptr(f(noise["action"]).view(B, d.A))
+            if draws_mode:
+                a.eps_mode = ptr(f(noise["mode"]).view(d.n_entropy, B, d.A))
             a.eps_explore = ptr(f(noise["explore"]).view(B, 2 if d.discrete_actions else d.A)) if explore else None
         else:
             a.seed, a.step = self.rng_seed, self._rng_step.get("act", 0)
             self._rng_step["act"] = a.step + 1
         a.stream_post, a.stream_action, a.stream_explore = (self.RNG_STREAMS[k] for k in ("act_post", "act_action", "act_explore"))
+        a.stream_mode = self.RNG_STREAMS["act_mode"]
         a.min_std = self.hp["min_std_dev"]
         a.act_raw_init_std, a.act_min_std, a.act_mean_scale = ACT_RAW_INIT_STD, ACT_MIN_STD, ACT_MEAN_SCALE
         a.action_noise, a.explore = float(action_noise), int(bool(explore))
@@ -1196,6 +1227,30 @@ class DreamerEngine:
         with self.span(name):
             cabi.check(getattr(lib, "bd_" + name)(C.byref(a), cabi.stream()))
         return out
+
+    def tanh_normal_mode(self, mean: torch.Tensor, std: torch.Tensor, eps: Optional[torch.Tensor] = None):
+        """SampleDist.mode (src/models.py:708-723) on the actor's (mean, std) (N,A) in one launch (bd_tanh_normal_mode, the
+        selection rule of act_step's action_mode="mode"): of the n draws tanh(mean + std * eps[j]) per row the one with
+        the largest log-density, first maximum winning.  eps: (n,N,A) standard normals, or None: n_entropy draws of the
+        Philox stream act_mode at the next decision counter (which advances, as in act_step).  Returns (action (N,A),
+        index (N,) int32), fresh tensors."""
+        f = lambda t: t.to(self.dev).float().contiguous()
+        mean, std = f(mean), f(std)
+        N, A = mean.shape
+        seed = step = 0
+        if eps is not None:
+            eps = f(eps)
+            n = eps.shape[0]
+            eps = eps.view(n, N, A)
+        else:
+            n, seed, step = self.d.n_entropy, self.rng_seed, self._rng_step.get("act", 0)
+            self._rng_step["act"] = step + 1
+        action = torch.empty(N, A, device=self.dev)
+        index = torch.empty(N, dtype=torch.int32, device=self.dev)
+        with self.span("tanh_normal_mode"):
+            cabi.check(lib.bd_tanh_normal_mode(ptr(mean), ptr(std), ptr(eps), seed, step, self.RNG_STREAMS["act_mode"], N, A, n,
+                                               ptr(action), index.data_ptr(), cabi.stream()))
+        return action, index
 
     def _plan_args(self, rows: int, H: int, cand: int):
         """bd_plan_args with the dims, latent_cat and every weight of the engine's latent kind; inputs, outputs and noise
@@ -1332,7 +1387,8 @@ class DreamerEngine:
 
     # noise streams of the perf-mode generator (csrc/bd_rng.h: counter = (index, stream id, step))
     RNG_STREAMS = {"obs_post": 1, "action": 2, "img_prior": 3, "entropy": 4, "obs_prior": 5, "plan_prior": 7,   # (6: pixel dequantisation)
-                   "act_post": 8, "act_action": 9, "act_explore": 10}     # bd_act_step: counter step = decision index
+                   "act_post": 8, "act_action": 9, "act_explore": 10,     # bd_act_step: counter step = decision index
+                   "act_mode": 11}                                        # the evaluation policy's n_entropy draws, same counter
 
     def make_noise(self, B: int, part: str = "all") -> Dict[str, torch.Tensor]:
         """Noise of one step in perf mode (parity tests pass explicit arrays): ONE bd_rng_fill launch per phase on the

@@ -26,14 +26,21 @@ def frame_shape(n: int) -> Tuple[int, int, int]:
 
 @torch.no_grad()
 def run_evaluation(agent, envs, max_steps: int, video: bool = False,
-                   _noise: Optional[Callable[[int], Dict[str, torch.Tensor]]] = None) -> Dict[str, Any]:
+                   _noise: Optional[Callable[[int], Dict[str, torch.Tensor]]] = None, action_mode: str = "sample",
+                   state_mean: bool = False) -> Dict[str, Any]:
     """The reference's test loop (src/main.py:199-272) on `envs` (an EnvBatcher): at most `max_steps` decisions from the
     zero belief / state / action, ``explore=False``, stopping once every environment is done.  `_noise(step)` (parity
     tests) is handed to ``update_belief_and_act`` as its ``_noise``; None passes no such keyword (Planet has none).
+    `action_mode` ("sample", "mode", "mean") and `state_mean` are the evaluation policy (Dreamer.update_belief_and_act);
+    they are passed on only when they differ from the defaults, so a Planet or a stub without them evaluates as before.
     Returns Eval_{min,avg,max,std}_return (floats; std is the population std), ``returns`` (n,), ``steps`` and ``video``:
     uint8 (steps, 3, GH, GW) -- frame t pairs the observations decision t consumed with the reconstruction from the belief
     and posterior it produced -- or None."""
+    from .config import ACTION_MODES
+    if action_mode not in ACTION_MODES:
+        raise ValueError(f"action_mode {action_mode!r} is none of {ACTION_MODES}")
     n, dev = envs.n, agent.device
+    policy = {} if (action_mode == "sample" and not state_mean) else {"action_mode": action_mode, "state_mean": bool(state_mean)}
     agent.eval()
     observation = envs.reset()
     total = np.zeros((n,))
@@ -44,7 +51,7 @@ def run_evaluation(agent, envs, max_steps: int, video: bool = False,
     steps = 0
     for t in range(max_steps):
         observation = observation.to(device=dev)       # the one upload: the encoder and the frame kernel both read it
-        kw = {} if _noise is None else {"_noise": _noise(t)}
+        kw = dict(policy) if _noise is None else dict(policy, _noise=_noise(t))
         belief, posterior_state, action, next_observation, reward, done = agent.update_belief_and_act(
             envs, belief, posterior_state, action, observation, explore=False, **kw)
         total += reward.numpy()

@@ -48,8 +48,13 @@ class Planet(Dreamer):
         return self.planner(belief, state, _noise=_noise)
 
     @torch.no_grad()
-    def update_belief_and_act(self, env, belief, posterior_state, action, observation, explore=False):
-        """src/planet.py:370-403 (see the module docstring for the one deviation)."""
+    def update_belief_and_act(self, env, belief, posterior_state, action, observation, explore=False,
+                              action_mode: str = "sample", state_mean: bool = False):
+        """src/planet.py:370-403 (see the module docstring for the one deviation).  PlaNet chooses its action by planning:
+        the evaluation policy of Dreamer.update_belief_and_act does not apply, anything but the defaults is refused."""
+        if action_mode != "sample" or state_mean:
+            raise ValueError(f"Planet.update_belief_and_act: action_mode={action_mode!r}, state_mean={state_mean!r}: PlaNet plans "
+                             "its actions (CEM); the evaluation policy (mode / mean actions, mean latents) is Dreamer's")
         embedding = self.encoder(observation.to(self.device)).unsqueeze(dim=0)
         belief, _, _, posterior_state, _ = self.transition_model(posterior_state, action.unsqueeze(dim=0), belief,
                                                                  embedding)

@@ -759,7 +759,26 @@ int bd_cem_refit(const float* returns, int ret_steps, const float* actions, int 
  * The kernel never writes its inputs: belief_out / state_out / action_out must be other buffers than belief / state /
  * action (the host ping-pongs).  One workgroup per 16 rows.  A <= 64; LDS as csrc/act.hip states (<= 160 KiB):
  * bd_act_step_supported / bd_act_step_cat_supported answer from the launcher's own arithmetic without raising an error
- * (O = 0: the embedding form). */
+ * (O = 0: the embedding form).
+ * Evaluation policy (Dreamer v1 / v2 evaluate with the actor's mode, v2 optionally with the posterior mean): the fields
+ * behind action_out.  All zero: the step above, from the same four kernels as before the fields existed; anything set
+ * selects a second instantiation of the same body, so the sampling kernels carry none of it.
+ *   action_mode = BD_POLICY_MODE, tanh-Normal actor: SampleDist.mode (src/models.py:708-723).  Of n_mode draws y_j =
+ *     tanh(mean + std * eps_mode[j, row, :]) the action is the y_j with the largest log-density summed over the A
+ *     dimensions (the formula of the entropy estimator, csrc/bd_scan.h: clamp at 1 - 2^-24, atanh, log-det), the FIRST
+ *     maximum winning.  One wave per row, a lane per draw in passes of 64, a wave argmax; mode_index_out gets j.
+ *   action_mode = BD_POLICY_MEAN, tanh-Normal actor: action = tanh(mean), no draw (bit-equal to eps_action = 0).
+ *   actor_cat, either mode: the exact one-hot of argmax p, the first maximum winning (q = 1 in the sampler).
+ *   Exploration, where asked for, is applied on top as in the sampling step.
+ *   latent_mean: Gaussian latents s' = mean_q (bit-equal to eps_post = 0); Categorical latents the per-factor argmax of
+ *     the posterior logits (bit-equal to eps_post = 1).
+ *   Noise: a buffer is required only for a draw that is consumed (eps_post unless latent_mean, eps_action with
+ *     BD_POLICY_SAMPLE, eps_mode with BD_POLICY_MODE and the tanh-Normal actor, eps_explore with explore); as above either every
+ *     consumed buffer is given or every one is NULL, and then element i of eps_mode, layout (n_mode, B, A), is what
+ *     bd_rng_fill(BD_RNG_NORMAL, seed, step, stream_mode) writes at i. */
+#define BD_POLICY_SAMPLE 0
+#define BD_POLICY_MODE 1
+#define BD_POLICY_MEAN 2
 typedef struct {
     int B, Be, D, C, S, A, Hd, E, O;
     int latent_cat, actor_cat;
@@ -794,12 +813,27 @@ typedef struct {
     float* belief_out;         /* [B x Be] */
     float* state_out;          /* [B x S]  */
     float* action_out;         /* [B x A]  */
+    /* evaluation policy (appended: a zeroed tail is the sampling step above, bit for bit) */
+    int action_mode;           /* BD_POLICY_SAMPLE | BD_POLICY_MODE | BD_POLICY_MEAN */
+    int latent_mean;           /* s' = the posterior's mean (Gaussian) / per-factor argmax of its logits (Categorical) */
+    int n_mode;                /* draws of BD_POLICY_MODE with the tanh-Normal actor (SampleDist's n_samples = 100), >= 1 */
+    const float* eps_mode;     /* [n_mode x B x A] standard normal, or NULL; read only by BD_POLICY_MODE, tanh-Normal actor */
+    unsigned stream_mode;      /* Philox stream id of the in-kernel eps_mode */
+    float* act_stats_out;      /* [B x 2A] actor mean | std per row; may be NULL; tanh-Normal actor, action_mode != 0 */
+    int* mode_index_out;       /* [B] index of the winning draw; may be NULL; BD_POLICY_MODE, tanh-Normal actor */
 } bd_act_args;
 typedef bd_act_args bd_act_cat_args;
 int bd_act_step_supported(int Be, int S, int A, int Hd, int E, int O);
 int bd_act_step(const bd_act_args* a, void* stream);
 int bd_act_step_cat_supported(int Be, int D, int C, int S, int A, int Hd, int E, int O, int latent_cat, int actor_cat);
 int bd_act_step_cat(const bd_act_cat_args* a, void* stream);
+/* SampleDist.mode on given statistics, the selection rule of BD_POLICY_MODE by the same device function: mean, std [N x A],
+ * eps_mode [n x N x A] standard normal or NULL (then element i is what bd_rng_fill(BD_RNG_NORMAL, seed, step, stream_id)
+ * writes at i) -> action [N x A] = tanh(mean + std * eps_mode[j]) of the first j with the largest summed log-density,
+ * index [N] = j (may be NULL).  One wave per row; any N >= 1, 1 <= A <= 64, 1 <= n <= 2^20. */
+int bd_tanh_normal_mode(const float* mean, const float* std, const float* eps_mode, unsigned long long seed,
+                        unsigned long long step, unsigned stream_id, int N, int A, int n, float* action, int* index,
+                        void* stream);
 
 /* ---- losses (src/planet.py:252-284, src/dreamer.py:110-146,342-383) ---------------------------
  * Reductions write RAW SUMS into a small device "scalar board" (float array); the host turns them

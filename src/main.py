@@ -41,7 +41,10 @@ def evaluate(model, params, step, rank):
     data-parallel runs, so every rank evaluates; rank 0 prints and saves."""
     video = (bool(params["pixel_observation"]) and params["log_video_freq"] not in (-1, 0)
              and step % params["log_video_freq"] == 0)
-    result = model.evaluate(episodes=params["test_episodes"], video=video)
+    policy = {}
+    if params["eval_action"] != "sample" or params["eval_state_mean"]:      # (a Planet evaluates by planning: defaults only)
+        policy = {"action_mode": params["eval_action"], "state_mean": params["eval_state_mean"]}
+    result = model.evaluate(episodes=params["test_episodes"], video=video, **policy)
     if rank != 0:
         return
     for key in ("Eval_min_return", "Eval_avg_return", "Eval_max_return", "Eval_std_return"):
