@@ -215,6 +215,13 @@ class ReplayAppendArgs(C.Structure):
                 ("dst_reward", P), ("dst_nonterminal", P)]
 
 
+class ReplaySampleArgs(C.Structure):
+    _fields_ = (_ptr_fields(["obs", "act", "reward", "nonterminal"]) + [(n, I32) for n in (
+        "obs_width", "A", "size", "lanes", "lane_size", "idx", "full", "n", "L", "bit_depth")] + [
+        (n, C.c_ulonglong) for n in ("seed", "step", "pix_seed", "pix_step")] + _ptr_fields(
+        ["dst_obs", "dst_act", "dst_reward", "dst_nonterminal", "idx_out"]))
+
+
 # every symbol include/bigdreamer_hip.h declares, with its signature
 _SIGS = {
     "bd_last_error": (C.c_char_p, []),
@@ -287,6 +294,7 @@ _SIGS = {
     "bd_replay_gather_pixels": (I32, [P, P, I32, I32, I32, P, P, P]),
     "bd_replay_gather_pixels_rng": (I32, [P, P, I32, I32, I32, C.c_ulonglong, C.c_ulonglong, P, P]),
     "bd_replay_append": (I32, [C.POINTER(ReplayAppendArgs), P]),
+    "bd_replay_sample_gather": (I32, [C.POINTER(ReplaySampleArgs), P]),
     "bd_reduce_ws_floats": (C.c_size_t, []),
     "bd_conv_gemm": (I32, [C.POINTER(ConvArgs), P]),
     "bd_conv_thin_forward": (I32, [P, I32, I32, I32, I32, I32, P, I32, P, I32, P, P, P]),

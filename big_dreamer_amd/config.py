@@ -48,4 +48,6 @@ def load_config(overrides: List[str] = (), path: str = DEFAULT_CONFIG) -> Dict[s
         raise ValueError(f"eval_action={cfg['eval_action']!r} is none of {ACTION_MODES}")
     if not isinstance(cfg.get("eval_state_mean", False), bool):
         raise ValueError(f"eval_state_mean={cfg['eval_state_mean']!r} is not a boolean")
+    if not isinstance(cfg.get("sample_on_device", False), bool):
+        raise ValueError(f"sample_on_device={cfg['sample_on_device']!r} is not a boolean")
     return cfg

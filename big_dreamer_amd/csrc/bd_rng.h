@@ -7,6 +7,8 @@
 //     key     = (seed lo, seed hi)                       -- per process: torch.initial_seed()
 //     counter = (index lo, index hi, stream id, step)    -- index: which group of 4 values; stream id: which noise tensor
 //                                                            (observe / action / prior / entropy ...); step: train step
+// Stream ids in use: 1 obs_post, 2 action, 3 img_prior, 4 entropy, 5 obs_prior, 6 pixel dequantisation, 7 plan_prior,
+// 8 act_post, 9 act_action, 10 act_explore, 11 act_mode, 12 replay_sample (index: sequence of the batch; step: sample call).
 // One call yields four 32-bit words = four normals (two Box-Muller pairs), four Exp(1) variates or four uniforms in [0, 1).
 #pragma once
 #include <hip/hip_runtime.h>

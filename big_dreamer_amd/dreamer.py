@@ -126,7 +126,8 @@ class Dreamer:
         if self.use_discount:       # src/dreamer.py:80-85
             self.discount_model = DenseModel(feat, self.hidden_size, 1, engine=e, module="discount_model", prefix="dsc")
         self.buffer = ExperienceReplay(params["experience_size"], env.action_size, params["bit_depth"], px,
-                                       env.observation_size, self.device, lanes=self.collect_envs)
+                                       env.observation_size, self.device, lanes=self.collect_envs,
+                                       device_sampler=bool(params.get("sample_on_device", False)))
         self.load(params)
 
     # ---------------------------------------------------------------------------------------- checkpoints

@@ -10,7 +10,11 @@ the device by bd_replay_gather_pixels; the dequantisation noise is drawn by torc
 the mirror in step) and ``_sample_idx`` draws every chunk inside one lane ("Laned replay").
 
 ``save`` / ``load`` write and read the filled rows, the counters and the pixel noise state as one uncompressed ``.npz`` of
-plain arrays ("Checkpoint and resume")."""
+plain arrays ("Checkpoint and resume").
+
+``device_sampler=True`` moves the draw itself to the device: ``sample`` is ONE bd_replay_sample_gather launch that draws the
+chunks from its own Philox stream and gathers them -- nothing from ``np.random``, no index upload ("Device-side
+sampling").  ``device_draw`` restates the kernel's draw in Python integers."""
 from __future__ import annotations
 
 import numpy as np
@@ -19,9 +23,25 @@ import torch
 from . import _cabi as cabi
 from .checkpoint import atomic_write
 
+_M32 = 0xFFFFFFFF
+SAMPLE_STREAM = 12            # csrc/bd_rng.h: the Philox stream id of the device sampler ("replay_sample")
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 (csrc/bd_rng.h) in Python integers: four counter words, two key words -> four 32-bit words."""
+    M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+    c0, c1, c2, c3 = (int(v) & _M32 for v in ctr)
+    k0, k1 = (int(v) & _M32 for v in key)
+    for _ in range(10):
+        p0, p1 = M0 * c0, M1 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & _M32, p1 & _M32, ((p0 >> 32) ^ c3 ^ k1) & _M32, p0 & _M32
+        k0, k1 = (k0 + W0) & _M32, (k1 + W1) & _M32
+    return [c0, c1, c2, c3]
+
 
 class ExperienceReplay:
-    def __init__(self, size, action_size, bit_depth, pixel_observation, observation_size, device, lanes=1):
+    def __init__(self, size, action_size, bit_depth, pixel_observation, observation_size, device, lanes=1,
+                 device_sampler=False):
         self.device = torch.device(device)
         self.size = size
         self.lanes = int(lanes)
@@ -49,6 +69,8 @@ class ExperienceReplay:
         self._ring_i = 0
         self._stage = []          # pinned staging buffers of append_batch: [rows | rewards | nonterminals | actions | obs]
         self._stage_i = 0
+        self.device_sampler = bool(device_sampler)        # sample() draws on the device (bd_replay_sample_gather)
+        self._smp_seed, self._smp_step = None, 0          # its Philox key (drawn at the first device sample) and counter
 
     # -- reference semantics (src/memory.py:33-49) --
     def append(self, observation, action, reward, done):
@@ -226,6 +248,9 @@ class ExperienceReplay:
                  episodes=np.asarray(self.episodes, dtype=np.int64), pix_step=np.asarray(self._pix_step, dtype=np.int64),
                  pix_seed_drawn=np.asarray(self._pix_seed is not None),      # False: keyed at the first pixel sample
                  pix_seed=np.asarray(self._pix_seed or 0, dtype=np.uint64))
+        if self.device_sampler:
+            z.update(smp_step=np.asarray(self._smp_step, dtype=np.int64), smp_seed_drawn=np.asarray(self._smp_seed is not None),
+                     smp_seed=np.asarray(self._smp_seed or 0, dtype=np.uint64))
         atomic_write(path, lambda fh: np.savez(fh, **z))
 
     def load(self, path: str) -> None:
@@ -255,6 +280,9 @@ class ExperienceReplay:
             self.steps, self.episodes = int(z["steps"]), int(z["episodes"])
             self._pix_step = int(z["pix_step"])
             self._pix_seed = int(z["pix_seed"]) if bool(z["pix_seed_drawn"]) else None
+            drawn = "smp_seed_drawn" in z.files and bool(z["smp_seed_drawn"])      # a file without the keys: (undrawn, 0)
+            self._smp_seed = int(z["smp_seed"]) if drawn else None
+            self._smp_step = int(z["smp_step"]) if "smp_step" in z.files else 0
         self.mark_dirty()
 
     def _upload_indices(self, vec: np.ndarray) -> torch.Tensor:
@@ -285,9 +313,92 @@ class ExperienceReplay:
         self._out_i[(key, numel)] = (i + 1) % 4
         return ring[i]
 
-    def sample(self, n, L):
+    # -- device-side sampling ("Device-side sampling") --
+    def _draw_geometry(self, n, L):
+        """(R, n_valid) of a draw of n chunks of L rows: the ring a chunk lives in and the number of accepted starts.
+        ValueError where the host route raises one (its message), or would never find a chunk."""
+        n, L = int(n), int(L)
+        R = self.lane_size if self.lanes > 1 else self.size
+        if not 1 <= n <= 4096:
+            raise ValueError(f"ExperienceReplay: the device sampler draws 1 to 4096 sequences per call (got {n})")
+        if L < 1:
+            raise ValueError(f"ExperienceReplay: a chunk has at least one row (got L={L})")
+        if L > R:
+            raise ValueError(f"ExperienceReplay: a chunk of {L} does not fit a ring of {R} rows")
+        if not self.full and self.idx <= L:
+            if self.lanes > 1:
+                raise ValueError(f"ExperienceReplay: each of the {self.lanes} lanes holds {self.idx} transitions, a chunk "
+                                 f"of {L} needs more (seed more steps, or collect from fewer environments)")
+            raise ValueError(f"ExperienceReplay: the buffer holds {self.idx} transitions, a chunk of {L} needs more")
+        return R, (R - L + 1 if self.full else self.idx - L)
+
+    def device_draw(self, n, L, step=None, seed=None) -> np.ndarray:
+        """The rows bd_replay_sample_gather draws for (seed, step), restated in Python integers: int64 [L * n], time-major
+        (element t * n + b).  Needs no device.  `step` None: the current counter, which is not advanced; `seed` None: the
+        buffer's key (``int(torch.initial_seed())`` where it has not been drawn yet, which is what the first device sample
+        will draw).  Sequence b: x = philox4x32_10((b, 0, 12, step), seed); lane = x[0] * lanes >> 32;
+        u = (x[2] | x[3] << 32) * n_valid >> 64; start = u (not full) or (idx + u) mod R (full)."""
+        n, L = int(n), int(L)
+        R, n_valid = self._draw_geometry(n, L)
+        step = self._smp_step if step is None else int(step)
+        if seed is None:
+            seed = self._smp_seed if self._smp_seed is not None else int(torch.initial_seed())
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        out = np.empty((L, n), dtype=np.int64)
+        for b in range(n):
+            x = philox4x32_10((b, 0, SAMPLE_STREAM, step & _M32), (seed & _M32, seed >> 32))
+            out[:, b] = self._chunk_rows((x[0] * self.lanes) >> 32, ((x[2] | x[3] << 32) * n_valid) >> 64, L)
+        return out.reshape(-1)
+
+    def _chunk_rows(self, lane, u, L):
+        """Rows of the chunk that the uniform draws (lane, u in [0, n_valid)) select."""
+        R = self.lane_size if self.lanes > 1 else self.size
+        start = (self.idx + u) % R if self.full else u
+        return [lane * R + (start + t) % R for t in range(L)]
+
+    def _sample_device(self, n, L, _idx_out=None):
+        n, L = int(n), int(L)
+        self._draw_geometry(n, L)
+        if _idx_out is not None and not (isinstance(_idx_out, torch.Tensor) and _idx_out.is_cuda and _idx_out.dtype == torch.int64
+                                         and _idx_out.is_contiguous() and _idx_out.numel() == L * n):
+            raise ValueError(f"ExperienceReplay.sample: _idx_out must be a contiguous CUDA int64 tensor of {L * n} elements")
+        if self._dev is None or self._dirty:
+            self.sync_device()
+        if self._smp_seed is None:
+            self._smp_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        px = self.pixel_observation
+        if px and self._pix_seed is None:
+            self._pix_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        dev = self._dev
+        O, A = self.observations[0].size, self.actions.shape[1]
+        a = cabi.ReplaySampleArgs()
+        a.obs, a.act = dev["observations"].data_ptr(), dev["actions"].data_ptr()
+        a.reward, a.nonterminal = dev["rewards"].data_ptr(), dev["nonterminals"].data_ptr()
+        a.obs_width, a.A, a.size, a.lanes, a.lane_size = O, A, self.size, self.lanes, self.lane_size
+        a.idx, a.full, a.n, a.L, a.bit_depth = self.idx, int(self.full), n, L, (self.bit_depth if px else 0)
+        a.seed, a.step = self._smp_seed, self._smp_step & _M32
+        a.pix_seed, a.pix_step = (self._pix_seed, self._pix_step) if px else (0, 0)
+        obs = self._out("pixels" if px else "observations", L * n * O)
+        act, rew, non = self._out("actions", L * n * A), self._out("rewards", L * n), self._out("nonterminals", L * n)
+        a.dst_obs, a.dst_act, a.dst_reward, a.dst_nonterminal = obs.data_ptr(), act.data_ptr(), rew.data_ptr(), non.data_ptr()
+        if _idx_out is not None:
+            a.idx_out = _idx_out.data_ptr()
+        cabi.check(cabi.lib.bd_replay_sample_gather(a, cabi.stream()))
+        self._smp_step += 1
+        if px:
+            self._pix_step += 1
+        return [obs.view(L, n, 3, 64, 64) if px else obs.view(L, n, -1), act.view(L, n, -1), rew.view(L, n), non.view(L, n, 1)]
+
+    def sample(self, n, L, _idx_out=None):
         """Time-major batch [obs (L,n,O), actions (L,n,A), rewards (L,n), nonterminals (L,n,1)] on the device
-        (src/memory.py:70-104)."""
+        (src/memory.py:70-104).  With ``device_sampler`` the chunks are drawn on the device too (one launch, nothing from
+        ``np.random``); `_idx_out` (CUDA int64 [L * n]) then receives the rows drawn."""
+        if self.device_sampler:
+            if self.device.type != "cuda":
+                raise RuntimeError("ExperienceReplay.sample: the HIP path needs a GPU device (no CPU fallback)")
+            return self._sample_device(n, L, _idx_out)
+        if _idx_out is not None:
+            raise ValueError("ExperienceReplay.sample: _idx_out belongs to the device sampler (device_sampler=True)")
         idxs = np.asarray([self._sample_idx(L) for _ in range(n)])
         vec = np.ascontiguousarray(idxs.transpose().reshape(-1)).astype(np.int64)
         if self.device.type != "cuda":

@@ -913,6 +913,51 @@ typedef struct {
 } bd_replay_append_args;
 int bd_replay_append(const bd_replay_append_args* a, void* stream);
 
+/* ---- replay sample: ExperienceReplay.sample (src/memory.py:51-104) drawn AND gathered on the device (csrc/replay.hip) ----
+ * ONE launch draws n chunks of L consecutive rows from the device mirror and writes them time-major (output row t * n + b)
+ * into the four destinations: no host RNG, no index upload.
+ *   The ring of a chunk has R = size rows (lanes = 1) or lane_size rows (lanes > 1, lane e = rows [e * R, (e + 1) * R));
+ *   idx is the write head inside the ring.  The reference's rule -- a uniform start, redrawn while the head is among rows
+ *   1 .. L-1 of the chunk -- accepts one cyclic range of starts, so sequence b draws
+ *     x       = philox4x32_10(ctr = (b, 0, 12, step lo 32), key = (seed lo, seed hi))          (stream 12, "replay_sample")
+ *     lane    = (x[0] * lanes) >> 32
+ *     u       = ((x[2] | x[3] << 32) * n_valid) >> 64
+ *     not full: n_valid = idx - L,      start = u                      (needs idx > L)
+ *     full:     n_valid = R - L + 1,    start = (idx + u) mod R        (needs R >= L)
+ *   and takes rows lane * R + (start + t) mod R, t = 0 .. L-1.
+ *   bit_depth = 0: state observations, obs float [size x obs_width], copied;
+ *   bit_depth = 1 .. 8: pixels, obs unsigned char [size x obs_width] (obs_width a multiple of 4, obs 4-byte and dst_obs
+ *     16-byte aligned), dequantised as bd_replay_gather_pixels_rng does with (pix_seed, pix_step): bit for bit what that
+ *     entry point writes from the same rows.
+ * Every destination element is written exactly once; idx_out (may be NULL) receives the rows drawn.  Asynchronous on
+ * `stream`; never allocates, never synchronises.  1 <= n <= 4096, 1 <= L <= R. */
+typedef struct {
+    const void* obs;             /* mirror: float* (bit_depth = 0) or unsigned char* [size x obs_width] */
+    const float* act;            /* [size x A] */
+    const float* reward;         /* [size] */
+    const float* nonterminal;    /* [size] */
+    int obs_width;
+    int A;
+    int size;                    /* rows of the mirror */
+    int lanes;
+    int lane_size;
+    int idx;                     /* write head inside the ring */
+    int full;
+    int n;                       /* sequences */
+    int L;                       /* chunk length */
+    int bit_depth;               /* 0: fp32 copy; 1 .. 8: dequantise bytes */
+    unsigned long long seed;     /* sampler key */
+    unsigned long long step;     /* sampler counter (low 32 bits used) */
+    unsigned long long pix_seed; /* pixels: key and counter of the dequantisation noise (stream 6) */
+    unsigned long long pix_step;
+    float* dst_obs;              /* [L*n x obs_width] */
+    float* dst_act;              /* [L*n x A] */
+    float* dst_reward;           /* [L*n] */
+    float* dst_nonterminal;      /* [L*n] */
+    int64_t* idx_out;            /* [L*n] rows drawn, element t * n + b; NULL: not written */
+} bd_replay_sample_args;
+int bd_replay_sample_gather(const bd_replay_sample_args* a, void* stream);
+
 size_t bd_reduce_ws_floats(void);
 
 #ifdef __cplusplus

@@ -10,6 +10,9 @@ without exploration noise and prints ``Eval_{min,avg,max,std}_return``; ``test=t
 context steps, prints ``openl_mse_context`` / ``openl_mse_open`` and saves the video as ``Openl_<step>.npy`` in ``eval_video_dir``.
 ``collect_envs=n`` (n > 1) collects from n environments side by side (big_dreamer_amd/collect.py): one loop iteration is one
 decision for all of them = n environment steps, with the same update-to-data ratio.
+``sample_on_device=true``: every training batch is drawn and gathered by one launch on the device (the replay's own Philox
+stream, keyed by the torch seed) instead of ``np.random`` index draws and an index upload; the draw's counter is saved with
+the replay (``experience_<step>.npz``), so a resumed run draws the batches the uninterrupted run draws.
 ``checkpoint_dir=<dir>``: at the end of every loop iteration whose step is a multiple of ``checkpoint_interval`` (with
 ``collect_envs=n``: whose n steps hold one) every rank writes ``<dir>/models_<step>.pth`` and, with
 ``checkpoint_experience=true``, ``<dir>/experience_<step>.npz`` (``_rank<r>`` before the extension in multi-GPU runs), <step>
