@@ -17,6 +17,8 @@ import ctypes as C
 import math
 import os
 import weakref
+from functools import partial
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -311,14 +313,9 @@ class DreamerEngine:
         # critic) produces, while behaviour learning k needs the world model k and the posteriors k.  So the two
         # halves run on two HIP streams: the latency-bound observe scan (52 CUs) of step k+1 runs underneath the
         # imagination of step k (154 CUs) instead of leaving 200 CUs idle.  Same kernels, same operands, same order of
-        # every read-after-write: results are bit-identical to the serial schedule (parity-tested both ways).
-        #   s_wm:  [wait BH(k-1) done] encoder, observe fwd/bwd, heads, wgrad  [wait BH(k) done with the world model]
-        #          clip+Adam+pack -> ev_wm_done
-        #   s_bh:  [wait ev_wm_done] imagine fwd, heads, lambda-return -> ev_ret, imagine bwd -> ev_bh_wm_free; actor update
-        #          -> ev_bh_done
-        #   _side: [wait ev_ret] critic fwd/bwd, wgrad, clip+Adam+pack -> ev_cr_done  (under the next step's imagination)
-        # `feat` (posterior features, read by behaviour learning), the imagined features and the lambda-returns (read by
-        # the critic update) are double-buffered by step parity.
+        # every read-after-write: results are bit-identical to the serial schedule (parity-tested both ways).  DESIGN.md
+        # ("Chunked behaviour chain", Stages) has the stream diagram.  `feat` (posterior features, read by behaviour learning), the
+        # imagined features and the lambda-returns (read by the critic update) are double-buffered by step parity.
         self.pipeline = os.environ.get("BD_PIPELINE", "1") != "0"
         self._s_wm = _engine_stream(self.dev, "wm", int(os.environ.get("BD_WM_PRIO", "-1")))   # the scan is latency-bound: dispatch it first
         # state observations: the actor chain bounds the step; pixels: the conv-heavy dynamics chain does, and behaviour
@@ -1549,45 +1546,40 @@ class DreamerEngine:
                                                               "grad_norm_model")}
 
     def _dynamics_phase(self, batch: Dict[str, torch.Tensor], noise: Dict[str, torch.Tensor], feat_tag: str) -> torch.Tensor:
-        """Dynamics learning (src/dreamer.py:263-302) on the current stream; returns the posterior features."""
+        """Dynamics learning (src/dreamer.py:263-302) on the current stream; returns the posterior features.  `w`, this
+        step's record, carries the saves and gradients on to _observe_backward and _dynamics_tail."""
         d, hp = self.d, self.hp
         obs, actions, rewards, nonterm = (batch[k] for k in ("observations", "actions", "rewards", "nonterminals"))
-        L, B = obs.shape[0], obs.shape[1]
-        T = L - 1
-        N = T * B
-        F = d.Be + d.S
-        W = self.world_size
-        st = cabi.stream()
-        sc, ws = ptr(self.scalars), ptr(self.red_ws)
-
-        # ======================= dynamics learning (dreamer.py:263-302) =======================
+        T, B = obs.shape[0] - 1, obs.shape[1]
+        N, F, W = T * B, d.Be + d.S, self.world_size
+        st, sc, ws = cabi.stream(), ptr(self.scalars), ptr(self.red_ws)
+        w = SimpleNamespace(T=T, B=B, N=N, F=F, actions=actions[:-1], nonterm=nonterm[:-1], eps_post=noise["obs_post"],
+                            om_acts=None, om_dpre=None, dc_acts=None, dc_dpre=None)
         obs_t = obs[1:].reshape(N, d.O)                     # targets and encoder input
         with self.span("encoder_fwd"):
-            emb, pre_emb = self.encode_pixels(obs[1:].reshape(N, 3, 64, 64)) if self.pixel else self.encode(obs_t, N)
-        init_belief = self.buf("init_belief", B, d.Be).zero_()
+            w.emb, pre_emb = self.encode_pixels(obs[1:].reshape(N, 3, 64, 64)) if self.pixel else self.encode(obs_t, N)
+        w.init_belief = self.buf("init_belief", B, d.Be).zero_()
         init_state = self.buf("init_state", B, d.S).zero_()
-        feat, qm, qs = self.observe(actions[:-1], nonterm[:-1], pre_emb, noise["obs_post"], init_belief, init_state, T, B,
-                                    feat_tag=feat_tag)
+        w.feat, qm, qs = self.observe(w.actions, w.nonterm, pre_emb, w.eps_post, w.init_belief, init_state, T, B,
+                                      feat_tag=feat_tag)
+        feat = w.feat
         cat = d.categorical
         sidx = self._buf[feat_tag + "sidx"] if cat else None      # the posterior's class indices (observe left them there)
         with self.span("wm_heads_fwd"):
             _, pm, ps = self.prior_head(feat, N, None if cat else noise.get("obs_prior"))
             if self.pixel:
-                om_out, om_acts, om_layers = self.conv.decode(feat).view(N, d.O), None, None
+                om_out = self.conv.decode(feat).view(N, d.O)
                 obs_t = self.conv.acts_enc[0].view(N, d.O)      # the same images in the NHWC order of the prediction
             else:
-                om_out, om_acts, om_layers = self.dense_forward("observation_model", "obs", "om", feat, F, N, d.O,
-                                                                sidx=sidx)
-            rw_out, rw_acts, rw_layers = self.dense_forward("reward_model", "rew", "rw", feat, F, N, 1, sidx=sidx)
-
+                om_out, w.om_acts, om_layers = self.dense_forward("observation_model", "obs", "om", feat, F, N, d.O, sidx=sidx)
+            rw_out, w.rw_acts, rw_layers = self.dense_forward("reward_model", "rew", "rw", feat, F, N, 1, sidx=sidx)
+        w.obs_t = obs_t
         inv_rows = self.dp.mean_grad_scale(N)
-        dc_state = None
         if d.use_discount:      # _discount_loss (src/dreamer.py:239-251): Bernoulli(logits).log_prob(nonterminal), weight 5
-            dc_out, dc_acts, dc_layers = self.dense_forward("discount_model", "dsc", "dc", feat, F, N, 1, sidx=sidx)
+            dc_out, w.dc_acts, dc_layers = self.dense_forward("discount_model", "dsc", "dc", feat, F, N, 1, sidx=sidx)
             d_dc = self.buf("d_dc_out", N, 1)
-            cabi.check(lib.bd_bernoulli_nll(ptr(dc_out), ptr(nonterm[:-1]), N, hp["discount_weight"] * inv_rows, ptr(d_dc), sc,
+            cabi.check(lib.bd_bernoulli_nll(ptr(dc_out), ptr(w.nonterm), N, hp["discount_weight"] * inv_rows, ptr(d_dc), sc,
                                             SLOT_DISC, ws, st))
-            dc_state = (d_dc, dc_acts, dc_layers)
         d_om, d_rw = self.buf("d_om_out", N, d.O), self.buf("d_rw_out", N, 1)
         cabi.check(lib.bd_normal_nll(ptr(om_out), d.O, ptr(obs_t), d.O, N, d.O, inv_rows, ptr(d_om), d.O, sc, SLOT_OBS, ws, st))
         cabi.check(lib.bd_normal_nll(ptr(rw_out), 1, ptr(rewards[:-1]), 1, N, 1, inv_rows, ptr(d_rw), 1, sc, SLOT_REW, ws, st))
@@ -1616,9 +1608,9 @@ class DreamerEngine:
 
         # ---- backward of the world model ----
         dfeat = self.buf("dfeat", N, F)
-        rw_dpre = [self.buf(f"rw_dpre{l}", N, d.Hd) for l in range(DENSE_LAYERS)] + [d_rw]
+        w.rw_dpre = [self.buf(f"rw_dpre{l}", N, d.Hd) for l in range(DENSE_LAYERS)] + [d_rw]
         if self.pixel:
-            self.mlp_backward(N, d_rw, 1, rw_layers, rw_acts + [None], rw_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F)
+            self.mlp_backward(N, d_rw, 1, rw_layers, w.rw_acts + [None], w.rw_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F)
             with self.span("decoder_bwd"):
                 # the decoder's weight-gradient GEMMs (60 % of the pass) are ready here: they run on their own stream
                 # underneath the observe-scan backward (52 CUs) instead of after it
@@ -1627,41 +1619,35 @@ class DreamerEngine:
                 with torch.cuda.stream(self._s_early):
                     self._wbatch["model_early"].run()
         else:
-            om_dpre = [self.buf(f"om_dpre{l}", N, d.Hd) for l in range(DENSE_LAYERS)] + [d_om]
-            self.mlp_backward(N, d_om, d.O, om_layers, om_acts + [None], om_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F)
-            self.mlp_backward(N, d_rw, 1, rw_layers, rw_acts + [None], rw_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F,
+            w.om_dpre = [self.buf(f"om_dpre{l}", N, d.Hd) for l in range(DENSE_LAYERS)] + [d_om]
+            self.mlp_backward(N, d_om, d.O, om_layers, w.om_acts + [None], w.om_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F)
+            self.mlp_backward(N, d_rw, 1, rw_layers, w.rw_acts + [None], w.rw_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F,
                               accumulate=True)
-        dc_dpre = None
-        if dc_state is not None:
-            d_dc, dc_acts, dc_layers = dc_state
-            dc_dpre = [self.buf(f"dc_dpre{l}", N, d.Hd) for l in range(DENSE_LAYERS)] + [d_dc]
-            self.mlp_backward(N, d_dc, 1, dc_layers, dc_acts + [None], dc_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F,
+        if d.use_discount:
+            w.dc_dpre = [self.buf(f"dc_dpre{l}", N, d.Hd) for l in range(DENSE_LAYERS)] + [d_dc]
+            self.mlp_backward(N, d_dc, 1, dc_layers, w.dc_acts + [None], w.dc_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F,
                               accumulate=True)
-        self._dc_wgrad = (dc_dpre, dc_state[1]) if dc_state is not None else None
         # prior head: KL gradient on (mean, std) -> belief part of dfeat
-        p_out, p_hid = self._buf["p_out"], self._buf["p_hid"]
+        p_out, w.p_hid = self._buf["p_out"], self._buf["p_hid"]
         HO = d.head_out
-        d_p_hid = self.buf("d_p_hid", N, d.Hd)
+        w.d_p_hid = self.buf("d_p_hid", N, d.Hd)
         if cat:
-            d_p_out = dpm                                   # the KL gradient w.r.t. the prior logits IS d(head output)
+            w.d_p_out = dpm                                 # the KL gradient w.r.t. the prior logits IS d(head output)
         else:
-            d_p_out = self.buf("d_p_out", N, HO)
-            cabi.check(lib.bd_gauss_head_backward(ptr(p_out), None, None, ptr(dpm), ptr(dps), N, d.S, ptr(d_p_out), st))
+            w.d_p_out = self.buf("d_p_out", N, HO)
+            cabi.check(lib.bd_gauss_head_backward(ptr(p_out), None, None, ptr(dpm), ptr(dps), N, d.S, ptr(w.d_p_out), st))
         p_layers = [("p1", None, d.Hd, d.Be, cabi.ACT_ELU), ("p2", None, HO, d.Hd, cabi.ACT_NONE)]
-        self.mlp_backward(N, d_p_out, HO, p_layers, [p_hid, None], [d_p_hid, None], din0=dfeat, ld0=F, w0=d.Be,
+        self.mlp_backward(N, w.d_p_out, HO, p_layers, [w.p_hid, None], [w.d_p_hid, None], din0=dfeat, ld0=F, w0=d.Be,
                           accumulate=True)
-        d_e, d_gi, d_gh, d_q1, d_q2 = self._observe_backward(T, B, nonterm[:-1], noise["obs_post"], feat)
-        self._dynamics_tail(batch, emb, obs_t, feat, init_belief, actions, d_e, d_gi, d_gh, d_q1, d_q2, d_p_hid, d_p_out,
-                            p_hid, rw_dpre, rw_acts, om_dpre if (not self.pixel) else None,
-                            om_acts if (not self.pixel) else None, N, B, F)
+        self._observe_backward(w)
+        self._dynamics_tail(w)
         return feat
 
-    def _observe_backward(self, T: int, B: int, nonterm, eps_post, feat):
+    def _observe_backward(self, w) -> None:
         """Backward of the observe scan, both latent families: from dfeat and the KL gradient w.r.t. the posterior (buffers
-        the dynamics phase has just filled) to the pre-activation gradients of the recurrence, which it returns:
-        d_embed_pre, d_gi, d_gh, d_q1_pre, d_q2_out."""
-        d, pk, buf = self.d, self.pk, self._buf
-        N = T * B
+        the dynamics phase has just filled) to the pre-activation gradients of the recurrence, which it leaves in the
+        step's record: d_e (embed), d_gi, d_gh, d_q1 (posterior hidden), d_q2 (posterior head output)."""
+        d, pk, buf, T, B, N = self.d, self.pk, self._buf, w.T, w.B, w.N
         if d.categorical:
             b = cabi.ObserveCatBwdArgs()
             b.D, b.C = d.cat_D, d.cat_C
@@ -1672,26 +1658,23 @@ class DreamerEngine:
             b = cabi.ObserveBwdArgs()
             b.S = d.S
             b.wt_q2m, b.wt_q2s = ptr(pk["q2m.T"]), ptr(pk["q2s.T"])
-            b.eps_post, b.post_std, b.min_std = ptr(eps_post), ptr(buf["post_std"]), self.hp["min_std_dev"]
+            b.eps_post, b.post_std, b.min_std = ptr(w.eps_post), ptr(buf["post_std"]), self.hp["min_std_dev"]
             b.dpost_mean, b.dpost_std = ptr(buf["dqm"]), ptr(buf["dqs"])
             scan, scan_cluster = lib.bd_observe_backward, lib.bd_observe_backward_cluster
         b.T, b.B, b.Be, b.A, b.Hd = T, B, d.Be, d.A, d.Hd
         self._bind_rssm_t(b)
         b.wt_q1h = ptr(pk["q1h.T"])
-        b.init_belief, b.nonterm, b.feat, b.dfeat = ptr(buf["init_belief"]), ptr(nonterm), ptr(feat), ptr(buf["dfeat"])
+        b.init_belief, b.nonterm, b.feat, b.dfeat = ptr(buf["init_belief"]), ptr(w.nonterm), ptr(w.feat), ptr(buf["dfeat"])
         b.sv_x, b.sv_gates, b.sv_q = ptr(buf["sv_x"]), ptr(buf["sv_gates"]), ptr(buf["sv_q"])
-        d_e, d_gi, d_gh = self.buf("d_embed_pre", N, d.Be), self.buf("d_gi", N, 3 * d.Be), self.buf("d_gh", N, 3 * d.Be)
-        d_q1, d_q2 = self.buf("d_q1_pre", N, d.Hd), self.buf("d_q2_out", N, d.head_out)
-        b.d_embed_pre, b.d_gi, b.d_gh, b.d_q1_pre, b.d_q2_out = ptr(d_e), ptr(d_gi), ptr(d_gh), ptr(d_q1), ptr(d_q2)
+        w.d_e, w.d_gi, w.d_gh = self.buf("d_embed_pre", N, d.Be), self.buf("d_gi", N, 3 * d.Be), self.buf("d_gh", N, 3 * d.Be)
+        w.d_q1, w.d_q2 = self.buf("d_q1_pre", N, d.Hd), self.buf("d_q2_out", N, d.head_out)
+        b.d_embed_pre, b.d_gi, b.d_gh, b.d_q1_pre, b.d_q2_out = ptr(w.d_e), ptr(w.d_gi), ptr(w.d_gh), ptr(w.d_q1), ptr(w.d_q2)
         with self.span("observe_bwd"):
             self._run_observe_scan(b, B, scan, scan_cluster)
-        return d_e, d_gi, d_gh, d_q1, d_q2
 
-    def _dynamics_tail(self, batch, emb, obs_t, feat, init_belief, actions, d_e, d_gi, d_gh, d_q1, d_q2, d_p_hid, d_p_out,
-                       p_hid, rw_dpre, rw_acts, om_dpre, om_acts, N, B, F) -> None:
+    def _dynamics_tail(self, w) -> None:
         """Encoder backward, the grouped weight-gradient launch of the world model, its optimiser step."""
-        d, hp = self.d, self.hp
-        HO = d.head_out
+        d, hp, N, F, HO, feat, d_q1 = self.d, self.hp, w.N, w.F, self.d.head_out, w.feat, w.d_q1
         # encoder (+ hoisted projection as its last layer)
         if self.pixel:
             d_emb = self.buf("d_emb", N, d.E)
@@ -1706,30 +1689,30 @@ class DreamerEngine:
             self.mlp_backward(N, d_q1, d.Hd, enc_layers, enc_acts + [None, None], enc_dpre + [None])
 
         # ---- weight gradients (into the flat model gradient buffer): one grouped launch ----
-        Gt = lambda n: self.G("transition_model", n)
-        wb = self._wbatch["model"]
-        wb.add(d_gi, 3 * d.Be, self._buf["sv_x"], d.Be, N, 3 * d.Be, d.Be, Gt("rnn.weight_ih"), d.Be, Gt("rnn.bias_ih"))
+        wb, Gt = self._wbatch["model"], lambda n: self.G("transition_model", n)
+        wb.add(w.d_gi, 3 * d.Be, self._buf["sv_x"], d.Be, N, 3 * d.Be, d.Be, Gt("rnn.weight_ih"), d.Be, Gt("rnn.bias_ih"))
         # previous belief: the initial belief for step 0 (rows < B), the belief part of feat[t-1] afterwards
-        wb.add(d_gh, 3 * d.Be, init_belief, d.Be, N, 3 * d.Be, d.Be, Gt("rnn.weight_hh"), d.Be, Gt("rnn.bias_hh"),
-               act2=feat, lda2=F, M1=B)
+        wb.add(w.d_gh, 3 * d.Be, w.init_belief, d.Be, N, 3 * d.Be, d.Be, Gt("rnn.weight_hh"), d.Be, Gt("rnn.bias_hh"),
+               act2=feat, lda2=F, M1=w.B)
         gWe = Gt("fc_embed_state_action.0.weight")
-        wb.add(d_e, d.Be, self._buf["sv_s"], d.S, N, d.Be, d.S, gWe, d.S + d.A, Gt("fc_embed_state_action.0.bias"))
-        wb.add(d_e, d.Be, actions[:-1], d.A, N, d.Be, d.A, gWe[:, d.S:], d.S + d.A)
-        wb.add(d_p_hid, d.Hd, feat, F, N, d.Hd, d.Be, Gt("belief_prior.model.0.weight"), d.Be, Gt("belief_prior.model.0.bias"))
-        wb.add(d_p_out, HO, p_hid, d.Hd, N, HO, d.Hd, Gt("belief_prior.model.2.weight"), d.Hd,
+        wb.add(w.d_e, d.Be, self._buf["sv_s"], d.S, N, d.Be, d.S, gWe, d.S + d.A, Gt("fc_embed_state_action.0.bias"))
+        wb.add(w.d_e, d.Be, w.actions, d.A, N, d.Be, d.A, gWe[:, d.S:], d.S + d.A)
+        wb.add(w.d_p_hid, d.Hd, feat, F, N, d.Hd, d.Be, Gt("belief_prior.model.0.weight"), d.Be,
+               Gt("belief_prior.model.0.bias"))
+        wb.add(w.d_p_out, HO, w.p_hid, d.Hd, N, HO, d.Hd, Gt("belief_prior.model.2.weight"), d.Hd,
                Gt("belief_prior.model.2.bias"))
         gWq1 = Gt("belief_posterior.model.0.weight")
         wb.add(d_q1, d.Hd, feat, F, N, d.Hd, d.Be, gWq1, d.Be + d.E, Gt("belief_posterior.model.0.bias"))
-        wb.add(d_q1, d.Hd, emb, d.E, N, d.Hd, d.E, gWq1[:, d.Be:], d.Be + d.E)
-        wb.add(d_q2, HO, self._buf["sv_q"], d.Hd, N, HO, d.Hd, Gt("belief_posterior.model.2.weight"), d.Hd,
+        wb.add(d_q1, d.Hd, w.emb, d.E, N, d.Hd, d.E, gWq1[:, d.Be:], d.Be + d.E)
+        wb.add(w.d_q2, HO, self._buf["sv_q"], d.Hd, N, HO, d.Hd, Gt("belief_posterior.model.2.weight"), d.Hd,
                Gt("belief_posterior.model.2.bias"))
         dense_sizes = lambda i, o: [i] + [d.Hd] * DENSE_LAYERS + [o]
-        self._dense_wgrads(wb, "reward_model", N, rw_dpre, feat, F, rw_acts, dense_sizes(F, 1))
-        if self._dc_wgrad is not None:
-            self._dense_wgrads(wb, "discount_model", N, self._dc_wgrad[0], feat, F, self._dc_wgrad[1], dense_sizes(F, 1))
+        self._dense_wgrads(wb, "reward_model", N, w.rw_dpre, feat, F, w.rw_acts, dense_sizes(F, 1))
+        if w.dc_dpre is not None:
+            self._dense_wgrads(wb, "discount_model", N, w.dc_dpre, feat, F, w.dc_acts, dense_sizes(F, 1))
         if not self.pixel:      # (pixel mode: the conv stacks queued their weight gradients themselves)
-            self._dense_wgrads(wb, "observation_model", N, om_dpre, feat, F, om_acts, dense_sizes(F, d.O))
-            self._dense_wgrads(wb, "encoder", N, enc_dpre, obs_t, d.O, enc_acts, dense_sizes(d.O, d.E))
+            self._dense_wgrads(wb, "observation_model", N, w.om_dpre, feat, F, w.om_acts, dense_sizes(F, d.O))
+            self._dense_wgrads(wb, "encoder", N, enc_dpre, w.obs_t, d.O, enc_acts, dense_sizes(d.O, d.E))
         with self.span("wgrad_model"):
             wb.run()
         if self.pixel:
@@ -1760,247 +1743,263 @@ class DreamerEngine:
     def _behaviour_phase(self, feat: torch.Tensor, noise: Dict[str, torch.Tensor], T: int, B: int,
                          red_ws: torch.Tensor, par: Optional[int]) -> None:
         """Behaviour learning (src/dreamer.py:308-391) on the current stream: imagination with the post-update world
-        model (packed by the model optimiser step) from the detached posteriors, actor update, critic update."""
-        d, hp, pk = self.d, self.hp, self.pk
-        Hm = d.Hm
-        N = T * B
-        Mi = Hm * N
-        F = d.Be + d.S
-        st = cabi.stream()
-        sc, ws = ptr(self.scalars), ptr(red_ws)
-        sum_form = int(hp["kl_balance"] == -1)
-        # Pipelined (par = step parity): the critic update of this step runs on a third stream underneath the NEXT
-        # step's imagination (it only needs the imagined features and the lambda-returns, and nothing on the actor's
-        # chain reads the critic -- the value head there is the critic TARGET), so both are double-buffered by parity.
-        ptag = "" if par is None else f"p{par}_"
+        model (packed by the model optimiser step) from the detached posteriors, actor update, critic update.  The stages
+        are queued in the order of the calls below ("Chunked behaviour chain", Stages)."""
+        d = self.d
+        # Pipelined (par = step parity): the critic update of this step runs underneath the NEXT step's imagination (nothing
+        # on the actor's chain reads the critic: the value head there is the critic TARGET), its inputs double-buffered.
         if par is not None and self._ev_cr_done[par] is not None:
             torch.cuda.current_stream().wait_event(self._ev_cr_done[par])     # critic of two steps ago: last reader
+        s = self._behaviour_record(feat, noise, T * B, red_ws, par)
+        self._imagine_and_heads(s)
+        self._returns_and_sums(s)
+        # the overlapped actor chains share the critic's stream: they go first (the critic has a step of slack)
+        critic_last = s.windows and self._s_ov is self._side
+        if par is not None and not critic_last:
+            self._critic_handoff(s)
+        if s.dyn:
+            if not s.fused:
+                self._imagined_heads_backward(s)
+            self._imagine_backward(s)
+            if s.windows:
+                self._world_model_free()            # the scan is the last reader of the world model: the chains are not
+        if s.mix is not None:
+            self._actor_reinforce(s)
+        if s.windows:
+            self._actor_rows(s, 0, s.tb[1])         # the first window's chain: nothing left to hide it under
+            s.cur.wait_event(s.ev_ov)               # every row of d_actor_pre, for the one weight-gradient launch
+            if par is not None and critic_last:
+                self._critic_handoff(s)
+        else:
+            if s.actor_chain:
+                self._actor_rows(s, 0, s.Hm)
+            self._world_model_free()                # last reader of the world model in this step
+        self._actor_update(s)
+        if par is None:
+            self._critic_phase(s, red_ws)
+        self._counts = dict(N=s.N, Mi=s.Mi, S=(d.cat_D if d.categorical else d.S), sum_form=int(self.hp["kl_balance"] == -1))
+
+    def _behaviour_record(self, feat, noise, N: int, red_ws: torch.Tensor, par: Optional[int]) -> SimpleNamespace:
+        """What the stages of one behaviour phase share: sizes, the chunk plan, the switches of the objective and the phase's
+        buffers, each named here once.  The stages add ifeat, ent, act, isidx, wts and dret (use_discount), the separate
+        heads' r_out, v_out and saves, ev_ret, and ev_ov: the end of the latest overlapped launch (one stream: it covers all)."""
+        d, hp = self.d, self.hp
+        Hm, F, ptag = d.Hm, d.Be + d.S, "" if par is None else f"p{par}_"
+        Mi = Hm * N
         # gradient_mixing rho (DESIGN.md, "Mixed actor gradient"): None = -1 / 1, today's dynamics-backprop objective and
         # launches; in (0, 1) both terms; 0 = REINFORCE alone: no lambda-return / head / imagination backward at all
         mix = self._mix
         dyn = mix is None or mix > 0
-        start_sidx = self._buf[ptag + "sidx"] if d.categorical else None
-        act_us = self.buf("act_us", Mi, 2 * d.A) if mix is not None and not d.discrete_actions else None
+        inv_mi = self.dp.mean_grad_scale(Mi)
         # the chunk plan of this step (one chunk: today's single launches) and its time bounds
         plan = self._bh_plan_used = self.behaviour_plan(Hm, N)
-        chunked = len(plan) > 1
-        tb = [sum(plan[:i]) for i in range(len(plan) + 1)]
-        cur, ov = torch.cuda.current_stream(), self._s_ov
-        ev_ov: List[torch.cuda.Event] = []         # ends of the overlapped launches (one stream: the last covers all)
-        if chunked:
-            # d returns needs neither rewards nor values, so the heads' output gradients exist before the scan starts and
-            # the fused heads of a finished chunk run on the overlap stream underneath the next chunk of the scan
-            inv_mi = self.dp.mean_grad_scale(Mi)
-            d_r, d_v, difeat = self.buf("d_ir_out", Mi), self.buf("d_iv_out", Mi), self.buf("difeat", Mi, F)
-            r_out, v_out = self.buf("ir_out", Mi, 1), self.buf("iv_out", Mi, 1)
-            cabi.check(lib.bd_lambda_return_backward(None, -inv_mi, Hm, N, hp["discount"], hp["disclam"], ptr(d_r), ptr(d_v), st))
+        # the actor's hidden layers leave the backward scan (their result feeds nothing on the recurrence: detached input)
+        # and run as one dense chain over all Hm x N rows from d_actor_out -- always with mixing, where bd_actor_reinforce
+        # adds to d_actor_out after the scan, and with the Categorical actor, whose scans only write d_actor_out
+        actor_chain = os.environ.get("BD_ACTOR_BWD_CHAIN", "1") == "1" or mix is not None or d.discrete_actions
+        s = SimpleNamespace(
+            N=N, Hm=Hm, Mi=Mi, F=F, par=par, ptag=ptag, feat=feat, noise=noise, red_ws=red_ws, mix=mix, dyn=dyn, inv_mi=inv_mi,
+            fused=dyn and self.heads_fused, plan=plan, tb=[sum(plan[:i]) for i in range(len(plan) + 1)], chunked=len(plan) > 1,
+            actor_chain=actor_chain, windows=len(plan) > 1 and self.bh_chunks_bwd and actor_chain,    # backward scan split too
+            dconst=-inv_mi if mix is None else -mix * inv_mi,
+            dentropy=-hp["entropy_weight"] * inv_mi if hp["entropy_weight"] != -1 else 0.0,
+            cur=torch.cuda.current_stream(), st=cabi.stream(), sc=ptr(self.scalars), ws=ptr(red_ws),
+            start_sidx=self._buf[ptag + "sidx"] if d.categorical else None, wts=None, dret=None, ev_ov=None, ev_ret=None)
+        s.act_us = self.buf("act_us", Mi, 2 * d.A) if mix is not None and not d.discrete_actions else None
+        if dyn:
+            s.d_r, s.d_v, s.difeat = self.buf("d_ir_out", Mi), self.buf("d_iv_out", Mi), self.buf("difeat", Mi, F)
+        if s.fused:
+            s.r_out, s.v_out = self.buf("ir_out", Mi, 1), self.buf("iv_out", Mi, 1)
+        s.returns = self.buf(ptag + "returns", Mi)
+        s.d_apre, s.d_aout = self.buf("d_actor_pre", DENSE_LAYERS, Mi, d.Hd), self.buf("d_actor_out", Mi, d.actor_out)
+        return s
 
-            def heads_rows(t0, t1, x, more):
-                r = slice(t0 * N, t1 * N)
-                with self.span("img_heads_bwd", more=more):
-                    self.img_heads_fused((t1 - t0) * N, x[r], d_r[r], d_v[r], r_out[r], v_out[r], difeat[r])
+    def _on_overlap_stream(self, s, work, *args) -> None:
+        """work(*args) on the overlap stream behind what the behaviour stream has queued so far; s.ev_ov = its end."""
+        ov, ev = self._s_ov, torch.cuda.Event()
+        ev.record(s.cur)
+        with torch.cuda.stream(ov):
+            ov.wait_event(ev)
+            work(*args)
+            s.ev_ov = torch.cuda.Event()
+            s.ev_ov.record(ov)
 
-            def heads_chunk(t0, t1, x):
-                ev = torch.cuda.Event()
-                ev.record(cur)
-                with torch.cuda.stream(ov):
-                    ov.wait_event(ev)
-                    heads_rows(t0, t1, x, t0 > 0)
-                    ev_ov.append(torch.cuda.Event())
-                    ev_ov[-1].record(ov)
-        ifeat, ent, act = self.imagine(feat, N, Hm, noise, feat_tag=ptag, start_sidx=start_sidx, rec_saves=dyn,
-                                       act_us=act_us, chunks=plan if chunked else None,
-                                       after_chunk=heads_chunk if chunked else None)
-        isidx = self._buf[ptag + "isidx"] if d.categorical else None
-        inv_mi = self.dp.mean_grad_scale(Mi)
-        wts = dret = None
+    def _returns_backward(self, s) -> None:
+        """d returns -> d_r, d_v.  It reads only dret / dconst, neither rewards nor values, so the heads' output gradients
+        can exist before the heads run -- chunked, before the scan starts."""
+        cabi.check(lib.bd_lambda_return_backward(ptr(s.dret), s.dconst, s.Hm, s.N, self.hp["discount"], self.hp["disclam"],
+                                                 ptr(s.d_r), ptr(s.d_v), s.st))
+
+    def _heads_rows(self, s, t0: int, t1: int, x) -> None:
+        """The fused heads over the rows of steps [t0, t1) of the imagined features x (imagine()'s after_chunk)."""
+        r = slice(t0 * s.N, t1 * s.N)
+        with self.span("img_heads_bwd", more=t0 > 0):
+            self.img_heads_fused((t1 - t0) * s.N, x[r], s.d_r[r], s.d_v[r], s.r_out[r], s.v_out[r], s.difeat[r])
+
+    def _imagine_and_heads(self, s) -> None:
+        """The imagination scan, then rewards and target values of all rows (r_out, v_out) and, with the fused heads, their
+        input gradients (difeat).  Chunked: d returns first, one scan launch per chunk with the heads of every chunk but
+        the last on the overlap stream underneath the next chunk.  Separate heads: their backward follows later."""
+        d, hp, Hm, N, Mi, F = self.d, self.hp, s.Hm, s.N, s.Mi, s.F
+        if s.chunked:
+            self._returns_backward(s)
+        s.ifeat, s.ent, s.act = self.imagine(
+            s.feat, N, Hm, s.noise, feat_tag=s.ptag, start_sidx=s.start_sidx, rec_saves=s.dyn, act_us=s.act_us,
+            chunks=s.plan if s.chunked else None,
+            after_chunk=partial(self._on_overlap_stream, s, self._heads_rows, s) if s.chunked else None)
+        s.isidx = self._buf[s.ptag + "isidx"] if d.categorical else None
         if d.use_discount:
             # Cumulative discount weights of the actor objective and the value loss (src/dreamer.py:323-326,346-351,
             # 374-379): discount * round(sigmoid(discount head)), trajectory 0 forced to 1 at every step (the reference's
             # `discount_arr[:, 0, 0] = 1.0`), cumprod over time.  No gradient flows through them (round; frozen head):
             # a handful of elementwise torch ops on (Hm, N) -- this switch is off by default (conf/config.yaml:76).
-            dl, _, _ = self.dense_forward("discount_model", "dsc", "idc", ifeat, F, Mi, 1, sidx=isidx)
+            dl, _, _ = self.dense_forward("discount_model", "dsc", "idc", s.ifeat, F, Mi, 1, sidx=s.isidx)
             arr = hp["discount"] * torch.round(torch.sigmoid(dl.view(Hm, N)))
             arr[:, 0] = 1.0
-            wts = self.buf(ptag + "disc_w", Mi)
-            wts.view(Hm, N).copy_(torch.cumprod(arr, 0))
-            if mix is None:
-                dret = self.buf("dret_w", Mi)
-                torch.mul(wts, -inv_mi, out=dret)
-            elif dyn:
-                dret = self.buf("dret_w", Mi)
-                torch.mul(wts, -mix * inv_mi, out=dret)
-        # d returns does not depend on the rewards or values (bd_lambda_return_backward reads only dret / dconst), so
-        # with the fused heads their output gradients are known before the heads run
-        fused = dyn and self.heads_fused
-        if dyn:
-            d_r, d_v = self.buf("d_ir_out", Mi), self.buf("d_iv_out", Mi)
-            dconst = -inv_mi if mix is None else -mix * inv_mi
-            difeat = self.buf("difeat", Mi, F)
-        if chunked:
-            heads_rows(tb[-2], Hm, ifeat, True)         # the last chunk's heads: nothing left to hide them under
-            cur.wait_event(ev_ov[-1])                   # every row of r_out / v_out / difeat
-        elif fused:
-            cabi.check(lib.bd_lambda_return_backward(ptr(dret), dconst, Hm, N, hp["discount"], hp["disclam"], ptr(d_r),
-                                                     ptr(d_v), st))
-            r_out, v_out = self.buf("ir_out", Mi, 1), self.buf("iv_out", Mi, 1)
-            with self.span("img_heads_bwd"):
-                self.img_heads_fused(Mi, ifeat, d_r, d_v, r_out, v_out, difeat)
+            s.wts = self.buf(s.ptag + "disc_w", Mi)
+            s.wts.view(Hm, N).copy_(torch.cumprod(arr, 0))
+            if s.dyn:
+                s.dret = self.buf("dret_w", Mi)
+                torch.mul(s.wts, s.dconst, out=s.dret)
+        if s.chunked:
+            self._heads_rows(s, s.tb[-2], Hm, s.ifeat)      # the last chunk's heads: nothing left to hide them under
+            s.cur.wait_event(s.ev_ov)                       # every row of r_out / v_out / difeat
+        elif s.fused:
+            self._returns_backward(s)
+            self._heads_rows(s, 0, Hm, s.ifeat)
         else:
             with self.span("img_heads_fwd"):
-                r_out, r_acts, r_layers = self.dense_forward("reward_model", "rew", "ir", ifeat, F, Mi, 1, sidx=isidx)
-                v_out, v_acts, v_layers = self.dense_forward("critic_target", "tgt", "iv", ifeat, F, Mi, 1, sidx=isidx)
-        returns = self.buf(ptag + "returns", Mi)
-        cabi.check(lib.bd_lambda_return_forward(ptr(r_out), ptr(v_out), Hm, N, hp["discount"], hp["disclam"], ptr(returns), st))
+                s.r_out, s.r_acts, s.r_layers = self.dense_forward("reward_model", "rew", "ir", s.ifeat, F, Mi, 1, sidx=s.isidx)
+                s.v_out, s.v_acts, s.v_layers = self.dense_forward("critic_target", "tgt", "iv", s.ifeat, F, Mi, 1, sidx=s.isidx)
+
+    def _imagined_heads_backward(self, s) -> None:
+        """The separate heads: d returns, then the two dgrad chains into difeat."""
+        self._returns_backward(s)
+        with self.span("img_heads_bwd"):
+            self.mlp_backward(s.Mi, s.d_r, 1, s.r_layers, s.r_acts + [None], None, din0=s.difeat, ld0=s.F, w0=s.F)
+            self.mlp_backward(s.Mi, s.d_v, 1, s.v_layers, s.v_acts + [None], None, din0=s.difeat, ld0=s.F, w0=s.F, accumulate=True)
+
+    def _returns_and_sums(self, s) -> None:
+        """Lambda-returns and the logged sums; pipelined, ev_ret marks them for the critic's stream."""
+        hp, Mi, st, sc, ws, returns, ent, wts, mix = self.hp, s.Mi, s.st, s.sc, s.ws, s.returns, s.ent, s.wts, s.mix
+        cabi.check(lib.bd_lambda_return_forward(ptr(s.r_out), ptr(s.v_out), s.Hm, s.N, hp["discount"], hp["disclam"],
+                                                ptr(returns), st))
         cabi.check(lib.bd_sum(ptr(returns), Mi, sc, SLOT_RET, ws, st))
         cabi.check(lib.bd_sum(ptr(ent), Mi, sc, SLOT_ENT, ws, st))
-        if d.use_discount:
+        if wts is not None:
             ew_ = hp["entropy_weight"] if hp["entropy_weight"] != -1 else 0.0
             if mix is None:
                 self.scalars[SLOT_WOBJ] = (wts * (returns + ew_ * ent)).sum()
             else:       # the REINFORCE part of the objective joins in _logs_from (SLOT_RF)
                 self.scalars[SLOT_WOBJ] = (wts * (mix * returns + ew_ * ent)).sum()
-        actor_chain = os.environ.get("BD_ACTOR_BWD_CHAIN", "1") == "1" or mix is not None or d.discrete_actions
-        chunked_bwd = chunked and self.bh_chunks_bwd and actor_chain
-        if par is not None:
-            ev_ret = torch.cuda.Event()
-            ev_ret.record(torch.cuda.current_stream())
+        if s.par is not None:
+            s.ev_ret = torch.cuda.Event()
+            s.ev_ret.record(torch.cuda.current_stream())
 
-            def critic_phase():
-                with torch.cuda.stream(self._side):
-                    self._side.wait_event(ev_ret)
-                    self._critic_phase(ifeat, returns, Mi, F, inv_mi, self.red_ws_side, isidx, wts)
-                    self._ev_cr_done[par] = torch.cuda.Event()
-                    self._ev_cr_done[par].record(self._side)
-            # the overlapped actor chains share the critic's stream: they go first (the critic has a step of slack)
-            critic_last = chunked_bwd and ov is self._side
-            if not critic_last:
-                critic_phase()
-        dentropy = -hp["entropy_weight"] * inv_mi if hp["entropy_weight"] != -1 else 0.0
-        d_apre, d_aout = self.buf("d_actor_pre", DENSE_LAYERS, Mi, d.Hd), self.buf("d_actor_out", Mi, d.actor_out)
-        sv_actor = self._buf["sv_actor"]
-        a_layers = [("a0h", None, d.Hd, F, cabi.ACT_ELU)] + [(f"a{l}", None, d.Hd, d.Hd, cabi.ACT_ELU)
-                                                              for l in range(1, DENSE_LAYERS)] + \
-                   [("a4", None, d.actor_out, d.Hd, cabi.ACT_NONE)]
+    def _critic_handoff(self, s) -> None:
+        """Pipelined: the critic update on its own stream, behind the returns; its end is kept per step parity."""
+        with torch.cuda.stream(self._side):
+            self._side.wait_event(s.ev_ret)
+            self._critic_phase(s, self.red_ws_side)
+            self._ev_cr_done[s.par] = torch.cuda.Event()
+            self._ev_cr_done[s.par].record(self._side)
 
-        def actor_rows(t0, t1, more):
-            """The actor's hidden dgrad chain over the rows of steps [t0, t1), in the form of the chain over all rows."""
-            r = slice(t0 * N, t1 * N)
-            with self.span("actor_hidden_bwd", more=more):
-                self.mlp_backward((t1 - t0) * N, d_aout[r], d.actor_out, a_layers,
-                                  [sv_actor[l][r] for l in range(DENSE_LAYERS)] + [None],
-                                  [d_apre[l][r] for l in range(DENSE_LAYERS)] + [None], form_M=Mi)
-        # the actor's hidden layers leave the backward scan (their result feeds nothing on the recurrence: detached
-        # input) and run as one dense chain over all Hm x N rows from d_actor_out
-        # (always with mixing: bd_actor_reinforce adds to d_actor_out after the scan)
-        # (always with mixing and with the Categorical actor, whose scans only write d_actor_out)
-        if dyn:
-            if not fused:
-                cabi.check(lib.bd_lambda_return_backward(ptr(dret), dconst, Hm, N, hp["discount"], hp["disclam"],
-                                                         ptr(d_r), ptr(d_v), st))
-                with self.span("img_heads_bwd"):
-                    self.mlp_backward(Mi, d_r, 1, r_layers, r_acts + [None], None, din0=difeat, ld0=F, w0=F)
-                    self.mlp_backward(Mi, d_v, 1, v_layers, v_acts + [None], None, din0=difeat, ld0=F, w0=F,
-                                      accumulate=True)
-            if d.categorical:
-                c = cabi.ImagineCatBwdArgs()
-                c.N, c.Hm, c.Be, c.D, c.C, c.A, c.Hd = N, Hm, d.Be, d.cat_D, d.cat_C, d.A, d.Hd
-                c.wt_p2 = ptr(pk["p2.T"])
-                c.prior_logits = ptr(self._buf["iprior_logits"])
-            else:
-                c = cabi.ImagineBwdArgs()
-                c.N, c.Hm, c.Be, c.S, c.A, c.Hd = N, Hm, d.Be, d.S, d.A, d.Hd
-                c.wt_p2m, c.wt_p2s = ptr(pk["p2m.T"]), ptr(pk["p2s.T"])
-                c.prior_std, c.eps_prior, c.min_std = ptr(self._buf["iprior_std"]), ptr(noise["img_prior"]), hp["min_std_dev"]
-            self._bind_rssm_t(c)
-            c.wt_embed_a, c.wt_p1 = ptr(pk["embed_a.T"]), ptr(pk["p1.T"])
-            for l in range(1, DENSE_LAYERS):
-                c.wt_a[l - 1] = ptr(pk[f"a{l}.T"])
-            if d.discrete_actions:
-                c.wt_a4m, c.discrete_actions = ptr(pk["a4.T"]), 1
-            else:
-                c.wt_a4m, c.wt_a4s = ptr(pk["a4m.T"]), ptr(pk["a4s.T"])
-            c.start_feat, c.feat, c.action = ptr(feat), ptr(ifeat), ptr(act)
-            c.eps_action = ptr(noise["action"])
-            c.sv_actor, c.sv_act_stats = ptr(sv_actor), ptr(self._buf["sv_act_stats"])
-            c.sv_x, c.sv_gates, c.sv_p = ptr(self._buf["isv_x"]), ptr(self._buf["isv_gates"]), ptr(self._buf["isv_p"])
-            c.dfeat = ptr(difeat)
-            c.dentropy = dentropy
-            c.d_actor_pre, c.d_actor_out = (None if actor_chain else ptr(d_apre)), ptr(d_aout)
-            c.ent_weight = ptr(wts)
-            with self.span("imagine_bwd"):
-                if chunked_bwd:
-                    # one launch per window, latest first; the gradient of the recurrence crosses the borders through
-                    # `carry` (a workgroup reads its rows before its first step and writes them after its last: one buffer).
-                    # The hidden chain of a finished window runs on the overlap stream underneath the next window.
-                    carry = self.buf("img_bwd_carry", N, F)
-                    for i in reversed(range(len(plan))):
-                        c.t_begin, c.t_end = tb[i], tb[i + 1]
-                        c.d_carry_in = ptr(carry) if tb[i + 1] < Hm else None
-                        c.d_carry_out = ptr(carry) if tb[i] > 0 else None
-                        cabi.check(lib.bd_imagine_backward(C.byref(c), st))
-                        if i > 0:
-                            ev = torch.cuda.Event()
-                            ev.record(cur)
-                            with torch.cuda.stream(ov):
-                                ov.wait_event(ev)
-                                actor_rows(tb[i], tb[i + 1], i + 1 < len(plan))
-                                ev_ov.append(torch.cuda.Event())
-                                ev_ov[-1].record(ov)
-                else:
-                    cabi.check((lib.bd_imagine_cat_backward if d.categorical else lib.bd_imagine_backward)(C.byref(c), st))
-            if chunked_bwd and self.pipeline:       # the scan is the last reader of the world model: the chains are not
-                self._ev_bh_wm_free = torch.cuda.Event()
-                self._ev_bh_wm_free.record(cur)
-        if mix is not None:
-            # REINFORCE: the baseline of slot k is the target value of the state its action was taken in -- the start
-            # features for k = 0 (one dense forward over the N start rows), value_pred[k - 1] after (read shifted by N)
-            with self.span("actor_reinforce"):
-                b0, _, _ = self.dense_forward("critic_target", "tgt", "ib0", feat, F, N, 1, sidx=start_sidx)
-                if d.discrete_actions:
-                    cabi.check(lib.bd_actor_reinforce_cat(ptr(act), ptr(self._buf["sv_act_stats"]), ptr(returns), ptr(b0),
-                                                          ptr(v_out), ptr(wts), Hm, N, d.A, mix, inv_mi, dentropy,
-                                                          int(not dyn), ptr(d_aout), sc, SLOT_RF, ws, st))
-                else:
-                    cabi.check(lib.bd_actor_reinforce(ptr(noise["action"]), ptr(act_us), ptr(self._buf["sv_act_stats"]),
-                                                      ptr(returns), ptr(b0), ptr(v_out), ptr(wts), Hm, N, d.A, mix, inv_mi,
-                                                      dentropy, int(not dyn), ptr(d_aout), sc, SLOT_RF, ws, st))
-        if chunked_bwd:
-            actor_rows(0, tb[1], True)              # the first window's chain: nothing left to hide it under
-            cur.wait_event(ev_ov[-1])               # every row of d_actor_pre, for the one weight-gradient launch
-            if par is not None and critic_last:
-                critic_phase()
-        elif actor_chain:
-            actor_rows(0, Hm, False)
-        if self.pipeline and not chunked_bwd:       # last reader of the world model in this step
+    def _imagine_backward(self, s) -> None:
+        """Backward of the imagination scan, both latent families: from difeat and the entropy term to d_actor_out (and
+        d_actor_pre, unless the actor's hidden chain runs outside the scan).  s.windows: one launch per chunk of the plan,
+        latest first; the gradient of the recurrence crosses the borders through `carry` (a workgroup reads its rows before its
+        first step and writes them after its last: one buffer); a finished window's hidden chain runs on the overlap stream."""
+        d, pk, buf, noise = self.d, self.pk, self._buf, s.noise
+        if d.categorical:
+            c = cabi.ImagineCatBwdArgs()
+            c.D, c.C, c.wt_p2, c.prior_logits = d.cat_D, d.cat_C, ptr(pk["p2.T"]), ptr(buf["iprior_logits"])
+            scan = lib.bd_imagine_cat_backward
+        else:
+            c = cabi.ImagineBwdArgs()
+            c.S, c.wt_p2m, c.wt_p2s = d.S, ptr(pk["p2m.T"]), ptr(pk["p2s.T"])
+            c.prior_std, c.eps_prior, c.min_std = ptr(buf["iprior_std"]), ptr(noise["img_prior"]), self.hp["min_std_dev"]
+            scan = lib.bd_imagine_backward
+        c.N, c.Hm, c.Be, c.A, c.Hd = s.N, s.Hm, d.Be, d.A, d.Hd
+        self._bind_rssm_t(c)
+        c.wt_embed_a, c.wt_p1 = ptr(pk["embed_a.T"]), ptr(pk["p1.T"])
+        for l in range(1, DENSE_LAYERS):
+            c.wt_a[l - 1] = ptr(pk[f"a{l}.T"])
+        if d.discrete_actions:
+            c.wt_a4m, c.discrete_actions = ptr(pk["a4.T"]), 1
+        else:
+            c.wt_a4m, c.wt_a4s = ptr(pk["a4m.T"]), ptr(pk["a4s.T"])
+        c.start_feat, c.feat, c.action, c.eps_action = ptr(s.feat), ptr(s.ifeat), ptr(s.act), ptr(noise["action"])
+        c.sv_actor, c.sv_act_stats = ptr(buf["sv_actor"]), ptr(buf["sv_act_stats"])
+        c.sv_x, c.sv_gates, c.sv_p = ptr(buf["isv_x"]), ptr(buf["isv_gates"]), ptr(buf["isv_p"])
+        c.dfeat, c.dentropy, c.ent_weight = ptr(s.difeat), s.dentropy, ptr(s.wts)
+        c.d_actor_pre, c.d_actor_out = (None if s.actor_chain else ptr(s.d_apre)), ptr(s.d_aout)
+        with self.span("imagine_bwd"):
+            if not s.windows:
+                cabi.check(scan(C.byref(c), s.st))
+                return
+            tb, carry = s.tb, self.buf("img_bwd_carry", s.N, s.F)
+            for i in reversed(range(len(s.plan))):
+                c.t_begin, c.t_end = tb[i], tb[i + 1]
+                c.d_carry_in = ptr(carry) if tb[i + 1] < s.Hm else None
+                c.d_carry_out = ptr(carry) if tb[i] > 0 else None
+                cabi.check(scan(C.byref(c), s.st))
+                if i > 0:
+                    self._on_overlap_stream(s, self._actor_rows, s, tb[i], tb[i + 1])
+
+    def _world_model_free(self) -> None:
+        """Pipelined: mark the step's last read of the world model on the current stream (the model optimiser waits for it)."""
+        if self.pipeline:
             self._ev_bh_wm_free = torch.cuda.Event()
             self._ev_bh_wm_free.record(torch.cuda.current_stream())
-        Ga = lambda n: self.G("actor", n)
-        wa = self._wbatch["actor"]
+
+    def _actor_reinforce(self, s) -> None:
+        """REINFORCE: the baseline of slot k is the target value of the state its action was taken in -- the start
+        features for k = 0 (one dense forward over the N start rows), value_pred[k - 1] after (read shifted by N)."""
+        d, noise, stats = self.d, s.noise, self._buf["sv_act_stats"]
+        tail = (ptr(s.wts), s.Hm, s.N, d.A, s.mix, s.inv_mi, s.dentropy, int(not s.dyn), ptr(s.d_aout), s.sc, SLOT_RF, s.ws, s.st)
+        with self.span("actor_reinforce"):
+            b0, _, _ = self.dense_forward("critic_target", "tgt", "ib0", s.feat, s.F, s.N, 1, sidx=s.start_sidx)
+            if d.discrete_actions:
+                cabi.check(lib.bd_actor_reinforce_cat(ptr(s.act), ptr(stats), ptr(s.returns), ptr(b0), ptr(s.v_out), *tail))
+            else:
+                cabi.check(lib.bd_actor_reinforce(ptr(noise["action"]), ptr(s.act_us), ptr(stats), ptr(s.returns), ptr(b0),
+                                                  ptr(s.v_out), *tail))
+
+    def _actor_rows(self, s, t0: int, t1: int) -> None:
+        """The actor's hidden dgrad chain over the rows of steps [t0, t1), in the form of the chain over all rows."""
+        d, sv_actor = self.d, self._buf["sv_actor"]
+        hidden = [(f"a{l}", None, d.Hd, d.Hd, cabi.ACT_ELU) for l in range(1, DENSE_LAYERS)]
+        a_layers = [("a0h", None, d.Hd, s.F, cabi.ACT_ELU)] + hidden + [("a4", None, d.actor_out, d.Hd, cabi.ACT_NONE)]
+        r = slice(t0 * s.N, t1 * s.N)
+        with self.span("actor_hidden_bwd", more=t1 < s.Hm):       # the latest rows open the span
+            self.mlp_backward((t1 - t0) * s.N, s.d_aout[r], d.actor_out, a_layers,
+                              [sv_actor[l][r] for l in range(DENSE_LAYERS)] + [None],
+                              [s.d_apre[l][r] for l in range(DENSE_LAYERS)] + [None], form_M=s.Mi)
+
+    def _actor_update(self, s) -> None:
+        """The actor's weight gradients over all rows in one grouped launch, then its optimiser step."""
+        d, F, Mi, feat, d_apre, sv_actor = self.d, s.F, s.Mi, s.feat, s.d_apre, self._buf["sv_actor"]
+        wa, Ga = self._wbatch["actor"], lambda n: self.G("actor", n)
         # layer 0 input = [h_t; s_t]: start features for t = 0 (rows < N), imagined features of step t-1 afterwards
-        wa.add(d_apre[0], d.Hd, feat, F, Mi, d.Hd, F, Ga("model.0.weight"), F, Ga("model.0.bias"), act2=ifeat, lda2=F, M1=N)
+        wa.add(d_apre[0], d.Hd, feat, F, Mi, d.Hd, F, Ga("model.0.weight"), F, Ga("model.0.bias"), act2=s.ifeat, lda2=F, M1=s.N)
         for l in range(1, DENSE_LAYERS):
             wa.add(d_apre[l], d.Hd, sv_actor[l - 1], d.Hd, Mi, d.Hd, d.Hd, Ga(f"model.{2 * l}.weight"), d.Hd,
                    Ga(f"model.{2 * l}.bias"))
-        wa.add(d_aout, d.actor_out, sv_actor[DENSE_LAYERS - 1], d.Hd, Mi, d.actor_out, d.Hd,
+        wa.add(s.d_aout, d.actor_out, sv_actor[DENSE_LAYERS - 1], d.Hd, Mi, d.actor_out, d.Hd,
                Ga(f"model.{2 * DENSE_LAYERS}.weight"), d.Hd, Ga(f"model.{2 * DENSE_LAYERS}.bias"))
         with self.span("wgrad_actor"):
             wa.run()
-        self._optimizer_step_or_defer("opt_actor", "actor", SLOT_GN_ACTOR, hp["actor_learning_rate"], red_ws)
+        self._optimizer_step_or_defer("opt_actor", "actor", SLOT_GN_ACTOR, self.hp["actor_learning_rate"], s.red_ws)
 
-        if par is None:
-            self._critic_phase(ifeat, returns, Mi, F, inv_mi, red_ws, isidx, wts)
-        self._counts = dict(N=N, Mi=Mi, S=(d.cat_D if d.categorical else d.S), sum_form=sum_form)
-
-    def _critic_phase(self, ifeat, returns, Mi: int, F: int, inv_mi: float, red_ws: torch.Tensor, isidx=None, wts=None) -> None:
+    def _critic_phase(self, s, red_ws: torch.Tensor) -> None:
         """Critic update (src/dreamer.py:370-391) on the current stream: forward on the detached imagined features,
         Normal(v, 1) NLL against the detached returns, dgrad chain, grouped weight gradients, clip + Adam, re-pack."""
-        d, hp = self.d, self.hp
-        st, sc = cabi.stream(), ptr(self.scalars)
+        d, hp, ifeat, returns, Mi, F, wts = self.d, self.hp, s.ifeat, s.returns, s.Mi, s.F, s.wts
         with self.span("critic_fwd_bwd"):
-            c_out, c_acts, c_layers = self.dense_forward("critic", "cri", "ic", ifeat, F, Mi, 1, sidx=isidx)
+            c_out, c_acts, c_layers = self.dense_forward("critic", "cri", "ic", ifeat, F, Mi, 1, sidx=s.isidx)
             d_c = self.buf("d_ic_out", Mi, 1)
-            cabi.check(lib.bd_normal_nll(ptr(c_out), 1, ptr(returns), 1, Mi, 1, inv_mi, ptr(d_c), 1, sc, SLOT_VAL, ptr(red_ws), st))
+            cabi.check(lib.bd_normal_nll(ptr(c_out), 1, ptr(returns), 1, Mi, 1, s.inv_mi, ptr(d_c), 1, s.sc, SLOT_VAL, ptr(red_ws),
+                                         cabi.stream()))
             if wts is not None:     # use_discount=True: -(discount * log_prob).mean() (src/dreamer.py:378-379)
                 d_c.view(Mi).mul_(wts)
                 diff = c_out.view(Mi) - returns
