@@ -187,6 +187,14 @@ constexpr size_t kWideLdsBytes = 147456;   // >= 3 x 16 x (80 + 592) x 4 = 129 0
 static_assert((size_t)kWRing * kWRows * (kWLdNarrow + kWLdDeep) * sizeof(float) <= kWideLdsBytes, "deep stage ring");
 static_assert((size_t)kWRing * kWRowsTall * (kWLdMid + kWLd) * sizeof(float) <= kWideLdsBytes, "mid stage ring");
 constexpr int kWThreads = 512;        // 8 waves: 2 per SIMD, so LDS latency and the stage barrier hide under the other wave
+// Slab row pitch of the wide form: K + bias padded to whole float4s.  Every row of every split's partial tile then starts
+// 16-byte aligned (the workspace base is), so the dense body flushes and the reduce reads with dwordx4.  The pad columns
+// belong to the slab alone: the reduce never reads them.  The plan, the wide kernel and the reduce all derive it here.
+__host__ __device__ __forceinline__ int wgrad_pitch(int Kext) { return (Kext + 3) & ~3; }
+// Dense launches: at most this many whole rounds of 256 workgroups, of units no shorter than the floor (bd_wgrad_plan;
+// 1 .. 4 rounds measured in step, profiles/r06a_README.md)
+constexpr int kWMaxRounds = 3;
+constexpr int kWUnitFloor = 256;
 
 // WN x WK = 16-blocks per wave (the 2 x 4 waves cover up to 2WN x 4WK blocks).  The MFMA loop is branch-free: a wave
 // whose share is smaller multiplies zero-filled LDS columns (the workgroup runs at the pace of its fullest wave
@@ -354,7 +362,8 @@ __device__ __forceinline__ void wgrad_wide_body(const bd_wgrad_desc& d, float* _
         BD_DSTAMP(sb, 4);
     }
     // lane holds D[n = 4*(lane>>4) + r][k = lane&15] of each 16x16 block
-    float* slab = ws + d.ws_off + (size_t)z * d.N * Kext;
+    const int pitch = wgrad_pitch(Kext);
+    float* slab = ws + d.ws_off + (size_t)z * d.N * pitch;
 #pragma unroll
     for (int i = 0; i < WN; ++i) {
         if (i < my_nb) {
@@ -365,7 +374,7 @@ __device__ __forceinline__ void wgrad_wide_body(const bd_wgrad_desc& d, float* _
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int nn = n0 + (my_nb0 + i) * 16 + 4 * lrow + r;
-                        if (nn < d.N && k < Kext) slab[(size_t)nn * Kext + k] = acc[i][j][r];
+                        if (nn < d.N && k < Kext) slab[(size_t)nn * pitch + k] = acc[i][j][r];
                     }
                 }
             }
@@ -395,10 +404,6 @@ __device__ __forceinline__ void wgrad_dense_body(const bd_wgrad_desc& d, float* 
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
     typedef const __attribute__((address_space(1))) void* glb_ptr_t;
     const int ncol = min(nb_cnt * 16, d.N - n0), kcol = min(kb_cnt * 16, d.K - k0);
-    for (int i = threadIdx.x; i < kWRing * kWStage; i += kWThreads) wlds[i] = 0.f;
-    __syncthreads();
-    if (hb && d.K >= k0 && d.K < k0 + kb_cnt * 16 && threadIdx.x < kWRing * kWRows)
-        wlds[(threadIdx.x >> 4) * kWStage + kWRows * kWLd + (threadIdx.x & 15) * kWLd + (d.K - k0)] = 1.f;
     const bool lp = 4 * lane < ncol, la = 4 * lane < kcol;
     const float* __restrict__ pl = d.dpre + n0 + 4 * lane;
     const float* __restrict__ a1l = d.act1 + k0 + 4 * lane;
@@ -426,9 +431,29 @@ __device__ __forceinline__ void wgrad_dense_body(const bd_wgrad_desc& d, float* 
         }
     };
     const int nst = cdiv(m_end - m_begin, kWRows);
-    __syncthreads();
+    // A workgroup may live for a dozen stages only (bd_wgrad_plan), so its fixed cost counts.  The DMA of the first two
+    // stages goes out at once; under it, only the ring columns that the MFMAs read and no DMA ever writes are set: dpre
+    // columns [ncol, 208) and act columns [kcol, 16 kb_cnt) of every ring row, fewer than 16 each.  The first of those
+    // act columns is the ones column of the bias gradient where this tile holds column K.  It stays zero in a row past
+    // the split's last row; such rows exist in a split's final stage only, where issue() clears them -- for the two
+    // stages in flight here that may race with these stores, so they write the same zeros.
     issue(wlds, m_begin);
     if (nst > 1) issue(wlds + kWStage, m_begin + kWRows);
+    {
+        const int one = (hb && d.K >= k0 && d.K < k0 + kb_cnt * 16) ? d.K - k0 : -1;
+        const int npad = nb_cnt * 16 - ncol, pad = npad + kb_cnt * 16 - kcol;
+        for (int i = threadIdx.x; i < kWRing * kWRows * pad; i += kWThreads) {
+            const int row = i / pad, c = i - row * pad;               // row of the ring: stage buffer row >> 4, row & 15
+            float* P = wlds + (row >> 4) * kWStage + (row & 15) * kWLd;
+            if (c < npad) {
+                P[ncol + c] = 0.f;
+            } else {
+                const int kc = kcol + c - npad;
+                const bool live = row >= 2 * kWRows || m_begin + row < m_end;
+                P[kWRows * kWLd + kc] = (kc == one && live) ? 1.f : 0.f;
+            }
+        }
+    }
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
     const int lrow = lane >> 4, lcol = lane & 15;
@@ -465,18 +490,32 @@ __device__ __forceinline__ void wgrad_dense_body(const bd_wgrad_desc& d, float* 
         lds_barrier();
         BD_DSTAMP(sb, 4);
     }
-    float* slab = ws + d.ws_off + (size_t)z * d.N * Kext;
+    // Flush.  A lane holds four ROWS of one column per block: stored as they lie, that is one dword store per value, each
+    // instruction touching four 64-byte pieces.  The ring is idle now (every wave has left the last stage's barrier: all
+    // LDS reads have returned and all DMA has landed), so each wave turns 16 rows of its share at a time through a
+    // private corner of it into whole row pieces of 16 WK floats and stores them as dwordx4 (slab rows are 16-byte
+    // aligned: wgrad_pitch).  Pad columns up to the pitch are written too (zeros); the reduce never reads them.
+    const int pitch = wgrad_pitch(Kext);
+    float* slab = ws + d.ws_off + (size_t)z * d.N * pitch;
+    constexpr int kFl = WK * 16 + 4;           // staging row stride: 4 kFl == 16 mod 64, the four row groups on disjoint banks
+    constexpr int kQ = WK * 4;                 // float4s per row piece
+    float* mine = wlds + wave * (16 * (4 * 16 + 4));
+    const int kw0 = k0 + my_kb0 * 16;
 #pragma unroll
     for (int i = 0; i < WN; ++i) {
 #pragma unroll
-        for (int j = 0; j < WK; ++j) {
-            const int k = k0 + (my_kb0 + j) * 16 + lcol;
+        for (int j = 0; j < WK; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int nn = n0 + (my_nb0 + i) * 16 + 4 * lrow + r;
-                if (nn < d.N && k < Kext) slab[(size_t)nn * Kext + k] = acc[i][j][r];
-            }
+            for (int r = 0; r < 4; ++r) mine[(4 * lrow + r) * kFl + j * 16 + lcol] = acc[i][j][r];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the wave's own stores, before other lanes read them
+#pragma unroll
+        for (int t = 0; t < WK; ++t) {
+            const int idx = t * 64 + lane, row = idx / kQ, q = idx - row * kQ;
+            const floatx4 v = *reinterpret_cast<const floatx4*>(mine + row * kFl + 4 * q);
+            const int nn = n0 + (my_nb0 + i) * 16 + row, k = kw0 + 4 * q;
+            if (nn < d.N && k < pitch) *reinterpret_cast<floatx4*>(slab + (size_t)nn * pitch + k) = v;
         }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // ... and those reads, before the next 16 rows overwrite them
     }
 }
 
@@ -611,7 +650,8 @@ __device__ __forceinline__ void wgrad_thin_body(const bd_wgrad_desc& d, float* _
         BS[(wave * 2 + i) * 64 + lane] = bsum[i];
     }
     __syncthreads();
-    float* slab = ws + d.ws_off + (size_t)z * d.N * Kext;
+    const int pitch = wgrad_pitch(Kext);
+    float* slab = ws + d.ws_off + (size_t)z * d.N * pitch;
     for (int e = threadIdx.x; e < 2 * KB * 64; e += blockDim.x) {
         const int blk = e >> 6, l = e & 63;
         floatx4 s4 = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -620,7 +660,7 @@ __device__ __forceinline__ void wgrad_thin_body(const bd_wgrad_desc& d, float* _
         const int k = j * 16 + (l & 15);
         if (k < d.K) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) slab[(size_t)(i * 16 + 4 * (l >> 4) + r) * Kext + k] = s4[r];
+            for (int r = 0; r < 4; ++r) slab[(size_t)(i * 16 + 4 * (l >> 4) + r) * pitch + k] = s4[r];
         }
     }
     if (hb && threadIdx.x < 32) {
@@ -628,7 +668,7 @@ __device__ __forceinline__ void wgrad_thin_body(const bd_wgrad_desc& d, float* _
         float t = 0.f;
         for (int w = 0; w < 8; ++w)
             for (int qq = 0; qq < 4; ++qq) t += BS[(w * 2 + i) * 64 + qq * 16 + nn];
-        slab[(size_t)(i * 16 + nn) * Kext + d.K] = t;
+        slab[(size_t)(i * 16 + nn) * pitch + d.K] = t;
     }
 }
 
@@ -770,6 +810,40 @@ __global__ __launch_bounds__(256) void wgrad_grouped_reduce_kernel(const bd_wgra
     else d.db[nn] = s;
 }
 
+// Reduce of the wide form's slabs (row pitch wgrad_pitch): a thread sums one float4 of a row over the splits, in split
+// order as above, with kRedFly splits' loads in flight -- the one-dword, one-split-at-a-time form read the 28 MB of an
+// actor pass at 1.5 TB/s alone on the chip, and its time grows with the split count.  Single-wave workgroups: the 42 k
+// float4s of such a pass spread over every CU.
+constexpr int kRedWideThreads = 64;
+constexpr int kRedFly = 16;
+__global__ __launch_bounds__(kRedWideThreads) void wgrad_wide_reduce_kernel(const bd_wgrad_desc* __restrict__ descs, int n,
+                                                                            const float* __restrict__ ws) {
+    int g = 0;
+    while (g + 1 < n && (int)blockIdx.x >= descs[g + 1].red_begin) ++g;
+    const bd_wgrad_desc d = descs[g];
+    const int hb = d.db != nullptr;
+    const int q4 = wgrad_pitch(d.K + hb) >> 2;                   // float4s per slab row
+    const int total4 = d.N * q4;
+    const int e = (blockIdx.x - d.red_begin) * kRedWideThreads + threadIdx.x;
+    if (e >= total4) return;
+    const floatx4* p = reinterpret_cast<const floatx4*>(ws + d.ws_off) + e;
+    floatx4 s = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int z = 0; z < d.splits; z += kRedFly) {
+        floatx4 v[kRedFly];          // a short last batch re-reads the last split (branch-free loads) and does not add it
+#pragma unroll
+        for (int i = 0; i < kRedFly; ++i) v[i] = p[(size_t)min(z + i, d.splits - 1) * total4];
+#pragma unroll
+        for (int i = 0; i < kRedFly; ++i)
+            if (z + i < d.splits) s += v[i];
+    }
+    const int nn = e / q4, k = (e - nn * q4) * 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (k + r < d.K) d.dW[(size_t)nn * d.ldw + k + r] = s[r];
+        else if (k + r == d.K && hb) d.db[nn] = s[r];
+    }
+}
+
 #ifdef BD_STAMPS
 extern "C" int bd_debug_wstamps(unsigned long long* out64) {
     return hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_dstamps), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -1;
@@ -822,8 +896,27 @@ int bd_wgrad_plan(bd_wgrad_desc* descs, int n, int* total_blocks, int* total_red
                      cdiv(descs[i].M > 0 ? descs[i].M : 1, R);
             return t;
         };
-        rows_wide = 128;
-        while (wgs(rows_wide) > 256 && rows_wide < (1 << 20)) rows_wide += kWRows;
+        auto rows_for_rounds = [&](int k) {
+            int R = 128;
+            while (wgs(R) > 256L * k && R < (1 << 20)) R += kWRows;
+            return R;
+        };
+        rows_wide = rows_for_rounds(1);
+        // One round of workgroups that each live for the whole launch is the shortest form ALONE on the chip, and the
+        // worst in company: a CU changes hands only when a workgroup ends, so a launch on a high-priority stream that
+        // arrives behind another one waits for whole workgroups of it.  A dense launch whose
+        // one-round unit is long therefore takes k whole rounds of shorter units, as long as a unit keeps kWUnitFloor
+        // rows (its fixed cost: prologue, flush, its slab in the reduce).  Launches with a gathered operand choose their
+        // rows below.
+        bool dense = true;
+        for (int i = 0; i < n; ++i) dense = dense && descs[i].g_nseg <= 0;
+        for (int k = kWMaxRounds; dense && k > 1; --k) {
+            const int R = rows_for_rounds(k);
+            if (R >= kWUnitFloor) {
+                rows_wide = R;
+                break;
+            }
+        }
     }
     // Launches that contain conv weight gradients (gathered operand) mix row counts from 2 450 to 2.4 M: one row count
     // for all would leave a single workgroup streaming millions of rows.  There every GEMM gets rows_per = T / cost,
@@ -928,8 +1021,14 @@ int bd_wgrad_plan(bd_wgrad_desc* descs, int n, int* total_blocks, int* total_red
         d.red_begin = red;
         d.ws_off = off;
         blocks += d.tiles_n * d.tiles_k * d.splits;
-        red += cdiv(d.N * (d.K + hb), 256);
-        off += (size_t)d.splits * d.N * (d.K + hb);
+        if (wgrad_wide()) {      // slab rows padded to whole float4s, one float4 per reduce thread
+            const int pitch = wgrad_pitch(d.K + hb);
+            red += cdiv(d.N * (pitch >> 2), kRedWideThreads);
+            off += (size_t)d.splits * d.N * pitch;
+        } else {
+            red += cdiv(d.N * (d.K + hb), 256);
+            off += (size_t)d.splits * d.N * (d.K + hb);
+        }
     }
     *total_blocks = blocks;
     *total_red_blocks = red;
@@ -947,6 +1046,7 @@ int bd_wgrad_grouped_phase(const bd_wgrad_desc* descs_dev, int n, int total_bloc
     using namespace bd;
     BD_REQUIRE(descs_dev && ws && n > 0 && n <= 4096 && total_blocks > 0 && total_red_blocks > 0 && phase >= 0 && phase <= 2,
                "bd_wgrad_grouped: bad arguments");
+    BD_REQUIRE(!wgrad_wide() || (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "bd_wgrad_grouped: the workspace must be 16-byte aligned");
     if (phase == 2) {
     } else if (wgrad_wide()) {
         static_assert(kThreads == 256, "the 64x64-tile wgrad kernels are written for four waves");
@@ -962,8 +1062,12 @@ int bd_wgrad_grouped_phase(const bd_wgrad_desc* descs_dev, int n, int total_bloc
     }
     BD_CHECK_LAUNCH("bd_wgrad_grouped");
     if (phase == 1) return 0;
-    hipLaunchKernelGGL(wgrad_grouped_reduce_kernel, dim3(total_red_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n,
-                       ws);
+    if (wgrad_wide())
+        hipLaunchKernelGGL(wgrad_wide_reduce_kernel, dim3(total_red_blocks), dim3(kRedWideThreads), 0, (hipStream_t)stream,
+                           descs_dev, n, ws);
+    else
+        hipLaunchKernelGGL(wgrad_grouped_reduce_kernel, dim3(total_red_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n,
+                           ws);
     BD_CHECK_LAUNCH("bd_wgrad_grouped(reduce)");
     return 0;
 }

@@ -128,7 +128,8 @@ int bd_wgrad(const float* dpre, int ldp, const float* act, int lda, int M, int N
 /* Grouped form: every weight-gradient GEMM of one backward pass in ONE launch (+ one grouped reduce).  Fill the
  * caller fields of each descriptor on the host, let bd_wgrad_plan add the launch plan (and tell the slab workspace
  * size), copy the table to device memory once, then call bd_wgrad_grouped every step.  Rows [0, M1) take their
- * activations from act1, rows [M1, M) from act2[row - M1] (set M1 = M and act2 = NULL for a single source). */
+ * activations from act1, rows [M1, M) from act2[row - M1] (set M1 = M and act2 = NULL for a single source).
+ * The slab workspace `ws` must be 16-byte aligned (slab rows are written and read as float4s). */
 typedef struct {
     const float* dpre; int ldp;               /* [M x N] pre-activation gradients                            */
     const float* act1; int lda1; int M1;
