@@ -222,6 +222,17 @@ class ReplaySampleArgs(C.Structure):
         ["dst_obs", "dst_act", "dst_reward", "dst_nonterminal", "idx_out"]))
 
 
+BD_FP_MAX_BUFFERS = 16
+
+
+class FingerprintBuf(C.Structure):
+    _fields_ = [("p", P), ("n", C.c_size_t)]
+
+
+class FingerprintArgs(C.Structure):
+    _fields_ = [("n_buf", I32), ("buf", FingerprintBuf * BD_FP_MAX_BUFFERS)]
+
+
 # every symbol include/bigdreamer_hip.h declares, with its signature
 _SIGS = {
     "bd_last_error": (C.c_char_p, []),
@@ -308,6 +319,7 @@ _SIGS = {
     "bd_openl_error": (I32, [P, P, I32, I32, I32, I32, P, P]),
     "bd_colsum_ws_floats": (C.c_size_t, [I32]),
     "bd_colsum": (I32, [P, C.c_size_t, I32, P, P, P]),
+    "bd_fingerprint": (I32, [C.POINTER(FingerprintArgs), P, P]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

@@ -9,7 +9,19 @@ import yaml
 
 ACTION_MODES = ("sample", "mode", "mean")        # eval_action, and action_mode of the acting step
 
-DEFAULT_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "conf", "config.yaml")
+REPLICA_POLICIES = ("raise", "resync")           # replica_on_mismatch
+
+
+def check_replica_options(interval, policy):
+    """replica_check_interval: an integer >= 0 (0 = off); replica_on_mismatch: one of REPLICA_POLICIES."""
+    if isinstance(interval, bool) or not isinstance(interval, (int, float)) or int(interval) != interval or interval < 0:
+        raise ValueError(f"replica_check_interval={interval!r} is not an integer >= 0")
+    if policy not in REPLICA_POLICIES:
+        raise ValueError(f"replica_on_mismatch={policy!r} is none of {REPLICA_POLICIES}")
+    return int(interval), policy
+
+
+DEFAULT_CONFIG =os.path.join(os.path.dirname(os.path.abspath(__file__)), "conf", "config.yaml")
 
 
 def _coerce(x: Any) -> Any:
@@ -50,4 +62,7 @@ def load_config(overrides: List[str] = (), path: str = DEFAULT_CONFIG) -> Dict[s
         raise ValueError(f"eval_state_mean={cfg['eval_state_mean']!r} is not a boolean")
     if not isinstance(cfg.get("sample_on_device", False), bool):
         raise ValueError(f"sample_on_device={cfg['sample_on_device']!r} is not a boolean")
+    check_replica_options(cfg.get("replica_check_interval", 0), cfg.get("replica_on_mismatch", "raise"))
+    if not isinstance(cfg.get("replica_sync_at_start", False), bool):
+        raise ValueError(f"replica_sync_at_start={cfg['replica_sync_at_start']!r} is not a boolean")
     return cfg

@@ -84,7 +84,9 @@ class Dreamer:
                          use_discount=self.use_discount, discrete_actions=self.action_distribution == "Categorical",
                          cnn_act=self.cnn_activation_function)
         self.engine = DreamerEngine(self.dims, _hp_from_params(params), self.device, world_size=world_size,
-                                    process_group=process_group)
+                                    process_group=process_group,
+                                    replica_check_interval=params.get("replica_check_interval", 0),
+                                    replica_on_mismatch=params.get("replica_on_mismatch", "raise"))
         e = self.engine
         # PyTorch-default initialisation happens in the nn.Modules below (their parameters alias the engine's
         # flat buffers), so seeding torch before construction reproduces a run (src/main.py:56-58).
@@ -196,6 +198,26 @@ class Dreamer:
         self.engine.load_noise_state(rs["noise"])
         restore_generators(rs["generators"], self.device)
         return dict(rs["extra"])
+
+    # ---------------------------------------------------------------------------------------- replicas
+    def fingerprint(self) -> Dict[str, Tuple[int, int]]:
+        """{"actor.flat": (hash, nonfinite), ...}: a 64-bit fingerprint of the bit patterns and the number of non-finite
+        elements of every flat buffer the agent owns (weights and Adam moments of the three optimisers, the critic target),
+        computed on the device in one launch (bd_fingerprint).  Two agents with equal dicts are bit-identical.  Synchronises;
+        data-parallel: a COLLECTIVE, as ``save`` is (it issues the held-back optimiser steps)."""
+        words, names = self.engine.fingerprint()
+        w = words.cpu().numpy().view("uint64")
+        return {f"{g}.{b}": (int(w[i, 0]), int(w[i, 1])) for i, (g, b) in enumerate(names)}
+
+    def check_replicas(self) -> Dict[str, Any]:
+        """Do all ranks hold the same weights, Adam moments and step counts?  {"agree", "mismatch", "nonfinite"}, the same
+        on every rank; a synchronous COLLECTIVE.  One rank: the non-finite counts only."""
+        return self.engine.check_replicas()
+
+    def sync_replicas(self, src: int = 0) -> None:
+        """Make every rank a bit-identical copy of rank `src` (weights, optimiser state, everything packed from them).
+        A synchronous COLLECTIVE."""
+        self.engine.sync_replicas(src)
 
     def eval(self) -> None:      # no dropout / batch-norm anywhere on the path
         pass

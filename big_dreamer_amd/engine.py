@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _cabi as cabi
+from .config import check_replica_options
 from .parallel import DataParallel
 from .params import ParamGroup, _adam_state_dict, _load_adam_state_dict
 from .synth import CNN_ACTIVATIONS, DENSE_LAYERS, MODEL_MODULES, Dims, model_modules, param_shapes
@@ -87,6 +88,22 @@ def check_action_distribution(value) -> str:
     if value not in ACTION_DISTRIBUTIONS:
         raise ValueError(f"action_distribution must be one of {ACTION_DISTRIBUTIONS}, got {value!r}")
     return value
+
+
+class ReplicaMismatch(RuntimeError):
+    """Data-parallel replicas no longer hold bit-identical weights, Adam moments or step counts."""
+
+
+class _ReplicaVerdict:
+    """One periodic replica check in flight: pinned host memory for the step counts going up and the verdict coming
+    down, and the event behind the D2H copy."""
+
+    def __init__(self, n_buf: int):
+        self.steps = torch.zeros(3, dtype=torch.int64).pin_memory()
+        self.host = torch.zeros(2 * (2 * n_buf + 3), dtype=torch.int64).pin_memory()     # max | min over ranks of the words
+        self.event: Optional[torch.cuda.Event] = None
+        self.step = 0
+        self.collective = False
 
 
 class _LogRecord:
@@ -228,8 +245,10 @@ def _parse_bh_chunks(text: str):
 
 class DreamerEngine:
     def __init__(self, dims: Dims, hp: Optional[dict] = None, device="cuda", params: Optional[dict] = None,
-                 world_size: int = 1, process_group=None, phase_groups: Optional[dict] = None):
+                 world_size: int = 1, process_group=None, phase_groups: Optional[dict] = None,
+                 replica_check_interval: int = 0, replica_on_mismatch: str = "raise"):
         self.d = dims
+        self.set_replica_check(replica_check_interval, replica_on_mismatch)
         self.pixel = bool(dims.pixel)   # 64x64 pixel observations: conv encoder / decoder on csrc/conv.hip (conv_stack.py)
         self.hp = dict(DEFAULT_HP)
         if hp:
@@ -347,6 +366,14 @@ class DreamerEngine:
             torch.cuda.set_stream(self._main_stream)
         self._pending_opt: List[tuple] = []
         self._opt_over: Dict[str, dict] = {}
+        # replica watch ("Replica agreement"): nothing below is touched while replica_check_interval is 0
+        self._fp: Optional[tuple] = None                     # (buffer names, bd_fingerprint argument block)
+        self._n_train_steps = 0
+        self._checks_out: List[_ReplicaVerdict] = []         # issued, not yet read; oldest first
+        self._check_pool: List[_ReplicaVerdict] = []
+        self._ev_fp: Optional[torch.cuda.Event] = None       # end of the latest periodic fingerprint
+        self._fp_wait: set = set()                           # optimisers that have not yet been ordered behind it
+        self._resync_warned = False
         # perf-mode noise: Philox keyed by the process seed (torch.manual_seed before building the agent, src/main.py:56-58)
         # and the rank, counter = step index per phase
         # (read at the FIRST perf-mode draw, so that seeding torch any time before training reproduces the run)
@@ -443,6 +470,7 @@ class DreamerEngine:
 
     def optimizer_state_dict(self, group: str) -> dict:
         """torch.optim.Adam-layout state of one optimiser ("model" | "actor" | "critic"); synchronises."""
+        self.resolve_replica_checks()
         self.flush_optimizers()
         self.join()
         torch.cuda.current_stream().synchronize()
@@ -636,7 +664,10 @@ class DreamerEngine:
         `rec`: log record that receives this phase's snapshot of the scalar board (lazy logs)."""
         g = self.groups[group]
         red_ws = self.red_ws if red_ws is None else red_ws
-        self._allreduce(g.grad, group)       # grads already carry 1/global-count: SUM over ranks = global-mean gradient
+        if group in self._fp_wait:           # a periodic fingerprint read these buffers on another stream: write after it
+            self._fp_wait.discard(group)
+            torch.cuda.current_stream().wait_event(self._ev_fp)
+        self._allreduce(g.grad, group)     # grads already carry 1/global-count: SUM over ranks = global-mean gradient
         g.step += 1
         hp = self.hp
         ov = self._opt_over.get(group)          # hyper-parameters adopted from a checkpoint (load_optimizer_state_dict)
@@ -732,6 +763,165 @@ class DreamerEngine:
         t, s = self.groups["critic_target"], self.groups["critic"]
         cabi.check(lib.bd_polyak(ptr(t.flat), ptr(s.flat), t.numel, float(self.hp["polyak_avg"]), cabi.stream()))
         self.pack("critic_target")
+
+    # ------------------------------------------------------------------------------------------ replica agreement
+    # DESIGN.md, "Replica agreement".  The data-parallel step is exact only while every rank holds bit-identical weights,
+    # Adam moments and step counts; one bd_fingerprint launch reduces each flat buffer to a 64-bit word (and a count of
+    # non-finite elements) on the device, one small MAX all-reduce compares the words.
+    _FP_BUFFERS = tuple((g, b) for g in ("model", "actor", "critic") for b in ("flat", "m", "v")) + (("critic_target", "flat"),)
+    _STEP_GROUPS = ("model", "actor", "critic")
+
+    def set_replica_check(self, interval: int = 0, on_mismatch: str = "raise") -> None:
+        """The periodic check of train_step: every `interval`-th step (0 = off); a mismatch raises ReplicaMismatch
+        ("raise") or warns once and broadcasts rank 0's state ("resync").  Every rank sets the same values."""
+        self.replica_check_interval, self.replica_on_mismatch = check_replica_options(interval, on_mismatch)
+
+    def _fp_table(self):
+        if self._fp is None:
+            a = cabi.FingerprintArgs()
+            a.n_buf = len(self._FP_BUFFERS)
+            for i, (g, b) in enumerate(self._FP_BUFFERS):
+                t = getattr(self.groups[g], b)
+                a.buf[i].p, a.buf[i].n = t.data_ptr(), t.numel()
+            self._fp = (self._FP_BUFFERS, a)
+        return self._fp
+
+    def _fingerprint_into(self, out: torch.Tensor) -> None:
+        """ONE launch over every flat buffer, on the current stream."""
+        cabi.check(lib.bd_fingerprint(C.byref(self._fp_table()[1]), out.data_ptr(), cabi.stream()))
+
+    def fingerprint(self):
+        """(words, names): a device int64 tensor [n_buf, 2] of (hash, non-finite count) per flat buffer -- flat, m, v of
+        model, actor and critic, flat of critic_target, padding floats included -- and the buffers' names in table order,
+        e.g. ("actor", "flat").  Ordered behind pending optimiser work as optimizer_state_dict is (data-parallel: a
+        collective, it issues the held-back optimiser steps), without the host synchronisation."""
+        self.flush_optimizers()
+        self.join()
+        names = self._fp_table()[0]
+        out = torch.empty(len(names), 2, dtype=torch.int64, device=self.dev)
+        self._fingerprint_into(out)
+        return out, list(names)
+
+    def _replica_words(self, fp: torch.Tensor, steps: torch.Tensor) -> torch.Tensor:
+        """What the ranks compare: the hashes, the three Adam step counts, then the non-finite counts (whose maximum over
+        ranks tells every rank about a NaN on any).  Not the Philox key or counters: they differ per rank by design."""
+        return torch.cat([fp[:, 0], steps, fp[:, 1]])
+
+    def _replica_names(self) -> List[str]:
+        return [f"{g}.{b}" for g, b in self._FP_BUFFERS] + [f"{g}.step" for g in self._STEP_GROUPS]
+
+    def _read_verdict(self, hi: np.ndarray, lo: np.ndarray) -> dict:
+        n, names = len(self._FP_BUFFERS), self._replica_names()
+        mismatch = [names[i] for i in range(n + 3) if hi[i] != lo[i]]
+        nonfinite = {names[i]: int(hi[n + 3 + i]) for i in range(n) if hi[n + 3 + i] != 0}
+        return {"agree": not mismatch, "mismatch": mismatch, "nonfinite": nonfinite}
+
+    def check_replicas(self) -> dict:
+        """{"agree": bool, "mismatch": [names], "nonfinite": {name: count}}, the same on every rank.  Synchronous, and a
+        COLLECTIVE on the caller's communicator: every rank calls it at the same point.  One rank: the non-finite counts
+        only (agree = True).  Verdicts of periodic checks still in flight are resolved first."""
+        self.resolve_replica_checks()
+        fp, _ = self.fingerprint()
+        steps = torch.tensor([self.groups[g].step for g in self._STEP_GROUPS], dtype=torch.int64, device=self.dev)
+        hi, lo = self.dp.max_min_(self._replica_words(fp, steps))
+        return self._read_verdict(hi.cpu().numpy(), lo.cpu().numpy())
+
+    def sync_replicas(self, src: int = 0) -> None:
+        """Make every rank a bit-identical copy of rank `src`: flat, m, v of the three optimisers, the critic target, the
+        Adam step counts and checkpoint hyper-parameters adopted by load_optimizer_state_dict; then everything derived
+        from the weights is rebuilt as __init__ does (pack() of the four groups: packed weights, the Categorical plain
+        copies, the conv stacks' packs).  A COLLECTIVE on the caller's communicator; synchronous."""
+        self.resolve_replica_checks()
+        self.flush_optimizers()
+        self.join()
+        if self.world_size > 1:
+            for g, b in self._FP_BUFFERS:
+                self.dp.broadcast_(getattr(self.groups[g], b), src)
+            keys = ("lr", "eps", "weight_decay")
+            meta = [float(self.groups[g].step) for g in self._STEP_GROUPS]
+            for g in self._STEP_GROUPS:
+                ov = self._opt_over.get(g) or {}
+                meta += [x for k in keys for x in (float(k in ov), float(ov.get(k, 0.0)))]
+            meta = self.dp.broadcast_(torch.tensor(meta, dtype=torch.float64, device=self.dev), src).cpu().tolist()
+            for i, g in enumerate(self._STEP_GROUPS):
+                self.groups[g].step = int(meta[i])
+                part = meta[3 + 6 * i:9 + 6 * i]
+                ov = {k: part[2 * j + 1] for j, k in enumerate(keys) if part[2 * j]}
+                if ov:
+                    self._opt_over[g] = ov
+                else:
+                    self._opt_over.pop(g, None)
+        for g in ("model", "actor", "critic", "critic_target"):
+            self.pack(g)
+        torch.cuda.current_stream().synchronize()
+
+    def _replica_check_due(self) -> bool:
+        """Is this train step one that issues the periodic check?  If so, first read the verdicts train_step has not read
+        (without the host throttle nothing else reads them), on the caller's stream: "resync" is a collective there."""
+        k = self.replica_check_interval
+        if k <= 0 or self._n_train_steps % k:
+            return False
+        if self._checks_out:
+            throttled = self.pipeline and self.host_ahead > 0
+            self.resolve_replica_checks(self._n_train_steps - self.host_ahead if throttled else None)
+        return True
+
+    def _enqueue_replica_check(self) -> None:
+        """Fingerprint + agree + asynchronous D2H of the verdict, on the current stream, which the caller has ordered behind
+        the optimiser steps issued so far.  One rank: the fingerprint alone (the NaN watch), no collective."""
+        n = len(self._FP_BUFFERS)
+        rec = self._check_pool.pop() if self._check_pool else _ReplicaVerdict(n)
+        rec.step, rec.collective = self._n_train_steps, self.world_size > 1 or self.dp.force
+        fp = torch.empty(n, 2, dtype=torch.int64, device=self.dev)
+        self._fingerprint_into(fp)
+        self._ev_fp = torch.cuda.Event()
+        self._ev_fp.record(torch.cuda.current_stream())
+        self._fp_wait = set(self._STEP_GROUPS)
+        if rec.collective:
+            for i, g in enumerate(self._STEP_GROUPS):
+                rec.steps[i] = self.groups[g].step
+            steps = rec.steps.to(self.dev, non_blocking=True)
+            # the critic's communicator, from the critic's stream: behind the critic all-reduce of the previous step and
+            # before this step's, never in front of a KL / world-model collective
+            hi, lo = self.dp.max_min_(self._replica_words(fp, steps), "critic")
+            rec.host.copy_(torch.cat([hi, lo]), non_blocking=True)
+        else:
+            rec.host[:2 * n].copy_(fp.view(-1), non_blocking=True)
+        rec.event = torch.cuda.Event()
+        rec.event.record(torch.cuda.current_stream())
+        self._checks_out.append(rec)
+
+    def resolve_replica_checks(self, upto: Optional[int] = None) -> None:
+        """Read the verdicts of the periodic checks issued at train steps <= `upto` (None: all), oldest first, and act on
+        them.  Data-parallel: every rank calls it at the same host step (train_step does; so do check_replicas,
+        sync_replicas and optimizer_state_dict, hence Dreamer.save) -- "resync" is a collective."""
+        while self._checks_out and (upto is None or self._checks_out[0].step <= upto):
+            rec = self._checks_out.pop(0)
+            rec.event.synchronize()
+            h, n = rec.host.numpy(), len(self._FP_BUFFERS)
+            if rec.collective:
+                v = self._read_verdict(h[:2 * n + 3].copy(), h[2 * n + 3:].copy())
+            else:
+                names = self._replica_names()
+                v = {"mismatch": [], "nonfinite": {names[i]: int(h[2 * i + 1]) for i in range(n) if h[2 * i + 1] != 0}}
+            self._check_pool.append(rec)
+            if v["nonfinite"]:       # under both policies: copying NaNs around repairs nothing
+                raise FloatingPointError(f"replica check at train step {rec.step}: non-finite values in "
+                                         + ", ".join(f"{k} ({c})" for k, c in v["nonfinite"].items()))
+            if v["mismatch"]:
+                text = (f"replica check at train step {rec.step}: the ranks differ in " + ", ".join(v["mismatch"])
+                        + " (data-parallel replicas must be bit-identical)")
+                if self.replica_on_mismatch == "raise":
+                    raise ReplicaMismatch(text)
+                if not self._resync_warned:
+                    import warnings
+                    warnings.warn(text + ": broadcasting rank 0's state (replica_on_mismatch='resync')")
+                    self._resync_warned = True
+                for r in self._checks_out:           # issued before the repair: stale
+                    r.event.synchronize()
+                self._check_pool += self._checks_out
+                self._checks_out = []
+                self.sync_replicas(0)
 
     # ------------------------------------------------------------------------------------------ forward pieces
     def encode(self, obs2d: torch.Tensor, M: int, save: bool = True):
@@ -1468,12 +1658,15 @@ class DreamerEngine:
         obs = batch["observations"]
         B = obs.shape[1]
         self._timer_tick += 1
+        self._n_train_steps += 1
         lazy = sync_logs == "lazy"
         rec = self._cur_rec = self._new_record() if lazy else None
         if not self.pipeline:
             if noise is None:
                 noise = self.make_noise(B)
             feat = self._dynamics_phase(batch, noise, "")
+            if self._replica_check_due():
+                self._enqueue_replica_check()
             self._behaviour_phase(feat, noise, obs.shape[0] - 1, B, self.red_ws, None)
             return self._finish_step(rec, sync_logs)
         cur = torch.cuda.current_stream()
@@ -1503,6 +1696,17 @@ class DreamerEngine:
             if os.environ.get("BD_BATCH_GUARD", "1") != "0":      # "0": diagnosis only (tests show the race without it)
                 cur.wait_event(ev_old)
         self._flush_pending_opt()                   # actor / critic updates of the previous step (data-parallel runs)
+        if self._replica_check_due():
+            # The replica check, at the one point of a host step where every optimiser step issued so far is whole and the
+            # same on every rank: world model k (ev_wm_done), actor and critic k - 1 (issued by now also on the deferred
+            # schedule).  It runs on the critic's stream, which has a step of slack and carries the critic update k - 1
+            # already: the behaviour phase below never waits for it.  The optimiser steps issued from here on wait for the
+            # fingerprint's end (optimizer_step) -- long past by the time they run.  On a shared communicator the collective
+            # is issued after kl, model (k), actor, critic (k - 1), all of which it depends on anyway.
+            with torch.cuda.stream(self._side):
+                self._side.wait_event(ev_wm_done)
+                self._side.wait_stream(s_bh)
+                self._enqueue_replica_check()
         with torch.cuda.stream(s_bh):
             s_bh.wait_event(ev_wm_done)
             nz = noise if noise is not None else self.make_noise(B, "bh")
@@ -1518,6 +1722,8 @@ class DreamerEngine:
             self._bh_hist.append(self._ev_bh_done[par])
             if len(self._bh_hist) > self.host_ahead:
                 self._bh_hist.pop(0).synchronize()
+            if self._checks_out:                    # the verdict of `host_ahead` steps ago: complete, the same step on every rank
+                self.resolve_replica_checks(self._n_train_steps - self.host_ahead)
         return self._finish_step(rec, sync_logs)
 
     def _finish_step(self, rec: Optional[_LogRecord], sync_logs):

@@ -58,9 +58,39 @@ class DataParallel:
         return t
 
     def broadcast_(self, t: torch.Tensor, src: int = 0) -> torch.Tensor:
+        """`t` of rank `src` (a rank of this object's group) on every rank, on the caller's communicator."""
         if self.world_size > 1:
-            torch.distributed.broadcast(t, src=src, group=self.pg)
+            gsrc = torch.distributed.get_global_rank(self.pg, src) if self.pg is not None else src
+            if t.is_cuda and torch.distributed.get_backend(self.pg) == "gloo":
+                h = t.detach().cpu()                   # test transport only, as in allreduce_sum_
+                torch.distributed.broadcast(h, src=gsrc, group=self.pg)
+                t.copy_(h)
+            else:
+                torch.distributed.broadcast(t, src=gsrc, group=self.pg)
         return t
+
+    def max_min_(self, words: torch.Tensor, key: Optional[str] = None):
+        """Element-wise (max, min) over ranks of an int64 vector with ONE MAX all-reduce over [x, ~x]: bitwise NOT
+        (~x = -x - 1) reverses the signed order, so max(~x) = ~min(x).  Identical on every rank."""
+        assert words.dtype == torch.int64 and words.dim() == 1, "an int64 vector"
+        if not (self.world_size > 1 or self.force):
+            return words, words
+        n = words.numel()
+        both = torch.cat([words, ~words])
+        pg = self.groups.get(key, self.pg)
+        if both.is_cuda and torch.distributed.get_backend(pg) == "gloo":
+            h = both.cpu()                             # test transport only, as in allreduce_sum_
+            torch.distributed.all_reduce(h, op=torch.distributed.ReduceOp.MAX, group=pg)
+            both.copy_(h)
+        else:
+            torch.distributed.all_reduce(both, op=torch.distributed.ReduceOp.MAX, group=pg)
+        return both[:n], ~both[n:]
+
+    def agree(self, words: torch.Tensor, key: Optional[str] = None) -> torch.Tensor:
+        """Per position of an int64 vector: do all ranks hold the same word?  A bool vector, identical on every rank; one
+        small collective (max_min_), on the caller's communicator unless `key` names one of `groups`."""
+        hi, lo = self.max_min_(words, key)
+        return hi == lo
 
     # ---- sharding ----------------------------------------------------------------------------------------
     def shard_batch(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

@@ -961,6 +961,29 @@ int bd_replay_sample_gather(const bd_replay_sample_args* a, void* stream);
 
 size_t bd_reduce_ws_floats(void);
 
+/* ---- replica fingerprint (csrc/fingerprint.hip): are two sets of fp32 buffers bit-identical, and is anything non-finite?
+ * For each of n_buf <= BD_FP_MAX_BUFFERS buffers, ONE launch (plus a memset of `out`) writes two words to device memory,
+ * out[2 b] = hash and out[2 b + 1] = nonfinite.  For element i (0-based, 64-bit) with 32-bit pattern u, arithmetic mod 2^64:
+ *     x = u64(u) ^ ((i + 1) * 0x9E3779B97F4A7C15)
+ *     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9
+ *     x = (x ^ (x >> 27)) * 0x94D049BB133111EB
+ *     x =  x ^ (x >> 31)
+ *     hash      = sum of x over the buffer
+ *     nonfinite = number of i with (u & 0x7F800000) == 0x7F800000          (+-Inf and NaNs of any payload)
+ * Over bit patterns on purpose: -0.0 and +0.0, or two NaN payloads, differ.  The mixer is a bijection of u for a fixed i, so
+ * a change of one element always changes the hash.  The sum is commutative: the words do not depend on scheduling.
+ * A buffer needs 4-byte alignment only; n = 0 is legal (p may be NULL then) and gives (0, 0).  Asynchronous on `stream`;
+ * never allocates, never synchronises.  Bad arguments are refused before anything is enqueued. */
+#define BD_FP_MAX_BUFFERS 16
+typedef struct {
+    int n_buf;
+    struct {
+        const float* p;
+        size_t n;                 /* elements */
+    } buf[BD_FP_MAX_BUFFERS];
+} bd_fingerprint_args;
+int bd_fingerprint(const bd_fingerprint_args* a, unsigned long long* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

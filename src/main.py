@@ -176,6 +176,10 @@ def my_app(argv):
     env = Env(params) if n_envs == 1 else VecEnv(Env, params, n_envs)
     agent_cls = {"planet": Planet, "dreamer": Dreamer, "dreamerV2": DreamerV2}[params["algorithm"]]
     model = agent_cls(params, env, world_size=world)
+    if params.get("replica_sync_at_start", False) and world > 1:
+        # every rank becomes a copy of rank 0 as built and loaded (models= may exist on rank 0 only); `resume` below still
+        # restores each rank's own run state
+        model.sync_replicas(0)
     torch.manual_seed(params["seed"] + rank)
     if params["test"]:                                # evaluate the agent as built (models= loads a checkpoint) and stop
         evaluate(model, params, 0, rank)
