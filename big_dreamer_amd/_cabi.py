@@ -233,6 +233,18 @@ class FingerprintArgs(C.Structure):
     _fields_ = [("n_buf", I32), ("buf", FingerprintBuf * BD_FP_MAX_BUFFERS)]
 
 
+BD_MOMENTS_MAX_BUFFERS, BD_MOMENTS_WORDS = 16, 6
+BD_LATENT_WORDS, BD_LATENT_CAT_WORDS, BD_SEGMENTS_MAX = 15, 5, 32
+
+
+class MomentsBuf(C.Structure):
+    _fields_ = [("p", P), ("q", P), ("n", C.c_size_t)]
+
+
+class MomentsArgs(C.Structure):
+    _fields_ = [("n_buf", I32), ("buf", MomentsBuf * BD_MOMENTS_MAX_BUFFERS)]
+
+
 # every symbol include/bigdreamer_hip.h declares, with its signature
 _SIGS = {
     "bd_last_error": (C.c_char_p, []),
@@ -320,6 +332,11 @@ _SIGS = {
     "bd_colsum_ws_floats": (C.c_size_t, [I32]),
     "bd_colsum": (I32, [P, C.c_size_t, I32, P, P, P]),
     "bd_fingerprint": (I32, [C.POINTER(FingerprintArgs), P, P]),
+    "bd_diag_ws_floats": (C.c_size_t, []),
+    "bd_moments": (I32, [C.POINTER(MomentsArgs), P, P, P]),
+    "bd_latent_stats": (I32, [P, P, P, P, I32, I32, P, P, P, P]),
+    "bd_latent_stats_categorical": (I32, [P, P, I32, I32, I32, P, P, P, P, P]),
+    "bd_segment_sumsq": (I32, [P, I32, C.POINTER(C.c_size_t), P, P, P]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

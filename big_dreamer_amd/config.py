@@ -21,6 +21,13 @@ def check_replica_options(interval, policy):
     return int(interval), policy
 
 
+def check_diagnostics_interval(interval) -> int:
+    """diagnostics_interval: an integer >= 0 (0 = off), validated like replica_check_interval."""
+    if isinstance(interval, bool) or not isinstance(interval, (int, float)) or int(interval) != interval or interval < 0:
+        raise ValueError(f"diagnostics_interval={interval!r} is not an integer >= 0")
+    return int(interval)
+
+
 DEFAULT_CONFIG =os.path.join(os.path.dirname(os.path.abspath(__file__)), "conf", "config.yaml")
 
 
@@ -63,6 +70,7 @@ def load_config(overrides: List[str] = (), path: str = DEFAULT_CONFIG) -> Dict[s
     if not isinstance(cfg.get("sample_on_device", False), bool):
         raise ValueError(f"sample_on_device={cfg['sample_on_device']!r} is not a boolean")
     check_replica_options(cfg.get("replica_check_interval", 0), cfg.get("replica_on_mismatch", "raise"))
+    check_diagnostics_interval(cfg.get("diagnostics_interval", 0))
     if not isinstance(cfg.get("replica_sync_at_start", False), bool):
         raise ValueError(f"replica_sync_at_start={cfg['replica_sync_at_start']!r} is not a boolean")
     return cfg

@@ -4,6 +4,7 @@
 #include "bd_device.h"
 #include "bd_host.h"
 #include "bd_discrete.h"
+#include "bd_latent.h"
 
 namespace bd {
 
@@ -67,14 +68,6 @@ __global__ __launch_bounds__(256) void bernoulli_nll_kernel(const float* __restr
     }
     s = block_sum_d(s, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-
-// torch.distributions.kl._kl_normal_normal
-__device__ __forceinline__ float kl_elem(float qm, float qs, float pm, float ps) {
-    const float ratio = qs / ps;
-    const float vr = ratio * ratio;
-    const float t = (qm - pm) / ps;
-    return 0.5f * (vr + t * t - 1.f - logf(vr));
 }
 
 __global__ __launch_bounds__(256) void kl_fwd_kernel(const float* __restrict__ qm, const float* __restrict__ qs,
@@ -322,41 +315,7 @@ __global__ __launch_bounds__(256) void polyak_kernel(float* __restrict__ t, cons
         t[i] = s[i] * w + t[i] * (1.f - w);
 }
 
-// ---- Categorical latents (CategoricalBeliefModel, src/models.py:101-117; KL branch src/dreamer.py:102-106,131-144) ----
-// rows x D groups of C classes (reference: 32 x 32).  A 32-lane half wave owns one group; a lane holds classes
-// c = l, l+32, ... (C <= 128).  Reductions are xor-shuffles with offsets < 32, which stay inside the half wave.
-constexpr int kCatPer = 4;     // classes per lane
-
-__device__ __forceinline__ float half_max(float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float half_sum(float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// normalised log-probabilities of one group, as Categorical(logits=...) keeps them: x - logsumexp(x)
-// (torch/distributions/categorical.py); lp[i] is class l + 32 i (-inf beyond C)
-__device__ __forceinline__ void group_log_softmax(const float* __restrict__ x, int C, int l, float (&lp)[kCatPer]) {
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < kCatPer; ++i) {
-        const int c = l + 32 * i;
-        lp[i] = c < C ? x[c] : -INFINITY;
-        m = fmaxf(m, lp[i]);
-    }
-    m = half_max(m);
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < kCatPer; ++i) s += (l + 32 * i < C) ? expf(lp[i] - m) : 0.f;
-    const float lse = m + logf(half_sum(s));
-#pragma unroll
-    for (int i = 0; i < kCatPer; ++i) lp[i] -= lse;
-}
-
+// ---- Categorical latents: the group layout, log-softmax and KL of a group are in bd_latent.h ----
 // state = one_hot(argmax(probs / q)) with q ~ Exp(1): torch.multinomial's single-draw path (ATen
 // native/Distributions.cpp: `q = empty_like(probs).exponential_(1); argmax(probs / q)`), reached from
 // OneHotCategoricalStraightThrough.rsample(); the straight-through term probs - probs.detach() is exactly zero.
@@ -426,23 +385,6 @@ __global__ __launch_bounds__(256) void cat_head_bwd_kernel(const float* __restri
             if (c < C) dlogits[base + c] = pr[i] * (gr[i] - dot);
         }
     }
-}
-
-// KL(q || p) of one group from normalised log-probabilities (torch.distributions.kl._kl_categorical_categorical:
-// t = q.probs * (q.logits - p.logits); t[p.probs == 0] = inf; t[q.probs == 0] = 0)
-__device__ __forceinline__ float group_kl(const float (&lq)[kCatPer], const float (&lp)[kCatPer], int C, int l) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < kCatPer; ++i) {
-        if (l + 32 * i < C) {
-            const float qv = expf(lq[i]), pv = expf(lp[i]);
-            float t = qv * (lq[i] - lp[i]);
-            if (pv == 0.f) t = INFINITY;
-            if (qv == 0.f) t = 0.f;
-            s += t;
-        }
-    }
-    return half_sum(s);
 }
 
 // unit of work = one group (balanced form: mean over all rows x D groups) or one row (sum form: max(sum_D, free_nats))

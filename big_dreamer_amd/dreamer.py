@@ -86,7 +86,8 @@ class Dreamer:
         self.engine = DreamerEngine(self.dims, _hp_from_params(params), self.device, world_size=world_size,
                                     process_group=process_group,
                                     replica_check_interval=params.get("replica_check_interval", 0),
-                                    replica_on_mismatch=params.get("replica_on_mismatch", "raise"))
+                                    replica_on_mismatch=params.get("replica_on_mismatch", "raise"),
+                                    diagnostics_interval=params.get("diagnostics_interval", 0))
         e = self.engine
         # PyTorch-default initialisation happens in the nn.Modules below (their parameters alias the engine's
         # flat buffers), so seeding torch before construction reproduces a run (src/main.py:56-58).
@@ -250,13 +251,21 @@ class Dreamer:
         batch = {"observations": obs, "actions": actions, "rewards": rewards, "nonterminals": nonterminals}
         if os.environ.get("BD_LAZY_LOGS", "1") == "0":       # eager: every call waits for the GPU, like the reference's .item()
             logs = self.engine.train_step(batch)
-            return {k: v for k, v in logs.items() if not k.startswith("grad_norm")}
+            return {k: v for k, v in logs.items() if not k.startswith("grad_norm_")}
         # Lazy mapping with the reference's keys: values are fetched when a key is first read, so the collect loop's burst
         # `for _ in range(collect_interval): logs = model.train_step()` (src/main.py:105-108) keeps the cross-step
         # pipeline full and only the dict it actually reads waits for the device.
         logs = self.engine.train_step(batch, sync_logs="lazy")
-        logs._drop = ("grad_norm",)
+        logs._drop = ("grad_norm_",)        # the optimisers' totals; the per-module "grad_norm/<module>" of a diagnosed step stay
         return logs
+
+    def set_diagnostics(self, interval: int = 0) -> None:
+        """Training diagnostics in the log dict of every `interval`-th train step (0 = off; diagnostics.py has the keys)."""
+        self.engine.set_diagnostics(interval)
+
+    @property
+    def diagnostics_interval(self) -> int:
+        return self.engine.diagnostics_interval
 
     def update_critic(self) -> None:
         self.engine.update_critic()

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _cabi as cabi
+from . import diagnostics
 from .config import check_replica_options
 from .parallel import DataParallel
 from .params import ParamGroup, _adam_state_dict, _load_adam_state_dict
@@ -118,6 +119,9 @@ class _LogRecord:
         self.counts: Optional[dict] = None
         self.owner = None          # weakref to the LazyLogs handed to the caller
         self.need = (0, 1, 2)
+        # diagnosed steps only: pinned copy of the step's diagnostic block, a region per phase behind the same three events
+        self.diag: Optional[torch.Tensor] = None
+        self.diag_mem: Optional[torch.Tensor] = None
 
 
 class LazyLogs(collections.abc.MutableMapping):
@@ -158,6 +162,43 @@ class LazyLogs(collections.abc.MutableMapping):
 
     def __repr__(self):
         return repr(dict(self.items()))
+
+
+class _Diagnostics:
+    """Device side of the training diagnostics ("Training diagnostics"), built when the interval is first set
+    above 0: the diagnostic block (diagnostics.Layout), one reduction workspace per phase stream, and the per-module
+    segment tables of the three optimisers' flat buffers."""
+
+    def __init__(self, eng: "DreamerEngine"):
+        d = eng.d
+        segs = {g: eng.groups[g].module_segments() for g in diagnostics.REGIONS}
+        self.lay = diagnostics.Layout(d.categorical, d.cat_D if d.categorical else d.S, d.cat_C, True, d.discrete_actions,
+                                      d.A, {g: names for g, (names, _) in segs.items()})
+        self.block = torch.zeros(self.lay.size, dtype=torch.float64, device=eng.dev)
+        n_ws = int(lib.bd_diag_ws_floats())
+        self.ws = {g: torch.zeros(n_ws, dtype=torch.float32, device=eng.dev) for g in diagnostics.REGIONS}
+        self.offsets = {g: (C.c_size_t * len(offs))(*offs) for g, (_, offs) in segs.items()}
+        self.n_seg = {g: len(names) for g, (names, _) in segs.items()}
+        self.colsum_ws = (torch.zeros(int(lib.bd_colsum_ws_floats(d.A)), dtype=torch.float32, device=eng.dev)
+                          if d.discrete_actions else None)
+
+    def at(self, field: str, word: int = 0) -> int:
+        """Device address of double `word` of a field of the block."""
+        return self.block.data_ptr() + 8 * (self.lay.fields[field][0] + word)
+
+    def moments(self, group: str, field: str, entries) -> None:
+        """One bd_moments launch on the current stream: entries = [(p, q or None), ...] -> consecutive sextuples of `field`."""
+        a = cabi.MomentsArgs()
+        a.n_buf = len(entries)
+        for i, (p, q) in enumerate(entries):
+            a.buf[i].p, a.buf[i].q, a.buf[i].n = ptr(p), ptr(q), p.numel()
+        cabi.check(lib.bd_moments(C.byref(a), self.at(field), ptr(self.ws[group]), cabi.stream()))
+
+    def norms(self, group: str, g: ParamGroup) -> None:
+        """Per-module sums of squares of the group's gradient and weights, on the current stream."""
+        for field, buf in (("gsq_", g.grad), ("wsq_", g.flat)):
+            cabi.check(lib.bd_segment_sumsq(ptr(buf), self.n_seg[group], self.offsets[group], self.at(field + group),
+                                            ptr(self.ws[group]), cabi.stream()))
 
 
 class WgradBatch:
@@ -246,9 +287,16 @@ def _parse_bh_chunks(text: str):
 class DreamerEngine:
     def __init__(self, dims: Dims, hp: Optional[dict] = None, device="cuda", params: Optional[dict] = None,
                  world_size: int = 1, process_group=None, phase_groups: Optional[dict] = None,
-                 replica_check_interval: int = 0, replica_on_mismatch: str = "raise"):
+                 replica_check_interval: int = 0, replica_on_mismatch: str = "raise", diagnostics_interval: int = 0):
         self.d = dims
         self.set_replica_check(replica_check_interval, replica_on_mismatch)
+        # training diagnostics ("Training diagnostics"): nothing is built, launched or logged while the interval is 0
+        self.diagnostics_interval = diagnostics.check_interval(diagnostics_interval)
+        self._diag: Optional[_Diagnostics] = None
+        self._diag_now = False               # the step being queued is a diagnosed one
+        self._diag_regions: Tuple[str, ...] = ()      # the regions the latest step filled (eager logs)
+        self._n_wm_steps = 0                 # world_model_step calls (PlaNet): its cadence counter
+        self._diag_keys: Tuple[str, ...] = ()         # the diagnostic keys of the latest eager log dict
         self.pixel = bool(dims.pixel)   # 64x64 pixel observations: conv encoder / decoder on csrc/conv.hip (conv_stack.py)
         self.hp = dict(DEFAULT_HP)
         if hp:
@@ -659,9 +707,10 @@ class DreamerEngine:
         self.dp.allreduce_sum_(t, key)
 
     def optimizer_step(self, group: str, slot: int, lr: float, red_ws: Optional[torch.Tensor] = None,
-                       rec: Optional[_LogRecord] = None) -> None:
+                       rec: Optional[_LogRecord] = None, diag: Optional[bool] = None) -> None:
         """all-reduce (data-parallel) + global-norm clip + Adam + re-pack of one optimiser, on the current stream.
-        `rec`: log record that receives this phase's snapshot of the scalar board (lazy logs)."""
+        `rec`: log record that receives this phase's snapshot of the scalar board (lazy logs); `diag`: whether the step
+        this update belongs to is a diagnosed one (None: the step being queued)."""
         g = self.groups[group]
         red_ws = self.red_ws if red_ws is None else red_ws
         if group in self._fp_wait:           # a periodic fingerprint read these buffers on another stream: write after it
@@ -675,6 +724,8 @@ class DreamerEngine:
             lr = ov.get("lr", lr)
         eps, wd = (ov or {}).get("eps", hp["adam_epsilon"]), (ov or {}).get("weight_decay", hp["weight_decay"])
         cabi.check(lib.bd_sumsq(ptr(g.grad), g.numel, ptr(self.scalars), slot, ptr(red_ws), cabi.stream()))
+        if self._diag_now if diag is None else diag:
+            self._diag.norms(group, g)       # the gradient the clip sees (reduced over ranks), the weights before the update
         cabi.check(lib.bd_adam_step(ptr(g.flat), ptr(g.grad), ptr(g.m), ptr(g.v), g.numel, lr, 0.9, 0.999,
                                     eps, wd, g.step, hp["grad_clip_norm"],
                                     ptr(self.scalars), slot, cabi.stream()))
@@ -697,6 +748,11 @@ class DreamerEngine:
                 owner.resolve()
         rec.events = [None, None, None]
         rec.owner, rec.counts = None, None
+        rec.diag = None
+        if self._diag_now:
+            if rec.diag_mem is None or rec.diag_mem.numel() != self._diag.lay.size:
+                rec.diag_mem = torch.zeros(self._diag.lay.size, dtype=torch.float64).pin_memory()
+            rec.diag = rec.diag_mem
         return rec
 
     def _snapshot(self, rec: _LogRecord, row: int) -> None:
@@ -705,6 +761,9 @@ class DreamerEngine:
         rec.host[row, :N_SLOTS].copy_(self.scalars, non_blocking=True)
         if row == 0 and self._obs_ws is not None and self._obs_err_off is not None:
             rec.host[row, N_SLOTS:].copy_(self._cluster_error_word(), non_blocking=True)
+        if rec.diag is not None:
+            lo, hi = self._diag.lay.region[diagnostics.REGIONS[row]]
+            rec.diag[lo:hi].copy_(self._diag.block[lo:hi], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         rec.events[row] = ev
@@ -731,7 +790,10 @@ class DreamerEngine:
         for slot in (SLOT_VAL, SLOT_GN_CRITIC):
             s[slot] = h[2, slot]
         self._raise_on_cluster_error(int(h[0, N_SLOTS:].view(np.uint32)[0]))
-        return self._logs_from(s, rec.counts)
+        out = self._logs_from(s, rec.counts)
+        if rec.diag is not None:
+            out.update(diagnostics.entries(rec.diag.numpy(), self._diag.lay, rec.counts["N"], rec.counts["Mi"]))
+        return out
 
     def _cluster_error_word(self) -> torch.Tensor:
         """The sticky error word of the cluster scans as one float32-typed element (bit pattern of the uint32 word).
@@ -775,6 +837,22 @@ class DreamerEngine:
         """The periodic check of train_step: every `interval`-th step (0 = off); a mismatch raises ReplicaMismatch
         ("raise") or warns once and broadcasts rank 0's state ("resync").  Every rank sets the same values."""
         self.replica_check_interval, self.replica_on_mismatch = check_replica_options(interval, on_mismatch)
+
+    def set_diagnostics(self, interval: int = 0) -> None:
+        """Training diagnostics on every `interval`-th train step (0 = off): the steps whose count so far is a multiple of
+        `interval`, i.e. the next one if the count is.  Data-parallel: every rank sets the same value (no collective is
+        involved, but the diagnosed step should be the same one)."""
+        self.diagnostics_interval = diagnostics.check_interval(interval)
+        if self.diagnostics_interval and self._diag is None:
+            self._diag = _Diagnostics(self)
+
+    def _diagnostics_due(self, count: int) -> bool:
+        k = self.diagnostics_interval
+        if k <= 0:
+            return False
+        if self._diag is None:
+            self._diag = _Diagnostics(self)
+        return count % k == 0
 
     def _fp_table(self):
         if self._fp is None:
@@ -1618,7 +1696,8 @@ class DreamerEngine:
         front of the KL / world-model all-reduces of step k+1 and stall dynamics learning k+1 half-way.  Deferred, the
         order per host step is kl, model (k+1), actor, critic (k): each is ready by the time its turn comes."""
         if self.pipeline and self.defer_opt:
-            self._pending_opt.append((span, group, slot, lr, red_ws, torch.cuda.current_stream(), self._cur_rec))
+            self._pending_opt.append((span, group, slot, lr, red_ws, torch.cuda.current_stream(), self._cur_rec,
+                                      self._diag_now))
             return
         with self.span(span):
             self.optimizer_step(group, slot, lr, red_ws)
@@ -1631,10 +1710,10 @@ class DreamerEngine:
         only one rank makes (e.g. rank 0 rendering a video with observation_model, src/main.py:244) cannot reorder the
         ranks' collectives on the shared communicator."""
         pend, self._pending_opt = self._pending_opt, []
-        for span, group, slot, lr, red_ws, stream, rec in pend:
+        for span, group, slot, lr, red_ws, stream, rec, diag in pend:
             with torch.cuda.stream(stream):
                 with self.span(span):
-                    self.optimizer_step(group, slot, lr, red_ws, rec)
+                    self.optimizer_step(group, slot, lr, red_ws, rec, diag)
 
     _flush_pending_opt = flush_optimizers
 
@@ -1658,6 +1737,8 @@ class DreamerEngine:
         obs = batch["observations"]
         B = obs.shape[1]
         self._timer_tick += 1
+        self._diag_now = self._diagnostics_due(self._n_train_steps)
+        self._diag_regions = diagnostics.REGIONS if self._diag_now else ()
         self._n_train_steps += 1
         lazy = sync_logs == "lazy"
         rec = self._cur_rec = self._new_record() if lazy else None
@@ -1743,13 +1824,17 @@ class DreamerEngine:
         obs = batch["observations"]
         T, B = obs.shape[0] - 1, obs.shape[1]
         self._timer_tick += 1
+        self._diag_now = self._diagnostics_due(self._n_wm_steps)
+        self._diag_regions = ("model",) if self._diag_now else ()
+        self._n_wm_steps += 1
         self._dynamics_phase(batch, noise if noise is not None else self.make_noise(B, "wm"), "")
         self._counts = dict(N=T * B, Mi=1, S=(self.d.cat_D if self.d.categorical else self.d.S),
                             sum_form=int(self.hp["kl_balance"] == -1))
         if not sync_logs:
             return {}
-        return {k: v for k, v in self.logs().items() if k in ("observation_loss", "reward_loss", "kl_loss", "model_loss",
-                                                              "grad_norm_model")}
+        keep = ("observation_loss", "reward_loss", "kl_loss", "model_loss", "grad_norm_model")
+        logs = self.logs()
+        return {k: v for k, v in logs.items() if k in keep or k in self._diag_keys}
 
     def _dynamics_phase(self, batch: Dict[str, torch.Tensor], noise: Dict[str, torch.Tensor], feat_tag: str) -> torch.Tensor:
         """Dynamics learning (src/dreamer.py:263-302) on the current stream; returns the posterior features.  `w`, this
@@ -1797,6 +1882,15 @@ class DreamerEngine:
         else:
             cabi.check(lib.bd_kl_forward(ptr(qm), ptr(qs), ptr(pm), ptr(ps), N, d.S, hp["free_nats"], sum_form, sc, SLOT_KL,
                                          ws, st))
+        if self._diag_now:          # the latents and rewards of this rank's shard, while they are live (no collective)
+            dg = self._diag
+            if cat:
+                cabi.check(lib.bd_latent_stats_categorical(ptr(qm), ptr(pm), N, d.cat_D, d.cat_C, dg.at("latent"),
+                                                           dg.at("kl_cols"), dg.at("used"), ptr(dg.ws["model"]), st))
+            else:
+                cabi.check(lib.bd_latent_stats(ptr(qm), ptr(qs), ptr(pm), ptr(ps), N, d.S, dg.at("latent"), dg.at("kl_cols"),
+                                               ptr(dg.ws["model"]), st))
+            dg.moments("model", "mom_wm", [(rewards[:-1], None), (rw_out, None)])
         if W > 1 and not sum_form:                          # the free-nats clamp acts on the GLOBAL mean
             self._kl_local = self.scalars[SLOT_KL:SLOT_KL + 1].clone()
             self._allreduce(self.scalars[SLOT_KL:SLOT_KL + 1], "model")
@@ -2010,7 +2104,8 @@ class DreamerEngine:
             dconst=-inv_mi if mix is None else -mix * inv_mi,
             dentropy=-hp["entropy_weight"] * inv_mi if hp["entropy_weight"] != -1 else 0.0,
             cur=torch.cuda.current_stream(), st=cabi.stream(), sc=ptr(self.scalars), ws=ptr(red_ws),
-            start_sidx=self._buf[ptag + "sidx"] if d.categorical else None, wts=None, dret=None, ev_ov=None, ev_ret=None)
+            start_sidx=self._buf[ptag + "sidx"] if d.categorical else None, wts=None, dret=None, ev_ov=None, ev_ret=None,
+            diag=self._diag_now)
         s.act_us = self.buf("act_us", Mi, 2 * d.A) if mix is not None and not d.discrete_actions else None
         if dyn:
             s.d_r, s.d_v, s.difeat = self.buf("d_ir_out", Mi), self.buf("d_iv_out", Mi), self.buf("difeat", Mi, F)
@@ -2098,6 +2193,12 @@ class DreamerEngine:
                 self.scalars[SLOT_WOBJ] = (wts * (returns + ew_ * ent)).sum()
             else:       # the REINFORCE part of the objective joins in _logs_from (SLOT_RF)
                 self.scalars[SLOT_WOBJ] = (wts * (mix * returns + ew_ * ent)).sum()
+        if self._diag_now:
+            dg = self._diag
+            dg.moments("actor", "mom_bh", [(s.r_out, None), (s.v_out, None), (returns, None)]
+                       + ([] if self.d.discrete_actions else [(s.act, None)]))
+            if self.d.discrete_actions:     # one-hot actions: their column sums are the class counts
+                cabi.check(lib.bd_colsum(ptr(s.act), Mi, self.d.A, dg.at("act_freq"), ptr(dg.colsum_ws), st))
         if s.par is not None:
             s.ev_ret = torch.cuda.Event()
             s.ev_ret.record(torch.cuda.current_stream())
@@ -2206,6 +2307,8 @@ class DreamerEngine:
             d_c = self.buf("d_ic_out", Mi, 1)
             cabi.check(lib.bd_normal_nll(ptr(c_out), 1, ptr(returns), 1, Mi, 1, s.inv_mi, ptr(d_c), 1, s.sc, SLOT_VAL, ptr(red_ws),
                                          cabi.stream()))
+            if s.diag:
+                self._diag.moments("critic", "mom_cr", [(c_out, None), (returns, c_out)])
             if wts is not None:     # use_discount=True: -(discount * log_prob).mean() (src/dreamer.py:378-379)
                 d_c.view(Mi).mul_(wts)
                 diff = c_out.view(Mi) - returns
@@ -2257,7 +2360,18 @@ class DreamerEngine:
             s = both[:N_SLOTS].astype(np.float32)
         else:
             s = self.scalars.cpu().numpy().astype(np.float32)
-        return self._logs_from(s, self._counts)
+        out = self._logs_from(s, self._counts)
+        self._diag_keys = ()
+        if self._diag_regions:
+            extra = self._diagnostic_entries()
+            self._diag_keys = tuple(extra)
+            out.update(extra)
+        return out
+
+    def _diagnostic_entries(self) -> Dict[str, object]:
+        """Eager logs of a diagnosed step: the block is read where the scalar board is (after join())."""
+        return diagnostics.entries(self._diag.block.cpu().numpy(), self._diag.lay, self._counts["N"], self._counts["Mi"],
+                                   self._diag_regions)
 
     def _logs_from(self, s: np.ndarray, c: dict) -> Dict[str, float]:
         hp = self.hp

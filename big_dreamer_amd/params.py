@@ -49,6 +49,18 @@ class ParamGroup:
                 self.gs[(mod, name)], self.g[(mod, name)] = views(self.grad)
             off += al(k)
 
+    def module_segments(self) -> Tuple[List[str], List[int]]:
+        """The modules of the group in storage order and the n + 1 element offsets of their contiguous stretches of the flat
+        buffers (pad floats belong to the module they follow; the last stretch ends at `numel`)."""
+        names: List[str] = []
+        offsets: List[int] = []
+        for mod, name, _ in self.specs:
+            if not names or names[-1] != mod:
+                assert mod not in names, f"module {mod} is not contiguous in the flat buffer"
+                names.append(mod)
+                offsets.append(self._layout[(mod, name)][0])
+        return names, offsets + [self.numel]
+
     def logical(self, buf: torch.Tensor, mod: str, name: str) -> torch.Tensor:
         """View of `buf` (a flat buffer laid out like `flat`: grad, m, v) with the reference's shape of (mod, name)."""
         off, k, sshape, perm = self._layout[(mod, name)]

@@ -36,7 +36,7 @@ class Planet(Dreamer):
         obs, actions, rewards, nonterminals = self.buffer.sample(self.batch_size, self.seq_len)
         logs = self.engine.world_model_step({"observations": obs, "actions": actions, "rewards": rewards,
                                              "nonterminals": nonterminals})
-        return {k: v for k, v in logs.items() if not k.startswith("grad_norm")}
+        return {k: v for k, v in logs.items() if not k.startswith("grad_norm_")}
 
     def update_critic(self) -> None:
         raise NotImplementedError("PlaNet has no critic (src/main.py:110 updates it for dreamer / dreamerV2 only)")

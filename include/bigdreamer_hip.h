@@ -984,6 +984,57 @@ typedef struct {
 } bd_fingerprint_args;
 int bd_fingerprint(const bd_fingerprint_args* a, unsigned long long* out, void* stream);
 
+/* ---- training diagnostics (csrc/diag.hip): statistics of buffers a train step holds anyway, reduced on the device.
+ * Common to the four entry points: asynchronous on `stream`, never allocate, never synchronise; bad arguments are refused
+ * before anything is enqueued.  Deterministic: every workgroup writes fp64 partials into `ws`, a second launch combines them
+ * in a fixed order (no floating-point atomics).  Per-element terms are fp32 with the formulas of the loss kernels
+ * (bd_kl_forward, bd_kl_categorical_forward), accumulation is fp64, results are doubles; nothing but `out`, `colsum`, `used`
+ * and `ws` is written.  fp32 inputs need 4-byte alignment, `out` / `colsum` / `ws` 8-byte alignment.
+ * ws: bd_diag_ws_floats() floats, private to the stream while a call is in flight.
+ *
+ * A "moments sextuple" of a set of fp32 values is six doubles: the number of finite values, their sum, their sum of squares
+ * (each square formed in fp64), their minimum (+Inf if none), their maximum (-Inf if none), and the number of non-finite values. */
+size_t bd_diag_ws_floats(void);
+
+/* bd_moments: out[6 b ..] = sextuple of entry b, b < n_buf <= BD_MOMENTS_MAX_BUFFERS.  Element i of an entry is p[i], or the
+ * fp32 difference p[i] - q[i] when q is not NULL.  n = 0 is legal (p may be NULL) and gives 0, 0, 0, +Inf, -Inf, 0. */
+#define BD_MOMENTS_MAX_BUFFERS 16
+#define BD_MOMENTS_WORDS 6
+typedef struct {
+    int n_buf;
+    struct {
+        const float* p;
+        const float* q;           /* NULL: the values are p[i] */
+        size_t n;                 /* elements */
+    } buf[BD_MOMENTS_MAX_BUFFERS];
+} bd_moments_args;
+int bd_moments(const bd_moments_args* a, double* out, float* ws, void* stream);
+
+/* bd_latent_stats: Gaussian posterior N(qm, qs) and prior N(pm, ps), each [rows x S] dense.  out (BD_LATENT_WORDS doubles):
+ *   out[0] = sum over rows and j of 0.5 ln(2 pi e) + ln qs            (posterior entropy)
+ *   out[1] = the same for ps                                          (prior entropy)
+ *   out[2] = sum over rows and j of KL_j = ln(ps / qs) + (qs^2 + (qm - pm)^2) / (2 ps^2) - 1/2    (raw: no free nats, no balancing)
+ *   out[3..8] = sextuple of qs, out[9..14] = sextuple of ps
+ * colsum[j] = sum over rows of KL_j (S doubles). */
+#define BD_LATENT_WORDS 15
+int bd_latent_stats(const float* qm, const float* qs, const float* pm, const float* ps, int rows, int S, double* out,
+                    double* colsum, float* ws, void* stream);
+
+/* bd_latent_stats_categorical: logits [rows x D x C] of posterior q and prior p (softmax per factor), 1 <= C <= 128 as
+ * bd_kl_categorical_forward.  out (BD_LATENT_CAT_WORDS doubles), each a sum over rows and factors d:
+ *   out[0] = H(q_d), out[1] = H(p_d), out[2] = KL(q_d || p_d) (0 ln 0 = 0), out[3] = max_c q, out[4] = max_c p
+ * colsum[d] = sum over rows of KL(q_d || p_d) (D doubles).  used[d C + c] (D*C 32-bit words) is 1 iff some row's posterior
+ * argmax of factor d is class c (the first maximum wins on ties), else 0. */
+#define BD_LATENT_CAT_WORDS 5
+int bd_latent_stats_categorical(const float* post_logits, const float* prior_logits, int rows, int D, int C, double* out,
+                                double* colsum, unsigned* used, float* ws, void* stream);
+
+/* bd_segment_sumsq: out[s] = sum of x[i]^2 (squares in fp64) over offsets[s] <= i < offsets[s + 1], s < n_seg <=
+ * BD_SEGMENTS_MAX.  `offsets` is a HOST array of n_seg + 1 non-decreasing element indices (read before the call returns);
+ * empty segments give 0. */
+#define BD_SEGMENTS_MAX 32
+int bd_segment_sumsq(const float* x, int n_seg, const size_t* offsets, double* out, float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

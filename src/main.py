@@ -136,7 +136,8 @@ def collect_many(model, env, params, rank, world):
         if any(s % params["log_freq"] == 0 for s in steps) and rank == 0:
             logs["env_update_per_sec"] = (step + n - logged) / max(time.time() - past, 1e-9)
             past, logged = time.time(), step + n
-            print(step, {k: (round(v, 5) if isinstance(v, float) else v) for k, v in logs.items()}, flush=True)
+            print(step, {k: (round(v, 5) if isinstance(v, float) else v) for k, v in logs.items()
+                         if not isinstance(v, (list, tuple))}, flush=True)      # (list-valued diagnostics are left out)
         if params["evaluation"] and any(s % params["test_interval"] == 0 for s in steps):
             evaluate(model, params, step, rank)
         if params["openl_freq"] > 0 and rank == 0 and any(s % params["openl_freq"] == 0 for s in steps):
@@ -218,7 +219,8 @@ def my_app(argv):
         if step % params["log_freq"] == 0 and rank == 0:
             logs["env_update_per_sec"] = params["log_freq"] / max(time.time() - past, 1e-9)
             past = time.time()
-            print(step, {k: (round(v, 5) if isinstance(v, float) else v) for k, v in logs.items()}, flush=True)
+            print(step, {k: (round(v, 5) if isinstance(v, float) else v) for k, v in logs.items()
+                         if not isinstance(v, (list, tuple))}, flush=True)      # (list-valued diagnostics are left out)
         if params["evaluation"] and step % params["test_interval"] == 0:
             evaluate(model, params, step, rank)
         if params["openl_freq"] > 0 and rank == 0 and step % params["openl_freq"] == 0:
