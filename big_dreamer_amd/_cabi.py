@@ -53,7 +53,7 @@ class LayerBwd(C.Structure):
 class MlpBwdArgs(C.Structure):
     _fields_ = [("M", I32), ("dout", P), ("lddo", I32), ("dout_scale", F32), ("n_layers", I32),
                 ("layer", LayerBwd * BD_MAX_LAYERS), ("din0", P), ("ld0", I32), ("w0", I32),
-                ("din1", P), ("ld1", I32), ("w1", I32), ("accumulate", I32), ("form_M", I32)]
+                ("din1", P), ("ld1", I32), ("w1", I32), ("accumulate", I32)]
 
 
 BD_HEAD_HIDDEN = 4
@@ -125,8 +125,7 @@ class ImagineBwdArgs(C.Structure):
          "wt_p2s"]) + [("wt_a", P * 3)] + _ptr_fields(
         ["wt_a4m", "wt_a4s", "start_feat", "feat", "prior_std", "action", "eps_action", "eps_prior", "sv_actor",
          "sv_act_stats", "sv_x", "sv_gates", "sv_p"]) + [("min_std", F32)] + _ptr_fields(["dfeat"]) + [
-        ("dentropy", F32)] + _ptr_fields(["d_actor_pre", "d_actor_out", "ent_weight"]) + [("discrete_actions", I32),
-        ("t_begin", I32), ("t_end", I32)] + _ptr_fields(["d_carry_in", "d_carry_out"]))
+        ("dentropy", F32)] + _ptr_fields(["d_actor_pre", "d_actor_out", "ent_weight"]) + [("discrete_actions", I32)])
 
 
 U8P = C.c_void_p

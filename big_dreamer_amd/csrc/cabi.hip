@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void gather_pixels_kernel(const unsigned char*
 extern "C" {
 
 const char* bd_last_error(void) { return bd::err_buf(); }
-int bd_version(void) { return 1; }
+int bd_version(void) { return 2; }
 
 size_t bd_packed_floats(int N, int K) { return (size_t)bd::cdiv(N, 16) * bd::cdiv(K, 16) * 256; }
 

@@ -395,27 +395,14 @@ __global__ __launch_bounds__(kThreads) void imagine_bwd_kernel(bd_imagine_bwd_ar
     float* ds_plain = dAr + na;   // [16][S]
     float* scratch = ds_plain + 16 * a.S;   // split-K partials (kSplitScratchFloats)
 
-    // The gradient carry of the recurrence: zero behind the last step of the rollout, or -- a launch over the window
-    // [t_begin, t_end) with t_end < Hm -- what the launch over the later steps left in d_carry_in (row-major
-    // [N x (Be+S)]: d belief | d state).  Plain copies; padded rows and columns are zero either way.
-    if (a.d_carry_in == nullptr) {
-        for (int i = threadIdx.x; i < nh; i += blockDim.x) dhc[i] = 0.f;
-        for (int i = threadIdx.x; i < 16 * a.S; i += blockDim.x) ds_plain[i] = 0.f;
-    } else {
-        for (int i = threadIdx.x; i < 16 * d.Kb_h * 16; i += blockDim.x) {
-            const int r = i / (d.Kb_h * 16), k = i - r * (d.Kb_h * 16);
-            dhc[frag_idx(r, k)] = (row0 + r < a.N && k < a.Be) ? a.d_carry_in[(size_t)(row0 + r) * F + k] : 0.f;
-        }
-        for (int i = threadIdx.x; i < 16 * a.S; i += blockDim.x) {
-            const int r = i / a.S, k = i - r * a.S;
-            ds_plain[i] = (row0 + r < a.N) ? a.d_carry_in[(size_t)(row0 + r) * F + a.Be + k] : 0.f;
-        }
-    }
+    // The gradient carry of the recurrence (d belief | d state) is zero behind the last step of the rollout.
+    for (int i = threadIdx.x; i < nh; i += blockDim.x) dhc[i] = 0.f;
+    for (int i = threadIdx.x; i < 16 * a.S; i += blockDim.x) ds_plain[i] = 0.f;
     lds_barrier();
 
     const size_t act_stride = (size_t)a.Hm * a.N * a.Hd;
 
-    for (int t = a.t_end - 1; t >= a.t_begin; --t) {     // (the host resolves t_begin = t_end = 0 to [0, Hm))
+    for (int t = a.Hm - 1; t >= 0; --t) {
         const size_t tn = (size_t)t * a.N;
         const int tid = bd_tid();                   // opaque: nothing thread-dependent leaves this step (bd_tid)
         const int lane = tid & 63, wave = bd_wave(tid);
@@ -625,18 +612,6 @@ __global__ __launch_bounds__(kThreads) void imagine_bwd_kernel(bd_imagine_bwd_ar
         }
         BD_STAMP(26);
     }
-    // hand the carry to the launch over the earlier steps (every step ends behind a barrier: dhc / ds_plain are complete)
-    BD_KARGS_FRESH(ap);
-    if (a.d_carry_out != nullptr) {
-        for (int i = threadIdx.x; i < 16 * d.Kb_h * 16; i += blockDim.x) {
-            const int r = i / (d.Kb_h * 16), k = i - r * (d.Kb_h * 16);
-            if (row0 + r < a.N && k < a.Be) a.d_carry_out[(size_t)(row0 + r) * F + k] = dhc[frag_idx(r, k)];
-        }
-        for (int i = threadIdx.x; i < 16 * a.S; i += blockDim.x) {
-            const int r = i / a.S, k = i - r * a.S;
-            if (row0 + r < a.N) a.d_carry_out[(size_t)(row0 + r) * F + a.Be + k] = ds_plain[i];
-        }
-    }
 #undef a
 }
 
@@ -728,23 +703,13 @@ int bd_imagine_backward(const bd_imagine_bwd_args* a, void* stream) {
                    a->sv_act_stats && a->sv_x && a->sv_gates && a->sv_p && a->dfeat,
                "bd_imagine_backward: missing forward tensors");
     BD_REQUIRE(a->d_actor_out, "bd_imagine_backward: missing outputs");
-    // the window of time steps: 0 / 0 = the whole rollout.  Every [Hm x ...] array (d_actor_pre's layers, Hm*N*Hd floats
-    // apart, included) keeps its whole-rollout indexing, so the launches of one rollout get the same pointers.
-    bd_imagine_bwd_args w = *a;
-    if (w.t_begin == 0 && w.t_end == 0) w.t_end = w.Hm;
-    BD_REQUIRE(0 <= w.t_begin && w.t_begin < w.t_end && w.t_end <= w.Hm,
-               "bd_imagine_backward: bad window [t_begin = %d, t_end = %d) of Hm = %d steps", a->t_begin, a->t_end, a->Hm);
-    BD_REQUIRE((w.d_carry_in != nullptr) == (w.t_end < w.Hm),
-               "bd_imagine_backward: d_carry_in is needed exactly when t_end < Hm (t_end = %d, Hm = %d)", w.t_end, w.Hm);
-    BD_REQUIRE((w.d_carry_out != nullptr) == (w.t_begin > 0),
-               "bd_imagine_backward: d_carry_out is needed exactly when t_begin > 0 (t_begin = %d)", w.t_begin);
     const ImgDims d(a->Be, a->S, a->A, a->Hd);
     // (the backward kernels have no element-wise Gaussian head: the split-K partials alone)
     const size_t lds = ((size_t)(6 * d.Kb_h + 3 * d.Kb_hd + 2 * d.Kb_s + 2 * d.Kb_a) * kFragFloats + 16 * a->S +
                         kSplitPartialFloats) * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_imagine_backward: needs %zu B of LDS", lds);
     if (lds > 64 * 1024 && allow_big_lds(imagine_bwd_kernel)) return -1;
-    hipLaunchKernelGGL(imagine_bwd_kernel, dim3(cdiv(a->N, 16)), dim3(kThreads), lds, (hipStream_t)stream, w);
+    hipLaunchKernelGGL(imagine_bwd_kernel, dim3(cdiv(a->N, 16)), dim3(kThreads), lds, (hipStream_t)stream, *a);
     BD_CHECK_LAUNCH("bd_imagine_backward");
     return 0;
 }

@@ -498,9 +498,7 @@ int bd_mlp_backward(const bd_mlp_bwd_args* a, void* stream) {
         kb = cdiv(L.N, 16) > kb ? cdiv(L.N, 16) : kb;
     }
     if (want_din) BD_REQUIRE(a->w0 + a->w1 == a->layer[0].K, "bd_mlp_backward: din widths != K of layer 0");
-    BD_REQUIRE(a->form_M >= 0, "bd_mlp_backward: bad form_M");
-    const int Mf = a->form_M > 0 ? a->form_M : a->M;      // the rows that pick the form (bd_mlp_bwd_args.form_M)
-    if (tall_enabled() && cdiv(Mf, 16) >= (tall_mode == 2 ? 1 : kTallMinTiles)) {
+    if (tall_enabled() && cdiv(a->M, 16) >= (tall_mode == 2 ? 1 : kTallMinTiles)) {
         bool ok = true;
         size_t widest = (size_t)(a->ld0 > a->ld1 ? a->ld0 : a->ld1);
         auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
@@ -515,7 +513,7 @@ int bd_mlp_backward(const bd_mlp_bwd_args* a, void* stream) {
         if (ok && any) return launch_tall(mlp_bwd_tall_kernel<kTallRT, true>, "bd_mlp_backward(tall)", a->M, kb, (hipStream_t)stream, *a);
         if (ok) return launch_tall(mlp_bwd_tall_kernel<kTallRT, false>, "bd_mlp_backward(tall)", a->M, kb, (hipStream_t)stream, *a);
     }
-    const int rt = pick_rt(Mf, KbA, KbB);
+    const int rt = pick_rt(a->M, KbA, KbB);
     if (any) {
         if (rt == 2) return launch_chain(mlp_bwd_kernel<2, true>, "bd_mlp_backward", a->M, 2, KbA, KbB, (hipStream_t)stream, *a);
         return launch_chain(mlp_bwd_kernel<1, true>, "bd_mlp_backward", a->M, 1, KbA, KbB, (hipStream_t)stream, *a);

@@ -362,19 +362,13 @@ class DreamerEngine:
                             and bool(lib.bd_img_heads_supported(self.d.Be + self.d.S, self.d.Hd)))
         # pixel mode: decoder weight gradients under the observe scan
         self._s_early = _engine_stream(self.dev, "early", int(os.environ.get("BD_EARLY_PRIO", "0")))
-        # Behaviour chunk plan ("Chunked behaviour chain"): the two imagination scans run as K launches over
-        # consecutive time steps, and the recurrence-free work of a finished chunk -- the fused heads behind the forward
-        # scan, the actor's hidden dgrad chain behind the backward scan -- runs on `_s_ov` on the CUs the scans leave idle
-        # while the scan walks on.  bh_chunks: None = the default rule (behaviour_plan), 1 = single launches, K = K
-        # near-equal chunks, a tuple = the chunk lengths (BD_BH_CHUNKS: "", "1", "3", "5,5,4").  bh_chunks_bwd
-        # (BD_BH_CHUNKS_BWD=1) also splits the backward scan and the actor chain: off by default -- the critic update
-        # already fills the CUs the backward scan leaves idle, and the step got slower (profiles/r05a_README.md).
+        # Behaviour chunk plan ("Chunked behaviour chain"): the forward imagination scan runs as K launches over
+        # consecutive time steps, and the fused heads of a finished chunk run on the CUs the scan leaves idle while the
+        # scan walks on.  They run on `_side`, the critic's stream (no fifth active stream: the process has four
+        # hardware queues; the decoder-wgrad stream `_s_early`, idle with state observations, was slower in the A/B).
+        # bh_chunks: None = the default rule (behaviour_plan), 1 = single launches, K = K near-equal chunks, a tuple =
+        # the chunk lengths (BD_BH_CHUNKS: "", "1", "3", "5,5,4").
         self.bh_chunks = _parse_bh_chunks(os.environ.get("BD_BH_CHUNKS", ""))
-        self.bh_chunks_bwd = os.environ.get("BD_BH_CHUNKS_BWD", "0") == "1"
-        # the overlap stream: the critic's (no fifth active stream: the process has four hardware queues).  With the
-        # backward split too, the critic phase, which has a whole step of slack, is queued behind the step's overlapped
-        # chunks.  (The decoder-wgrad stream `_s_early`, idle with state observations, was slower in the A/B.)
-        self._s_ov = self._side
         # Cross-step software pipeline (on unless BD_PIPELINE=0).  Dynamics learning of step k+1 reads only the world
         # model that step k's model optimiser wrote, never what step k's behaviour learning (imagination, actor,
         # critic) produces, while behaviour learning k needs the world model k and the posteriors k.  So the two
@@ -673,11 +667,10 @@ class DreamerEngine:
         cabi.check(lib.bd_mlp_forward(C.byref(a), cabi.stream()))
 
     def mlp_backward(self, M, dout, lddo, layers, saves, dpres, din0=None, ld0=0, w0=0, din1=None, ld1=0, w1=0,
-                     accumulate=False, dout_scale=1.0, raw_packs=False, form_M=0) -> None:
-        """layers as in mlp_forward; with raw_packs the first entry is the packed TRANSPOSED weight tensor.
-        form_M: the rows of the whole chain when this launch covers a slice of them (bd_mlp_bwd_args.form_M)."""
+                     accumulate=False, dout_scale=1.0, raw_packs=False) -> None:
+        """layers as in mlp_forward; with raw_packs the first entry is the packed TRANSPOSED weight tensor."""
         a = cabi.MlpBwdArgs()
-        a.M, a.dout, a.lddo, a.dout_scale, a.form_M = M, ptr(dout), lddo, dout_scale, form_M
+        a.M, a.dout, a.lddo, a.dout_scale = M, ptr(dout), lddo, dout_scale
         a.n_layers = len(layers)
         for i, (key, _bias, N, K, act) in enumerate(layers):
             wt = key if raw_packs else self.pk.get(key + ".T")
@@ -2053,27 +2046,17 @@ class DreamerEngine:
         s = self._behaviour_record(feat, noise, T * B, red_ws, par)
         self._imagine_and_heads(s)
         self._returns_and_sums(s)
-        # the overlapped actor chains share the critic's stream: they go first (the critic has a step of slack)
-        critic_last = s.windows and self._s_ov is self._side
-        if par is not None and not critic_last:
+        if par is not None:
             self._critic_handoff(s)
         if s.dyn:
             if not s.fused:
                 self._imagined_heads_backward(s)
             self._imagine_backward(s)
-            if s.windows:
-                self._world_model_free()            # the scan is the last reader of the world model: the chains are not
         if s.mix is not None:
             self._actor_reinforce(s)
-        if s.windows:
-            self._actor_rows(s, 0, s.tb[1])         # the first window's chain: nothing left to hide it under
-            s.cur.wait_event(s.ev_ov)               # every row of d_actor_pre, for the one weight-gradient launch
-            if par is not None and critic_last:
-                self._critic_handoff(s)
-        else:
-            if s.actor_chain:
-                self._actor_rows(s, 0, s.Hm)
-            self._world_model_free()                # last reader of the world model in this step
+        if s.actor_chain:
+            self._actor_rows(s)
+        self._world_model_free()                    # last reader of the world model in this step
         self._actor_update(s)
         if par is None:
             self._critic_phase(s, red_ws)
@@ -2100,8 +2083,7 @@ class DreamerEngine:
         s = SimpleNamespace(
             N=N, Hm=Hm, Mi=Mi, F=F, par=par, ptag=ptag, feat=feat, noise=noise, red_ws=red_ws, mix=mix, dyn=dyn, inv_mi=inv_mi,
             fused=dyn and self.heads_fused, plan=plan, tb=[sum(plan[:i]) for i in range(len(plan) + 1)], chunked=len(plan) > 1,
-            actor_chain=actor_chain, windows=len(plan) > 1 and self.bh_chunks_bwd and actor_chain,    # backward scan split too
-            dconst=-inv_mi if mix is None else -mix * inv_mi,
+            actor_chain=actor_chain, dconst=-inv_mi if mix is None else -mix * inv_mi,
             dentropy=-hp["entropy_weight"] * inv_mi if hp["entropy_weight"] != -1 else 0.0,
             cur=torch.cuda.current_stream(), st=cabi.stream(), sc=ptr(self.scalars), ws=ptr(red_ws),
             start_sidx=self._buf[ptag + "sidx"] if d.categorical else None, wts=None, dret=None, ev_ov=None, ev_ret=None,
@@ -2116,8 +2098,9 @@ class DreamerEngine:
         return s
 
     def _on_overlap_stream(self, s, work, *args) -> None:
-        """work(*args) on the overlap stream behind what the behaviour stream has queued so far; s.ev_ov = its end."""
-        ov, ev = self._s_ov, torch.cuda.Event()
+        """work(*args) on the overlap stream (the critic's) behind what the behaviour stream has queued so far; s.ev_ov =
+        its end."""
+        ov, ev = self._side, torch.cuda.Event()
         ev.record(s.cur)
         with torch.cuda.stream(ov):
             ov.wait_event(ev)
@@ -2213,9 +2196,7 @@ class DreamerEngine:
 
     def _imagine_backward(self, s) -> None:
         """Backward of the imagination scan, both latent families: from difeat and the entropy term to d_actor_out (and
-        d_actor_pre, unless the actor's hidden chain runs outside the scan).  s.windows: one launch per chunk of the plan,
-        latest first; the gradient of the recurrence crosses the borders through `carry` (a workgroup reads its rows before its
-        first step and writes them after its last: one buffer); a finished window's hidden chain runs on the overlap stream."""
+        d_actor_pre, unless the actor's hidden chain runs outside the scan)."""
         d, pk, buf, noise = self.d, self.pk, self._buf, s.noise
         if d.categorical:
             c = cabi.ImagineCatBwdArgs()
@@ -2241,17 +2222,7 @@ class DreamerEngine:
         c.dfeat, c.dentropy, c.ent_weight = ptr(s.difeat), s.dentropy, ptr(s.wts)
         c.d_actor_pre, c.d_actor_out = (None if s.actor_chain else ptr(s.d_apre)), ptr(s.d_aout)
         with self.span("imagine_bwd"):
-            if not s.windows:
-                cabi.check(scan(C.byref(c), s.st))
-                return
-            tb, carry = s.tb, self.buf("img_bwd_carry", s.N, s.F)
-            for i in reversed(range(len(s.plan))):
-                c.t_begin, c.t_end = tb[i], tb[i + 1]
-                c.d_carry_in = ptr(carry) if tb[i + 1] < s.Hm else None
-                c.d_carry_out = ptr(carry) if tb[i] > 0 else None
-                cabi.check(scan(C.byref(c), s.st))
-                if i > 0:
-                    self._on_overlap_stream(s, self._actor_rows, s, tb[i], tb[i + 1])
+            cabi.check(scan(C.byref(c), s.st))
 
     def _world_model_free(self) -> None:
         """Pipelined: mark the step's last read of the world model on the current stream (the model optimiser waits for it)."""
@@ -2272,16 +2243,15 @@ class DreamerEngine:
                 cabi.check(lib.bd_actor_reinforce(ptr(noise["action"]), ptr(s.act_us), ptr(stats), ptr(s.returns), ptr(b0),
                                                   ptr(s.v_out), *tail))
 
-    def _actor_rows(self, s, t0: int, t1: int) -> None:
-        """The actor's hidden dgrad chain over the rows of steps [t0, t1), in the form of the chain over all rows."""
+    def _actor_rows(self, s) -> None:
+        """The actor's hidden dgrad chain over all Hm x N rows, from d_actor_out to d_actor_pre."""
         d, sv_actor = self.d, self._buf["sv_actor"]
         hidden = [(f"a{l}", None, d.Hd, d.Hd, cabi.ACT_ELU) for l in range(1, DENSE_LAYERS)]
         a_layers = [("a0h", None, d.Hd, s.F, cabi.ACT_ELU)] + hidden + [("a4", None, d.actor_out, d.Hd, cabi.ACT_NONE)]
-        r = slice(t0 * s.N, t1 * s.N)
-        with self.span("actor_hidden_bwd", more=t1 < s.Hm):       # the latest rows open the span
-            self.mlp_backward((t1 - t0) * s.N, s.d_aout[r], d.actor_out, a_layers,
-                              [sv_actor[l][r] for l in range(DENSE_LAYERS)] + [None],
-                              [s.d_apre[l][r] for l in range(DENSE_LAYERS)] + [None], form_M=s.Mi)
+        with self.span("actor_hidden_bwd"):
+            self.mlp_backward(s.Mi, s.d_aout, d.actor_out, a_layers,
+                              [sv_actor[l] for l in range(DENSE_LAYERS)] + [None],
+                              [s.d_apre[l] for l in range(DENSE_LAYERS)] + [None])
 
     def _actor_update(self, s) -> None:
         """The actor's weight gradients over all rows in one grouped launch, then its optimiser step."""

@@ -103,9 +103,6 @@ typedef struct {
     float* din0; int ld0, w0;       /* optional gradient w.r.t. the input, split like the forward   */
     float* din1; int ld1, w1;
     int accumulate;                 /* 1: din += , 0: din =                                         */
-    int form_M;                     /* 0, or the row count that picks the kernel form (tall / chain, rows per workgroup)
-                                     * instead of M: a launch over a slice of the rows of a chain then runs the form of
-                                     * the launch over all form_M rows and gives its bits (the forms sum in different orders) */
 } bd_mlp_bwd_args;
 int bd_mlp_backward(const bd_mlp_bwd_args* a, void* stream);
 
@@ -413,17 +410,6 @@ typedef struct {
                              * d out = p * (g - p.g) + dent * (-p * (norm + H)) with g = d loss / d action and
                              * dent = dentropy (* ent_weight); wt_a4m is the (Hd, A) head transpose, wt_a4s, eps_action
                              * unused; d_actor_pre must be NULL (the hidden layers run as the caller's chain)         */
-    /* A launch over the window [t_begin, t_end) of time steps (walked t_end-1 ... t_begin); 0 / 0 = the whole rollout.
-     * Every [Hm x ...] array above keeps its whole-rollout indexing: the launches of one rollout get the same pointers
-     * and the same Hm, and write only the rows of their steps.  The gradient that the recurrence carries from step t+1
-     * to step t crosses a window border through the carry, row-major [N x (Be+S)] fp32: d belief | d state.
-     * d_carry_in is required exactly when t_end < Hm (NULL: the carry starts at zero), d_carry_out exactly when
-     * t_begin > 0.  A workgroup reads its 16 rows of d_carry_in before the first step and writes the same rows of
-     * d_carry_out after the last, so both may be one buffer.  The windows of a plan, launched in descending time on one
-     * stream, give the bits of the single launch (plain copies; the arithmetic of a step does not see the window). */
-    int t_begin, t_end;
-    const float* d_carry_in;
-    float* d_carry_out;
 } bd_imagine_bwd_args;
 int bd_imagine_backward(const bd_imagine_bwd_args* a, void* stream);
 

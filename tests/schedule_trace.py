@@ -11,10 +11,9 @@ from tests.helpers import CASES as GAUSS, CAT_CASES
 
 PATCHED_MODULES = ("big_dreamer_amd.engine", "big_dreamer_amd.conv", "big_dreamer_amd.conv_stack")
 ROLES = (("wm", "_s_wm"), ("bh", "_s_bh"), ("side", "_side"), ("early", "_s_early"))
-# fields of the argument block that select a window, a kernel form or an accumulation
+# fields of the argument block that select a kernel form or an accumulation
 BLOCK_SCALARS = {
-    "bd_imagine_backward": lambda a: f"t=[{a.t_begin},{a.t_end}) carry_in={_null(a.d_carry_in)} carry_out={_null(a.d_carry_out)}",
-    "bd_mlp_backward": lambda a: f"M={a.M} form_M={a.form_M} accumulate={a.accumulate}",
+    "bd_mlp_backward": lambda a: f"M={a.M} accumulate={a.accumulate}",
 }
 
 
@@ -107,16 +106,13 @@ def _small(attrs=None, hp=None, env=None):
 
 DISCRETE_TINY = (dataclasses.replace(synth.TINY, A=6, discrete_actions=True), 0, {}, True)    # tests/test_discrete_actions_gpu.py
 SHAPES = {**GAUSS, **CAT_CASES, "discrete_tiny": DISCRETE_TINY}
-SPLIT = dict(bh_chunks=(2, 2, 1), bh_chunks_bwd=True)
 
 # name -> dims (a key of SHAPES), engine attributes set after construction, hyper-parameters, environment, the step
 SCHEDULE_CASES = {
     "small-pipelined": _small(),
     "small-serial": _small(dict(pipeline=False)),
     "small-one-chunk": _small(dict(bh_chunks=1)),
-    "small-chunks-221": _small(dict(bh_chunks=(2, 2, 1), bh_chunks_bwd=False)),
-    "small-chunks-221-bwd": _small(SPLIT),
-    "small-chunks-221-bwd-early": _small(dict(SPLIT, _s_ov="_s_early")),
+    "small-chunks-221": _small(dict(bh_chunks=(2, 2, 1))),
     "small-mix-0.5": _small(hp=dict(gradient_mixing=0.5)),
     "small-mix-0.0": _small(hp=dict(gradient_mixing=0.0)),
     "small-heads-unfused": _small(dict(heads_fused=False)),
@@ -144,7 +140,7 @@ def trace_case(name, setenv):
     torch.manual_seed(1234)
     eng = DreamerEngine(d, dict(hp, **case.get("hp", {})), "cuda", params=synth.make_params(d, seed))
     for k, v in case.get("attrs", {}).items():
-        setattr(eng, k, getattr(eng, v) if k == "_s_ov" else v)
+        setattr(eng, k, v)
     batches = [{k: torch.as_tensor(v).cuda().contiguous() for k, v in synth.make_batch(d, seed + i).items()} for i in range(3)]
     torch.cuda.synchronize()
     with ScheduleTrace(eng) as trace:

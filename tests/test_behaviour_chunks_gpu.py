@@ -1,6 +1,6 @@
-"""The chunked behaviour chain ("Chunked behaviour chain"): the imagination scans launched over windows of time
-steps, and whole train steps under a chunk plan, against the single launches -- bit for bit.  Splitting in time changes
-no arithmetic, so every comparison is torch.equal."""
+"""The chunked behaviour chain ("Chunked behaviour chain"): the forward imagination scan launched over segments
+of time steps, and whole train steps under a chunk plan, against the single launches -- bit for bit.  Splitting in time
+changes no arithmetic, so every comparison is torch.equal."""
 import ctypes as C
 
 import pytest
@@ -9,7 +9,7 @@ import torch
 from big_dreamer_amd import synth
 from tests import scan_ref as R
 from tests.helpers import CASES, CAT_CASES
-from tests.test_scan_kernels_gpu import ImagineCase, cabi, pout, ptr, same_bits, sync
+from tests.test_scan_kernels_gpu import ImagineCase, cabi, pout, same_bits, sync
 
 pytestmark = pytest.mark.gpu
 
@@ -22,8 +22,8 @@ def _bounds(plan):
     return [(sum(plan[:i]), sum(plan[:i + 1])) for i in range(len(plan))]
 
 
-class WindowCase(ImagineCase):
-    """ImagineCase with the forward in any number of time segments and the backward in windows."""
+class SegmentCase(ImagineCase):
+    """ImagineCase with the forward in any number of time segments."""
 
     def forward_plan(self, plan):
         c, d, pk, p = cabi(), self.d, self.pk, self.pin
@@ -59,61 +59,10 @@ class WindowCase(ImagineCase):
             assert v.outside_unchanged(), f"imagine forward {plan}: {k} written outside its rows"
         return out
 
-    def backward_plan(self, fwd, plan, actor_pre, zero_fields=False):
-        """plan None: the call as the parent made it (the window fields never touched); zero_fields: the same with the
-        new fields written as 0 / 0 / NULL / NULL."""
-        c, d, pkT, p = cabi(), self.d, self.pkT, self.pin
-        M, A, F = d.T * d.B, d.A, d.Be + d.S
-        b = c.ImagineBwdArgs()
-        b.N, b.Hm, b.Be, b.S, b.A, b.Hd = d.B, d.T, d.Be, d.S, d.A, d.Hd
-        b.wt_embed_s, b.wt_embed_a = pkT["embed_s"].data_ptr(), pkT["embed_a"].data_ptr()
-        b.wt_ir, b.wt_iz, b.wt_in = (pkT[k].data_ptr() for k in ("ir", "iz", "in"))
-        b.wt_hr, b.wt_hz, b.wt_hn = (pkT[k].data_ptr() for k in ("hr", "hz", "hn"))
-        b.wt_p1, b.wt_p2m, b.wt_p2s = pkT["p1"].data_ptr(), pkT["p2m"].data_ptr(), pkT["p2s"].data_ptr()
-        for l in range(3):
-            b.wt_a[l] = pkT[f"a{l + 1}"].data_ptr()
-        b.wt_a4m, b.wt_a4s = pkT["a4m"].data_ptr(), pkT["a4s"].data_ptr()
-        for k, v in self.saved(fwd).items():
-            setattr(b, k, v.ptr)
-        b.start_feat, b.eps_action, b.eps_prior = p["start_feat"].ptr, p["eps_action"].ptr, p["eps_prior"].ptr
-        b.min_std, b.dfeat, b.dentropy, b.ent_weight = self.min_std, p["dfeat"].ptr, self.dentropy, ptr(p["ent_weight"])
-        out = dict(d_actor_out=pout(M, 2 * A), d_actor_pre=pout(4 * M, d.Hd) if actor_pre else None)
-        b.d_actor_out, b.d_actor_pre = out["d_actor_out"].ptr, ptr(out["d_actor_pre"])
-        b.discrete_actions = 0
-        if plan is None:
-            if zero_fields:
-                b.t_begin, b.t_end, b.d_carry_in, b.d_carry_out = 0, 0, None, None
-            c.check(c.lib.bd_imagine_backward(C.byref(b), c.stream()))
-            sync()
-        else:
-            carry = pout(d.B, F)        # one buffer for both directions; SENTINEL until the first window has written it
-            for t0, t1 in reversed(_bounds(plan)):
-                b.t_begin, b.t_end = t0, t1
-                b.d_carry_in, b.d_carry_out = (carry.ptr if t1 < d.T else None), (carry.ptr if t0 > 0 else None)
-                c.check(c.lib.bd_imagine_backward(C.byref(b), c.stream()))
-                sync()
-            assert carry.outside_unchanged(), f"imagine backward {plan}: carry written outside its rows"
-        for k, v in out.items():
-            assert v is None or v.outside_unchanged(), f"imagine backward {plan}: {k} written outside its rows"
-        return out
-
-    def saved(self, fwd):
-        """The forward's tensors as the backward's inputs, built once (slots 2, 3 of sv_act_stats: arbitrary numbers)."""
-        if getattr(self, "_saved", None) is None:
-            from tests.dense_ref import placed_input
-            d, A = self.d, self.d.A
-            M = d.T * d.B
-            stats = fwd["sv_act_stats"].view.clone()
-            stats[:, 2 * A:3 * A], stats[:, 3 * A:] = self.G["slot2"].reshape(M, A), self.G["slot3"].reshape(M, A)
-            self._saved = {k: placed_input(fwd[k].view.clone(), fwd[k].cols)
-                           for k in ("feat", "prior_std", "action", "sv_actor", "sv_x", "sv_gates", "sv_p")}
-            self._saved["sv_act_stats"] = placed_input(stats, 4 * A)
-        return self._saved
-
 
 @pytest.fixture(scope="module")
 def case():
-    c = WindowCase(DIMS, 31)
+    c = SegmentCase(DIMS, 31)
     c.fwd = c.forward_plan((DIMS.T,))
     return c
 
@@ -124,18 +73,6 @@ def test_forward_segments_give_the_bits_of_the_single_launch(case):
     same_bits(case.forward(), case.fwd, "forward through forward_plan((5,))")
     for plan in PLANS[1:]:
         same_bits(case.fwd, case.forward_plan(plan), f"forward in segments {plan}")
-
-
-@pytest.mark.parametrize("actor_pre", [False, True], ids=["chain_form", "in_scan_form"])
-def test_backward_windows_give_the_bits_of_the_single_launch(case, actor_pre):
-    """d_actor_out (and d_actor_pre in the in-scan form) for every window plan; the single launch with the new fields
-    zeroed is the parent's call."""
-    parent = case.backward_plan(case.fwd, None, actor_pre)
-    assert bool(torch.isfinite(parent["d_actor_out"].view).all()) and float(parent["d_actor_out"].view.abs().max()) > 0
-    same_bits(parent, case.backward_plan(case.fwd, None, actor_pre, zero_fields=True), "backward, fields zeroed")
-    keys = dict(d_actor_out=parent["d_actor_out"], d_actor_pre=parent["d_actor_pre"])
-    for plan in PLANS:
-        same_bits(keys, case.backward_plan(case.fwd, plan, actor_pre), f"backward in windows {plan}")
 
 
 # ---- engine ---------------------------------------------------------------------------------------------------------------
@@ -150,7 +87,7 @@ def _run(name, plan, pipeline, hp_extra=None, steps=3):
     d, seed, hp, _ = {**CASES, **CAT_CASES}[name]
     torch.manual_seed(1234)
     eng = DreamerEngine(d, dict(hp, **(hp_extra or {})), "cuda", params=synth.make_params(d, seed))
-    eng.pipeline, eng.bh_chunks, eng.bh_chunks_bwd = pipeline, plan, True       # both directions
+    eng.pipeline, eng.bh_chunks = pipeline, plan
     logs = [eng.train_step(_dev(synth.make_batch(d, seed + i))) for i in range(steps)]
     eng.join()
     torch.cuda.synchronize()
@@ -178,25 +115,6 @@ def test_train_steps_under_a_chunk_plan_are_bit_identical(pipeline):
         _assert_same(ref, got, plan)
 
 
-def test_backward_switch_keeps_the_bits():
-    """bh_chunks_bwd off (forward chunks only: the default) and the other overlap stream: the same bits again."""
-    from big_dreamer_amd.engine import DreamerEngine
-    ref = _run("small", 1, True)
-    d, seed, hp, _ = CASES["small"]
-    for bwd, early in ((False, False), (True, True)):
-        torch.manual_seed(1234)
-        eng = DreamerEngine(d, hp, "cuda", params=synth.make_params(d, seed))
-        eng.bh_chunks, eng.bh_chunks_bwd = (2, 2, 1), bwd
-        if early:
-            eng._s_ov = eng._s_early
-        logs = [eng.train_step(_dev(synth.make_batch(d, seed + i))) for i in range(3)]
-        eng.join()
-        torch.cuda.synchronize()
-        assert logs == ref[1], (bwd, early)
-        for g in ("model", "actor", "critic"):
-            assert torch.equal(eng.groups[g].flat, ref[2][g + ".p"]), (bwd, early, g)
-
-
 @pytest.mark.parametrize("name, hp_extra, plan", [
     ("cat_tiny", None, (1, 1, 1)),
     ("small", dict(gradient_mixing=0.5), (2, 2, 1)),
@@ -214,7 +132,7 @@ def test_chunk_spans_report_the_sum_over_chunks():
     from big_dreamer_amd.engine import DreamerEngine
     d, seed, hp, _ = CASES["small"]
     eng = DreamerEngine(d, hp, "cuda", params=synth.make_params(d, seed))
-    eng.bh_chunks, eng.bh_chunks_bwd = (2, 2, 1), True
+    eng.bh_chunks = (2, 2, 1)
     eng.enable_timers(True)
     for i in range(2):
         eng.train_step(_dev(synth.make_batch(d, seed + i)), sync_logs=False)
@@ -223,4 +141,4 @@ def test_chunk_spans_report_the_sum_over_chunks():
     summary = eng.timer_summary()
     for k in ("imagine_fwd", "img_heads_bwd", "imagine_bwd", "actor_hidden_bwd", "wgrad_actor"):
         assert summary[k][1] == 2 and summary[k][0] > 0, (k, summary[k])
-    assert len(eng._timer_more["img_heads_bwd"]) == 4 and len(eng._timer_more["actor_hidden_bwd"]) == 4
+    assert len(eng._timer_more["img_heads_bwd"]) == 4 and "actor_hidden_bwd" not in eng._timer_more

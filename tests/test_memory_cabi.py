@@ -24,6 +24,26 @@ def test_cabi_exports_every_declared_symbol():
     assert _cabi.lib.bd_reduce_ws_floats() > 0
 
 
+def test_backward_argument_blocks_have_the_size_the_kernels_take():
+    """The ctypes mirrors of the two backward argument blocks against the kernel-argument sizes the compiler reports for
+    gfx950 (`.kernarg_segment_size` in the metadata of `hipcc --cuda-device-only -S`, the Makefile's flags).  A kernel's
+    segment is its explicit arguments followed by 256 bytes of hidden ones (block counts, group sizes ...: the `.args`
+    list of the same metadata):
+      imagine_bwd_kernel(bd_imagine_bwd_args):        552 = 296 + 256
+      mlp_bwd_tall_kernel(bd_mlp_bwd_args):           568 = 312 + 256
+      mlp_bwd_kernel(bd_mlp_bwd_args, int, int):      576 = 312 + 2 * 4 + 256
+    Both blocks end with the field the header ends with; bd_mlp_bwd_args keeps its size when its tail changes (alignment
+    padding), so its last field is pinned by name and offset."""
+    import ctypes as C
+    from big_dreamer_amd import _cabi
+    hidden = 256
+    assert C.sizeof(_cabi.ImagineBwdArgs) == 552 - hidden
+    assert _cabi.ImagineBwdArgs._fields_[-1][0] == "discrete_actions" and _cabi.ImagineBwdArgs.discrete_actions.offset == 288
+    assert C.sizeof(_cabi.MlpBwdArgs) == 568 - hidden == 576 - 2 * 4 - hidden
+    assert _cabi.MlpBwdArgs._fields_[-1][0] == "accumulate" and _cabi.MlpBwdArgs.accumulate.offset == 304
+    assert _cabi.lib.bd_version() >= 2      # the two blocks changed with version 2
+
+
 def test_cabi_rejects_bad_arguments_without_gpu():
     """Argument validation happens before any launch: errors come back as codes + text, never exceptions."""
     from big_dreamer_amd import _cabi
