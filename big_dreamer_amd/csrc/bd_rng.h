@@ -36,8 +36,15 @@ __host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t 
     return Philox4{{c0, c1, c2, c3}};
 }
 
-// uniform in (0, 1): 24 random bits, never 0 or 1 (so that log(u) is finite)
-__host__ __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+// uniform in (0, 1): 24 random bits k = x >> 8, u = (k + 0.5) * 2^-24, never 0 or 1 (so that log(u) is finite and
+// non-zero).  In float32 k + 0.5 is exact only for k < 2^23; from there on the sum is a tie that rounds to even, so
+// k = 2^23 .. 2^24 - 2 give u = k' * 2^-24 with k' = k or k + 1 (at most 1 - 2^-23), and k = 2^24 - 1 gives 2^24, which
+// would be u = 1.0f: -logf(u) = -0.0f, a Categorical sampler's p / q = -inf (the class that drew the smallest Exp(1)
+// variate could never win) and a Box-Muller radius of 0.  The clamp to the largest float32 below 1 changes that one
+// result (probability 2^-24 per word) and no other: every other draw of every stream keeps its bits.
+__host__ __device__ __forceinline__ float u01(uint32_t x) {
+    return fminf(((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
+}
 
 struct Rng {
     uint32_t k0, k1, stream, step;

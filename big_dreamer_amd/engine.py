@@ -1266,7 +1266,8 @@ class DreamerEngine:
             a.sidx = ptr(self._buf_u8(tag + feat_tag + "isidx", Mi, d.cat_D))      # read by the critic update: double-buffered like ifeat
             a.prior_logits = ptr(self.buf(tag + "iprior_logits", Mi, d.S))
             scan = lib.bd_imagine_cat_forward
-            # this scan estimates the entropy itself from explicit draws; perf mode: the estimator draws in-kernel
+            # explicit draws: bd_imagine_cat_forward estimates the entropy itself (inside the scan without saves, with
+            # bd_actor_entropy behind it with them); perf mode: bd_actor_entropy_rng draws in-kernel, same summation order
             entropy_after = noise.get("entropy") is None
         else:
             a = cabi.ImagineFwdArgs()

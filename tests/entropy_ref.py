@@ -413,17 +413,11 @@ SCAN_GAUSS, SCAN_CAT, SCAN_NS = ("n1_h1", "ragged42", "a17"), ("n1_h1", "c16_d20
 
 
 def rng_gather_index(Hm, N, A, ns):
-    """Element of a bd_rng_fill(BD_RNG_NORMAL) buffer that bd_actor_entropy_rng uses as draw k of (row, j): counter
-    base + m / 4, word m % 4 with k = part + 16 m and base = ((row A + j) 16 + part) ((ns / 16 + 4) / 4) (imagine.hip);
-    the fill writes counter i4 at elements 4 i4 .. 4 i4 + 3 (rng.hip).  Returns (index [Hm, ns, N, A], buffer length)."""
-    per = (ns // K_ENT_PARTS + 4) // 4
-    k = torch.arange(ns).view(1, ns, 1, 1)
-    row = (torch.arange(Hm).view(Hm, 1, 1, 1) * N + torch.arange(N).view(1, 1, N, 1))
-    j = torch.arange(A).view(1, 1, 1, A)
-    part, m = k % K_ENT_PARTS, k // K_ENT_PARTS
-    base = ((row * A + j) * K_ENT_PARTS + part) * per
-    idx = 4 * (base + m // 4) + m % 4
-    return idx, 4 * Hm * N * A * K_ENT_PARTS * per
+    """Element of a bd_rng_fill(BD_RNG_NORMAL) buffer that bd_actor_entropy_rng uses as draw k of (row, j): the counter
+    map is stated once, in rng_ref.rng_gather_index.  Returns (index [Hm, ns, N, A], buffer length)."""
+    from tests import rng_ref
+    idx, n = rng_ref.rng_gather_index(Hm, N, A, ns)
+    return torch.from_numpy(idx), n
 
 
 # ---- one whole train step that can see the entropy gradient ----------------------------------------------------------------

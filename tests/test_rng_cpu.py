@@ -3,11 +3,7 @@ distribution (kat_vectors, philox4x32 10 rounds) through the host build of the s
 the GPU tests use to check the device output."""
 import ctypes as C
 
-from tests.test_rng_gpu import _philox_ref
-
-KAT = [([0, 0, 0, 0], [0, 0], [0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8]),
-       ([0xffffffff] * 4, [0xffffffff] * 2, [0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd]),
-       ([0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344], [0xa4093822, 0x299f31d0], [0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1])]
+from tests.rng_ref import KAT, philox as _philox_ref      # the shared restatement and the published vectors
 
 
 def test_python_restatement_matches_known_answers():

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.rng_ref import philox as _philox_ref      # Philox4x32-10 in Python integers (Salmon et al., SC'11)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -20,17 +22,6 @@ def _fill(tensors, seed, step):
         a.t[i] = cabi.RngTensor(t.data_ptr(), t.numel(), kind, sid)
     cabi.check(cabi.lib.bd_rng_fill(C.byref(a), cabi.stream()))
     torch.cuda.synchronize()
-
-
-def _philox_ref(ctr, key):
-    """Philox4x32-10 in Python integers (Salmon et al., SC'11)."""
-    M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-    c, k = list(ctr), list(key)
-    for _ in range(10):
-        p0, p1 = M0 * c[0], M1 * c[2]
-        c = [((p1 >> 32) ^ c[1] ^ k[0]) & 0xFFFFFFFF, p1 & 0xFFFFFFFF, ((p0 >> 32) ^ c[3] ^ k[1]) & 0xFFFFFFFF, p0 & 0xFFFFFFFF]
-        k = [(k[0] + W0) & 0xFFFFFFFF, (k[1] + W1) & 0xFFFFFFFF]
-    return c
 
 
 def test_python_philox_matches_the_published_known_answers():
