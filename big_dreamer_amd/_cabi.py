@@ -195,6 +195,10 @@ class ActArgs(C.Structure):
 
 
 ActCatArgs = ActArgs       # bd_act_cat_args is a typedef of bd_act_args
+# bd_scan_lds_bytes: kernel ids in the order of bigdreamer_hip.h (BD_SCAN_*)
+SCAN_KERNELS = {name: i for i, name in enumerate((
+    "observe_fwd", "observe_bwd", "observe_cfwd", "observe_cbwd", "observe_kfwd", "observe_kbwd", "imagine_fwd", "imagine_bwd",
+    "observe_cat_fwd", "observe_cat_bwd", "imagine_cat_fwd", "imagine_cat_bwd", "observe_cat_cfwd", "observe_cat_cbwd"))}
 BD_POLICY_SAMPLE, BD_POLICY_MODE, BD_POLICY_MEAN = 0, 1, 2
 ACTION_MODES = {"sample": BD_POLICY_SAMPLE, "mode": BD_POLICY_MODE, "mean": BD_POLICY_MEAN}
 
@@ -266,6 +270,7 @@ _SIGS = {
     "bd_observe_backward_cluster": (I32, [C.POINTER(ObserveBwdArgs), P, C.c_size_t, P]),
     "bd_observe_cluster_status": (I32, [P, I32, P]),
     "bd_observe_cluster_err_offset": (C.c_size_t, [I32]),
+    "bd_scan_lds_bytes": (C.c_size_t, [I32] * 8),
     "bd_observe_cluster_set_spin_limit": (I32, [C.c_uint]),
     "bd_observe_cluster_set_ksplit": (I32, [I32]),
     "bd_gauss_head_forward": (I32, [P, P, I32, I32, F32, P, P, P, P]),

@@ -11,26 +11,19 @@
 //   Every spin is bounded: on timeout the member ORs its code into the STICKY error word and stops waiting (outputs are
 //   then wrong, the launch still terminates).  The error word is NOT part of the per-launch header memset: it survives
 //   later launches until bd_observe_cluster_status reads (and clears) it -- the engine reads it with every log fetch.
-// Workspace header (floats): [flags: tiles * kMaxCluster u32][err: 16 u32, sticky]; payload layouts belong to the kernels.
+// Workspace header and per-tile payload layouts: bd_scan_layout.h.
 #pragma once
 #include "bd_device.h"
 #include "bd_host.h"
+#include "bd_scan_layout.h"      // kMaxCluster, kLocalBlocks, the workspace header and the payload layouts
 #include <stdlib.h>
 
 namespace bd {
 
-constexpr int kMaxCluster = 16;
-
-constexpr int kLocalBlocks = 2;             // column blocks a member owns at most (host picks C accordingly)
 constexpr unsigned kSpinLimit = 1u << 22;   // ~ seconds; far beyond any legitimate wait
 // host copy of the spin limit, passed to every launch (bd_observe_cluster_set_spin_limit: tests); one per process
 unsigned& cluster_spin_limit();      // observe_cluster.hip
 constexpr unsigned kErrFwd = 1u, kErrBwd = 2u;
-
-
-// workspace: [flags: tiles*kMaxCluster u32][err: 16 u32, sticky][payload: tiles * 2 parities * nvec * Kb_h*256 floats]
-__host__ __device__ inline size_t cluster_ws_flag_floats(int tiles) { return (size_t)tiles * kMaxCluster; }
-__host__ __device__ inline size_t cluster_ws_header_floats(int tiles) { return cluster_ws_flag_floats(tiles) + 16; }
 
 __device__ __forceinline__ void st_sc1(float* p, float v) {
     __hip_atomic_store(reinterpret_cast<unsigned*>(p), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -102,7 +95,6 @@ inline size_t launch_lds(K kernel, size_t need, const char* who) {
 
 // K-split form of the Gaussian cluster scan (observe_ksplit.hip): used by bd_observe_forward_cluster / _backward_cluster when
 // the cluster has one member per 16-column belief block (ksplit_ok); bd_observe_cluster_set_ksplit(0) keeps the round-1 form
-size_t ksplit_ws_floats_per_tile(int C);
 bool ksplit_ok(int Be, int S, int A, int Hd, int C);
 int& ksplit_mode();
 int launch_observe_kfwd(const bd_observe_fwd_args* a, float* ws, int C, int tiles, hipStream_t stream);

@@ -1,9 +1,17 @@
-// bd_scan.h -- device helpers shared by the imagination scans (imagine.hip: Gaussian latents; scan_cat.hip: Categorical
-// latents): the tanh-Normal entropy sample, hidden-layer / pre-activation-gradient epilogues.
+// bd_scan.h -- what the recurrent scans share: the 16-wide block counts of a shape (ScanDims, every scan) and the device
+// helpers of the imagination scans (imagine.hip: Gaussian latents; scan_cat.hip: Categorical latents): the tanh-Normal
+// entropy sample, hidden-layer / pre-activation-gradient epilogues.  The LDS and workspace maps are in bd_scan_layout.h.
 #pragma once
 #include "bd_device.h"
 
 namespace bd {
+
+// 16-wide K / column blocks of the belief, state, action and hidden widths (Categorical latents: S = 0, the state is D x C)
+struct ScanDims {
+    int Kb_h, Kb_s, Kb_a, Kb_hd;
+    __host__ __device__ ScanDims(int Be, int S, int A, int Hd)
+        : Kb_h(cdiv(Be, 16)), Kb_s(cdiv(S, 16)), Kb_a(cdiv(A, 16)), Kb_hd(cdiv(Hd, 16)) {}
+};
 
 // One sample of the entropy estimate: log-density of y = tanh(mean + std*e) under the tanh-Normal, and its
 // derivatives w.r.t. mean and std following the reference's autograd graph (rsample -> tanh -> clamp ->

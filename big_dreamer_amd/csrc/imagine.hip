@@ -11,7 +11,7 @@
 //   x = ELU(W_e [s; a] + b_e);  h' = GRUCell(x, h);  p = ELU(W_p1 h' + b);  s' = mean_p + std_p * eps_p
 #include "bd_device.h"
 #include "bd_host.h"
-#include "bd_scan.h"
+#include "bd_scan_layout.h"
 #include "bd_rng.h"
 #include "bd_discrete.h"
 
@@ -34,33 +34,29 @@ __device__ unsigned long long g_stamps[64];
 #define BD_STAMP(slot)
 #endif
 
-struct ImgDims {
-    int Kb_h, Kb_s, Kb_a, Kb_hd;
-    __host__ __device__ ImgDims(int Be, int S, int A, int Hd)
-        : Kb_h(cdiv(Be, 16)), Kb_s(cdiv(S, 16)), Kb_a(cdiv(A, 16)), Kb_hd(cdiv(Hd, 16)) {}
-};
-
 
 __global__ __launch_bounds__(kThreads) void imagine_fwd_kernel(bd_imagine_fwd_args a_) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     BD_KARGS(bd_imagine_fwd_args, ap);
 #define a (*ap)
-    const ImgDims d(a.Be, a.S, a.A, a.Hd);
+    const ScanDims d(a.Be, a.S, a.A, a.Hd);
     const int row0 = blockIdx.x * 16;
     const int F = a.Be + a.S, A = a.A;
-    const int nh = d.Kb_h * kFragFloats, nhd = d.Kb_hd * kFragFloats;
-    float* h_cur = smem;
-    float* h_nxt = h_cur + nh;
-    float* xf = h_nxt + nh;
-    float* bufA = xf + nh;
-    float* bufB = bufA + nhd;
-    float* sf = bufB + nhd;
-    float* af = sf + d.Kb_s * kFragFloats;
-    float* mean_s = af + d.Kb_a * kFragFloats;    // [16][A]
-    float* std_s = mean_s + 16 * A;               // [16][A]
-    float* lp_rj = std_s + 16 * A;                // [16][A]
-    float* part = lp_rj + 16 * A;                 // [kWaves][16][A][3]
-    float* scratch = part + kWaves * 16 * A * 3;  // split-K partials (kSplitScratchFloats); 16-byte aligned: see host
+    const ImagineFwdLds L(d, A);
+    // (chained off the layout's offsets: the same addresses as `smem + L.region`, in the form that keeps this kernel's
+    // registers and floating-point contraction where they were -- bd_scan_layout.h)
+    float* h_cur = smem + L.h_cur;
+    float* h_nxt = h_cur + (L.h_nxt - L.h_cur);
+    float* xf = h_nxt + (L.xf - L.h_nxt);
+    float* bufA = xf + (L.bufA - L.xf);
+    float* bufB = bufA + (L.bufB - L.bufA);
+    float* sf = bufB + (L.sf - L.bufB);
+    float* af = sf + (L.af - L.sf);
+    float* mean_s = af + (L.mean_s - L.af);       // [16][A]
+    float* std_s = mean_s + (L.std_s - L.mean_s); // [16][A]
+    float* lp_rj = std_s + (L.lp_rj - L.std_s);   // [16][A]
+    float* part = lp_rj + (L.part - L.lp_rj);     // [kWaves][16][A][3]
+    float* scratch = part + (L.scratch - L.part); // split-K scratch
 
     load_tile_concat<1>(h_cur, d.Kb_h, row0, a.N, a.start_feat, F, a.Be, nullptr, 0, 0);
     load_tile_concat<1>(sf, d.Kb_s, row0, a.N, a.start_feat + a.Be, F, a.S, nullptr, 0, 0);
@@ -374,26 +370,26 @@ __global__ __launch_bounds__(kThreads) void imagine_bwd_kernel(bd_imagine_bwd_ar
     extern __shared__ __attribute__((aligned(16))) float smem[];
     BD_KARGS(bd_imagine_bwd_args, ap);
 #define a (*ap)
-    const ImgDims d(a.Be, a.S, a.A, a.Hd);
+    const ScanDims d(a.Be, a.S, a.A, a.Hd);
     const int row0 = blockIdx.x * 16;
     const int F = a.Be + a.S, A = a.A;
-    const int nh = d.Kb_h * kFragFloats, nhd = d.Kb_hd * kFragFloats, ns = d.Kb_s * kFragFloats,
-              na = d.Kb_a * kFragFloats;
-    float* dhc = smem;
-    float* dR = dhc + nh;
-    float* dZ = dR + nh;
-    float* dNI = dZ + nh;
-    float* dNH = dNI + nh;
-    float* dE = dNH + nh;
-    float* dP = dE + nh;          // Kb_hd
-    float* bufA = dP + nhd;
-    float* bufB = bufA + nhd;
-    float* dM = bufB + nhd;       // Kb_s
-    float* dRaw = dM + ns;
-    float* dAm = dRaw + ns;       // Kb_a
-    float* dAr = dAm + na;
-    float* ds_plain = dAr + na;   // [16][S]
-    float* scratch = ds_plain + 16 * a.S;   // split-K partials (kSplitScratchFloats)
+    const int nh = d.Kb_h * kFragFloats;
+    const ImagineBwdLds L(d, a.S);
+    float* dhc = smem + L.dhc;
+    float* dR = smem + L.dR;
+    float* dZ = smem + L.dZ;
+    float* dNI = smem + L.dNI;
+    float* dNH = smem + L.dNH;
+    float* dE = smem + L.dE;
+    float* dP = smem + L.dP;
+    float* bufA = smem + L.bufA;
+    float* bufB = smem + L.bufB;
+    float* dM = smem + L.dM;
+    float* dRaw = smem + L.dRaw;
+    float* dAm = smem + L.dAm;
+    float* dAr = smem + L.dAr;
+    float* ds_plain = smem + L.ds_plain;    // [16][S]
+    float* scratch = smem + L.scratch;      // split-K partials
 
     // The gradient carry of the recurrence (d belief | d state) is zero behind the last step of the rollout.
     for (int i = threadIdx.x; i < nh; i += blockDim.x) dhc[i] = 0.f;
@@ -646,10 +642,10 @@ static int imagine_forward_scan(const bd_imagine_fwd_args* a, void* stream) {
                "bd_imagine_forward: missing inputs (eps_entropy may be NULL only with sv_act_stats: the entropy estimate is then "
                "the caller's bd_actor_entropy / bd_actor_entropy_rng launch)");
     BD_REQUIRE(a->feat && a->prior_std && a->entropy && a->action, "bd_imagine_forward: missing outputs");
-    const ImgDims d(a->Be, a->S, a->A, a->Hd);
-    // (3*16 + kWaves*16*3)*A floats of small arrays: a multiple of 16 floats, so the scratch stays 16-byte aligned
-    const size_t lds = ((size_t)(3 * d.Kb_h + 2 * d.Kb_hd + d.Kb_s + d.Kb_a) * kFragFloats +
-                        (size_t)(3 * 16 + kWaves * 16 * 3) * a->A + kSplitScratchFloats) * sizeof(float);
+    const ScanDims d(a->Be, a->S, a->A, a->Hd);
+    const ImagineFwdLds L(d, a->A);
+    BD_REQUIRE(L.vec_ok(), "bd_imagine_forward: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_imagine_forward: needs %zu B of LDS", lds);
     if (lds > 64 * 1024 && allow_big_lds(imagine_fwd_kernel)) return -1;
     hipLaunchKernelGGL(imagine_fwd_kernel, dim3(cdiv(a->N, 16)), dim3(kThreads), lds, (hipStream_t)stream, *a);
@@ -703,10 +699,10 @@ int bd_imagine_backward(const bd_imagine_bwd_args* a, void* stream) {
                    a->sv_act_stats && a->sv_x && a->sv_gates && a->sv_p && a->dfeat,
                "bd_imagine_backward: missing forward tensors");
     BD_REQUIRE(a->d_actor_out, "bd_imagine_backward: missing outputs");
-    const ImgDims d(a->Be, a->S, a->A, a->Hd);
-    // (the backward kernels have no element-wise Gaussian head: the split-K partials alone)
-    const size_t lds = ((size_t)(6 * d.Kb_h + 3 * d.Kb_hd + 2 * d.Kb_s + 2 * d.Kb_a) * kFragFloats + 16 * a->S +
-                        kSplitPartialFloats) * sizeof(float);
+    const ScanDims d(a->Be, a->S, a->A, a->Hd);
+    const ImagineBwdLds L(d, a->S);
+    BD_REQUIRE(L.vec_ok(), "bd_imagine_backward: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_imagine_backward: needs %zu B of LDS", lds);
     if (lds > 64 * 1024 && allow_big_lds(imagine_bwd_kernel)) return -1;
     hipLaunchKernelGGL(imagine_bwd_kernel, dim3(cdiv(a->N, 16)), dim3(kThreads), lds, (hipStream_t)stream, *a);

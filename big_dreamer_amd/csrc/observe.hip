@@ -12,29 +12,27 @@
 //   mean, raw = W_q2 q + b_q2; std = softplus(raw)+min_std; s' = mean + std*eps   (models.py:70-73)
 #include "bd_device.h"
 #include "bd_host.h"
+#include "bd_scan_layout.h"
 
 namespace bd {
 
-struct ObsDims {
-    int Kb_h, Kb_s, Kb_a, Kb_hd;
-    __host__ __device__ ObsDims(int Be, int S, int A, int Hd)
-        : Kb_h(cdiv(Be, 16)), Kb_s(cdiv(S, 16)), Kb_a(cdiv(A, 16)), Kb_hd(cdiv(Hd, 16)) {}
-};
-
 __global__ __launch_bounds__(kThreads) void observe_fwd_kernel(bd_observe_fwd_args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const ObsDims d(a.Be, a.S, a.A, a.Hd);
+    const ScanDims d(a.Be, a.S, a.A, a.Hd);
     const int lane = threadIdx.x & 63;
     const int row0 = blockIdx.x * 16;
     const int F = a.Be + a.S;
-    float* h_cur = smem;
-    float* h_nxt = h_cur + d.Kb_h * kFragFloats;
-    float* xf = h_nxt + d.Kb_h * kFragFloats;
-    float* qf = xf + d.Kb_h * kFragFloats;
-    float* sf = qf + d.Kb_hd * kFragFloats;
-    float* af = sf + d.Kb_s * kFragFloats;
-    float* s_plain = af + d.Kb_a * kFragFloats;   // [16][S] unmasked posterior state of the previous step
-    float* scratch = s_plain + 16 * a.S;          // split-K partials (kSplitScratchFloats)
+    const ObserveFwdLds L(d, a.S, kObsFwdScratch);
+    // (chained off the layout's offsets: the same addresses as `smem + L.region`, in the form that keeps this kernel's
+    // registers and floating-point contraction where they were -- bd_scan_layout.h)
+    float* h_cur = smem + L.h_cur;
+    float* h_nxt = h_cur + (L.h_nxt - L.h_cur);
+    float* xf = h_nxt + (L.xf - L.h_nxt);
+    float* qf = xf + (L.qf - L.xf);
+    float* sf = qf + (L.sf - L.qf);
+    float* af = sf + (L.af - L.sf);
+    float* s_plain = af + (L.s_plain - L.af);     // [16][S] unmasked posterior state of the previous step
+    float* scratch = s_plain + (L.scratch - L.s_plain);   // split-K partials
 
     load_tile_concat<1>(h_cur, d.Kb_h, row0, a.B, a.init_belief, a.Be, a.Be, nullptr, 0, 0);
     for (int i = threadIdx.x; i < 16 * a.S; i += blockDim.x) {
@@ -145,22 +143,23 @@ __global__ __launch_bounds__(kThreads) void observe_fwd_kernel(bd_observe_fwd_ar
 // ---- backward ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void observe_bwd_kernel(bd_observe_bwd_args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const ObsDims d(a.Be, a.S, a.A, a.Hd);
+    const ScanDims d(a.Be, a.S, a.A, a.Hd);
     const int lane = threadIdx.x & 63;
     const int row0 = blockIdx.x * 16;
     const int F = a.Be + a.S;
-    const int nh = d.Kb_h * kFragFloats, ns = d.Kb_s * kFragFloats;
-    float* dhc = smem;            // carry: d loss / d belief_t (through the recurrence)
-    float* dR = dhc + nh;
-    float* dZ = dR + nh;
-    float* dNI = dZ + nh;
-    float* dNH = dNI + nh;
-    float* dE = dNH + nh;
-    float* dQ = dE + nh;                               // Kb_hd
-    float* dM = dQ + d.Kb_hd * kFragFloats;            // Kb_s
-    float* dRaw = dM + ns;
-    float* ds_plain = dRaw + ns;                       // [16][S] carry: d loss / d posterior_state_t
-    float* scratch = ds_plain + 16 * a.S;              // split-K partials (kSplitScratchFloats)
+    const int nh = d.Kb_h * kFragFloats;
+    const ObserveBwdLds L(d, a.S, kObsBwdScratch);
+    float* dhc = smem + L.dhc;    // carry: d loss / d belief_t (through the recurrence)
+    float* dE = smem + L.dE;
+    float* dR = smem + L.dR;
+    float* dZ = smem + L.dZ;
+    float* dNI = smem + L.dNI;
+    float* dNH = smem + L.dNH;
+    float* dQ = smem + L.dQ;
+    float* dM = smem + L.dM;
+    float* dRaw = smem + L.dRaw;
+    float* ds_plain = smem + L.ds_plain;               // [16][S] carry: d loss / d posterior_state_t
+    float* scratch = smem + L.scratch;                 // split-K partials
 
     for (int i = threadIdx.x; i < nh; i += blockDim.x) dhc[i] = 0.f;
     for (int i = threadIdx.x; i < 16 * a.S; i += blockDim.x) ds_plain[i] = 0.f;
@@ -297,9 +296,10 @@ int bd_observe_forward(const bd_observe_fwd_args* a, void* stream) {
     BD_REQUIRE(a->init_belief && a->init_state && a->actions && a->pre_emb && a->eps_post,
                "bd_observe_forward: missing inputs");
     BD_REQUIRE(a->feat && a->post_mean && a->post_std, "bd_observe_forward: missing outputs");
-    const ObsDims d(a->Be, a->S, a->A, a->Hd);
-    const size_t lds = ((size_t)(3 * d.Kb_h + d.Kb_hd + d.Kb_s + d.Kb_a) * kFragFloats + 16 * a->S + kSplitScratchFloats) *
-                       sizeof(float);
+    const ScanDims d(a->Be, a->S, a->A, a->Hd);
+    const ObserveFwdLds L(d, a->S, kObsFwdScratch);
+    BD_REQUIRE(L.vec_ok(), "bd_observe_forward: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_observe_forward: needs %zu B of LDS", lds);
     if (lds > 64 * 1024 && allow_big_lds(observe_fwd_kernel)) return -1;
     hipLaunchKernelGGL(observe_fwd_kernel, dim3(cdiv(a->B, 16)), dim3(kThreads), lds, (hipStream_t)stream, *a);
@@ -314,9 +314,10 @@ int bd_observe_backward(const bd_observe_bwd_args* a, void* stream) {
     BD_REQUIRE(a->init_belief && a->eps_post && a->feat && a->post_std && a->sv_x && a->sv_gates && a->sv_q && a->dfeat,
                "bd_observe_backward: missing forward tensors");
     BD_REQUIRE(a->d_embed_pre && a->d_gi && a->d_gh && a->d_q1_pre && a->d_q2_out, "bd_observe_backward: missing outputs");
-    const ObsDims d(a->Be, a->S, a->A, a->Hd);
-    const size_t lds = ((size_t)(6 * d.Kb_h + d.Kb_hd + 2 * d.Kb_s) * kFragFloats + 16 * a->S + kSplitScratchFloats) *
-                       sizeof(float);
+    const ScanDims d(a->Be, a->S, a->A, a->Hd);
+    const ObserveBwdLds L(d, a->S, kObsBwdScratch);
+    BD_REQUIRE(L.vec_ok(), "bd_observe_backward: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_observe_backward: needs %zu B of LDS", lds);
     if (lds > 64 * 1024 && allow_big_lds(observe_bwd_kernel)) return -1;
     hipLaunchKernelGGL(observe_bwd_kernel, dim3(cdiv(a->B, 16)), dim3(kThreads), lds, (hipStream_t)stream, *a);

@@ -80,33 +80,36 @@ __global__ __launch_bounds__(kThreads) void observe_cat_cfwd_kernel(bd_observe_c
     BD_KARGS(bd_observe_cat_fwd_args, ap);
 #define a (*ap)
     const CatGeo g(a.D, a.C);
-    const int Kb_h = cdiv(a.Be, 16), Kb_a = cdiv(a.A, 16), Kb_hd = cdiv(a.Hd, 16);
+    const ScanDims d(a.Be, 0, a.A, a.Hd);
+    const int Kb_h = d.Kb_h, Kb_a = d.Kb_a, Kb_hd = d.Kb_hd;
     const int tile = blockIdx.x / Cm, c = blockIdx.x - tile * Cm;
     const int row0 = tile * 16;
     const int S = g.S, F = a.Be + S;
-    const int nh = Kb_h * kFragFloats, nhd = Kb_hd * kFragFloats;
+    const int nh = Kb_h * kFragFloats;
     const int rows_valid = a.B - row0 < 16 ? a.B - row0 : 16;
     const int Nb = Kb_h;
     const CatOwn own(a.D, a.C, Cm, c);
     const CatFull gl(own.nfm, a.C);                // image of the member's OWN logit columns (local factor index)
-    float* h_cur = smem;
-    float* h_nxt = h_cur + nh;
-    float* xf = h_nxt + nh;
-    float* qf = xf + nh;
-    float* af = qf + nhd;
-    float* xs = af + Kb_a * kFragFloats;          // [16][Be] gathered W_es s~
-    float* lg = xs + 16 * a.Be;                   // own logits (swizzled image)
-    float* sw_l = lg + gl.image_floats();         // [16][D]
-    float* mrow = sw_l + 16 * g.D;                // [16]
-    int* sidx_l = reinterpret_cast<int*>(mrow + 16);            // [16][D]
-    float* scratch = reinterpret_cast<float*>(sidx_l + 16 * g.D);   // GRU partials | logit partials
+    const CatObserveFwdLds L(d, a.Be, a.D, gl, cat_cluster_scratch(own.nbl, true));
+    float* h_cur = smem + L.h_cur;
+    float* h_nxt = smem + L.h_nxt;
+    float* xf = smem + L.xf;
+    float* qf = smem + L.qf;
+    float* af = smem + L.af;
+    float* xs = smem + L.xs;                      // [16][Be] gathered W_es s~
+    float* lg = smem + L.lg;                      // own logits (swizzled image)
+    float* sw_l = smem + L.sw_l;                  // [16][D]
+    float* mrow = smem + L.mrow;                  // [16]
+    int* sidx_l = reinterpret_cast<int*>(smem + L.sidx_l);      // [16][D]
+    float* scratch = smem + L.scratch;            // GRU partials | logit partials | split-K scratch
     floatx4* __restrict__ G4 = reinterpret_cast<floatx4*>(scratch);
 
     unsigned* flags = reinterpret_cast<unsigned*>(ws) + tile * kMaxCluster;
     unsigned* err = reinterpret_cast<unsigned*>(ws) + tiles * kMaxCluster;
-    const size_t per_tile = (size_t)2 * nh + (size_t)2 * 16 * g.D;
-    float* xbuf_h = ws + cluster_ws_header_floats(tiles) + (size_t)tile * per_tile;     // [2][nh]
-    unsigned* xbuf_s = reinterpret_cast<unsigned*>(xbuf_h + 2 * nh);                    // [2][16][D]
+    const CatClusterWs X(Kb_h, Kb_hd, a.D, Cm);
+    float* xbuf_t = ws + cluster_ws_header_floats(tiles) + (size_t)tile * X.fwd_tile;
+    float* xbuf_h = xbuf_t + X.fwd_h;                                                   // [2][nh]
+    unsigned* xbuf_s = reinterpret_cast<unsigned*>(xbuf_t + X.fwd_s);                   // [2][16][D]
 
     load_tile_concat<1>(h_cur, Kb_h, row0, a.B, a.init_belief, a.Be, a.Be, nullptr, 0, 0);
     state_to_indices(g, a.init_state, (size_t)S, row0, a.B, sidx_l, sw_l);
@@ -362,7 +365,8 @@ __global__ __launch_bounds__(kThreads) void observe_cat_cbwd_kernel(bd_observe_c
     BD_KARGS(bd_observe_cat_bwd_args, ap);
 #define a (*ap)
     const CatGeo g(a.D, a.C);
-    const int Kb_h = cdiv(a.Be, 16), Kb_hd = cdiv(a.Hd, 16), Kb_S = cdiv(g.S, 16);
+    const ScanDims d(a.Be, 0, a.A, a.Hd);
+    const int Kb_h = d.Kb_h, Kb_hd = d.Kb_hd, Kb_S = cdiv(g.S, 16);
     const int tile = blockIdx.x / Cm, c = blockIdx.x - tile * Cm;
     const int row0 = tile * 16;
     const int S = g.S, F = a.Be + S;
@@ -371,25 +375,29 @@ __global__ __launch_bounds__(kThreads) void observe_cat_cbwd_kernel(bd_observe_c
     const int Nb = Kb_h;
     const CatOwn own(a.D, a.C, Cm, c);
     const CatGeo go(own.nfm, a.C);                 // the member's own factors as a one-chunk geometry (ld = ncols + 8)
-    float* dhc = smem;                             // [dhc | dE] contiguous: one payload of 2*nh floats
-    float* dE = dhc + nh;
-    float* dR = dE + nh;
-    float* dZ = dR + nh;
-    float* dNI = dZ + nh;
-    float* dNH = dNI + nh;
-    float* dQ = dNH + nh;                          // Kb_hd
-    float* pl = dQ + nhd;                          // own columns: g, then d logits (swizzled image)
-    float* lgs = pl + go.image_floats();           // own logits (swizzled image)
-    float* dLf = lgs + go.image_floats();          // own d logits as a fragment tile (nbl K blocks)
-    float* mrow = dLf + own.nbl * kFragFloats;     // [16]
-    float* scratch = mrow + 16;
+    const CatObserveBwdLds L(d, go, cat_cluster_scratch(own.nbl, false));
+    // (chained off the layout's offsets: the same addresses as `smem + L.region`, in the form that keeps this kernel's
+    // registers and floating-point contraction where they were -- bd_scan_layout.h)
+    float* dhc = smem + L.dhc;                     // [dhc | dE] contiguous: one payload of 2*nh floats
+    float* dE = dhc + (L.dE - L.dhc);
+    float* dR = dE + (L.dR - L.dE);
+    float* dZ = dR + (L.dZ - L.dR);
+    float* dNI = dZ + (L.dNI - L.dZ);
+    float* dNH = dNI + (L.dNH - L.dNI);
+    float* dQ = dNH + (L.dQ - L.dNH);
+    float* pl = dQ + (L.pl - L.dQ);                // own columns: g, then d logits (swizzled image)
+    float* lgs = pl + (L.lgs - L.pl);              // own logits (swizzled image)
+    float* dLf = lgs + (L.dLf - L.lgs);            // own d logits as a fragment tile (nbl K blocks)
+    float* mrow = dLf + (L.mrow - L.dLf);          // [16]
+    float* scratch = mrow + (L.scratch - L.mrow);  // GRU dgrad partials | d hidden partials | split-K scratch
     floatx4* __restrict__ G4 = reinterpret_cast<floatx4*>(scratch);
 
     unsigned* flags = reinterpret_cast<unsigned*>(ws) + tile * kMaxCluster;
     unsigned* err = reinterpret_cast<unsigned*>(ws) + tiles * kMaxCluster;
-    const size_t per_tile = (size_t)2 * (2 * nh) + (size_t)2 * Cm * nhd;
-    float* xbuf_c = ws + cluster_ws_header_floats(tiles) + (size_t)tile * per_tile;     // [2][2*nh]   carry | d embed
-    float* xbuf_q = xbuf_c + 2 * (2 * nh);                                              // [2][Cm][nhd] d hidden partials
+    const CatClusterWs X(Kb_h, Kb_hd, a.D, Cm);
+    float* xbuf_t = ws + cluster_ws_header_floats(tiles) + (size_t)tile * X.bwd_tile;
+    float* xbuf_c = xbuf_t + X.bwd_c;                                                   // [2][2*nh]   carry | d embed
+    float* xbuf_q = xbuf_t + X.bwd_q;                                                   // [2][Cm][nhd] d hidden partials
 
     for (int i = threadIdx.x; i < 2 * nh; i += blockDim.x) dhc[i] = 0.f;
     lds_barrier();
@@ -718,15 +726,6 @@ static int pick_cat_cluster(int B, int Be, int D, int C, int max_wgs) {
     return 0;
 }
 
-// LDS scratch: split-K partials of the GRU blocks (forward: 4 gate accumulators per block, backward: 2), of the member's own
-// logit column blocks, and the narrow-head split-K scratch of the tile primitives
-static size_t cat_scratch_floats(int nbl, bool fwd) {
-    size_t n = (size_t)kWaves * kLocalBlocks * (fwd ? 4 : 2) * 64 * 4;
-    const size_t head = (size_t)kWaves * nbl * 64 * 4;
-    if (head > n) n = head;
-    return n > (size_t)kSplitScratchFloats ? n : (size_t)kSplitScratchFloats;
-}
-
 }  // namespace bd
 
 extern "C" {
@@ -742,10 +741,7 @@ int bd_observe_cat_cluster_size(int B, int Be, int D, int C, int max_wgs) { retu
 
 size_t bd_observe_cat_cluster_ws_floats(int B, int Be, int Hd, int D, int Cm) {
     const int tiles = cdiv(B, 16);
-    const size_t nh = (size_t)cdiv(Be, 16) * kFragFloats, nhd = (size_t)cdiv(Hd, 16) * kFragFloats;
-    const size_t fwd = 2 * nh + (size_t)2 * 16 * D;
-    const size_t bwd = 2 * (2 * nh) + (size_t)2 * Cm * nhd;
-    return cluster_ws_header_floats(tiles) + (size_t)tiles * (fwd > bwd ? fwd : bwd);
+    return cluster_ws_header_floats(tiles) + (size_t)tiles * CatClusterWs(cdiv(Be, 16), cdiv(Hd, 16), D, Cm).per_tile;
 }
 
 #define BD_CATC_GEO(who)                                                                                                     \
@@ -767,10 +763,10 @@ int bd_observe_cat_forward_cluster(const bd_observe_cat_fwd_args* a, int Cm, flo
     BD_REQUIRE(a->init_belief && a->init_state && a->actions && a->pre_emb && a->q_post, "bd_observe_cat_forward_cluster: missing inputs");
     BD_REQUIRE(a->feat && a->post_logits && a->sidx, "bd_observe_cat_forward_cluster: missing outputs");
     const int tiles = cdiv(a->B, 16);
-    const int Kb_h = cdiv(a->Be, 16), Kb_a = cdiv(a->A, 16), Kb_hd = cdiv(a->Hd, 16);
-    const CatFull gl(a->D / Cm, a->C);
-    const size_t lds = ((size_t)(3 * Kb_h + Kb_hd + Kb_a) * kFragFloats + 16 * a->Be + gl.image_floats() + 2 * 16 * g.D + 16 +
-                        cat_scratch_floats((a->D / Cm) * a->C / 16, true)) * sizeof(float);
+    const CatOwn own(a->D, a->C, Cm, 0);
+    const CatObserveFwdLds L(ScanDims(a->Be, 0, a->A, a->Hd), a->Be, a->D, CatFull(own.nfm, a->C), cat_cluster_scratch(own.nbl, true));
+    BD_REQUIRE(L.vec_ok(), "bd_observe_cat_forward_cluster: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_observe_cat_forward_cluster: needs %zu B of LDS", lds);
     if (allow_big_lds(observe_cat_cfwd_kernel)) return -1;
     const size_t dyn = launch_lds(observe_cat_cfwd_kernel, lds, "bd_observe_cat_forward_cluster");
@@ -792,10 +788,10 @@ int bd_observe_cat_backward_cluster(const bd_observe_cat_bwd_args* a, int Cm, fl
                "bd_observe_cat_backward_cluster: missing forward tensors");
     BD_REQUIRE(a->d_embed_pre && a->d_gi && a->d_gh && a->d_q1_pre && a->d_q2_out, "bd_observe_cat_backward_cluster: missing outputs");
     const int tiles = cdiv(a->B, 16);
-    const int Kb_h = cdiv(a->Be, 16), Kb_hd = cdiv(a->Hd, 16);
-    const CatGeo go(a->D / Cm, a->C);
-    const size_t lds = ((size_t)(6 * Kb_h + Kb_hd + (a->D / Cm) * a->C / 16) * kFragFloats + 2 * go.image_floats() + 16 +
-                        cat_scratch_floats((a->D / Cm) * a->C / 16, false)) * sizeof(float);
+    const CatOwn own(a->D, a->C, Cm, 0);
+    const CatObserveBwdLds L(ScanDims(a->Be, 0, a->A, a->Hd), CatGeo(own.nfm, a->C), cat_cluster_scratch(own.nbl, false));
+    BD_REQUIRE(L.vec_ok(), "bd_observe_cat_backward_cluster: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_observe_cat_backward_cluster: needs %zu B of LDS", lds);
     if (allow_big_lds(observe_cat_cbwd_kernel)) return -1;
     const size_t dyn = launch_lds(observe_cat_cbwd_kernel, lds, "bd_observe_cat_backward_cluster");

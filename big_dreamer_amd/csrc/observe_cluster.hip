@@ -33,11 +33,6 @@ __device__ unsigned long long g_cstamps[64];
 #else
 #define BD_CSTAMP(slot)
 #endif
-struct ObsDimsC {
-    int Kb_h, Kb_s, Kb_a, Kb_hd;
-    __host__ __device__ ObsDimsC(int Be, int S, int A, int Hd)
-        : Kb_h(cdiv(Be, 16)), Kb_s(cdiv(S, 16)), Kb_a(cdiv(A, 16)), Kb_hd(cdiv(Hd, 16)) {}
-};
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void observe_cfwd_kernel(bd_observe_fwd_args a_, float* __restrict__ ws, int C,
@@ -45,25 +40,27 @@ __global__ __launch_bounds__(kThreads) void observe_cfwd_kernel(bd_observe_fwd_a
     extern __shared__ __attribute__((aligned(16))) float smem[];
     BD_KARGS(bd_observe_fwd_args, ap);      // first kernel argument: offset 0 of the kernarg segment
 #define a (*ap)
-    const ObsDimsC d(a.Be, a.S, a.A, a.Hd);
+    const ScanDims d(a.Be, a.S, a.A, a.Hd);
     const int tile = blockIdx.x / C, c = blockIdx.x - tile * C;
     const int row0 = tile * 16;
     const int F = a.Be + a.S;
     const int nh = d.Kb_h * kFragFloats;
     const int Nb = d.Kb_h;
-    float* h_cur = smem;
-    float* h_nxt = h_cur + nh;
-    float* xf = h_nxt + nh;
-    float* qf = xf + nh;
-    float* sf = qf + d.Kb_hd * kFragFloats;
-    float* af = sf + d.Kb_s * kFragFloats;
-    float* s_plain = af + d.Kb_a * kFragFloats;          // [16][S]
-    float* scratch = s_plain + 16 * a.S;                 // max(split-K scratch, GRU partials)
+    const ObserveFwdLds L(d, a.S, kObsCfwdScratch);
+    float* h_cur = smem + L.h_cur;
+    float* h_nxt = smem + L.h_nxt;
+    float* xf = smem + L.xf;
+    float* qf = smem + L.qf;
+    float* sf = smem + L.sf;
+    float* af = smem + L.af;
+    float* s_plain = smem + L.s_plain;                   // [16][S]
+    float* scratch = smem + L.scratch;                   // GRU partials | split-K scratch
     floatx4* __restrict__ G4 = reinterpret_cast<floatx4*>(scratch);   // GRU partials [wave][blk][4][64]
 
     unsigned* flags = reinterpret_cast<unsigned*>(ws) + tile * kMaxCluster;
     unsigned* err = reinterpret_cast<unsigned*>(ws) + tiles * kMaxCluster;
-    float* xbuf = ws + cluster_ws_header_floats(tiles) + (size_t)tile * 2 * nh;
+    const ObsClusterWs X(d.Kb_h);
+    float* xbuf = ws + cluster_ws_header_floats(tiles) + (size_t)tile * X.fwd_tile;
 
     load_tile_concat<1>(h_cur, d.Kb_h, row0, a.B, a.init_belief, a.Be, a.Be, nullptr, 0, 0);
     for (int i = threadIdx.x; i < 16 * a.S; i += blockDim.x) {
@@ -176,7 +173,7 @@ __global__ __launch_bounds__(kThreads) void observe_cfwd_kernel(bd_observe_fwd_a
                 const floatx4* g = G4 + ((w * kLocalBlocks + wave) * 4) * 64 + lane;
                 R += g[0]; Z += g[64]; NI += g[128]; NH += g[192];
             }
-            float* xb = xbuf + (size_t)(t & 1) * nh;
+            float* xb = xbuf + (size_t)(t & 1) * X.fwd_copy;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int grow = row0 + 4 * (lane >> 4) + r;
@@ -209,7 +206,7 @@ __global__ __launch_bounds__(kThreads) void observe_cfwd_kernel(bd_observe_fwd_a
         BD_CSTAMP(6);
         wait_all(flags, C, (unsigned)(t + 1), err, spin_limit, kErrFwd);
         BD_CSTAMP(7);
-        gather_payload(xbuf + (size_t)(t & 1) * nh, h_nxt, nh);
+        gather_payload(xbuf + (size_t)(t & 1) * X.fwd_copy, h_nxt, nh);
         lds_barrier();
         BD_CSTAMP(8);
         BD_KARGS_FRESH(ap);
@@ -279,28 +276,30 @@ __global__ __launch_bounds__(kThreads) void observe_cbwd_kernel(bd_observe_bwd_a
     extern __shared__ __attribute__((aligned(16))) float smem[];
     BD_KARGS(bd_observe_bwd_args, ap);      // first kernel argument: offset 0 of the kernarg segment
 #define a (*ap)
-    const ObsDimsC d(a.Be, a.S, a.A, a.Hd);
+    const ScanDims d(a.Be, a.S, a.A, a.Hd);
     const int tile = blockIdx.x / C, c = blockIdx.x - tile * C;
     const int row0 = tile * 16;
     const int F = a.Be + a.S;
-    const int nh = d.Kb_h * kFragFloats, ns = d.Kb_s * kFragFloats;
+    const int nh = d.Kb_h * kFragFloats;
     const int Nb = d.Kb_h;
-    float* dhc = smem;                                  // [dE | dhc] are contiguous: one payload of 2*nh floats
-    float* dE = dhc + nh;
-    float* dR = dE + nh;
-    float* dZ = dR + nh;
-    float* dNI = dZ + nh;
-    float* dNH = dNI + nh;
-    float* dQ = dNH + nh;                               // Kb_hd
-    float* dM = dQ + d.Kb_hd * kFragFloats;             // Kb_s
-    float* dRaw = dM + ns;
-    float* ds_plain = dRaw + ns;                        // [16][S]
-    float* scratch = ds_plain + 16 * a.S;
+    const ObserveBwdLds L(d, a.S, kObsCbwdScratch);
+    float* dhc = smem + L.dhc;                          // [dhc | dE] are contiguous: one payload of 2*nh floats
+    float* dE = smem + L.dE;
+    float* dR = smem + L.dR;
+    float* dZ = smem + L.dZ;
+    float* dNI = smem + L.dNI;
+    float* dNH = smem + L.dNH;
+    float* dQ = smem + L.dQ;
+    float* dM = smem + L.dM;
+    float* dRaw = smem + L.dRaw;
+    float* ds_plain = smem + L.ds_plain;                // [16][S]
+    float* scratch = smem + L.scratch;                  // GRU dgrad partials | split-K partials
     floatx4* __restrict__ G4 = reinterpret_cast<floatx4*>(scratch);   // phase-4 partials [wave][blk][2][64]
 
     unsigned* flags = reinterpret_cast<unsigned*>(ws) + tile * kMaxCluster;
     unsigned* err = reinterpret_cast<unsigned*>(ws) + tiles * kMaxCluster;
-    float* xbuf = ws + cluster_ws_header_floats(tiles) + (size_t)tile * 2 * (2 * nh);
+    const ObsClusterWs X(d.Kb_h);
+    float* xbuf = ws + cluster_ws_header_floats(tiles) + (size_t)tile * X.bwd_tile;
 
     for (int i = threadIdx.x; i < 2 * nh; i += blockDim.x) dhc[i] = 0.f;
     for (int i = threadIdx.x; i < 16 * a.S; i += blockDim.x) ds_plain[i] = 0.f;
@@ -482,7 +481,7 @@ __global__ __launch_bounds__(kThreads) void observe_cbwd_kernel(bd_observe_bwd_a
                 DX += g[0]; DH += g[64];
             }
             const int col = my_nb * 16 + (lane & 15);
-            float* xb = xbuf + (size_t)(epoch & 1) * (2 * nh);
+            float* xb = xbuf + (size_t)(epoch & 1) * X.bwd_copy;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int grow = row0 + 4 * (lane >> 4) + r;
@@ -510,7 +509,7 @@ __global__ __launch_bounds__(kThreads) void observe_cbwd_kernel(bd_observe_bwd_a
         BD_CSTAMP(21);
         wait_all(flags, C, epoch, err, spin_limit, kErrBwd);
         BD_CSTAMP(22);
-        gather_payload(xbuf + (size_t)(epoch & 1) * (2 * nh), dhc, 2 * nh);
+        gather_payload(xbuf + (size_t)(epoch & 1) * X.bwd_copy, dhc, 2 * nh);
         lds_barrier();
         BD_KARGS_FRESH(ap);
         BD_CSTAMP(23);
@@ -547,15 +546,6 @@ unsigned& cluster_spin_limit() {
     return v;
 }
 
-static size_t scratch_floats_fwd() {
-    const size_t gru = (size_t)kWaves * kLocalBlocks * 4 * 64 * 4;
-    return gru > (size_t)kSplitScratchFloats ? gru : (size_t)kSplitScratchFloats;
-}
-static size_t scratch_floats_bwd() {
-    const size_t gru = (size_t)kWaves * kLocalBlocks * 2 * 64 * 4;
-    return gru > (size_t)kSplitPartialFloats ? gru : (size_t)kSplitPartialFloats;
-}
-
 }  // namespace bd
 
 extern "C" {
@@ -571,13 +561,51 @@ int bd_observe_cluster_size(int B, int Be) { return pick_cluster(B, Be); }
 
 size_t bd_observe_cluster_ws_floats(int B, int Be) {
     const int tiles = cdiv(B, 16);
-    size_t per_tile = (size_t)2 * 2 * cdiv(Be, 16) * kFragFloats;
+    size_t per_tile = ObsClusterWs(cdiv(Be, 16)).per_tile;
     const int C = pick_cluster(B, Be);
-    if (C > 0 && ksplit_ws_floats_per_tile(C) > per_tile) per_tile = ksplit_ws_floats_per_tile(C);   // K-split form (observe_ksplit.hip)
+    if (C > 0 && kKsCopies * KsBuf(C).total > per_tile) per_tile = kKsCopies * KsBuf(C).total;   // K-split form (observe_ksplit.hip)
     return cluster_ws_header_floats(tiles) + (size_t)tiles * per_tile;
 }
 
 size_t bd_observe_cluster_err_offset(int B) { return cluster_ws_flag_floats(cdiv(B, 16)); }
+
+// total of the kernel's LDS layout (bd_scan_layout.h) in bytes; 0 with the error text set when there is none.  Host only.
+size_t bd_scan_lds_bytes(int kernel, int Be, int S, int D, int C, int A, int Hd, int Cm) {
+    const bool cat = kernel >= BD_SCAN_OBSERVE_CAT_FWD && kernel <= BD_SCAN_OBSERVE_CAT_CBWD;
+    const bool catc = kernel == BD_SCAN_OBSERVE_CAT_CFWD || kernel == BD_SCAN_OBSERVE_CAT_CBWD;
+    if (kernel < BD_SCAN_OBSERVE_FWD || kernel > BD_SCAN_OBSERVE_CAT_CBWD) return fail("bd_scan_lds_bytes: unknown kernel %d", kernel), 0;
+    if (Be <= 0 || A <= 0 || Hd <= 0 || (cat ? (D <= 0 || C <= 0) : S <= 0)) return fail("bd_scan_lds_bytes: bad dims"), 0;
+    if (catc && (Cm <= 0 || D % Cm != 0)) return fail("bd_scan_lds_bytes: cluster size %d does not divide D=%d", Cm, D), 0;
+    const ScanDims d(Be, cat ? 0 : S, A, Hd);
+    const int nfm = catc ? D / Cm : D, nbl = nfm * C / 16;
+    int total = 0;
+    bool ok = false;
+#define BD_LAYOUT(id, ...)            \
+    case id: {                        \
+        const __VA_ARGS__;            \
+        total = L.total;              \
+        ok = L.vec_ok();              \
+    } break
+    switch (kernel) {
+        BD_LAYOUT(BD_SCAN_OBSERVE_FWD, ObserveFwdLds L(d, S, kObsFwdScratch));
+        BD_LAYOUT(BD_SCAN_OBSERVE_BWD, ObserveBwdLds L(d, S, kObsBwdScratch));
+        BD_LAYOUT(BD_SCAN_OBSERVE_CFWD, ObserveFwdLds L(d, S, kObsCfwdScratch));
+        BD_LAYOUT(BD_SCAN_OBSERVE_CBWD, ObserveBwdLds L(d, S, kObsCbwdScratch));
+        BD_LAYOUT(BD_SCAN_OBSERVE_KFWD, KsplitFwdLds L(d, S));
+        BD_LAYOUT(BD_SCAN_OBSERVE_KBWD, KsplitBwdLds L(d, S));
+        BD_LAYOUT(BD_SCAN_IMAGINE_FWD, ImagineFwdLds L(d, A));
+        BD_LAYOUT(BD_SCAN_IMAGINE_BWD, ImagineBwdLds L(d, S));
+        BD_LAYOUT(BD_SCAN_OBSERVE_CAT_FWD, CatObserveFwdLds L(d, Be, D, CatFull(D, C), 0));
+        BD_LAYOUT(BD_SCAN_OBSERVE_CAT_BWD, CatObserveBwdLds L(d, CatGeo(D, C), 0));
+        BD_LAYOUT(BD_SCAN_IMAGINE_CAT_FWD, CatImagineFwdLds L(d, Be, Hd, D, A, CatFull(D, C)));
+        BD_LAYOUT(BD_SCAN_IMAGINE_CAT_BWD, CatImagineBwdLds L(d, CatGeo(D, C)));
+        BD_LAYOUT(BD_SCAN_OBSERVE_CAT_CFWD, CatObserveFwdLds L(d, Be, D, CatFull(nfm, C), cat_cluster_scratch(nbl, true)));
+        BD_LAYOUT(BD_SCAN_OBSERVE_CAT_CBWD, CatObserveBwdLds L(d, CatGeo(nfm, C), cat_cluster_scratch(nbl, false)));
+    }
+#undef BD_LAYOUT
+    if (!ok) return fail("bd_scan_lds_bytes: kernel %d: misaligned LDS layout", kernel), 0;
+    return (size_t)total * sizeof(float);
+}
 
 // which cluster form bd_observe_forward_cluster / _backward_cluster run wherever the K-split form applies: -1 = the K-split
 // form (observe_ksplit.hip, the default), 0 = the round-1 form (GRU columns split, the rest redundant); anything else fails
@@ -618,9 +646,10 @@ int bd_observe_forward_cluster(const bd_observe_fwd_args* a, float* ws, size_t w
     BD_REQUIRE(C > 0, "bd_observe_forward_cluster: B=%d, Be=%d do not fit the cluster variant", a->B, a->Be);
     const int tiles = cdiv(a->B, 16);
     BD_REQUIRE(ws_floats >= bd_observe_cluster_ws_floats(a->B, a->Be), "bd_observe_forward_cluster: workspace too small");
-    const ObsDimsC d(a->Be, a->S, a->A, a->Hd);
-    const size_t lds = ((size_t)(3 * d.Kb_h + d.Kb_hd + d.Kb_s + d.Kb_a) * kFragFloats + 16 * a->S + scratch_floats_fwd()) *
-                       sizeof(float);
+    const ScanDims d(a->Be, a->S, a->A, a->Hd);
+    const ObserveFwdLds L(d, a->S, kObsCfwdScratch);
+    BD_REQUIRE(L.vec_ok(), "bd_observe_forward_cluster: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_observe_forward_cluster: needs %zu B of LDS", lds);
     if (ksplit_ok(a->Be, a->S, a->A, a->Hd, C))          // every layer split along K over the members, weights in registers
         return launch_observe_kfwd(a, ws, C, tiles, (hipStream_t)stream);      // (zeroes what its hand-off form polls)
@@ -646,9 +675,10 @@ int bd_observe_backward_cluster(const bd_observe_bwd_args* a, float* ws, size_t 
     BD_REQUIRE(C > 0, "bd_observe_backward_cluster: B=%d, Be=%d do not fit the cluster variant", a->B, a->Be);
     const int tiles = cdiv(a->B, 16);
     BD_REQUIRE(ws_floats >= bd_observe_cluster_ws_floats(a->B, a->Be), "bd_observe_backward_cluster: workspace too small");
-    const ObsDimsC d(a->Be, a->S, a->A, a->Hd);
-    const size_t lds = ((size_t)(6 * d.Kb_h + d.Kb_hd + 2 * d.Kb_s) * kFragFloats + 16 * a->S + scratch_floats_bwd()) *
-                       sizeof(float);
+    const ScanDims d(a->Be, a->S, a->A, a->Hd);
+    const ObserveBwdLds L(d, a->S, kObsCbwdScratch);
+    BD_REQUIRE(L.vec_ok(), "bd_observe_backward_cluster: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_observe_backward_cluster: needs %zu B of LDS", lds);
     if (ksplit_ok(a->Be, a->S, a->A, a->Hd, C)) return launch_observe_kbwd(a, ws, C, tiles, (hipStream_t)stream);
     if (allow_big_lds(observe_cbwd_kernel)) return -1;

@@ -56,7 +56,6 @@ __device__ __forceinline__ floatx4 ks_load4(const float* p) {
                    __uint_as_float((unsigned)(hi >> 32))};
 }
 // Hand-offs use form R1 of bd_cluster.h; why not the granule form (R2): DESIGN.md, "The floor of the K-split scan is the hand-off".
-constexpr int kKsImg = 256;        // an image = the float4 of 64 lanes
 
 __device__ __forceinline__ void ks_emit(float* img, int lane, floatx4 v) { ks_store4(img + lane * 4, v); }
 
@@ -108,18 +107,6 @@ __device__ __forceinline__ void ks_settle(floatx4 (&v)[N]) {
 __device__ __forceinline__ floatx4 ks_frag(const float* w, int nb, int Kb, int kb, int lane, bool ok) {
     return ok ? reinterpret_cast<const floatx4*>(w)[((size_t)nb * Kb + kb) * 64 + lane] : floatx4{0.f, 0.f, 0.f, 0.f};
 }
-
-// exchange buffers of one tile (floats); two copies (step parity)
-constexpr int kKsCopies = 2;
-struct KsBuf {
-    size_t g, q, s, total;
-    __host__ __device__ KsBuf(int C) {
-        g = 0;
-        q = g + (size_t)C * C * 4 * kKsImg;     // [dest][src][4][image]: forward belief blocks, backward (DX, DH)
-        s = q + (size_t)C * C * kKsImg;         // [dest][src][image]
-        total = s + (size_t)C * 8 * kKsImg;     // [src][<= 8 (block, mean | raw) pairs][image]
-    }
-};
 
 // Register layout of every activation block in these kernels ("fragment layout"): element i of a lane's float4 is
 // (row = lane & 15, column = 16 c + 4 (lane >> 4) + i).  Products are formed TRANSPOSED -- D^T = W X^T, the packed weight
@@ -173,19 +160,20 @@ __global__ __launch_bounds__(kThreads) void observe_kfwd_ns_kernel(bd_observe_fw
     extern __shared__ __attribute__((aligned(16))) float smem[];
     BD_KARGS(bd_observe_fwd_args, ap);
 #define a (*ap)
-    const int Kb_h = cdiv(a.Be, 16), Kb_s = cdiv(a.S, 16), Kb_a = cdiv(a.A, 16), Kb_hd = cdiv(a.Hd, 16);
+    const ScanDims d(a.Be, a.S, a.A, a.Hd);
+    const int Kb_h = d.Kb_h, Kb_s = d.Kb_s, Kb_a = d.Kb_a, Kb_hd = d.Kb_hd;
     const int tile = blockIdx.x / C, c = blockIdx.x - tile * C;
     const int row0 = tile * 16, F = a.Be + a.S, Np = Kb_s * 16;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    float* sf = smem;                               // masked state, fragment tiles
-    float* af = sf + Kb_s * kFragFloats;
-    float* s_plain = af + Kb_a * kFragFloats;       // [16][S]
-    float* red = s_plain + ((16 * a.S + 3) & ~3);   // [2][8 waves][64][4]: the two reductions of a step alternate
-    float* plain = red + 2 * kWaves * 256;          // [parts][2][16][Np]: head sums, one copy per helper wave group
-    float* xf = plain + kWaves * 256;               // x, all Kb_h blocks, fragment tiles
-    float* hf = xf + Kb_h * kFragFloats;            // h, all Kb_h blocks, fragment tiles
-    float* gpart = hf + Kb_h * kFragFloats;         // [8 waves][4 gates][64][4]: the waves' K-partial gate sums
+    const KsplitFwdLds L(d, a.S);
+    float* sf = smem + L.sf;                        // masked state, fragment tiles
+    float* af = smem + L.af;
+    float* red = smem + L.red;                      // [2][8 waves][64][4]: the two reductions of a step alternate
+    float* plain = smem + L.plain;                  // [parts][2][16][Np]: head sums, one copy per helper wave group
+    float* xf = smem + L.xf;                        // x, all Kb_h blocks, fragment tiles
+    float* hf = smem + L.hf;                        // h, all Kb_h blocks, fragment tiles
+    float* gpart = smem + L.gpart;                  // [8 waves][4 gates][64][4]: the waves' K-partial gate sums
 
     unsigned* flags = reinterpret_cast<unsigned*>(ws) + tile * kMaxCluster;
     unsigned* err = reinterpret_cast<unsigned*>(ws) + tiles * kMaxCluster;
@@ -469,17 +457,19 @@ __global__ __launch_bounds__(kThreads) void observe_kbwd_kernel(bd_observe_bwd_a
     extern __shared__ __attribute__((aligned(16))) float smem[];
     BD_KARGS(bd_observe_bwd_args, ap);
 #define a (*ap)
-    const int Kb_h = cdiv(a.Be, 16), Kb_s = cdiv(a.S, 16), Kb_hd = cdiv(a.Hd, 16);
+    const ScanDims d(a.Be, a.S, a.A, a.Hd);
+    const int Kb_h = d.Kb_h, Kb_s = d.Kb_s, Kb_hd = d.Kb_hd;
     const int tile = blockIdx.x / C, c = blockIdx.x - tile * C;
     const int row0 = tile * 16, F = a.Be + a.S;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    float* dM = smem;                               // Kb_s fragment tiles
-    float* dRaw = dM + Kb_s * kFragFloats;
-    float* ds_plain = dRaw + Kb_s * kFragFloats;    // [parts][16][S]: d state of the next step, one partial sum per wave group
-    const int nparts = kWaves / Kb_s;               // wave w: state block w % Kb_s, members part = w / Kb_s, part + nparts, ...
-    const int dsp_stride = (16 * a.S + 3) & ~3;
-    float* red = ds_plain + (size_t)nparts * dsp_stride;   // [2][8 waves][64][4]
+    const KsplitBwdLds L(d, a.S);
+    float* dM = smem + L.dM;                        // Kb_s fragment tiles
+    float* dRaw = smem + L.dRaw;
+    float* ds_plain = smem + L.ds_plain;            // [parts][16][S]: d state of the next step, one partial sum per wave group
+    const int nparts = L.nparts;                    // wave w: state block w % Kb_s, members part = w / Kb_s, part + nparts, ...
+    const int dsp_stride = L.dsp_stride;
+    float* red = smem + L.red;                      // [2][8 waves][64][4]
 
     unsigned* flags = reinterpret_cast<unsigned*>(ws) + tile * kMaxCluster;
     unsigned* err = reinterpret_cast<unsigned*>(ws) + tiles * kMaxCluster;
@@ -715,8 +705,6 @@ __global__ __launch_bounds__(kThreads) void observe_kbwd_kernel(bd_observe_bwd_a
 #undef a
 }
 
-size_t ksplit_ws_floats_per_tile(int C) { return kKsCopies * KsBuf(C).total; }
-
 int& ksplit_mode() {               // -1: the K-split form wherever the shapes allow it, 0: off (round-1 cluster form)
     static int m = -1;
     return m;
@@ -728,19 +716,6 @@ bool ksplit_ok(int Be, int S, int A, int Hd, int C) {
            S <= kHeadMaxN && 16 * S <= kThreads && 2 * cdiv(S, 16) <= kWaves;
 }
 
-// sf, af, s_plain, red, plain, then the x and h fragment tiles and the waves' gate partials
-static size_t ks_lds_fwd(int S, int A, int Be) {
-    const int Kb_s = cdiv(S, 16), Kb_a = cdiv(A, 16);
-    const int nparts = kWaves / (2 * Kb_s);
-    return ((size_t)(Kb_s + Kb_a) * kFragFloats + ((16 * S + 3) & ~3) + 2 * kWaves * 256 + (size_t)nparts * 2 * 16 * Kb_s * 16 +
-            (size_t)2 * cdiv(Be, 16) * kFragFloats + (size_t)kWaves * 4 * 256) * sizeof(float);
-}
-static size_t ks_lds_bwd(int S) {
-    const int Kb_s = cdiv(S, 16);
-    const int nparts = kWaves / Kb_s;
-    return ((size_t)2 * Kb_s * kFragFloats + (size_t)nparts * ((16 * S + 3) & ~3) + 2 * kWaves * 256) * sizeof(float);
-}
-
 // zero what the kernels poll: the member flags
 static int ks_reset(float* ws, int tiles, hipStream_t stream, const char* who) {
     if (hipMemsetAsync(ws, 0, cluster_ws_flag_floats(tiles) * sizeof(float), stream) != hipSuccess) return fail("%s: memset failed", who);
@@ -749,7 +724,9 @@ static int ks_reset(float* ws, int tiles, hipStream_t stream, const char* who) {
 
 int launch_observe_kfwd(const bd_observe_fwd_args* a, float* ws, int C, int tiles, hipStream_t stream) {
     if (allow_big_lds(observe_kfwd_ns_kernel)) return -1;
-    const size_t dyn = launch_lds(observe_kfwd_ns_kernel, ks_lds_fwd(a->S, a->A, a->Be), "bd_observe_forward_cluster");
+    const KsplitFwdLds L(ScanDims(a->Be, a->S, a->A, a->Hd), a->S);
+    BD_REQUIRE(L.vec_ok(), "bd_observe_forward_cluster: misaligned LDS layout");
+    const size_t dyn = launch_lds(observe_kfwd_ns_kernel, (size_t)L.total * sizeof(float), "bd_observe_forward_cluster");
     if (!dyn) return -1;
     if (ks_reset(ws, tiles, stream, "bd_observe_forward_cluster")) return -1;
     hipLaunchKernelGGL(observe_kfwd_ns_kernel, dim3(tiles * C), dim3(kThreads), dyn, stream, *a, ws, C, tiles, cluster_spin_limit());
@@ -758,7 +735,9 @@ int launch_observe_kfwd(const bd_observe_fwd_args* a, float* ws, int C, int tile
 }
 int launch_observe_kbwd(const bd_observe_bwd_args* a, float* ws, int C, int tiles, hipStream_t stream) {
     if (allow_big_lds(observe_kbwd_kernel)) return -1;
-    const size_t dyn = launch_lds(observe_kbwd_kernel, ks_lds_bwd(a->S), "bd_observe_backward_cluster");
+    const KsplitBwdLds L(ScanDims(a->Be, a->S, a->A, a->Hd), a->S);
+    BD_REQUIRE(L.vec_ok(), "bd_observe_backward_cluster: misaligned LDS layout");
+    const size_t dyn = launch_lds(observe_kbwd_kernel, (size_t)L.total * sizeof(float), "bd_observe_backward_cluster");
     if (!dyn) return -1;
     if (ks_reset(ws, tiles, stream, "bd_observe_backward_cluster")) return -1;
     hipLaunchKernelGGL(observe_kbwd_kernel, dim3(tiles * C), dim3(kThreads), dyn, stream, *a, ws, C, tiles, cluster_spin_limit());

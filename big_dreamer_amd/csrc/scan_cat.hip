@@ -14,8 +14,7 @@
 //     registers -- the carry between time steps is the embed gradient (Be wide), never an S-wide vector.
 #include "bd_device.h"
 #include "bd_host.h"
-#include "bd_scan.h"
-#include "bd_categorical.h"
+#include "bd_scan_layout.h"
 #include "bd_discrete.h"
 
 namespace bd {
@@ -39,23 +38,24 @@ __global__ __launch_bounds__(kThreads) void observe_cat_fwd_kernel(bd_observe_ca
     BD_KARGS(bd_observe_cat_fwd_args, ap);
 #define a (*ap)
     const CatGeo g(a.D, a.C);
-    const int Kb_h = cdiv(a.Be, 16), Kb_a = cdiv(a.A, 16), Kb_hd = cdiv(a.Hd, 16);
+    const ScanDims d(a.Be, 0, a.A, a.Hd);
+    const int Kb_h = d.Kb_h, Kb_a = d.Kb_a, Kb_hd = d.Kb_hd;
     const int lane = threadIdx.x & 63;
     const int row0 = blockIdx.x * 16;
     const int S = g.S, F = a.Be + S;
-    const int nh = Kb_h * kFragFloats, nhd = Kb_hd * kFragFloats;
     const int rows_valid = a.B - row0 < 16 ? a.B - row0 : 16;
-    float* h_cur = smem;
-    float* h_nxt = h_cur + nh;
-    float* xf = h_nxt + nh;
-    float* qf = xf + nh;
-    float* af = qf + nhd;
     const CatFull gf(a.D, a.C);
-    float* xs = af + Kb_a * kFragFloats;          // [16][Be] gathered W_es s~
-    float* lg = xs + 16 * a.Be;                   // all S logits of the tile (swizzled image)
-    float* sw_l = lg + gf.image_floats();         // [16][D]
-    float* mrow = sw_l + 16 * g.D;                // [16] nonterminal mask of the step
-    int* sidx_l = reinterpret_cast<int*>(mrow + 16);   // [16][D]
+    const CatObserveFwdLds L(d, a.Be, a.D, gf, 0);
+    float* h_cur = smem + L.h_cur;
+    float* h_nxt = smem + L.h_nxt;
+    float* xf = smem + L.xf;
+    float* qf = smem + L.qf;
+    float* af = smem + L.af;
+    float* xs = smem + L.xs;                      // [16][Be] gathered W_es s~
+    float* lg = smem + L.lg;                      // all S logits of the tile (swizzled image)
+    float* sw_l = smem + L.sw_l;                  // [16][D]
+    float* mrow = smem + L.mrow;                  // [16] nonterminal mask of the step
+    int* sidx_l = reinterpret_cast<int*>(smem + L.sidx_l);   // [16][D]
 
     load_tile_concat<1>(h_cur, Kb_h, row0, a.B, a.init_belief, a.Be, a.Be, nullptr, 0, 0);
     state_to_indices(g, a.init_state, (size_t)S, row0, a.B, sidx_l, sw_l);
@@ -282,22 +282,26 @@ __global__ __launch_bounds__(kThreads) void observe_cat_bwd_kernel(bd_observe_ca
     BD_KARGS(bd_observe_cat_bwd_args, ap);
 #define a (*ap)
     const CatGeo g(a.D, a.C);
-    const int Kb_h = cdiv(a.Be, 16), Kb_hd = cdiv(a.Hd, 16);
+    const ScanDims d(a.Be, 0, a.A, a.Hd);
+    const int Kb_h = d.Kb_h, Kb_hd = d.Kb_hd;
     const int row0 = blockIdx.x * 16;
     const int S = g.S, F = a.Be + S;
-    const int nh = Kb_h * kFragFloats, nhd = Kb_hd * kFragFloats;
+    const int nh = Kb_h * kFragFloats;
     const int rows_valid = a.B - row0 < 16 ? a.B - row0 : 16;
-    float* dhc = smem;
-    float* dR = dhc + nh;
-    float* dZ = dR + nh;
-    float* dNI = dZ + nh;
-    float* dNH = dNI + nh;
-    float* dE = dNH + nh;
-    float* dQ = dE + nh;                               // Kb_hd
-    float* pl = dQ + nhd;
-    float* lgs = pl + g.image_floats();
-    float* dLf = lgs + g.image_floats();               // CW/16 fragment blocks
-    float* mrow = dLf + (g.CW / 16) * kFragFloats;     // [16]
+    const CatObserveBwdLds L(d, g, 0);
+    // (chained off the layout's offsets: the same addresses as `smem + L.region`, in the form that keeps this kernel's
+    // registers and floating-point contraction where they were -- bd_scan_layout.h)
+    float* dhc = smem + L.dhc;
+    float* dE = dhc + (L.dE - L.dhc);
+    float* dR = dE + (L.dR - L.dE);
+    float* dZ = dR + (L.dZ - L.dR);
+    float* dNI = dZ + (L.dNI - L.dZ);
+    float* dNH = dNI + (L.dNH - L.dNI);
+    float* dQ = dNH + (L.dQ - L.dNH);
+    float* pl = dQ + (L.pl - L.dQ);
+    float* lgs = pl + (L.lgs - L.pl);
+    float* dLf = lgs + (L.dLf - L.lgs);                // CW/16 fragment blocks
+    float* mrow = dLf + (L.mrow - L.dLf);              // [16]
 
     for (int i = threadIdx.x; i < nh; i += blockDim.x) { dhc[i] = 0.f; dE[i] = 0.f; }
     lds_barrier();
@@ -417,30 +421,32 @@ __global__ __launch_bounds__(kThreads) void imagine_cat_fwd_kernel(bd_imagine_ca
     BD_KARGS(bd_imagine_cat_fwd_args, ap);
 #define a (*ap)
     const CatGeo g(a.D, a.C);
-    const int Kb_h = cdiv(a.Be, 16), Kb_a = cdiv(a.A, 16), Kb_hd = cdiv(a.Hd, 16);
+    const ScanDims d(a.Be, 0, a.A, a.Hd);
+    const int Kb_h = d.Kb_h, Kb_a = d.Kb_a, Kb_hd = d.Kb_hd;
     // a launch of fewer workgroups than tiles (host: whole rounds, see cat_grid) walks its tiles one after the other
     for (int tile_ = blockIdx.x; tile_ * 16 < a.N; tile_ += gridDim.x) {
     const int row0 = tile_ * 16;
     const int S = g.S, F = a.Be + S, A = a.A;
-    const int nh = Kb_h * kFragFloats, nhd = Kb_hd * kFragFloats;
     const int rows_valid = a.N - row0 < 16 ? a.N - row0 : 16;
-    const int wmax = a.Be > a.Hd ? a.Be : a.Hd;
-    float* h_cur = smem;
-    float* h_nxt = h_cur + nh;
-    float* xf = h_nxt + nh;
-    float* bufA = xf + nh;
-    float* bufB = bufA + nhd;
-    float* af = bufB + nhd;
-    float* xs = af + Kb_a * kFragFloats;          // [16][max(Be, Hd)] gathered state columns of the layer at hand
-    float* mean_s = xs + 16 * wmax;               // [16][A]
-    float* std_s = mean_s + 16 * A;
-    float* lp_rj = std_s + 16 * A;
-    float* sw_l = lp_rj + 16 * A;                 // [16][D]
-    int* sidx_l = reinterpret_cast<int*>(sw_l + 16 * g.D);
-    // one region, three tenants in disjoint phases: the actor head's split-K scratch, the entropy partial sums, the
-    // prior head's logits / draws images (16-byte aligned: the host rounds the offsets)
-    float* uni = reinterpret_cast<float*>(sidx_l + 16 * g.D);
     const CatFull gf(a.D, a.C);
+    const CatImagineFwdLds L(d, a.Be, a.Hd, a.D, A, gf);
+    // (chained off the layout's offsets: the same addresses as `smem + L.region`, in the form that keeps this kernel's
+    // registers and floating-point contraction where they were -- bd_scan_layout.h)
+    float* h_cur = smem + L.h_cur;
+    float* h_nxt = h_cur + (L.h_nxt - L.h_cur);
+    float* xf = h_nxt + (L.xf - L.h_nxt);
+    float* bufA = xf + (L.bufA - L.xf);
+    float* bufB = bufA + (L.bufB - L.bufA);
+    float* af = bufB + (L.af - L.bufB);
+    float* xs = af + (L.xs - L.af);               // [16][max(Be, Hd)] gathered state columns of the layer at hand
+    float* mean_s = xs + (L.mean_s - L.xs);       // [16][A]
+    float* std_s = mean_s + (L.std_s - L.mean_s);
+    float* lp_rj = std_s + (L.lp_rj - L.std_s);
+    float* sw_l = lp_rj + (L.sw_l - L.lp_rj);     // [16][D]
+    int* sidx_l = reinterpret_cast<int*>(sw_l + (L.sidx_l - L.sw_l));
+    // one region, three tenants in disjoint phases: the actor head's split-K scratch, the entropy partial sums, the
+    // prior head's logits / draws images
+    float* uni = reinterpret_cast<float*>(sidx_l + (L.uni - L.sidx_l));
     float* scratch = uni;
     float* part = uni;                            // [kWaves][16][A][3]
     float* lg = uni;                              // all S prior logits of the tile (swizzled image)
@@ -630,7 +636,7 @@ __global__ __launch_bounds__(kThreads) void imagine_cat_fwd_kernel(bd_imagine_ca
                     }
                 }
             }
-        }, uni);
+        }, scratch);
         lds_barrier();
         BD_KARGS_FRESH(ap);
         // ---- prior hidden, logits, sample ----
@@ -663,30 +669,34 @@ __global__ __launch_bounds__(kThreads) void imagine_cat_bwd_kernel(bd_imagine_ca
     BD_KARGS(bd_imagine_cat_bwd_args, ap);
 #define a (*ap)
     const CatGeo g(a.D, a.C);
-    const int Kb_h = cdiv(a.Be, 16), Kb_a = cdiv(a.A, 16), Kb_hd = cdiv(a.Hd, 16);
+    const ScanDims d(a.Be, 0, a.A, a.Hd);
+    const int Kb_h = d.Kb_h, Kb_a = d.Kb_a, Kb_hd = d.Kb_hd;
     // a launch of fewer workgroups than tiles (host: whole rounds, see cat_grid) walks its tiles one after the other
     for (int tile_ = blockIdx.x; tile_ * 16 < a.N; tile_ += gridDim.x) {
     const int row0 = tile_ * 16;
     const int S = g.S, F = a.Be + S, A = a.A;
-    const int nh = Kb_h * kFragFloats, nhd = Kb_hd * kFragFloats, na = Kb_a * kFragFloats;
+    const int nh = Kb_h * kFragFloats;
     const int rows_valid = a.N - row0 < 16 ? a.N - row0 : 16;
-    float* dhc = smem;
-    float* dR = dhc + nh;
-    float* dZ = dR + nh;
-    float* dNI = dZ + nh;
-    float* dNH = dNI + nh;
-    float* dE = dNH + nh;
-    float* dP = dE + nh;          // Kb_hd
-    float* dAm = dP + nhd;        // Kb_a
-    float* dAr = dAm + na;
+    const CatImagineBwdLds L(d, g);
+    // (chained off the layout's offsets: the same addresses as `smem + L.region`, in the form that keeps this kernel's
+    // registers and floating-point contraction where they were -- bd_scan_layout.h)
+    float* dhc = smem + L.dhc;
+    float* dR = dhc + (L.dR - L.dhc);
+    float* dZ = dR + (L.dZ - L.dR);
+    float* dNI = dZ + (L.dNI - L.dZ);
+    float* dNH = dNI + (L.dNH - L.dNI);
+    float* dE = dNH + (L.dE - L.dNH);
+    float* dP = dE + (L.dP - L.dE);
+    float* dAm = dP + (L.dAm - L.dP);
+    float* dAr = dAm + (L.dAr - L.dAm);
     // one region, tenants in disjoint phases: head backward images | split-K scratch | actor backward buffers
-    float* uni = dAr + na;
+    float* uni = dAr + (L.uni - L.dAr);
     float* pl = uni;
-    float* lgs = pl + g.image_floats();
-    float* dLf = lgs + g.image_floats();
+    float* lgs = pl + (L.lgs - L.pl);
+    float* dLf = lgs + (L.dLf - L.lgs);
     float* scratch = uni;
     float* bufA = uni;
-    float* bufB = bufA + nhd;
+    float* bufB = bufA + (L.bufB - L.bufA);
 
     for (int i = threadIdx.x; i < nh; i += blockDim.x) { dhc[i] = 0.f; dE[i] = 0.f; }
     lds_barrier();
@@ -804,7 +814,7 @@ __global__ __launch_bounds__(kThreads) void imagine_cat_bwd_kernel(bd_imagine_ca
                     }
                     dE[off] = de;
                 }
-            }, uni);
+            }, scratch);
         lds_barrier();
         BD_KARGS_FRESH(ap);
         // ---- 5: embed layer -> d action_t -> actor output gradients (d state_t is taken by the next iteration's head) ----
@@ -943,10 +953,9 @@ int bd_observe_cat_forward(const bd_observe_cat_fwd_args* a, void* stream) {
                    a->b_ih && a->b_hh && a->w_q1h && a->b_q1 && a->w_q2 && a->b_q2, "bd_observe_cat_forward: missing weights");
     BD_REQUIRE(a->init_belief && a->init_state && a->actions && a->pre_emb && a->q_post, "bd_observe_cat_forward: missing inputs");
     BD_REQUIRE(a->feat && a->post_logits && a->sidx, "bd_observe_cat_forward: missing outputs");
-    const int Kb_h = cdiv(a->Be, 16), Kb_a = cdiv(a->A, 16), Kb_hd = cdiv(a->Hd, 16);
-    const CatFull gf(a->D, a->C);
-    const size_t lds = ((size_t)(3 * Kb_h + Kb_hd + Kb_a) * kFragFloats + 16 * a->Be + gf.image_floats() + 2 * 16 * g.D + 16) *
-                       sizeof(float);
+    const CatObserveFwdLds L(ScanDims(a->Be, 0, a->A, a->Hd), a->Be, a->D, CatFull(a->D, a->C), 0);
+    BD_REQUIRE(L.vec_ok(), "bd_observe_cat_forward: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_observe_cat_forward: needs %zu B of LDS", lds);
     if (lds > 64 * 1024 && allow_big_lds(observe_cat_fwd_kernel)) return -1;
     hipLaunchKernelGGL(observe_cat_fwd_kernel, dim3(cdiv(a->B, 16)), dim3(kThreads), lds, (hipStream_t)stream, *a);
@@ -962,8 +971,9 @@ int bd_observe_cat_backward(const bd_observe_cat_bwd_args* a, void* stream) {
     BD_REQUIRE(a->init_belief && a->feat && a->post_logits && a->sv_x && a->sv_gates && a->sv_q && a->dfeat,
                "bd_observe_cat_backward: missing forward tensors");
     BD_REQUIRE(a->d_embed_pre && a->d_gi && a->d_gh && a->d_q1_pre && a->d_q2_out, "bd_observe_cat_backward: missing outputs");
-    const int Kb_h = cdiv(a->Be, 16), Kb_hd = cdiv(a->Hd, 16);
-    const size_t lds = ((size_t)(6 * Kb_h + Kb_hd + g.CW / 16) * kFragFloats + 2 * g.image_floats() + 16) * sizeof(float);
+    const CatObserveBwdLds L(ScanDims(a->Be, 0, a->A, a->Hd), g, 0);
+    BD_REQUIRE(L.vec_ok(), "bd_observe_cat_backward: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_observe_cat_backward: needs %zu B of LDS", lds);
     if (lds > 64 * 1024 && allow_big_lds(observe_cat_bwd_kernel)) return -1;
     hipLaunchKernelGGL(observe_cat_bwd_kernel, dim3(cdiv(a->B, 16)), dim3(kThreads), lds, (hipStream_t)stream, *a);
@@ -985,14 +995,9 @@ int bd_imagine_cat_forward(const bd_imagine_cat_fwd_args* a, void* stream) {
     BD_REQUIRE(!a->discrete_actions || a->sv_act_us == nullptr,
                "bd_imagine_cat_forward: sv_act_us is for the tanh-Normal actor only");
     BD_REQUIRE(a->feat && a->sidx && a->prior_logits && a->entropy && a->action, "bd_imagine_cat_forward: missing outputs");
-    const int Kb_h = cdiv(a->Be, 16), Kb_a = cdiv(a->A, 16), Kb_hd = cdiv(a->Hd, 16);
-    const int wmax = a->Be > a->Hd ? a->Be : a->Hd;
-    size_t uni = (size_t)kSplitScratchFloats;
-    if ((size_t)kWaves * 16 * a->A * 3 > uni) uni = (size_t)kWaves * 16 * a->A * 3;
-    const CatFull gf(a->D, a->C);
-    if ((size_t)gf.image_floats() > uni) uni = (size_t)gf.image_floats();
-    const size_t fixed = (size_t)(3 * Kb_h + 2 * Kb_hd + Kb_a) * kFragFloats + 16 * wmax + 3 * 16 * a->A + 2 * 16 * g.D;
-    const size_t lds = (fixed + uni) * sizeof(float);      // every term of `fixed` is a multiple of 16 floats
+    const CatImagineFwdLds L(ScanDims(a->Be, 0, a->A, a->Hd), a->Be, a->Hd, a->D, a->A, CatFull(a->D, a->C));
+    BD_REQUIRE(L.vec_ok(), "bd_imagine_cat_forward: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_imagine_cat_forward: needs %zu B of LDS", lds);
     int grid;
     const size_t dyn = cat_grid(imagine_cat_fwd_kernel, cdiv(a->N, 16), lds, &grid);
@@ -1017,11 +1022,9 @@ int bd_imagine_cat_backward(const bd_imagine_cat_bwd_args* a, void* stream) {
                    a->sv_actor && a->sv_act_stats &&
                    a->sv_x && a->sv_gates && a->sv_p && a->dfeat, "bd_imagine_cat_backward: missing forward tensors");
     BD_REQUIRE(a->d_actor_out, "bd_imagine_cat_backward: missing outputs");
-    const int Kb_h = cdiv(a->Be, 16), Kb_a = cdiv(a->A, 16), Kb_hd = cdiv(a->Hd, 16);
-    size_t uni = (size_t)2 * g.image_floats() + (size_t)(g.CW / 16) * kFragFloats;
-    if ((size_t)kSplitScratchFloats > uni) uni = (size_t)kSplitScratchFloats;
-    if ((size_t)2 * Kb_hd * kFragFloats > uni) uni = (size_t)2 * Kb_hd * kFragFloats;
-    const size_t lds = ((size_t)(6 * Kb_h + Kb_hd + 2 * Kb_a) * kFragFloats + uni) * sizeof(float);
+    const CatImagineBwdLds L(ScanDims(a->Be, 0, a->A, a->Hd), g);
+    BD_REQUIRE(L.vec_ok(), "bd_imagine_cat_backward: misaligned LDS layout");
+    const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_imagine_cat_backward: needs %zu B of LDS", lds);
     int grid;
     const size_t dyn = cat_grid(imagine_cat_bwd_kernel, cdiv(a->N, 16), lds, &grid);

@@ -316,6 +316,27 @@ int bd_observe_cluster_status(float* ws, int B, void* stream);
 size_t bd_observe_cluster_err_offset(int B);
 int bd_observe_cluster_set_spin_limit(unsigned limit);   /* returns 0 */
 
+/* Dynamic LDS, in bytes, that the launcher of one recurrent scan kernel asks for at a shape, before any rounding up to the
+ * CU's whole LDS: the total of the layout that kernel and launcher share (csrc/bd_scan_layout.h).  Gaussian kernels read
+ * (Be, S, A, Hd), Categorical ones (Be, D, C, A, Hd), the Categorical cluster forms also their cluster size Cm; what a kernel
+ * does not read is ignored.  Returns 0 with the error text set for an unknown kernel, a non-positive width, Cm not dividing
+ * D, or a layout whose float4 regions are misaligned.  Host only: no device call. */
+#define BD_SCAN_OBSERVE_FWD 0        /* observe_fwd_kernel        (bd_observe_forward) */
+#define BD_SCAN_OBSERVE_BWD 1        /* observe_bwd_kernel        (bd_observe_backward) */
+#define BD_SCAN_OBSERVE_CFWD 2       /* observe_cfwd_kernel       (bd_observe_forward_cluster, round-1 form) */
+#define BD_SCAN_OBSERVE_CBWD 3       /* observe_cbwd_kernel       (bd_observe_backward_cluster, round-1 form) */
+#define BD_SCAN_OBSERVE_KFWD 4       /* observe_kfwd_ns_kernel    (bd_observe_forward_cluster, K-split form) */
+#define BD_SCAN_OBSERVE_KBWD 5       /* observe_kbwd_kernel       (bd_observe_backward_cluster, K-split form) */
+#define BD_SCAN_IMAGINE_FWD 6        /* imagine_fwd_kernel */
+#define BD_SCAN_IMAGINE_BWD 7        /* imagine_bwd_kernel */
+#define BD_SCAN_OBSERVE_CAT_FWD 8    /* observe_cat_fwd_kernel */
+#define BD_SCAN_OBSERVE_CAT_BWD 9    /* observe_cat_bwd_kernel */
+#define BD_SCAN_IMAGINE_CAT_FWD 10   /* imagine_cat_fwd_kernel */
+#define BD_SCAN_IMAGINE_CAT_BWD 11   /* imagine_cat_bwd_kernel */
+#define BD_SCAN_OBSERVE_CAT_CFWD 12  /* observe_cat_cfwd_kernel   (bd_observe_cat_forward_cluster) */
+#define BD_SCAN_OBSERVE_CAT_CBWD 13  /* observe_cat_cbwd_kernel   (bd_observe_cat_backward_cluster) */
+size_t bd_scan_lds_bytes(int kernel, int Be, int S, int D, int C, int A, int Hd, int Cm);
+
 /* GaussianBeliefModel tail (src/models.py:70-73): out[M x 2S] -> mean, std=softplus(raw)+min_std,
  * state = mean + std*eps.  Used for the batched prior of the observe scan. */
 int bd_gauss_head_forward(const float* out, const float* eps, int M, int S, float min_std,

@@ -408,8 +408,9 @@ def case_seed(name: str, regime: str) -> int:
 
 # bd_actor_entropy_rng against bd_actor_entropy on the gathered draws: (Hm, N, A, n_samples)
 RNG_SHAPES = [(2, 7, A, ns) for A in (1, 3, 17) for ns in (1, 15, 16, 17, 64, 100)]
-# the in-scan forms: shape names of scan_ref.IMAGINE_SHAPES / scan_cat_ref.IMAGINE_SHAPES, and n_samples
-SCAN_GAUSS, SCAN_CAT, SCAN_NS = ("n1_h1", "ragged42", "a17"), ("n1_h1", "c16_d20", "c32_d32_a17"), (5, 33, 100)
+# the in-scan forms: shape names of scan_ref.IMAGINE_SHAPES / scan_cat_ref.IMAGINE_SHAPES, and n_samples (a28: the partial
+# sums of the in-scan estimate are the largest tenant of the Categorical forward's shared LDS region)
+SCAN_GAUSS, SCAN_CAT, SCAN_NS = ("n1_h1", "ragged42", "a17"), ("n1_h1", "c16_d20", "c32_d32_a17", "a28"), (5, 33, 100)
 
 
 def rng_gather_index(Hm, N, A, ns):

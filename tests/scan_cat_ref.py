@@ -455,10 +455,10 @@ def cat_scratch(nbl: int, fwd: bool) -> int:
 
 
 def lds_bytes(entry: str, Be, D, C, A, Hd, Cm: int = 0) -> int:
-    """Dynamic LDS the host formula of every entry point asks for (before cat_grid / launch_lds round it up).  The CPU
-    test holds it to the library through the figure in the "needs N B of LDS" error of shapes above 160 KiB.  `cat_grid`
-    below has no such tie: the library exports no query for its launch grid (which also follows BD_CAT_TILE_LOOP), so
-    the "grid is 129" assertions check this restatement of the host code, not the launch."""
+    """Dynamic LDS every entry point asks for (before cat_grid / launch_lds round it up).  The CPU test holds it to the
+    library at every table shape through bd_scan_lds_bytes, and through the figure in the "needs N B of LDS" error of shapes
+    above 160 KiB.  `cat_grid` below has no such tie: the library exports no query for its launch grid (which also follows
+    BD_CAT_TILE_LOOP), so the "grid is 129" assertions check this restatement of the host code, not the launch."""
     h, a, hd, g = cdiv(Be, 16), cdiv(A, 16), cdiv(Hd, 16), cat_geo(D, C)
     if entry == "observe_fwd":
         n = (3 * h + hd + a) * K_FRAG + 16 * Be + full_image(D, C) + 2 * 16 * D + 16
@@ -552,6 +552,9 @@ IMAGINE_SHAPES = {
     "c256_d2": CDims(2, 16, 32, 2, 256, 1, 16),
     "tile_loop": CDims(2, 4112, 32, 4, 8, 2, 32),
     "discrete": CDims(3, 19, 40, 4, 16, 5, 32),      # discrete_actions = 1: the Categorical actor on A = 5 classes
+    # the smallest shape at which the entropy partial sums [8 waves][16][A][3] decide the size of the forward scan's shared LDS
+    # region: 10752 floats against 10240 of split-K scratch and 1152 of logit image
+    "a28": CDims(2, 17, 24, 4, 16, 28, 32),
 }
 # dynamic LDS above 64 KiB: entry point -> shape names on the far side (every other shape of the table is below)
 OBSERVE_BIG_LDS = {"observe_fwd": {"c32_d32", "c64_d16", "full_width"},

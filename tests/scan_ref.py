@@ -474,7 +474,7 @@ def near_decision_fraction(pres) -> float:
     return max(float((p.abs() < DECISION_MARGIN).double().mean()) for p in pres)
 
 
-# ---- host dispatch, restated (observe_cluster.hip:538-543, observe_ksplit.hip:725-742, the launchers) --------------------
+# ---- host dispatch, restated (observe_cluster.hip pick_cluster, observe_ksplit.hip ksplit_ok, bd_scan_layout.h) --------------------
 
 K_WAVES, K_MAX_CLUSTER, K_LOCAL_BLOCKS = 8, 16, 2
 K_THREADS, K_FRAG, K_HEAD_MAX_N, K_MAX_LDS = K_WAVES * 64, 256, 64, 160 * 1024
@@ -511,7 +511,7 @@ def observe_forms(B, Be, S, A, Hd):
 
 
 def lds_bytes(entry: str, Be, S, A, Hd) -> int:
-    """Dynamic LDS of every entry point, from the host formulas."""
+    """Dynamic LDS of every entry point; the CPU test holds it to the library at every table shape (bd_scan_lds_bytes)."""
     h, s, a, hd = cdiv(Be, 16), cdiv(S, 16), cdiv(A, 16), cdiv(Hd, 16)
     if entry == "observe_fwd":
         n = (3 * h + hd + s + a) * K_FRAG + 16 * S + K_SPLIT_SCRATCH

@@ -529,6 +529,10 @@ def test_tables_and_mirror_match_the_library():
                     for Hd in (16, 200):
                         for cm in {Cm, 4, 16} - {0}:
                             assert lib.bd_observe_cat_cluster_ws_floats(B, Be, Hd, D, cm) == RC.cluster_ws_floats(B, Be, Hd, D, cm)
+    def lib_lds(kernel, d, Cm=0, **kw):    # the library's own figure: the total of the layout kernel and launcher share
+        dims = dict(dict(Be=d.Be, S=0, D=d.D, C=d.C, A=d.A, Hd=d.Hd, Cm=Cm), **kw)
+        return lib.bd_scan_lds_bytes(cabi.SCAN_KERNELS[kernel], *(dims[k] for k in ("Be", "S", "D", "C", "A", "Hd", "Cm")))
+
     seen = {}
     for name, (d, Cm, chunks, last, math_, staging, gather, rem) in RC.OBSERVE_SHAPES.items():
         assert RC.accepts(d.D, d.C, d.Hd), name
@@ -540,9 +544,12 @@ def test_tables_and_mirror_match_the_library():
         for entry in ("observe_fwd", "observe_bwd"):
             lds = RC.lds_bytes(entry, d.Be, d.D, d.C, d.A, d.Hd)
             assert lds <= RC.K_MAX_LDS and (lds > 64 * 1024) == (name in RC.OBSERVE_BIG_LDS[entry]), (name, entry, lds)
+            assert lib_lds("observe_cat_" + entry[8:], d) == lds, (name, entry)
         for cm in sizes:
             for entry in ("cluster_fwd", "cluster_bwd"):
-                assert RC.lds_bytes(entry, d.Be, d.D, d.C, d.A, d.Hd, cm) <= RC.K_MAX_LDS, (name, entry, cm)
+                lds = RC.lds_bytes(entry, d.Be, d.D, d.C, d.A, d.Hd, cm)
+                assert lds <= RC.K_MAX_LDS, (name, entry, cm)
+                assert lib_lds("observe_cat_c" + entry[8:], d, cm) == lds, (name, entry, cm)
         nt, init, dpl = RC.observe_variant(name)
         for kind in ("cluster" if Cm else None, "generic" if math_ == "generic" else None):
             if kind:
@@ -556,6 +563,16 @@ def test_tables_and_mirror_match_the_library():
         for entry in ("imagine_fwd", "imagine_bwd"):
             lds = RC.lds_bytes(entry, d.Be, d.D, d.C, d.A, d.Hd)
             assert lds <= RC.K_MAX_LDS and (lds > 64 * 1024) == (name in RC.IMAGINE_BIG_LDS[entry]), (name, entry, lds)
+            assert lib_lds("imagine_cat_" + entry[8:], d) == lds, (name, entry)
+    # a28: the entropy partial sums decide the size of the forward's shared region
+    d = RC.IMAGINE_SHAPES["a28"]
+    assert RC.K_WAVES * 16 * d.A * 3 == 10752 > max(RC.K_SPLIT_SCRATCH, RC.full_image(d.D, d.C)) == 10240
+    assert [RC.lds_bytes(e, d.Be, d.D, d.C, d.A, d.Hd) for e in ("imagine_fwd", "imagine_bwd")] == [63232, 59392]
+    # the query rejects what it cannot describe, with the reason
+    d = RC.OBSERVE_SHAPES["c32_d12"][0]
+    assert lib.bd_scan_lds_bytes(len(cabi.SCAN_KERNELS), d.Be, 0, d.D, d.C, d.A, d.Hd, 4) == 0 and b"unknown kernel" in lib.bd_last_error()
+    assert lib_lds("observe_cat_cfwd", d, 8) == 0 and b"does not divide D=12" in lib.bd_last_error()
+    assert lib_lds("observe_cat_cbwd", d, 0) == 0 and b"does not divide" in lib.bd_last_error()
     t = RC.IMAGINE_SHAPES["tile_loop"]
     assert RC.cdiv(t.B, 16) == 257 and RC.cat_grid(t.B) == 129        # workgroups walk two tiles, the last one walks one
     assert RC.cat_grid(4096) == 256 and RC.cat_grid(4900) == 154

@@ -392,8 +392,16 @@ def test_dispatch_tables_match_the_library():
     for B in (1, 15, 16, 17, 50, 64, 320, 2450, 5000):
         for Be in (16, 40, 42, 46, 48, 200, 256, 257, 300, 600):
             assert cabi.lib.bd_observe_cluster_size(B, Be) == R.pick_cluster(B, Be), (B, Be)
+    def lib_lds(kernel, d, **kw):          # the library's own figure: the total of the layout kernel and launcher share
+        dims = dict(dict(Be=d.Be, S=d.S, D=0, C=0, A=d.A, Hd=d.Hd, Cm=0), **kw)
+        return cabi.lib.bd_scan_lds_bytes(cabi.SCAN_KERNELS[kernel], *(dims[k] for k in ("Be", "S", "D", "C", "A", "Hd", "Cm")))
+
     for name, (d, Cn, form) in R.OBSERVE_SHAPES.items():
         assert R.pick_cluster(d.B, d.Be) == Cn, name
+        for kernel, entry in (("observe_fwd", "observe_fwd"), ("observe_bwd", "observe_bwd"), ("observe_cfwd", "cluster_fwd"),
+                              ("observe_cbwd", "cluster_bwd")) + ((("observe_kfwd", "ksplit_fwd"), ("observe_kbwd", "ksplit_bwd"))
+                                                                  if form == "ksplit" else ()):
+            assert lib_lds(kernel, d) == R.lds_bytes(entry, d.Be, d.S, d.A, d.Hd), (name, kernel)
         forms = R.observe_forms(d.B, d.Be, d.S, d.A, d.Hd)
         assert (forms[1] if len(forms) > 1 else None) == form, (name, forms)
         tiles = R.cdiv(d.B, 16)
@@ -414,8 +422,15 @@ def test_dispatch_tables_match_the_library():
         for entry in ("imagine_fwd", "imagine_bwd"):
             lds = R.lds_bytes(entry, d.Be, d.S, d.A, d.Hd)
             assert lds <= R.K_MAX_LDS and (lds > 64 * 1024) == (name in R.IMAGINE_BIG_LDS[entry]), (name, entry, lds)
+            assert lib_lds(entry, d) == lds, (name, entry)
     forms = {f for d, _, _ in R.OBSERVE_SHAPES.values() for f in R.observe_forms(d.B, d.Be, d.S, d.A, d.Hd)}
     assert forms == {"single", "ksplit", "round1"}
+    # the query rejects what it cannot describe, with the reason
+    d = R.OBSERVE_SHAPES["b16"][0]
+    assert cabi.lib.bd_scan_lds_bytes(len(cabi.SCAN_KERNELS), d.Be, d.S, 0, 0, d.A, d.Hd, 0) == 0
+    assert b"unknown kernel" in cabi.lib.bd_last_error()
+    assert cabi.lib.bd_scan_lds_bytes(-1, d.Be, d.S, 0, 0, d.A, d.Hd, 0) == 0 and b"unknown kernel" in cabi.lib.bd_last_error()
+    assert lib_lds("observe_fwd", d, S=0) == 0 and b"bad dims" in cabi.lib.bd_last_error()
 
 
 def _fake_ptrs(args, skip=()):
