@@ -32,6 +32,9 @@ ACTION_NOISE = 0.3      # conf/config.yaml
 # Relative gap between the best and the runner-up probs / q that every sampler call of every case must show (float64).
 # A gap g is a difference of two logits of g: the kernels' logits are Hd = 20-term fp32 sums of products below 1 on
 # activations held to 2e-5, i.e. off by less than 5e-5 each way; 1e-4 covers both, as tests/planner_cat_oracle.MIN_GAP.
+# That derivation is for the widths of CASES (Hd = 20) only.  At other widths the gap a row must show is derived from the
+# row's own float64 operands: tests/act_shapes.py `logit_bound` / `required_gap` = max(MIN_GAP, 2 * bound), computed,
+# printed and asserted per row by tests/test_act_shapes_cpu.py::test_no_sample_is_left_to_rounding.
 MIN_GAP = 1e-4
 ROWS = 33               # rows of data per case: B in {1, 16, 17, 33} takes the first B
 
@@ -101,7 +104,9 @@ def act_step_cat(P, d, belief, state, action, eps_post, eps_action, obs=None, em
                  eps_explore=None, action_noise=ACTION_NOISE):
     """(belief (B,Be), state (B,S), previous action (B,A), obs (B,O) | embedding (B,E)) -> (belief', state', action', info).
     info: post_logits / post_q and actor_out / actor_q of the Categorical samplers that ran, min_gap over them, and
-    `explored` (the rows epsilon-greedy replaced)."""
+    `explored` (the rows epsilon-greedy replaced); post_hidden and actor_in, the posterior's hidden layer and the actor's
+    input [h'; s'].  Every array is cast by `_f64` on the way in, so tests/act_shapes.float32_restatement can evaluate
+    the same statements in float32."""
     tm = {k: _f64(v) for k, v in P["transition_model"].items()}
     h, s, a = _f64(belief), _f64(state), _f64(action)
     Be = h.shape[1]
@@ -118,28 +123,29 @@ def act_step_cat(P, d, belief, state, action, eps_post, eps_action, obs=None, em
     out = q @ tm["belief_posterior.model.2.weight"].T + tm["belief_posterior.model.2.bias"]
     if d.categorical:
         idx, gap = _sample(out, eps_post, d.cat_D, d.cat_C)
-        s2 = CR.one_hot_rows(idx, d.cat_C).numpy()
+        s2 = _f64(CR.one_hot_rows(idx, d.cat_C).numpy())
         info.update(post_logits=out, post_q=np.asarray(eps_post), post_idx=idx.numpy(), min_gap=min(info["min_gap"], gap))
     else:
         s2 = out[:, :d.S] + (_softplus(out[:, d.S:]) + act_ref.MIN_STD_DEV) * _f64(eps_post)
-    ao = act_ref.dense(P["actor"], np.concatenate([h2, s2], 1))
+    info.update(post_hidden=q, actor_in=np.concatenate([h2, s2], 1))      # operands of the two logit layers (logit_bound)
+    ao = act_ref.dense(P["actor"], info["actor_in"])
     if d.discrete_actions:
         k, gap = _sample(ao, eps_action, 1, d.A)
         k = k.numpy()[:, 0]
         p = np.exp(ao - ao.max(1, keepdims=True))
         p /= p.sum(1, keepdims=True)
-        act = (np.eye(d.A)[k] + p) - p
+        act = (_f64(np.eye(d.A))[k] + p) - p
         info.update(actor_out=ao, actor_q=np.asarray(eps_action), actor_idx=k, min_gap=min(info["min_gap"], gap))
         if explore:
             u, v = np.float32(eps_explore[:, 0]), np.float32(eps_explore[:, 1])
             kr = np.minimum(np.floor(v * np.float32(d.A)).astype(np.int64), d.A - 1)
             hit = u < np.float32(action_noise)
-            act = np.where(hit[:, None], np.eye(d.A)[kr], act)
+            act = np.where(hit[:, None], _f64(np.eye(d.A))[kr], act)
             info["explored"] = hit
     else:
         A = d.A
         mean = act_ref.ACT_MEAN_SCALE * np.tanh(ao[:, :A] / act_ref.ACT_MEAN_SCALE)
-        std = _softplus(ao[:, A:] + np.log(np.expm1(act_ref.ACT_INIT_STD))) + act_ref.ACT_MIN_STD
+        std = _softplus(ao[:, A:] + float(np.log(np.expm1(act_ref.ACT_INIT_STD)))) + act_ref.ACT_MIN_STD
         act = np.tanh(mean + std * _f64(eps_action))
         if explore:
             act = np.clip(act + action_noise * _f64(eps_explore), -1.0, 1.0)
