@@ -33,7 +33,13 @@ I32 = C.c_int
 
 
 class PackDesc(C.Structure):
-    _fields_ = [("src", P), ("dst", P), ("ld", I32), ("N", I32), ("K", I32), ("transpose", I32)]
+    _fields_ = [("src", P), ("dst", P), ("ld", I32), ("N", I32), ("K", I32), ("transpose", I32),
+                ("kind", I32), ("src2", P), ("ld2", I32), ("E", I32)]
+
+
+PACK_COPY, PACK_PRODUCT, PACK_PRODUCT_VEC = 0, 1, 2
+PACK_PRODUCTS = 65536        # bd_pack_weights: n = descriptors + PACK_PRODUCTS * (trailing product descriptors)
+WGRAD_GEMM, WGRAD_CHAIN = 0, 1
 
 
 class Layer(C.Structure):
@@ -86,7 +92,9 @@ class WgradDesc(C.Structure):
                 ("splits", I32), ("rows_per", I32), ("tiles_n", I32), ("tiles_k", I32), ("block_begin", I32),
                 ("red_begin", I32), ("ws_off", C.c_ulonglong),
                 ("g_nseg", I32), ("g_seglen", I32), ("g_gh", I32), ("g_gw", I32), ("g_IH", I32), ("g_IW", I32), ("g_C", I32),
-                ("g_pad", I32)]
+                ("g_pad", I32),
+                ("kind", I32), ("c_E", I32), ("c_A", P), ("c_lda", I32), ("c_B", P), ("c_ldb", I32), ("c_b", P),
+                ("c_dA", P), ("c_ldda", I32), ("c_dB", P), ("c_lddb", I32), ("c_db", P)]
 
 
 def _ptr_fields(names):

@@ -12,14 +12,126 @@ char* err_buf() {
 // One block column per descriptor (blockIdx.y); blockIdx.x strides over its 16x16 blocks; each thread
 // writes one packed float4: dst[(nb*Kb + kb)*64 + lane] = {W[n][k0..k0+3]}, n = nb*16 + (lane&15),
 // k0 = kb*16 + 4*(lane>>4); transposed descriptors read W[k][n] instead.
-__global__ __launch_bounds__(256) void pack_kernel(const bd_pack_desc* __restrict__ descs) {
-    const bd_pack_desc d = descs[blockIdx.y];
+//
+// Product descriptors (BD_PACK_PRODUCT: dst = packed A.B, A = src [N x E], B = src2 [E x K]): a workgroup takes one 16x16
+// block C[n][k] of the product at a time and walks e in pieces of kPackE staged through LDS (each source element is
+// loaded once per block -- register-level broadcast loads made the same work four times as long; the next piece's loads
+// are in flight while this one is multiplied).  Wave w sums the w-th quarter of every piece, pieces in ascending order,
+// and the four partial sums are added in wave order: one fixed order whatever the grid.  The block is then written in
+// the packed lane order of A.B or of its transpose.  BD_PACK_PRODUCT_VEC (dst[n] = A[n].b): one wave per n, 64 strided
+// partial sums combined by a butterfly.
+//
+// The grid is one-dimensional: kPackCopyX workgroups per copy descriptor, then kPackProdX per trailing product descriptor
+// (bd_pack_weights).
+constexpr int kPackThreads = 256, kPackWaves = kPackThreads / 64;
+constexpr int kPackCopyX = 16;
+constexpr int kPackProdX = 192;      // product blocks of a 200 x 200 output (169) get a workgroup each
+constexpr int kPackE = 256;          // e per staged piece: 16 x 256 of A and 256 x 16 of B, four float4s each per thread
+struct alignas(16) PackLds {
+    float a[16][kPackE + 1];         // [n][e], odd pitch: the 16 rows a wave reads at one e lie in 16 banks
+    float b[kPackE][16];             // [e][k]
+    float part[kPackWaves][16][17];  // [wave][n][k]
+};
+__device__ __forceinline__ void pack_product(const bd_pack_desc& d, int bx, int nx, PackLds& L) {
+    const int Nb = (d.N + 15) >> 4, Kb = (d.K + 15) >> 4;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const float* __restrict__ A = d.src;
+    const float* __restrict__ B = d.src2;
+    // float4 loads along e (rows of A) / along k (rows of B) where every address they touch is 16-byte aligned
+    const bool vec = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && (d.ld & 3) == 0 &&
+                     (d.ld2 & 3) == 0 && (d.K & 3) == 0 && (d.E & 3) == 0;
+    floatx4* __restrict__ dst = reinterpret_cast<floatx4*>(d.dst);
+    for (int blk = bx; blk < Nb * Kb; blk += nx) {
+        const int nb = blk / Kb, kb = blk - nb * Kb;
+        const int n0 = nb * 16, k0 = kb * 16;
+        floatx4 ar[4], br[4];
+        // thread -> (row n0 + idx / 64, e = 4 (idx % 64)) of A and (e = idx / 4, k = k0 + 4 (idx % 4)) of B, idx = tid + 256 j
+        auto fetch = [&](int e0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int idx = tid + 256 * j;
+                const int n = n0 + (idx >> 6), ea = e0 + 4 * (idx & 63);
+                const int eb = e0 + (idx >> 2), k = k0 + 4 * (idx & 3);
+                if (vec) {
+                    ar[j] = (n < d.N && ea < d.E) ? *reinterpret_cast<const floatx4*>(A + (size_t)n * d.ld + ea) : floatx4{0.f, 0.f, 0.f, 0.f};
+                    br[j] = (eb < d.E && k < d.K) ? *reinterpret_cast<const floatx4*>(B + (size_t)eb * d.ld2 + k) : floatx4{0.f, 0.f, 0.f, 0.f};
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        ar[j][i] = (n < d.N && ea + i < d.E) ? A[(size_t)n * d.ld + ea + i] : 0.f;
+                        br[j][i] = (eb < d.E && k + i < d.K) ? B[(size_t)eb * d.ld2 + k + i] : 0.f;
+                    }
+                }
+            }
+        };
+        const int n = lane & 15, kq = 4 * (lane >> 4);        // this lane's C[n][kq .. kq + 3] over its wave's quarter
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        fetch(0);
+        for (int e0 = 0; e0 < d.E; e0 += kPackE) {
+            __syncthreads();            // the previous piece (and the previous block's partial sums) have been read
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int idx = tid + 256 * j;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) L.a[idx >> 6][4 * (idx & 63) + i] = ar[j][i];
+                *reinterpret_cast<floatx4*>(&L.b[idx >> 2][4 * (idx & 3)]) = br[j];
+            }
+            __syncthreads();
+            if (e0 + kPackE < d.E) fetch(e0 + kPackE);
+            const int w0 = wave * (kPackE / kPackWaves);
+#pragma unroll 8
+            for (int e = w0; e < w0 + kPackE / kPackWaves; ++e) {      // (entries past E are zero)
+                const float av = L.a[n][e];
+                const floatx4 bv = *reinterpret_cast<const floatx4*>(&L.b[e][kq]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i] = fmaf(av, bv[i], acc[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) L.part[wave][n][kq + i] = acc[i];
+        __syncthreads();
+        if (wave == 0) {                // packed lane order: (out, 4 x in) = (n, k ..) of A.B, (k, n ..) of its transpose
+            floatx4 v;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int cn = d.transpose ? kq + i : n, ck = d.transpose ? n : kq + i;
+                float t = L.part[0][cn][ck];
+#pragma unroll
+                for (int w = 1; w < kPackWaves; ++w) t += L.part[w][cn][ck];
+                v[i] = t;
+            }
+            const int ob = d.transpose ? kb * Nb + nb : blk;
+            dst[(size_t)ob * 64 + lane] = v;
+        }
+    }
+}
+
+__device__ __forceinline__ void pack_product_vec(const bd_pack_desc& d, int bx, int nx) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int n = bx * kPackWaves + wave; n < d.N; n += nx * kPackWaves) {
+        float s = 0.f;
+        for (int e = lane; e < d.E; e += 64) s = fmaf(d.src[(size_t)n * d.ld + e], d.src2[e], s);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        if (lane == 0) d.dst[n] = s;
+    }
+}
+
+__global__ __launch_bounds__(kPackThreads) void pack_kernel(const bd_pack_desc* __restrict__ descs, int n_copy) {
+    extern __shared__ floatx4 pack_lds[];       // sizeof(PackLds) when the table has product descriptors, else nothing
+    PackLds& lds = *reinterpret_cast<PackLds*>(pack_lds);
+    const int pb = (int)blockIdx.x - n_copy * kPackCopyX;         // >= 0: a workgroup of the product descriptors
+    const bd_pack_desc d = descs[pb < 0 ? blockIdx.x / kPackCopyX : n_copy + pb / kPackProdX];
+    // (a product descriptor must be counted in n_prod: its workgroups need the LDS the launch then asks for)
+    const int bx = pb < 0 ? blockIdx.x % kPackCopyX : pb % kPackProdX, nx = pb < 0 ? kPackCopyX : kPackProdX;
+    if (pb >= 0 && d.kind == BD_PACK_PRODUCT) return pack_product(d, bx, nx, lds);
+    if (pb >= 0 && d.kind == BD_PACK_PRODUCT_VEC) return pack_product_vec(d, bx, nx);
     const int No = d.transpose ? d.K : d.N;   // packed "out" dim
     const int Ki = d.transpose ? d.N : d.K;   // packed "in" dim
     const int Nb = (No + 15) >> 4, Kb = (Ki + 15) >> 4;
     const int total = Nb * Kb * 64;
     floatx4* __restrict__ dst = reinterpret_cast<floatx4*>(d.dst);
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+    for (int e = bx * kPackThreads + threadIdx.x; e < total; e += nx * kPackThreads) {
         const int lane = e & 63, blk = e >> 6;
         const int nb = blk / Kb, kb = blk - nb * Kb;
         const int n = nb * 16 + (lane & 15);
@@ -81,13 +193,16 @@ __global__ __launch_bounds__(256) void gather_pixels_kernel(const unsigned char*
 extern "C" {
 
 const char* bd_last_error(void) { return bd::err_buf(); }
-int bd_version(void) { return 2; }
+int bd_version(void) { return 3; }
 
 size_t bd_packed_floats(int N, int K) { return (size_t)bd::cdiv(N, 16) * bd::cdiv(K, 16) * 256; }
 
 int bd_pack_weights(const bd_pack_desc* descs, int n, void* stream) {
-    BD_REQUIRE(descs != nullptr && n > 0, "bd_pack_weights: no descriptors");
-    hipLaunchKernelGGL(bd::pack_kernel, dim3(16, n), dim3(256), 0, (hipStream_t)stream, descs);
+    const int n_prod = n > 0 ? n / BD_PACK_PRODUCTS : 0;
+    n = n > 0 ? n % BD_PACK_PRODUCTS : n;
+    BD_REQUIRE(descs != nullptr && n > 0 && n_prod <= n, "bd_pack_weights: no descriptors");
+    hipLaunchKernelGGL(bd::pack_kernel, dim3((n - n_prod) * bd::kPackCopyX + n_prod * bd::kPackProdX), dim3(bd::kPackThreads),
+                       n_prod > 0 ? sizeof(bd::PackLds) : 0, (hipStream_t)stream, descs, n - n_prod);
     BD_CHECK_LAUNCH("bd_pack_weights");
     return 0;
 }

@@ -844,6 +844,105 @@ __global__ __launch_bounds__(kRedWideThreads) void wgrad_wide_reduce_kernel(cons
     }
 }
 
+// Chain records (bigdreamer_hip.h, BD_WGRAD_CHAIN): the weight-space products that turn the reduced gradient of a composed
+// layer (dWc [N x K], dbc [N]; Wc = A.B, bc = A.b) into the gradients of its two factors, as two small tiled GEMMs
+//   MODE 0:  c_dA[n][e] = sum_{l <= K} X(n, l) Y(l, e),  X = [dWc | dbc],  Y = [B^T ; b^T]         (L = K + 1)
+//   MODE 1: [c_dB | c_db][e][j] = sum_n A[n][e] [dWc | dbc][n][j]                                   (L = N, J = K + 1)
+// blockIdx.y = record; blockIdx.x strides over the 32 x 64 output tiles of both.  A tile walks the contraction in pieces
+// of 64 staged through LDS (the next piece's global loads are in flight while this one is multiplied); a thread owns
+// 2 x 4 outputs and sums each in ascending l: no atomics, the same bits for any grid.  All operands are weight-sized and
+// L2-resident (<= 1 MB each at the benchmark shape, 82 MFLOP per product there): the kernel is bound by load latency,
+// hence one tile per CU (240 tiles at that shape) rather than longer loops on fewer.
+constexpr int kChainShift = 24;      // the plan word: reduce workgroups below, chain records above this bit
+constexpr int kChainBlocks = 256;
+constexpr int kChI = 32, kChJ = 64, kChL = 64;
+constexpr int kChXT = kChI * kChL / 256, kChYT = kChJ * kChL / 256;      // staged elements per thread and piece
+template <int MODE>
+__device__ __forceinline__ void wgrad_chain_tile(const bd_wgrad_desc& d, int i0, int j0, float (*Xs)[kChI + 1],
+                                                 float (*Ys)[kChJ + 1]) {
+    const int N = d.N, K = d.K, E = d.c_E;
+    const int I = MODE == 0 ? N : E, J = MODE == 0 ? E : K + 1, L = MODE == 0 ? K + 1 : N;
+    const float* __restrict__ dWc = d.dW;
+    const float* __restrict__ dbc = d.db;
+    auto x = [&](int i, int l) -> float {
+        if (i >= I || l >= L) return 0.f;
+        if (MODE == 0) return l < K ? dWc[(size_t)i * d.ldw + l] : dbc[i];
+        return d.c_A[(size_t)l * d.c_lda + i];
+    };
+    auto y = [&](int l, int j) -> float {
+        if (j >= J || l >= L) return 0.f;
+        if (MODE == 0) return l < K ? d.c_B[(size_t)j * d.c_ldb + l] : d.c_b[j];
+        return j < K ? dWc[(size_t)l * d.ldw + j] : dbc[l];
+    };
+    const int tid = threadIdx.x;
+    float xr[kChXT], yr[kChYT];
+    // the index that is contiguous in memory runs along the lanes: l in MODE 0, i / j in MODE 1
+    auto fetch = [&](int l0) {
+#pragma unroll
+        for (int t = 0; t < kChXT; ++t) {
+            const int idx = tid + 256 * t;
+            xr[t] = MODE == 0 ? x(i0 + idx / kChL, l0 + idx % kChL) : x(i0 + idx % kChI, l0 + idx / kChI);
+        }
+#pragma unroll
+        for (int t = 0; t < kChYT; ++t) {
+            const int idx = tid + 256 * t;
+            yr[t] = MODE == 0 ? y(l0 + idx % kChL, j0 + idx / kChL) : y(l0 + idx / kChJ, j0 + idx % kChJ);
+        }
+    };
+    const int ti = tid >> 4, tj = tid & 15;          // outputs (i0 + ti + 16 r, j0 + tj + 16 c)
+    float acc[2][4] = {};
+    fetch(0);
+    for (int l0 = 0; l0 < L; l0 += kChL) {
+        __syncthreads();                // the previous piece has been read
+#pragma unroll
+        for (int t = 0; t < kChXT; ++t) {
+            const int idx = tid + 256 * t;
+            if (MODE == 0) Xs[idx % kChL][idx / kChL] = xr[t];
+            else Xs[idx / kChI][idx % kChI] = xr[t];
+        }
+#pragma unroll
+        for (int t = 0; t < kChYT; ++t) {
+            const int idx = tid + 256 * t;
+            if (MODE == 0) Ys[idx % kChL][idx / kChL] = yr[t];
+            else Ys[idx / kChJ][idx % kChJ] = yr[t];
+        }
+        __syncthreads();
+        if (l0 + kChL < L) fetch(l0 + kChL);
+#pragma unroll 8
+        for (int l = 0; l < kChL; ++l) {             // (entries past L are zero)
+            const float x0 = Xs[l][ti], x1 = Xs[l][ti + 16];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float yv = Ys[l][tj + 16 * c];
+                acc[0][c] = fmaf(x0, yv, acc[0][c]);
+                acc[1][c] = fmaf(x1, yv, acc[1][c]);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int i = i0 + ti + 16 * r, j = j0 + tj + 16 * c;
+            if (i >= I || j >= J) continue;
+            if (MODE == 0) d.c_dA[(size_t)i * d.c_ldda + j] = acc[r][c];
+            else if (j < K) d.c_dB[(size_t)i * d.c_lddb + j] = acc[r][c];
+            else d.c_db[i] = acc[r][c];
+        }
+}
+
+__global__ __launch_bounds__(256) void wgrad_chain_kernel(const bd_wgrad_desc* __restrict__ descs) {
+    __shared__ float Xs[kChL][kChI + 1];
+    __shared__ float Ys[kChL][kChJ + 1];
+    const bd_wgrad_desc d = descs[blockIdx.y];
+    const int ja = cdiv(d.c_E, kChJ), ua = cdiv(d.N, kChI) * ja;
+    const int jb = cdiv(d.K + 1, kChJ), ub = cdiv(d.c_E, kChI) * jb;
+    for (int u = blockIdx.x; u < ua + ub; u += gridDim.x) {
+        if (u < ua) wgrad_chain_tile<0>(d, (u / ja) * kChI, (u % ja) * kChJ, Xs, Ys);
+        else wgrad_chain_tile<1>(d, ((u - ua) / jb) * kChI, ((u - ua) % jb) * kChJ, Xs, Ys);
+    }
+}
+
 #ifdef BD_STAMPS
 extern "C" int bd_debug_wstamps(unsigned long long* out64) {
     return hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_dstamps), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -1;
@@ -883,6 +982,12 @@ extern "C" {
 int bd_wgrad_plan(bd_wgrad_desc* descs, int n, int* total_blocks, int* total_red_blocks, size_t* ws_floats) {
     using namespace bd;
     BD_REQUIRE(descs && n > 0 && total_blocks && total_red_blocks && ws_floats, "bd_wgrad_plan: bad arguments");
+    // chain records close the table: everything below plans the GEMM descriptors in front of them
+    const int n_all = n;
+    while (n > 0 && descs[n - 1].kind == BD_WGRAD_CHAIN) --n;
+    BD_REQUIRE(n > 0 && n_all - n < 128, "bd_wgrad_plan: a table needs a GEMM descriptor, and at most 127 chain records");
+    for (int i = 0; i < n; ++i)
+        BD_REQUIRE(descs[i].kind == BD_WGRAD_GEMM, "bd_wgrad_plan: descriptor %d: chain records follow every GEMM descriptor", i);
     int blocks = 0, red = 0;
     size_t off = 0;
     // wide form: one workgroup per CU (402 registers per lane), so the launch should be ONE round of the chip: the
@@ -1030,8 +1135,24 @@ int bd_wgrad_plan(bd_wgrad_desc* descs, int n, int* total_blocks, int* total_red
             off += (size_t)d.splits * d.N * (d.K + hb);
         }
     }
+    for (int i = n; i < n_all; ++i) {       // no workgroup of the GEMM or the reduce launch maps to a chain record
+        bd_wgrad_desc& d = descs[i];
+        BD_REQUIRE(d.dW && d.db && d.N > 0 && d.K > 0 && d.ldw >= d.K && d.c_E > 0 && d.c_A && d.c_B && d.c_b && d.c_dA &&
+                       d.c_dB && d.c_db && d.c_lda >= d.c_E && d.c_ldda >= d.c_E && d.c_ldb >= d.K && d.c_lddb >= d.K,
+                   "bd_wgrad_plan: chain record %d is malformed", i);
+        bool fed = false;                   // its (dW, db) must be what a GEMM descriptor of this table leaves
+        for (int j = 0; j < n; ++j)
+            fed = fed || (descs[j].dW == d.dW && descs[j].db == d.db && descs[j].N == d.N && descs[j].K == d.K &&
+                          descs[j].ldw == d.ldw);
+        BD_REQUIRE(fed, "bd_wgrad_plan: chain record %d reads a gradient that no descriptor of the table writes", i);
+        d.splits = d.rows_per = d.tiles_n = d.tiles_k = 0;
+        d.block_begin = blocks;
+        d.red_begin = red;
+        d.ws_off = off;
+    }
+    BD_REQUIRE(red < (1 << kChainShift), "bd_wgrad_plan: too many reduce workgroups");
     *total_blocks = blocks;
-    *total_red_blocks = red;
+    *total_red_blocks = red | ((n_all - n) << kChainShift);
     *ws_floats = off;
     return 0;
 }
@@ -1044,6 +1165,9 @@ int bd_wgrad_grouped(const bd_wgrad_desc* descs_dev, int n, int total_blocks, in
 int bd_wgrad_grouped_phase(const bd_wgrad_desc* descs_dev, int n, int total_blocks, int total_red_blocks, float* ws,
                            int phase, void* stream) {
     using namespace bd;
+    const int n_chain = total_red_blocks > 0 ? total_red_blocks >> kChainShift : 0;      // the plan word (bd_wgrad_plan)
+    total_red_blocks &= (1 << kChainShift) - 1;
+    n -= n_chain;
     BD_REQUIRE(descs_dev && ws && n > 0 && n <= 4096 && total_blocks > 0 && total_red_blocks > 0 && phase >= 0 && phase <= 2,
                "bd_wgrad_grouped: bad arguments");
     BD_REQUIRE(!wgrad_wide() || (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "bd_wgrad_grouped: the workspace must be 16-byte aligned");
@@ -1069,6 +1193,10 @@ int bd_wgrad_grouped_phase(const bd_wgrad_desc* descs_dev, int n, int total_bloc
         hipLaunchKernelGGL(wgrad_grouped_reduce_kernel, dim3(total_red_blocks), dim3(256), 0, (hipStream_t)stream, descs_dev, n,
                            ws);
     BD_CHECK_LAUNCH("bd_wgrad_grouped(reduce)");
+    if (n_chain > 0) {
+        hipLaunchKernelGGL(wgrad_chain_kernel, dim3(kChainBlocks, n_chain), dim3(256), 0, (hipStream_t)stream, descs_dev + n);
+        BD_CHECK_LAUNCH("bd_wgrad_grouped(chain)");
+    }
     return 0;
 }
 

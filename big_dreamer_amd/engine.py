@@ -208,6 +208,7 @@ class WgradBatch:
     def __init__(self, eng: "DreamerEngine", name: str, ws_attr: str = "_wgrad_ws"):
         self.eng, self.name, self.ws_attr = eng, name, ws_attr
         self.items: List[tuple] = []
+        self.chains: List[tuple] = []
         self._cache: Dict[tuple, tuple] = {}
 
     def add(self, dpre, ldp, act, lda, M, N, K, dW, ldw, db=None, act2=None, lda2=0, M1=None, gather=None) -> None:
@@ -216,15 +217,26 @@ class WgradBatch:
         self.items.append((ptr(dpre), ldp, ptr(act), lda, M if M1 is None else M1, ptr(act2), lda2, M, N, K, ptr(dW), ldw,
                            ptr(db), tuple(gather) if gather else (0, 0, 0, 0, 0, 0, 0)))
 
+    def add_chain(self, dWc, dbc, N, K, E, A, lda, B, b, dA, ldda, dB, db) -> None:
+        """Chain record (include/bigdreamer_hip.h): a queued GEMM leaves dWc [N x K] and dbc [N] of the composed layer
+        Wc = A.B, bc = A.b (A [N x E] with row stride lda, B [E x K], b [E]); the same launch group then writes
+        dA (row stride ldda), dB and db."""
+        self.chains.append((ptr(dWc), ptr(dbc), N, K, E, ptr(A), lda, ptr(B), ptr(b), ptr(dA), ldda, ptr(dB), ptr(db)))
+
     def run(self) -> None:
         eng = self.eng
         if not self.items:
             return
-        key = tuple(self.items)
+        key = tuple(self.items) + tuple(self.chains)
         hit = self._cache.get(key)
         if hit is None:
-            n = len(self.items)
+            n = len(self.items) + len(self.chains)
             descs = (cabi.WgradDesc * n)()
+            for i, ch in enumerate(self.chains, len(self.items)):
+                c = descs[i]
+                c.kind = cabi.WGRAD_CHAIN
+                (c.dW, c.db, c.N, c.K, c.c_E, c.c_A, c.c_lda, c.c_B, c.c_b, c.c_dA, c.c_ldda, c.c_dB, c.c_db) = ch
+                c.ldw = c.c_ldb = c.c_lddb = c.K
             for i, it in enumerate(self.items):
                 (descs[i].dpre, descs[i].ldp, descs[i].act1, descs[i].lda1, descs[i].M1, descs[i].act2, descs[i].lda2,
                  descs[i].M, descs[i].N, descs[i].K, descs[i].dW, descs[i].ldw, descs[i].db) = it[:13]
@@ -248,7 +260,7 @@ class WgradBatch:
             cabi.check(lib.bd_wgrad_grouped_phase(table.data_ptr(), n, tb, tr, ws, 2, cabi.stream()))
         else:
             cabi.check(lib.bd_wgrad_grouped(table.data_ptr(), n, tb, tr, ws, cabi.stream()))
-        self.items = []
+        self.items, self.chains = [], []
 
 
 # Pipeline streams are per PROCESS and device, not per engine.  torch hands out streams from a fixed pool and HIP maps them
@@ -369,6 +381,10 @@ class DreamerEngine:
         # bh_chunks: None = the default rule (behaviour_plan), 1 = single launches, K = K near-equal chunks, a tuple =
         # the chunk lengths (BD_BH_CHUNKS: "", "1", "3", "5,5,4").
         self.bh_chunks = _parse_bh_chunks(os.environ.get("BD_BH_CHUNKS", ""))
+        # Composed encoder tail ("Composed encoder tail"): with state observations the encoder's
+        # linear last layer and the posterior's hoisted projection are trained as their product.  None = the default
+        # rule (composed_encoder_tail), True / False force a form.
+        self.encoder_composed: Optional[bool] = None
         # Cross-step software pipeline (on unless BD_PIPELINE=0).  Dynamics learning of step k+1 reads only the world
         # model that step k's model optimiser wrote, never what step k's behaviour learning (imagination, actor,
         # critic) produces, while behaviour learning k needs the world model k and the posteriors k.  So the two
@@ -618,12 +634,22 @@ class DreamerEngine:
             add("actor", "a4s", Wa4[A:], tr=True)
             add("actor", "a4", Wa4, fwd=False, tr=True)     # (mean | raw) rows together: the hidden-layer backward as one chain
 
+        # composed encoder tail: the product of the two source matrices, formed by the pack launch itself
+        # (key, A [N x E], B [E x K] | b [E], transposed); encq_b is the plain vector A.b
+        prod: Dict[str, List[tuple]] = {g: [] for g in ent}
+        if not self.pixel:
+            A, W4 = Wq1[:, Be:], self.W("encoder", f"model.{2 * DENSE_LAYERS}.weight")
+            prod["model"] += [("encq", A, W4, False), ("encq.T", A, W4, True),
+                              ("encq_b", A, self.W("encoder", f"model.{2 * DENSE_LAYERS}.bias"), False)]
+
         self.pk: Dict[str, torch.Tensor] = {}
         self._pack_tables = {}
         for group, lst in ent.items():
             total = sum(cabi.packed_floats(*(v.shape if not tr else v.shape[::-1])) for _, v, tr in lst)
+            total += sum(cabi.packed_floats(A.shape[0], B.shape[-1]) if B.dim() == 2 else -(-A.shape[0] // 4) * 4
+                         for _, A, B, _ in prod[group])
             store = torch.zeros(total, dtype=torch.float32, device=self.dev)
-            descs = (cabi.PackDesc * len(lst))()
+            descs = (cabi.PackDesc * (len(lst) + len(prod[group])))()
             off = 0
             for i, (key, v, tr) in enumerate(lst):
                 N, K = v.shape
@@ -631,8 +657,18 @@ class DreamerEngine:
                 self.pk[key] = store[off:off + n]
                 descs[i] = cabi.PackDesc(v.data_ptr(), self.pk[key].data_ptr(), v.stride(0), N, K, int(tr))
                 off += n
+            for i, (key, A, B, tr) in enumerate(prod[group], len(lst)):
+                N, E = A.shape
+                vec = B.dim() == 1
+                K = 1 if vec else B.shape[1]
+                n = -(-N // 4) * 4 if vec else cabi.packed_floats(N, K)      # (packed blocks stay 16-byte aligned)
+                self.pk[key] = store[off:off + (N if vec else n)]
+                descs[i] = cabi.PackDesc(A.data_ptr(), self.pk[key].data_ptr(), A.stride(0), N, K, int(tr),
+                                         cabi.PACK_PRODUCT_VEC if vec else cabi.PACK_PRODUCT, B.data_ptr(),
+                                         1 if vec else B.stride(0), E)
+                off += n
             raw = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(self.dev)
-            self._pack_tables[group] = (raw, len(lst), store)
+            self._pack_tables[group] = (raw, len(descs) + cabi.PACK_PRODUCTS * len(prod[group]), store)
 
     def pack(self, group: str) -> None:
         raw, n, _ = self._pack_tables[group]
@@ -1005,6 +1041,25 @@ class DreamerEngine:
         pre = self.buf("pre_emb", M, d.Hd)
         self.mlp_forward(M, obs2d, d.O, d.O, layers, acts + [emb, None], pre, d.Hd)
         return emb, pre
+
+    def composed_encoder_tail(self, M: int) -> bool:
+        """Whether a dynamics step over M rows trains the encoder's last layer and the posterior's embedding projection
+        as their product: state observations only; by default where the rows saved outweigh the
+        weight-space products (M >= 4 Hd)."""
+        if self.pixel:
+            return False
+        return M >= 4 * self.d.Hd if self.encoder_composed is None else bool(self.encoder_composed)
+
+    def encode_composed(self, obs2d: torch.Tensor, M: int) -> torch.Tensor:
+        """Training form of encode(): enc0..enc3, then the composed layer encq = q1e . enc4 (bias encq_b), straight into
+        pre_emb [M x Hd]; no embedding is formed."""
+        d = self.d
+        layers = self._dense_spec("encoder", "enc", d.O, d.E)[:DENSE_LAYERS] + [
+            ("encq", self.pk["encq_b"], d.Hd, d.Hd, cabi.ACT_NONE)]
+        acts = [self.buf(f"enc_act{l}", M, d.Hd) for l in range(DENSE_LAYERS)]
+        pre = self.buf("pre_emb", M, d.Hd)
+        self.mlp_forward(M, obs2d, d.O, d.O, layers, acts + [None], pre, d.Hd)
+        return pre
 
     # ---- pixel observations: the conv stacks (conv_stack.ConvStacks; same interface: tests/torch_conv_stacks.py) ----
     def encode_pixels(self, obs4d: torch.Tensor, grad: bool = True):
@@ -1841,8 +1896,12 @@ class DreamerEngine:
         w = SimpleNamespace(T=T, B=B, N=N, F=F, actions=actions[:-1], nonterm=nonterm[:-1], eps_post=noise["obs_post"],
                             om_acts=None, om_dpre=None, dc_acts=None, dc_dpre=None)
         obs_t = obs[1:].reshape(N, d.O)                     # targets and encoder input
+        w.composed = self.composed_encoder_tail(N)
         with self.span("encoder_fwd"):
-            w.emb, pre_emb = self.encode_pixels(obs[1:].reshape(N, 3, 64, 64)) if self.pixel else self.encode(obs_t, N)
+            if w.composed:
+                w.emb, pre_emb = None, self.encode_composed(obs_t, N)
+            else:
+                w.emb, pre_emb = self.encode_pixels(obs[1:].reshape(N, 3, 64, 64)) if self.pixel else self.encode(obs_t, N)
         w.init_belief = self.buf("init_belief", B, d.Be).zero_()
         init_state = self.buf("init_state", B, d.S).zero_()
         w.feat, qm, qs = self.observe(w.actions, w.nonterm, pre_emb, w.eps_post, w.init_belief, init_state, T, B,
@@ -1976,6 +2035,12 @@ class DreamerEngine:
                               w0=d.E)
             with self.span("encoder_bwd"):
                 self.conv.backward_encoder(d_emb, self._wbatch["model"])
+        elif w.composed:         # d_q1 is the pre-activation gradient of the composed layer itself
+            enc_layers = self._dense_spec("encoder", "enc", d.O, d.E)[:DENSE_LAYERS] + [
+                ("encq", None, d.Hd, d.Hd, cabi.ACT_NONE)]
+            enc_acts = [self._buf[f"enc_act{l}"] for l in range(DENSE_LAYERS)]
+            enc_dpre = [self.buf(f"enc_dpre{l}", N, d.Hd) for l in range(DENSE_LAYERS)]
+            self.mlp_backward(N, d_q1, d.Hd, enc_layers, enc_acts + [None], enc_dpre + [None])
         else:
             enc_layers = self._dense_spec("encoder", "enc", d.O, d.E) + [("q1e", None, d.Hd, d.E, cabi.ACT_NONE)]
             enc_acts = [self._buf[f"enc_act{l}"] for l in range(DENSE_LAYERS)]
@@ -1997,7 +2062,16 @@ class DreamerEngine:
                Gt("belief_prior.model.2.bias"))
         gWq1 = Gt("belief_posterior.model.0.weight")
         wb.add(d_q1, d.Hd, feat, F, N, d.Hd, d.Be, gWq1, d.Be + d.E, Gt("belief_posterior.model.0.bias"))
-        wb.add(d_q1, d.Hd, w.emb, d.E, N, d.Hd, d.E, gWq1[:, d.Be:], d.Be + d.E)
+        if w.composed:
+            # one Hd x Hd GEMM over the rows into scratch, then the chain record: dW_q1e, dW_enc4, db_enc4 in weight space
+            dWc, dbc = self.buf("d_encq", d.Hd, d.Hd), self.buf("d_encq_b", d.Hd)
+            wb.add(d_q1, d.Hd, enc_acts[-1], d.Hd, N, d.Hd, d.Hd, dWc, d.Hd, dbc)
+            L = 2 * DENSE_LAYERS
+            wb.add_chain(dWc, dbc, d.Hd, d.Hd, d.E, self.W("transition_model", "belief_posterior.model.0.weight")[:, d.Be:],
+                         d.Be + d.E, self.W("encoder", f"model.{L}.weight"), self.W("encoder", f"model.{L}.bias"),
+                         gWq1[:, d.Be:], d.Be + d.E, self.G("encoder", f"model.{L}.weight"), self.G("encoder", f"model.{L}.bias"))
+        else:
+            wb.add(d_q1, d.Hd, w.emb, d.E, N, d.Hd, d.E, gWq1[:, d.Be:], d.Be + d.E)
         wb.add(w.d_q2, HO, self._buf["sv_q"], d.Hd, N, HO, d.Hd, Gt("belief_posterior.model.2.weight"), d.Hd,
                Gt("belief_posterior.model.2.bias"))
         dense_sizes = lambda i, o: [i] + [d.Hd] * DENSE_LAYERS + [o]
@@ -2006,7 +2080,8 @@ class DreamerEngine:
             self._dense_wgrads(wb, "discount_model", N, w.dc_dpre, feat, F, w.dc_acts, dense_sizes(F, 1))
         if not self.pixel:      # (pixel mode: the conv stacks queued their weight gradients themselves)
             self._dense_wgrads(wb, "observation_model", N, w.om_dpre, feat, F, w.om_acts, dense_sizes(F, d.O))
-            self._dense_wgrads(wb, "encoder", N, enc_dpre, w.obs_t, d.O, enc_acts, dense_sizes(d.O, d.E))
+            self._dense_wgrads(wb, "encoder", N, enc_dpre, w.obs_t, d.O, enc_acts,
+                               dense_sizes(d.O, d.E)[:len(enc_dpre) + 1])
         with self.span("wgrad_model"):
             wb.run()
         if self.pixel:

@@ -50,16 +50,33 @@ const char* bd_last_error(void);
 int bd_version(void);
 
 /* ---- weight packing ------------------------------------------------------------------------- */
+#define BD_PACK_COPY 0       /* dst = packed src (or its transpose)                                                    */
+#define BD_PACK_PRODUCT 1    /* dst = packed A.B (or its transpose): A = src [N x E] (ld), B = src2 [E x K] (ld2)       */
+#define BD_PACK_PRODUCT_VEC 2 /* dst[n] = sum_e A[n][e] b[e], plain floats: A = src [N x E] (ld), b = src2 [E]; K unused */
 typedef struct {
     const float* src; /* PyTorch-layout matrix, element (n,k) at src[n*ld + k]                  */
     float* dst;       /* packed destination, bd_packed_floats(N,K) floats (transposed: (K,N))    */
     int ld;           /* leading dimension of src                                                 */
     int N, K;         /* logical sub-block to pack (rows n < N, cols k < K of src)                */
     int transpose;    /* 0: pack W (out=N,in=K); 1: pack W^T (out=K,in=N) for the dgrad kernels  */
+    /* Product kinds (kind = 0 and the fields below zero: a plain copy, as before).  Two linear layers with nothing
+     * between them are one layer: the pack launch forms the composed weight from the two SOURCE matrices (never from
+     * another packed output, so the descriptors of one launch stay independent).  Every dot product is summed in a fixed
+     * order (four contiguous quarters of e, each in ascending e, added in quarter order; the vector kind: 64 strided
+     * partial sums combined by a fixed butterfly), no atomics.  A product is ~E times the work of a copy, with a grid and
+     * an LDS allocation of its own: product descriptors close the table and the caller says how many there are,
+     * n = descriptors + BD_PACK_PRODUCTS * (trailing product descriptors).  (A product descriptor that is not counted is
+     * treated as a copy of src.) */
+    int kind;         /* BD_PACK_*                                                                */
+    const float* src2;/* B (element (e,k) at src2[e*ld2 + k]) or b                                */
+    int ld2;
+    int E;            /* contraction length                                                       */
 } bd_pack_desc;
 
 size_t bd_packed_floats(int N, int K);
-/* descs: DEVICE array of n descriptors. */
+/* descs: DEVICE array of n descriptors (the table lives on the device, so the count of trailing product descriptors,
+ * which take a grid of their own size, rides on n: see bd_pack_desc). */
+#define BD_PACK_PRODUCTS 65536
 int bd_pack_weights(const bd_pack_desc* descs, int n, void* stream);
 
 /* ---- dense chains: DenseModel / build_mlp (src/models.py:365-408, src/utils.py:368-404) ------ */
@@ -141,12 +158,32 @@ typedef struct {
      * over g_gh x g_gw per image takes act(m, k) = act1[((img*g_IH + 2y + s)*g_IW + 2x)*g_C + off], s = k / g_seglen,
      * off = k % g_seglen (K = g_nseg * g_seglen; lda1 / act2 unused, M1 = M). */
     int g_nseg, g_seglen, g_gh, g_gw, g_IH, g_IW, g_C, g_pad;
+    /* Chain records (kind = BD_WGRAD_CHAIN; they follow every GEMM descriptor of the table).  Where the forward ran a
+     * composed layer Wc = A.B, bc = A.b (BD_PACK_PRODUCT: A [N x E], B [E x K], b [E]) a GEMM descriptor of the same table
+     * leaves dWc [N x K] and dbc [N] in scratch; the chain record names that result as its (dW, ldw, db) and the call
+     * finishes the job after the reduce, in one more launch (fixed summation order, no atomics):
+     *   c_dA[n][e] = sum_k dWc[n][k] B[e][k] + dbc[n] b[e],   c_dB[e][k] = sum_n A[n][e] dWc[n][k],
+     *   c_db[e]    = sum_n A[n][e] dbc[n].
+     * Only the E columns of c_dA named here are written.  dpre / act1 / M are unused in a chain record. */
+    int kind;                                  /* BD_WGRAD_GEMM (0) | BD_WGRAD_CHAIN                            */
+    int c_E;
+    const float* c_A; int c_lda;
+    const float* c_B; int c_ldb;
+    const float* c_b;
+    float* c_dA; int c_ldda;
+    float* c_dB; int c_lddb;
+    float* c_db;
 } bd_wgrad_desc;
+#define BD_WGRAD_GEMM 0
+#define BD_WGRAD_CHAIN 1
+/* total_red_blocks is an opaque plan word (reduce workgroups, and the number of chain records above bit 24): pass it on
+ * as bd_wgrad_plan returned it. */
 int bd_wgrad_plan(bd_wgrad_desc* descs_host, int n, int* total_blocks, int* total_red_blocks, size_t* ws_floats);
 int bd_wgrad_grouped(const bd_wgrad_desc* descs_dev, int n, int total_blocks, int total_red_blocks, float* ws,
                      void* stream);
 /* The two launches of bd_wgrad_grouped separately (phase 1: the slab GEMM kernel; phase 2: the fixed-order reduce), so
- * that a benchmark can bracket the GEMM kernel alone with HIP events.  phase 0 = both = bd_wgrad_grouped. */
+ * that a benchmark can bracket the GEMM kernel alone with HIP events.  phase 0 = both = bd_wgrad_grouped.  The chain
+ * records' launch belongs to phase 2. */
 int bd_wgrad_grouped_phase(const bd_wgrad_desc* descs_dev, int n, int total_blocks, int total_red_blocks, float* ws,
                            int phase, void* stream);
 
