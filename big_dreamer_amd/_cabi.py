@@ -349,6 +349,10 @@ _SIGS = {
     "bd_latent_stats": (I32, [P, P, P, P, I32, I32, P, P, P, P]),
     "bd_latent_stats_categorical": (I32, [P, P, I32, I32, I32, P, P, P, P, P]),
     "bd_segment_sumsq": (I32, [P, I32, C.POINTER(C.c_size_t), P, P, P]),
+    "bd_return_range": (I32, [P, I32, I32, I32, C.c_double, C.c_double, P, P, P]),
+    "bd_return_seed": (I32, [P, F32, P, C.c_size_t, P, P, I32, P]),
+    "bd_actor_reinforce_norm": (I32, [P, P, P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, I32, P, P, I32, P, P]),
+    "bd_actor_reinforce_cat_norm": (I32, [P, P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, I32, P, P, I32, P, P]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

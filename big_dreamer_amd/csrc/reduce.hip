@@ -212,10 +212,11 @@ __global__ __launch_bounds__(256) void lambda_bwd_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void actor_reinforce_kernel(
     const float* __restrict__ eps, const float* __restrict__ us, const float* __restrict__ stats,
     const float* __restrict__ ret, const float* __restrict__ base0, const float* __restrict__ value,
-    const float* __restrict__ weight, int rows, int N, int A, float scale, float dentropy, int write,
-    float* __restrict__ dout, double* __restrict__ partials) {
+    const float* __restrict__ weight, const float* __restrict__ ret_scale, int rows, int N, int A, float scale,
+    float dentropy, int write, float* __restrict__ dout, double* __restrict__ partials) {
     __shared__ double red[kWaves];
     constexpr float kLn2 = 0.69314718055994531f;
+    if (ret_scale) scale /= ret_scale[0];                     // return normalisation: the advantage term alone
     double s = 0.0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += gridDim.x * blockDim.x) {
         const float w = weight ? weight[i] : 1.f;
@@ -256,10 +257,12 @@ __global__ __launch_bounds__(256) void actor_reinforce_kernel(
 // l = norm[k] (k: the hot column of the straight-through one-hot action), d l / d out = onehot(k) - p.
 __global__ __launch_bounds__(256) void actor_reinforce_cat_kernel(
     const float* __restrict__ action, const float* __restrict__ stats, const float* __restrict__ ret,
-    const float* __restrict__ base0, const float* __restrict__ value, const float* __restrict__ weight, int rows, int N,
-    int A, float scale, float dentropy, int write, float* __restrict__ dout, double* __restrict__ partials) {
+    const float* __restrict__ base0, const float* __restrict__ value, const float* __restrict__ weight,
+    const float* __restrict__ ret_scale, int rows, int N, int A, float scale, float dentropy, int write,
+    float* __restrict__ dout, double* __restrict__ partials) {
     __shared__ double red[kWaves];
     const int lane = threadIdx.x & 63;
+    if (ret_scale) scale /= ret_scale[0];                     // return normalisation: the advantage term alone
     const int nw = gridDim.x * (blockDim.x >> 6);
     const bool valid = lane < A;
     double s = 0.0;
@@ -481,39 +484,58 @@ int bd_sum(const float* x, size_t n, float* scalars, int slot, float* ws, void* 
     return finish((double*)ws, nb, scalars, slot, (hipStream_t)stream, "bd_sum(final)");
 }
 
-int bd_actor_reinforce(const float* eps_action, const float* act_us, const float* act_stats, const float* returns,
-                       const float* base0, const float* value, const float* weight, int Hm, int N, int A, float rho,
-                       float grad_scale, float dentropy, int write, float* d_actor_out, float* scalars, int slot, float* ws,
-                       void* stream) {
+int bd_actor_reinforce_norm(const float* eps_action, const float* act_us, const float* act_stats, const float* returns,
+                            const float* base0, const float* value, const float* weight, const float* ret_scale, int Hm,
+                            int N, int A, float rho, float grad_scale, float dentropy, int write, float* d_actor_out,
+                            float* scalars, int slot, float* ws, void* stream) {
     BD_REQUIRE(eps_action && act_us && act_stats && returns && base0 && (value || Hm == 1) && d_actor_out && scalars && ws,
                "bd_actor_reinforce: missing pointers");
     BD_REQUIRE(Hm > 0 && N > 0 && A > 0 && (size_t)Hm * N <= (size_t)INT32_MAX / 4 && slot >= 0,
                "bd_actor_reinforce: bad dims (Hm=%d N=%d A=%d slot=%d)", Hm, N, A, slot);
     BD_REQUIRE(rho >= 0.f && rho <= 1.f, "bd_actor_reinforce: gradient mixing %g outside [0, 1]", (double)rho);
+    BD_REQUIRE(((size_t)ret_scale & 3u) == 0, "bd_actor_reinforce: ret_scale is not 4-byte aligned");
     const int rows = Hm * N;
     const int nb = red_blocks((size_t)rows);
     hipLaunchKernelGGL(actor_reinforce_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, eps_action, act_us, act_stats,
-                       returns, base0, value, weight, rows, N, A, -(1.f - rho) * grad_scale, dentropy, write, d_actor_out,
-                       (double*)ws);
+                       returns, base0, value, weight, ret_scale, rows, N, A, -(1.f - rho) * grad_scale, dentropy, write,
+                       d_actor_out, (double*)ws);
     BD_CHECK_LAUNCH("bd_actor_reinforce");
     return finish((double*)ws, nb, scalars, slot, (hipStream_t)stream, "bd_actor_reinforce(final)");
+}
+
+int bd_actor_reinforce(const float* eps_action, const float* act_us, const float* act_stats, const float* returns,
+                       const float* base0, const float* value, const float* weight, int Hm, int N, int A, float rho,
+                       float grad_scale, float dentropy, int write, float* d_actor_out, float* scalars, int slot, float* ws,
+                       void* stream) {
+    return bd_actor_reinforce_norm(eps_action, act_us, act_stats, returns, base0, value, weight, nullptr, Hm, N, A, rho,
+                                   grad_scale, dentropy, write, d_actor_out, scalars, slot, ws, stream);
+}
+
+int bd_actor_reinforce_cat_norm(const float* action, const float* act_stats, const float* returns, const float* base0,
+                                const float* value, const float* weight, const float* ret_scale, int Hm, int N, int A,
+                                float rho, float grad_scale, float dentropy, int write, float* d_actor_out, float* scalars,
+                                int slot, float* ws, void* stream) {
+    BD_REQUIRE(action && act_stats && returns && base0 && (value || Hm == 1) && d_actor_out && scalars && ws,
+               "bd_actor_reinforce_cat: missing pointers");
+    BD_REQUIRE(Hm > 0 && N > 0 && A > 0 && A <= 64 && (size_t)Hm * N <= (size_t)INT32_MAX / 4 && slot >= 0,
+               "bd_actor_reinforce_cat: bad dims (Hm=%d N=%d A=%d slot=%d)", Hm, N, A, slot);
+    BD_REQUIRE(rho >= 0.f && rho <= 1.f, "bd_actor_reinforce_cat: gradient mixing %g outside [0, 1]", (double)rho);
+    BD_REQUIRE(((size_t)ret_scale & 3u) == 0, "bd_actor_reinforce_cat: ret_scale is not 4-byte aligned");
+    const int rows = Hm * N;
+    const int nb = red_blocks((size_t)rows);
+    hipLaunchKernelGGL(actor_reinforce_cat_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, action, act_stats, returns,
+                       base0, value, weight, ret_scale, rows, N, A, -(1.f - rho) * grad_scale, dentropy, write, d_actor_out,
+                       (double*)ws);
+    BD_CHECK_LAUNCH("bd_actor_reinforce_cat");
+    return finish((double*)ws, nb, scalars, slot, (hipStream_t)stream, "bd_actor_reinforce_cat(final)");
 }
 
 int bd_actor_reinforce_cat(const float* action, const float* act_stats, const float* returns, const float* base0,
                            const float* value, const float* weight, int Hm, int N, int A, float rho, float grad_scale,
                            float dentropy, int write, float* d_actor_out, float* scalars, int slot, float* ws,
                            void* stream) {
-    BD_REQUIRE(action && act_stats && returns && base0 && (value || Hm == 1) && d_actor_out && scalars && ws,
-               "bd_actor_reinforce_cat: missing pointers");
-    BD_REQUIRE(Hm > 0 && N > 0 && A > 0 && A <= 64 && (size_t)Hm * N <= (size_t)INT32_MAX / 4 && slot >= 0,
-               "bd_actor_reinforce_cat: bad dims (Hm=%d N=%d A=%d slot=%d)", Hm, N, A, slot);
-    BD_REQUIRE(rho >= 0.f && rho <= 1.f, "bd_actor_reinforce_cat: gradient mixing %g outside [0, 1]", (double)rho);
-    const int rows = Hm * N;
-    const int nb = red_blocks((size_t)rows);
-    hipLaunchKernelGGL(actor_reinforce_cat_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, action, act_stats, returns,
-                       base0, value, weight, rows, N, A, -(1.f - rho) * grad_scale, dentropy, write, d_actor_out, (double*)ws);
-    BD_CHECK_LAUNCH("bd_actor_reinforce_cat");
-    return finish((double*)ws, nb, scalars, slot, (hipStream_t)stream, "bd_actor_reinforce_cat(final)");
+    return bd_actor_reinforce_cat_norm(action, act_stats, returns, base0, value, weight, nullptr, Hm, N, A, rho, grad_scale,
+                                       dentropy, write, d_actor_out, scalars, slot, ws, stream);
 }
 
 int bd_sumsq(const float* x, size_t n, float* scalars, int slot, float* ws, void* stream) {

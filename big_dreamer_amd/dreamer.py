@@ -19,8 +19,8 @@ from torch import Tensor
 from . import _cabi as cabi
 from .collect import check_collect_envs
 from .config import ACTION_MODES
-from .engine import (DreamerEngine, check_action_distribution, check_cnn_activation, check_dense_activation,
-                     check_gradient_mixing)
+from .engine import (DEFAULT_HP, DreamerEngine, check_action_distribution, check_cnn_activation, check_dense_activation,
+                     check_gradient_mixing, check_return_normalization, RETURN_NORM_KEYS)
 from .memory import ExperienceReplay
 from .models import ActorModel, CnnImageEncoder, DenseModel, ObservationModel, TransitionModel, encoder_for
 from .synth import Dims
@@ -34,7 +34,8 @@ def _hp_from_params(params: Dict[str, Any]) -> Dict[str, float]:
         model_learning_rate=params["model_learning_rate"], actor_learning_rate=ac["actor_learning_rate"],
         value_learning_rate=ac["value_learning_rate"], adam_epsilon=params["adam_epsilon"],
         weight_decay=params["weight_decay"], entropy_weight=ac["entropy_weight"], polyak_avg=ac["polyak_avg"],
-        discount_weight=params.get("discount_weight", 5.0), gradient_mixing=ac.get("gradient_mixing", -1))
+        discount_weight=params.get("discount_weight", 5.0), gradient_mixing=ac.get("gradient_mixing", -1),
+        **{k: ac[k] for k in RETURN_NORM_KEYS if k in ac})
 
 
 class Dreamer:
@@ -49,6 +50,9 @@ class Dreamer:
         # -1: the reference's dynamics-backprop actor gradient; rho in [0, 1]: DreamerV2's REINFORCE / dynamics mix
         # (the reference raises for anything but -1, src/dreamer.py:336-339)
         check_gradient_mixing(params["ActorCritic"].get("gradient_mixing", -1))
+        # percentile return normalisation of the actor objective (DreamerV3); "none": the reference's objective
+        check_return_normalization(*(params["ActorCritic"].get(k, DEFAULT_HP[k]) for k in RETURN_NORM_KEYS),
+                                   algorithm=params.get("algorithm"))
         # the pixel conv stacks take ELU / ReLU / Tanh (no effect on state observations, as in the reference); the dense
         # chains and scans are ELU only, and say so instead of ignoring the key
         self.cnn_activation_function = check_cnn_activation(params.get("cnn_activation_function", "ELU"))
@@ -186,6 +190,8 @@ class Dreamer:
         d["value_optimizer"] = e.optimizer_state_dict("critic")
         d["run_state"] = {"format": 1, "noise": noise, "generators": capture_generators(self.device),
                           "extra": extra}
+        if e.hp["return_normalization"] != "none":      # (checkpoints of default runs stay what they were)
+            d["run_state"]["return_norm"] = e.return_norm_state()
         atomic_write(path, lambda fh: torch.save(d, fh))
 
     def load_run_state(self, path: str) -> Dict[str, Any]:
@@ -197,6 +203,8 @@ class Dreamer:
         from .checkpoint import read_run_state, restore_generators
         rs = read_run_state(path)
         self.engine.load_noise_state(rs["noise"])
+        if self.engine.hp["return_normalization"] != "none":     # a checkpoint without the key: the empty state
+            self.engine.load_return_norm_state(rs.get("return_norm") or dict(lo=0.0, hi=0.0, count=0.0, skipped=0.0))
         restore_generators(rs["generators"], self.device)
         return dict(rs["extra"])
 
@@ -219,6 +227,13 @@ class Dreamer:
         """Make every rank a bit-identical copy of rank `src` (weights, optimiser state, everything packed from them).
         A synchronous COLLECTIVE."""
         self.engine.sync_replicas(src)
+
+    def return_norm_state(self) -> Dict[str, float]:
+        """The running range of ``ActorCritic.return_normalization=percentile``: {"lo", "hi", "count", "skipped"}."""
+        return self.engine.return_norm_state()
+
+    def load_return_norm_state(self, state: Dict[str, float]) -> None:
+        self.engine.load_return_norm_state(state)
 
     def eval(self) -> None:      # no dropout / batch-norm anywhere on the path
         pass

@@ -13,6 +13,7 @@ become observe/imagine/MLP backward kernels + weight-gradient GEMMs).
 from __future__ import annotations
 
 import collections.abc
+import contextlib
 import ctypes as C
 import math
 import os
@@ -39,6 +40,7 @@ DEFAULT_HP = dict(
     model_learning_rate=2e-4, actor_learning_rate=4e-5, value_learning_rate=1e-4, adam_epsilon=1e-5,
     weight_decay=1e-6, entropy_weight=1e-5, polyak_avg=1.0, min_std_dev=0.1, discount_weight=5.0,
     gradient_mixing=-1,
+    return_normalization="none", return_norm_low=0.05, return_norm_high=0.95, return_norm_decay=0.99, return_norm_floor=1.0,
 )
 
 # actor constants (src/models.py:479-503)
@@ -50,7 +52,36 @@ ACT_MEAN_SCALE = 5.0
 SLOT_OBS, SLOT_REW, SLOT_KL, SLOT_RET, SLOT_ENT, SLOT_VAL, SLOT_GN_MODEL, SLOT_GN_ACTOR, SLOT_GN_CRITIC = range(9)
 SLOT_DISC, SLOT_WOBJ = 9, 10       # use_discount=True: Bernoulli loss sum (model phase); weighted actor objective sum
 SLOT_RF = 11                       # gradient_mixing in [0, 1): sum of w * log pi(a) * (R - b), the REINFORCE objective
+SLOT_RN = 12                       # return_normalization=percentile: the scale, low and high the step used (slots 12..14)
 N_SLOTS = 16
+
+RETURN_NORMALIZATIONS = ("none", "percentile")
+RETURN_NORM_KEYS = ("return_normalization", "return_norm_low", "return_norm_high", "return_norm_decay", "return_norm_floor")
+
+
+def check_return_normalization(mode="none", low=0.05, high=0.95, decay=0.99, floor=1.0, algorithm=None) -> tuple:
+    """ActorCritic.return_normalization and its four numbers ("Return normalisation"): "none" (the reference's
+    objective) or "percentile" -- the returns of the actor objective divided by max(floor, P_high - P_low) of the imagined
+    lambda-returns, smoothed with `decay`.  Quantiles 0 <= low < high <= 1, 0 <= decay < 1, floor > 0.  PlaNet
+    (`algorithm`) has no actor and refuses "percentile".  Returns the five values, the numbers as floats."""
+    if mode not in RETURN_NORMALIZATIONS:
+        raise ValueError(f"return_normalization must be one of {RETURN_NORMALIZATIONS}, got {mode!r}")
+    num = {}
+    for key, v in (("return_norm_low", low), ("return_norm_high", high), ("return_norm_decay", decay),
+                   ("return_norm_floor", floor)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{key} must be a finite number, got {v!r}")
+        num[key] = float(v)
+    low, high, decay, floor = num.values()
+    if not 0.0 <= low < high <= 1.0:
+        raise ValueError(f"return_norm_low / return_norm_high must satisfy 0 <= low < high <= 1, got {low!r}, {high!r}")
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"return_norm_decay must be in [0, 1), got {decay!r}")
+    if not 0.0 < floor <= 3.0e38:
+        raise ValueError(f"return_norm_floor must be a positive fp32 number, got {floor!r}")
+    if mode != "none" and algorithm == "planet":
+        raise ValueError("return_normalization=percentile: PlaNet has no actor objective to normalise")
+    return mode, low, high, decay, floor
 
 
 def check_gradient_mixing(value) -> float:
@@ -162,6 +193,33 @@ class LazyLogs(collections.abc.MutableMapping):
 
     def __repr__(self):
         return repr(dict(self.items()))
+
+
+class _ReturnNorm:
+    """Device side of the percentile return normalisation ("Return normalisation"), built only when it is on:
+    the running range `state` = (lo, hi, count, skipped) in fp64, and `range`, two rows of (scale, lo, hi) in fp32.  A step
+    reads row `cur` -- the range as it stood before the step -- and bd_return_range writes the other row for the next
+    step, so two steps in flight never share a row.  `ev` is the end of the latest bd_return_range."""
+
+    def __init__(self, eng: "DreamerEngine"):
+        hp = eng.hp
+        self.decay, self.floor = hp["return_norm_decay"], hp["return_norm_floor"]
+        self.q = (hp["return_norm_low"], hp["return_norm_high"])
+        self.state = torch.zeros(4, dtype=torch.float64, device=eng.dev)
+        self.range = torch.zeros(2, 4, dtype=torch.float32, device=eng.dev)
+        self.cur = 0
+        self.ev: Optional[torch.cuda.Event] = None
+        self.load(dict(lo=0.0, hi=0.0, count=0.0, skipped=0.0))
+
+    def ranks(self, M: int) -> Tuple[int, int]:
+        """k_q = floor(q (M - 1)), in Python floats."""
+        return tuple(int(math.floor(q * (M - 1))) for q in self.q)
+
+    def load(self, d: dict) -> None:
+        lo, hi = float(d["lo"]), float(d["hi"])
+        self.state.copy_(torch.tensor([lo, hi, float(d["count"]), float(d["skipped"])], dtype=torch.float64))
+        row = torch.tensor([max(self.floor, hi - lo), lo, hi, 0.0], dtype=torch.float64).to(torch.float32)
+        self.range.copy_(row.expand(2, 4))
 
 
 class _Diagnostics:
@@ -314,6 +372,7 @@ class DreamerEngine:
         if hp:
             self.hp.update({k: v for k, v in hp.items() if k in self.hp})
         self.hp["gradient_mixing"] = check_gradient_mixing(self.hp["gradient_mixing"])
+        self.hp.update(zip(RETURN_NORM_KEYS, check_return_normalization(*(self.hp[k] for k in RETURN_NORM_KEYS))))
         self.dev = torch.device(device)
         assert self.dev.type == "cuda", "the HIP path needs a GPU (there is no CPU fallback)"
         self.world_size = world_size
@@ -358,6 +417,8 @@ class DreamerEngine:
         if params is not None:
             self.load_params(params)
         self.scalars = torch.zeros(N_SLOTS, dtype=torch.float32, device=self.dev)
+        # percentile return normalisation: nothing is allocated, launched or logged while it is "none"
+        self._rn = _ReturnNorm(self) if self.hp["return_normalization"] == "percentile" else None
         self.red_ws = torch.zeros(int(lib.bd_reduce_ws_floats()), dtype=torch.float32, device=self.dev)
         self._wgrad_ws = torch.zeros(1, dtype=torch.float32, device=self.dev)
         self._wgrad_ws_side = torch.zeros(1, dtype=torch.float32, device=self.dev)
@@ -814,7 +875,7 @@ class DreamerEngine:
             rec.events[row].synchronize()
         h = rec.host.numpy()
         s = h[0, :N_SLOTS].copy()
-        for slot in (SLOT_RET, SLOT_ENT, SLOT_GN_ACTOR, SLOT_WOBJ, SLOT_RF):
+        for slot in (SLOT_RET, SLOT_ENT, SLOT_GN_ACTOR, SLOT_WOBJ, SLOT_RF, SLOT_RN, SLOT_RN + 1, SLOT_RN + 2):
             s[slot] = h[1, slot]
         for slot in (SLOT_VAL, SLOT_GN_CRITIC):
             s[slot] = h[2, slot]
@@ -960,7 +1021,39 @@ class DreamerEngine:
                     self._opt_over.pop(g, None)
         for g in ("model", "actor", "critic", "critic_target"):
             self.pack(g)
+        if self._rn is not None and self.world_size > 1:      # each rank's own shard's range until now
+            self._rn_join()
+            st = self.dp.broadcast_(self._rn.state.clone(), src).cpu().tolist()
+            self._rn.load(dict(zip(("lo", "hi", "count", "skipped"), st)))
         torch.cuda.current_stream().synchronize()
+
+    # ------------------------------------------------------------------------------------------ return normalisation
+    def return_norm_state(self) -> dict:
+        """The running range of the percentile return normalisation as plain floats: {"lo", "hi", "count", "skipped"}
+        (all zero on a fresh engine, and always with return_normalization="none").  Orders the pipeline streams before
+        the read (join()) and synchronises; no collective."""
+        if self._rn is None:
+            return dict(lo=0.0, hi=0.0, count=0.0, skipped=0.0)
+        self._rn_join()
+        return dict(zip(("lo", "hi", "count", "skipped"), self._rn.state.cpu().tolist()))
+
+    def _rn_join(self) -> None:
+        """join(), and the latest bd_return_range wherever it was queued."""
+        self.join()
+        if self._rn.ev is not None:
+            torch.cuda.current_stream().wait_event(self._rn.ev)
+
+    def load_return_norm_state(self, d: dict) -> None:
+        """Set what return_norm_state returned; the next step's scale is max(floor, hi - lo) of it."""
+        if self._rn is None:
+            raise ValueError("load_return_norm_state: return_normalization is 'none'")
+        lo, hi, count, skipped = (float(d[k]) for k in ("lo", "hi", "count", "skipped"))
+        if not (math.isfinite(lo) and math.isfinite(hi) and count >= 0 and skipped >= 0):
+            raise ValueError(f"load_return_norm_state: not a range state: {d!r}")
+        self._rn_join()
+        self._rn.load(dict(lo=lo, hi=hi, count=count, skipped=skipped))
+        self._rn.ev = torch.cuda.Event()
+        self._rn.ev.record(torch.cuda.current_stream())
 
     def _replica_check_due(self) -> bool:
         """Is this train step one that issues the periodic check?  If so, first read the verdicts train_step has not read
@@ -2170,6 +2263,12 @@ class DreamerEngine:
         if s.fused:
             s.r_out, s.v_out = self.buf("ir_out", Mi, 1), self.buf("iv_out", Mi, 1)
         s.returns = self.buf(ptag + "returns", Mi)
+        # percentile return normalisation: the step divides by the range as it stood before it (row `cur`), and its own
+        # returns update the other row for the next step
+        rn = s.rn = self._rn
+        if rn is not None:
+            s.rn_read, s.rn_write = rn.range[rn.cur], rn.range[rn.cur ^ 1]
+            rn.cur ^= 1
         s.d_apre, s.d_aout = self.buf("d_actor_pre", DENSE_LAYERS, Mi, d.Hd), self.buf("d_actor_out", Mi, d.actor_out)
         return s
 
@@ -2190,6 +2289,17 @@ class DreamerEngine:
         cabi.check(lib.bd_lambda_return_backward(ptr(s.dret), s.dconst, s.Hm, s.N, self.hp["discount"], self.hp["disclam"],
                                                  ptr(s.d_r), ptr(s.d_v), s.st))
 
+    def _return_seed(self, s) -> None:
+        """Return normalisation: d returns = dconst / scale (times the discount weights) for _returns_backward, filled on
+        the device behind the previous step's bd_return_range, and the scale and range the step uses onto the scalar
+        board.  Without a dynamics term (gradient_mixing = 0) only the board is written."""
+        if s.rn.ev is not None:
+            s.cur.wait_event(s.rn.ev)
+        if s.dyn:
+            s.dret = self.buf("dret_w", s.Mi)
+        cabi.check(lib.bd_return_seed(ptr(s.rn_read), s.dconst, ptr(s.wts), s.Mi if s.dyn else 0, ptr(s.dret), s.sc, SLOT_RN,
+                                      s.st))
+
     def _heads_rows(self, s, t0: int, t1: int, x) -> None:
         """The fused heads over the rows of steps [t0, t1) of the imagined features x (imagine()'s after_chunk)."""
         r = slice(t0 * s.N, t1 * s.N)
@@ -2201,6 +2311,8 @@ class DreamerEngine:
         input gradients (difeat).  Chunked: d returns first, one scan launch per chunk with the heads of every chunk but
         the last on the overlap stream underneath the next chunk.  Separate heads: their backward follows later."""
         d, hp, Hm, N, Mi, F = self.d, self.hp, s.Hm, s.N, s.Mi, s.F
+        if s.rn is not None and not d.use_discount:     # the seed needs only last step's range: before the scan, chunked or not
+            self._return_seed(s)
         if s.chunked:
             self._returns_backward(s)
         s.ifeat, s.ent, s.act = self.imagine(
@@ -2218,7 +2330,9 @@ class DreamerEngine:
             arr[:, 0] = 1.0
             s.wts = self.buf(s.ptag + "disc_w", Mi)
             s.wts.view(Hm, N).copy_(torch.cumprod(arr, 0))
-            if s.dyn:
+            if s.rn is not None:
+                self._return_seed(s)
+            elif s.dyn:
                 s.dret = self.buf("dret_w", Mi)
                 torch.mul(s.wts, s.dconst, out=s.dret)
         if s.chunked:
@@ -2248,10 +2362,11 @@ class DreamerEngine:
         cabi.check(lib.bd_sum(ptr(ent), Mi, sc, SLOT_ENT, ws, st))
         if wts is not None:
             ew_ = hp["entropy_weight"] if hp["entropy_weight"] != -1 else 0.0
+            ret_n = returns if s.rn is None else returns / s.rn_read[0]        # the objective's (normalised) returns
             if mix is None:
-                self.scalars[SLOT_WOBJ] = (wts * (returns + ew_ * ent)).sum()
+                self.scalars[SLOT_WOBJ] = (wts * (ret_n + ew_ * ent)).sum()
             else:       # the REINFORCE part of the objective joins in _logs_from (SLOT_RF)
-                self.scalars[SLOT_WOBJ] = (wts * (mix * returns + ew_ * ent)).sum()
+                self.scalars[SLOT_WOBJ] = (wts * (mix * ret_n + ew_ * ent)).sum()
         if self._diag_now:
             dg = self._diag
             dg.moments("actor", "mom_bh", [(s.r_out, None), (s.v_out, None), (returns, None)]
@@ -2261,6 +2376,26 @@ class DreamerEngine:
         if s.par is not None:
             s.ev_ret = torch.cuda.Event()
             s.ev_ret.record(torch.cuda.current_stream())
+        if s.rn is not None:
+            self._return_range(s)
+
+    def _return_range(self, s) -> None:
+        """Return normalisation: the step's returns update the running range and leave the next step's scale (one
+        launch, no host read).  Nothing in this step waits for it, and the next step's _return_seed waits for its end.
+        Pipelined it stays off the behaviour chain: with state observations on the decoder-wgrad stream, which is idle
+        there (measured against the critic's stream at configs[4]'s latents: 0.14 instead of 0.22-0.30 ms per step,
+        configs[1] alike); with pixels that stream carries the NEXT step's decoder weight gradients, which must not queue
+        behind this step's returns, so the launch goes in front of the critic on its stream (no cost that shows)."""
+        rn = s.rn
+        k_lo, k_hi = rn.ranks(s.Mi)
+        side = (self._side if self.pixel else self._s_early) if s.par is not None else None
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+            if side is not None:
+                side.wait_event(s.ev_ret)
+            cabi.check(lib.bd_return_range(ptr(s.returns), s.Mi, k_lo, k_hi, rn.decay, rn.floor, rn.state.data_ptr(),
+                                           ptr(s.rn_write), cabi.stream()))
+            rn.ev = torch.cuda.Event()
+            rn.ev.record(torch.cuda.current_stream())
 
     def _critic_handoff(self, s) -> None:
         """Pipelined: the critic update on its own stream, behind the returns; its end is kept per step parity."""
@@ -2313,11 +2448,13 @@ class DreamerEngine:
         tail = (ptr(s.wts), s.Hm, s.N, d.A, s.mix, s.inv_mi, s.dentropy, int(not s.dyn), ptr(s.d_aout), s.sc, SLOT_RF, s.ws, s.st)
         with self.span("actor_reinforce"):
             b0, _, _ = self.dense_forward("critic_target", "tgt", "ib0", s.feat, s.F, s.N, 1, sidx=s.start_sidx)
-            if d.discrete_actions:
-                cabi.check(lib.bd_actor_reinforce_cat(ptr(s.act), ptr(stats), ptr(s.returns), ptr(b0), ptr(s.v_out), *tail))
+            head = ((ptr(s.act),) if d.discrete_actions else (ptr(noise["action"]), ptr(s.act_us))) + (
+                ptr(stats), ptr(s.returns), ptr(b0), ptr(s.v_out))
+            if s.rn is not None:        # the advantage term over the step's return scale (the entropy term is not divided)
+                fn = lib.bd_actor_reinforce_cat_norm if d.discrete_actions else lib.bd_actor_reinforce_norm
+                cabi.check(fn(*head, tail[0], ptr(s.rn_read), *tail[1:]))
             else:
-                cabi.check(lib.bd_actor_reinforce(ptr(noise["action"]), ptr(s.act_us), ptr(stats), ptr(s.returns), ptr(b0),
-                                                  ptr(s.v_out), *tail))
+                cabi.check((lib.bd_actor_reinforce_cat if d.discrete_actions else lib.bd_actor_reinforce)(*head, *tail))
 
     def _actor_rows(self, s) -> None:
         """The actor's hidden dgrad chain over all Hm x N rows, from d_actor_out to d_actor_pre."""
@@ -2433,16 +2570,18 @@ class DreamerEngine:
         ew = f32(hp["entropy_weight"]) if hp["entropy_weight"] != -1 else f32(0)
         model_loss = obs + rew + kl * f32(hp["kl_loss_weight"])
         mix = self._mix
+        # return normalisation: the return terms over the scale the step used; the entropy term is not divided
+        scale = s[SLOT_RN] if self._rn is not None and s[SLOT_RN] > 0 else f32(1)      # (0: no behaviour phase has run)
         if mix is None:
-            objective = s[SLOT_RET] + ew * s[SLOT_ENT]
+            objective = s[SLOT_RET] / scale + ew * s[SLOT_ENT]
         else:           # w (rho R + (1 - rho) log pi(a) sg(R - b) + eta H), summed ("Mixed actor gradient")
-            objective = f32(mix) * s[SLOT_RET] + f32(1 - mix) * s[SLOT_RF] + ew * s[SLOT_ENT]
+            objective = (f32(mix) * s[SLOT_RET] + f32(1 - mix) * s[SLOT_RF]) / scale + ew * s[SLOT_ENT]
         out = {}
         if self.d.use_discount:         # src/dreamer.py:287-290, 346-352
             disc = s[SLOT_DISC] / N
             model_loss = model_loss + disc * f32(hp["discount_weight"])
             out["discount_loss"] = float(disc)
-            objective = s[SLOT_WOBJ] if mix is None else s[SLOT_WOBJ] + f32(1 - mix) * s[SLOT_RF]
+            objective = s[SLOT_WOBJ] if mix is None else s[SLOT_WOBJ] + f32(1 - mix) * s[SLOT_RF] / scale
         out.update({
             "observation_loss": float(obs), "reward_loss": float(rew), "kl_loss": float(kl),
             "model_loss": float(model_loss),
@@ -2452,4 +2591,6 @@ class DreamerEngine:
             "grad_norm_model": float(math.sqrt(s[SLOT_GN_MODEL])), "grad_norm_actor": float(math.sqrt(s[SLOT_GN_ACTOR])),
             "grad_norm_critic": float(math.sqrt(s[SLOT_GN_CRITIC])),
         })
+        if self._rn is not None:
+            out.update(return_scale=float(s[SLOT_RN]), return_p_low=float(s[SLOT_RN + 1]), return_p_high=float(s[SLOT_RN + 2]))
         return out

@@ -22,6 +22,8 @@ class Planet(Dreamer):
     def __init__(self, params: Dict[str, Any], env, **kw):
         if params.get("action_distribution", "Gaussian") == "Categorical":
             raise ValueError("action_distribution=Categorical: PlaNet's CEM planner searches a continuous action space")
+        if params["ActorCritic"].get("return_normalization", "none") != "none":
+            raise ValueError("return_normalization=percentile: PlaNet has no actor objective to normalise")
         p = dict(params)
         p["kl_balance"] = -1           # Planet._kl_loss ignores kl_balance: max(KL.sum(2), free_nats).mean()
         super().__init__(p, env, **kw)

@@ -530,6 +530,17 @@ int bd_actor_reinforce_cat(const float* action, const float* act_stats, const fl
                            const float* value, const float* weight, int Hm, int N, int A, float rho, float grad_scale,
                            float dentropy, int write, float* d_actor_out, float* scalars, int slot, float* ws,
                            void* stream);
+/* Both with the advantage term divided by a return scale held on the device (return normalisation, below): c =
+ * -(1 - rho) * (grad_scale / ret_scale[0]) * w * adv.  The entropy term (dentropy) and scalars[slot] are not divided.
+ * ret_scale = NULL is the entry point above. */
+int bd_actor_reinforce_norm(const float* eps_action, const float* act_us, const float* act_stats, const float* returns,
+                            const float* base0, const float* value, const float* weight, const float* ret_scale, int Hm,
+                            int N, int A, float rho, float grad_scale, float dentropy, int write, float* d_actor_out,
+                            float* scalars, int slot, float* ws, void* stream);
+int bd_actor_reinforce_cat_norm(const float* action, const float* act_stats, const float* returns, const float* base0,
+                                const float* value, const float* weight, const float* ret_scale, int Hm, int N, int A,
+                                float rho, float grad_scale, float dentropy, int write, float* d_actor_out, float* scalars,
+                                int slot, float* ws, void* stream);
 
 /* ---- perf-mode noise: Philox4x32-10, counter-based (csrc/bd_rng.h).  key = seed, counter = (index of a group of four
  * values, stream id, step): any element of any stream of any step is computable on its own.  The parity path never uses
@@ -1078,6 +1089,24 @@ int bd_latent_stats_categorical(const float* post_logits, const float* prior_log
  * empty segments give 0. */
 #define BD_SEGMENTS_MAX 32
 int bd_segment_sumsq(const float* x, int n_seg, const size_t* offsets, double* out, float* ws, void* stream);
+
+/* ---- percentile return normalisation (csrc/retnorm.hip; ActorCritic.return_normalization = percentile) -----------
+ * bd_return_range: ONE launch.  With the M fp32 `returns` sorted ascending (-0.0 and +0.0 are one value), p_lo and p_hi
+ * are elements k_lo and k_hi (0 <= k_lo <= k_hi < M), selected exactly by radix selection with integer counts: the same
+ * bits whatever the schedule.  state = four doubles on the device, {lo, hi, count, skipped}:
+ *     count == 0:  lo = p_lo, hi = p_hi;      else  lo = decay lo + (1 - decay) p_lo,  hi likewise   (fp64, each product
+ *     and the sum rounded once);  count += 1.
+ * If any return is NaN or +-Inf nothing changes but skipped += 1.  Then, from the state as it now stands,
+ *     range[0] = (float) max(floor, hi - lo)   (the scale of the NEXT step),   range[1] = (float) lo,   range[2] = (float) hi.
+ * 0 <= decay < 1, floor > 0.  returns / range need 4-byte alignment, state 8-byte.  One workgroup, no global workspace.
+ * Asynchronous on `stream`; never allocates, never synchronises; bad arguments are refused before anything is enqueued. */
+int bd_return_range(const float* returns, int M, int k_lo, int k_hi, double decay, double floor_, double* state,
+                    float* range, void* stream);
+/* bd_return_seed: the gradient seed of the normalised dynamics term, dreturns[i] = (dret_const / range[0]) * weight[i]
+ * (weight = NULL: 1), i < n, for bd_lambda_return_backward; and, scalars != NULL, scalars[slot .. slot + 2] = range[0 .. 2]
+ * (the scale and the range the step uses, for its logs).  n = 0 (dreturns may be NULL) only copies. */
+int bd_return_seed(const float* range, float dret_const, const float* weight, size_t n, float* dreturns, float* scalars,
+                   int slot, void* stream);
 
 #ifdef __cplusplus
 }

@@ -155,6 +155,8 @@ def my_app(argv):
     random.seed(params["seed"] + rank)
     if params["algorithm"] not in ("planet", "dreamer", "dreamerV2"):     # as src/main.py:73-81
         raise NotImplementedError(f'algorithm {params["algorithm"]} is not yet implemented.')
+    from big_dreamer_amd.engine import RETURN_NORM_KEYS, check_return_normalization
+    check_return_normalization(*(params["ActorCritic"][k] for k in RETURN_NORM_KEYS), algorithm=params["algorithm"])
     from big_dreamer_amd import checkpoint as ck
     for key in ("models", "experience_replay"):                    # multi-GPU: every rank loads its own ..._rank<r> file
         params[key] = ck.for_rank(params[key], rank, world)
