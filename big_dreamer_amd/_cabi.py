@@ -353,6 +353,9 @@ _SIGS = {
     "bd_return_seed": (I32, [P, F32, P, C.c_size_t, P, P, I32, P]),
     "bd_actor_reinforce_norm": (I32, [P, P, P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, I32, P, P, I32, P, P]),
     "bd_actor_reinforce_cat_norm": (I32, [P, P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, I32, P, P, I32, P, P]),
+    "bd_twohot_decode": (I32, [P, I32, I32, I32, F32, P, P, P]),
+    "bd_twohot_decode_backward": (I32, [P, I32, P, I32, I32, F32, P, I32, P]),
+    "bd_twohot_nll": (I32, [P, I32, P, P, I32, I32, F32, F32, P, I32, P, P, P]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

@@ -20,7 +20,8 @@ from . import _cabi as cabi
 from .collect import check_collect_envs
 from .config import ACTION_MODES
 from .engine import (DEFAULT_HP, DreamerEngine, check_action_distribution, check_cnn_activation, check_dense_activation,
-                     check_gradient_mixing, check_return_normalization, RETURN_NORM_KEYS)
+                     check_critic_head, check_gradient_mixing, check_return_normalization, CRITIC_HEAD_DEFAULTS,
+                     CRITIC_HEAD_KEYS, RETURN_NORM_KEYS)
 from .memory import ExperienceReplay
 from .models import ActorModel, CnnImageEncoder, DenseModel, ObservationModel, TransitionModel, encoder_for
 from .synth import Dims
@@ -53,6 +54,9 @@ class Dreamer:
         # percentile return normalisation of the actor objective (DreamerV3); "none": the reference's objective
         check_return_normalization(*(params["ActorCritic"].get(k, DEFAULT_HP[k]) for k in RETURN_NORM_KEYS),
                                    algorithm=params.get("algorithm"))
+        # "normal": the reference's width-1 critic; "twohot" (DreamerV3): K logits over symlog bins ("Two-hot critic")
+        self.critic_head, self.critic_bins, self.critic_bin_range = check_critic_head(
+            *(params["ActorCritic"].get(k, CRITIC_HEAD_DEFAULTS[k]) for k in CRITIC_HEAD_KEYS), algorithm=params.get("algorithm"))
         # the pixel conv stacks take ELU / ReLU / Tanh (no effect on state observations, as in the reference); the dense
         # chains and scans are ELU only, and say so instead of ignoring the key
         self.cnn_activation_function = check_cnn_activation(params.get("cnn_activation_function", "ELU"))
@@ -86,7 +90,8 @@ class Dreamer:
                          S=self.state_size, Hd=self.hidden_size, E=self.embedding_size, A=self.action_size,
                          O=obs_size, pixel=self.pixel_observation, cat_D=cat_D, cat_C=cat_C,
                          use_discount=self.use_discount, discrete_actions=self.action_distribution == "Categorical",
-                         cnn_act=self.cnn_activation_function)
+                         cnn_act=self.cnn_activation_function, critic_head=self.critic_head, critic_bins=self.critic_bins,
+                         critic_bin_range=self.critic_bin_range)
         self.engine = DreamerEngine(self.dims, _hp_from_params(params), self.device, world_size=world_size,
                                     process_group=process_group,
                                     replica_check_interval=params.get("replica_check_interval", 0),
@@ -106,7 +111,7 @@ class Dreamer:
             ("encoder", (lambda: _ref_init_cnn(E)) if px else
              (lambda: _ref_init_dense(env.observation_size, self.hidden_size, self.embedding_size))),
             ("actor", lambda: _ref_init_dense(feat, self.hidden_size, self.dims.actor_out)),
-            ("critic", lambda: _ref_init_dense(feat, self.hidden_size, 1)),
+            ("critic", lambda: _ref_init_dense(feat, self.hidden_size, self.dims.critic_out)),
         ) + ((("discount_model", lambda: _ref_init_dense(feat, self.hidden_size, 1)),) if self.use_discount else ()):
             init[mod] = {k: v.detach().numpy() for k, v in build().state_dict().items()}
         init["critic_target"] = init["critic"]                # copy.deepcopy(self.critic), src/dreamer.py:50
@@ -128,8 +133,9 @@ class Dreamer:
         self.reward_model = DenseModel(feat, self.hidden_size, 1, engine=e, module="reward_model", prefix="rew")
         self.actor = ActorModel(self.belief_size, self.state_size, self.hidden_size, self.action_size,
                                 action_distribution=self.action_distribution, engine=e)
-        self.critic = DenseModel(feat, self.hidden_size, 1, engine=e, module="critic", prefix="cri")
-        self.critic_target = DenseModel(feat, self.hidden_size, 1, engine=e, module="critic_target", prefix="tgt")
+        self.critic = DenseModel(feat, self.hidden_size, self.dims.critic_out, engine=e, module="critic", prefix="cri")
+        self.critic_target = DenseModel(feat, self.hidden_size, self.dims.critic_out, engine=e, module="critic_target",
+                                        prefix="tgt")
         if self.use_discount:       # src/dreamer.py:80-85
             self.discount_model = DenseModel(feat, self.hidden_size, 1, engine=e, module="discount_model", prefix="dsc")
         self.buffer = ExperienceReplay(params["experience_size"], env.action_size, params["bit_depth"], px,
@@ -146,6 +152,7 @@ class Dreamer:
         path = params.get("models", "")
         if path and os.path.exists(path):
             d = torch.load(path, map_location="cpu", weights_only=True)
+            self._check_checkpoint_head(d)          # before anything is copied
             for key in ("transition_model", "observation_model", "reward_model", "encoder"):
                 getattr(self, key).load_state_dict(d[key])
             if "model_optimizer" in d:
@@ -161,6 +168,22 @@ class Dreamer:
             for key, group in (("actor_optimizer", "actor"), ("value_optimizer", "critic")):
                 if key in d:
                     self.engine.load_optimizer_state_dict(group, d[key])
+
+    def _critic_head_record(self) -> Dict[str, Any]:
+        if self.critic_head == "normal":
+            return {"kind": "normal"}
+        return {"kind": self.critic_head, "bins": int(self.critic_bins), "range": float(self.critic_bin_range)}
+
+    def _check_checkpoint_head(self, d: Dict[str, Any]) -> None:
+        """ValueError unless the checkpoint's critic head is this agent's in kind, K and Z (a checkpoint without the record
+        holds the width-1 critic; one without a critic at all -- the reference's files -- has nothing to compare)."""
+        if "critic" not in d and "critic_target" not in d:
+            return
+        theirs = (d.get("run_state") or {}).get("critic_head") or {"kind": "normal"}
+        mine = self._critic_head_record()
+        if dict(theirs) != mine:
+            raise ValueError(f"checkpoint critic head {dict(theirs)} does not match the agent's {mine} "
+                             "(ActorCritic.critic_head / critic_bins / critic_bin_range)")
 
     def save(self, path: str, extra: Optional[Dict[str, Any]] = None) -> None:
         """Checkpoint in the layout ``Planet.load`` reads (src/planet.py:109-114: transition_model, observation_model,
@@ -192,6 +215,8 @@ class Dreamer:
                           "extra": extra}
         if e.hp["return_normalization"] != "none":      # (checkpoints of default runs stay what they were)
             d["run_state"]["return_norm"] = e.return_norm_state()
+        if self.critic_head != "normal":
+            d["run_state"]["critic_head"] = self._critic_head_record()
         atomic_write(path, lambda fh: torch.save(d, fh))
 
     def load_run_state(self, path: str) -> Dict[str, Any]:
@@ -284,6 +309,19 @@ class Dreamer:
 
     def update_critic(self) -> None:
         self.engine.update_critic()
+
+    @torch.no_grad()
+    def value(self, belief: Tensor, state: Tensor, target: bool = False) -> Tensor:
+        """The critic's (target=True: the target critic's) value of (belief, state), (..., 1): what the module returns
+        with critic_head="normal", the decoded logits -- symexp of the softmax mean over the bins, bd_twohot_decode --
+        with "twohot", where ``critic`` / ``critic_target`` themselves return the logits (..., K)."""
+        out = (self.critic_target if target else self.critic)(belief, state)
+        if self.critic_head == "normal":
+            return out
+        lead, K = out.shape[:-1], self.critic_bins
+        logits = out.reshape(-1, K).contiguous()
+        val = torch.empty(logits.shape[0], dtype=torch.float32, device=logits.device)
+        return self.engine.twohot_decode(logits, logits.shape[0], val).view(*lead, 1)
 
     # ---------------------------------------------------------------------------------------- acting / imagination
     @torch.no_grad()

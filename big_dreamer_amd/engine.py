@@ -84,6 +84,31 @@ def check_return_normalization(mode="none", low=0.05, high=0.95, decay=0.99, flo
     return mode, low, high, decay, floor
 
 
+CRITIC_HEAD_KEYS = ("critic_head", "critic_bins", "critic_bin_range")
+CRITIC_HEAD_DEFAULTS = dict(critic_head="normal", critic_bins=255, critic_bin_range=20.0)
+CRITIC_BINS_MAX = 1024
+CRITIC_BIN_RANGE_MAX = 80.0        # expm1 of more overflows fp32
+
+
+def check_critic_head(head="normal", bins=255, bin_range=20.0, algorithm=None) -> tuple:
+    """ActorCritic.critic_head and its two numbers ("Two-hot critic"): "normal" (the reference's width-1 critic
+    under a Normal(v, 1) loss) or "twohot" -- `bins` logits over bins uniform in symlog space on [-bin_range, bin_range],
+    decoded as symexp of the softmax mean, trained with the cross-entropy against the two-hot encoding of symlog(return).
+    bins: integer K, 2 <= K <= 1024; bin_range: Z, 0 < Z <= 80.  PlaNet (`algorithm`) has no critic and refuses "twohot".
+    Returns (head, int K, float Z)."""
+    from .synth import CRITIC_HEADS
+    if head not in CRITIC_HEADS:
+        raise ValueError(f"critic_head must be one of {CRITIC_HEADS}, got {head!r}")
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= CRITIC_BINS_MAX:
+        raise ValueError(f"critic_bins must be an integer in [2, {CRITIC_BINS_MAX}], got {bins!r}")
+    if (isinstance(bin_range, bool) or not isinstance(bin_range, (int, float)) or not math.isfinite(bin_range)
+            or not 0.0 < bin_range <= CRITIC_BIN_RANGE_MAX):
+        raise ValueError(f"critic_bin_range must be a number in (0, {CRITIC_BIN_RANGE_MAX:g}], got {bin_range!r}")
+    if head != "normal" and algorithm == "planet":
+        raise ValueError("critic_head=twohot: PlaNet has no critic")
+    return head, int(bins), float(bin_range)
+
+
 def check_gradient_mixing(value) -> float:
     """ActorCritic.gradient_mixing: -1 (the reference's objective, backpropagation through the learned dynamics) or
     rho in [0, 1], DreamerV2's ``actor_grad_mix`` -- the weight of the dynamics term against REINFORCE (1 = -1)."""
@@ -373,6 +398,7 @@ class DreamerEngine:
             self.hp.update({k: v for k, v in hp.items() if k in self.hp})
         self.hp["gradient_mixing"] = check_gradient_mixing(self.hp["gradient_mixing"])
         self.hp.update(zip(RETURN_NORM_KEYS, check_return_normalization(*(self.hp[k] for k in RETURN_NORM_KEYS))))
+        check_critic_head(dims.critic_head, dims.critic_bins, dims.critic_bin_range)
         self.dev = torch.device(device)
         assert self.dev.type == "cuda", "the HIP path needs a GPU (there is no CPU fallback)"
         self.world_size = world_size
@@ -430,8 +456,8 @@ class DreamerEngine:
         self._side = _engine_stream(self.dev, "side", int(os.environ.get("BD_SIDE_PRIO", "0")))    # critic (pipelined)
         # Frozen imagined heads (reward_model, critic_target) forward + dgrad in one launch (csrc/heads.hip) on the
         # dynamics-backprop path with Gaussian latents; BD_HEADS_FUSED=0 keeps the separate forward / backward chains
-        # (mlp.hip) for the A/B.
-        self.heads_fused = (os.environ.get("BD_HEADS_FUSED", "1") != "0" and not self.d.categorical
+        # (mlp.hip) for the A/B.  The fused kernel is a width-1 kernel: the two-hot critic takes the separate chains.
+        self.heads_fused = (os.environ.get("BD_HEADS_FUSED", "1") != "0" and not self.d.categorical and not self.d.twohot
                             and bool(lib.bd_img_heads_supported(self.d.Be + self.d.S, self.d.Hd)))
         # pixel mode: decoder weight gradients under the observe scan
         self._s_early = _engine_stream(self.dev, "early", int(os.environ.get("BD_EARLY_PRIO", "0")))
@@ -1381,6 +1407,22 @@ class DreamerEngine:
             w_in, gather = d.Be, (sidx, self._plain[f"{prefix}0sT"][0], d.cat_D, d.cat_C)
         self.mlp_forward(M, x, ldx, w_in, fl, acts + [None], out, out_width, gather=gather)
         return out, acts, layers
+
+    def twohot_decode(self, logits: torch.Tensor, M: int, out: torch.Tensor) -> torch.Tensor:
+        """Two-hot critic: out[M] = symexp(softmax(logits [M x K]) . bins) on the current stream (bd_twohot_decode)."""
+        d = self.d
+        cabi.check(lib.bd_twohot_decode(ptr(logits), d.critic_bins, M, d.critic_bins, d.critic_bin_range, ptr(out), None,
+                                        cabi.stream()))
+        return out
+
+    def _target_value(self, tag: str, x, M: int, sidx=None):
+        """critic_target over M rows of x = [h; s]: (values [M], saved activations, layers, head output).  The head
+        output is the value itself ("normal") or the K logits the values were decoded from ("twohot")."""
+        d = self.d
+        out, acts, layers = self.dense_forward("critic_target", "tgt", tag, x, d.Be + d.S, M, d.critic_out, sidx=sidx)
+        if not d.twohot:
+            return out, acts, layers, out
+        return self.twohot_decode(out, M, self.buf(f"{tag}_val", M)), acts, layers, out
 
     def _check_cat_start(self, state: torch.Tensor) -> None:
         """A dense start state [rows x S] handed to a kernel that carries class indices: all-zero or one-hot per factor."""
@@ -2344,14 +2386,22 @@ class DreamerEngine:
         else:
             with self.span("img_heads_fwd"):
                 s.r_out, s.r_acts, s.r_layers = self.dense_forward("reward_model", "rew", "ir", s.ifeat, F, Mi, 1, sidx=s.isidx)
-                s.v_out, s.v_acts, s.v_layers = self.dense_forward("critic_target", "tgt", "iv", s.ifeat, F, Mi, 1, sidx=s.isidx)
+                s.v_out, s.v_acts, s.v_layers, s.v_head = self._target_value("iv", s.ifeat, Mi, sidx=s.isidx)
 
     def _imagined_heads_backward(self, s) -> None:
-        """The separate heads: d returns, then the two dgrad chains into difeat."""
+        """The separate heads: d returns, then the two dgrad chains into difeat.  Two-hot critic: d values goes through
+        the decode backward into the K-wide chain of the frozen target."""
+        d = self.d
         self._returns_backward(s)
         with self.span("img_heads_bwd"):
             self.mlp_backward(s.Mi, s.d_r, 1, s.r_layers, s.r_acts + [None], None, din0=s.difeat, ld0=s.F, w0=s.F)
-            self.mlp_backward(s.Mi, s.d_v, 1, s.v_layers, s.v_acts + [None], None, din0=s.difeat, ld0=s.F, w0=s.F, accumulate=True)
+            d_v, K = s.d_v, 1
+            if d.twohot:
+                K = d.critic_bins
+                d_v = self.buf("d_iv_logits", s.Mi, K)
+                cabi.check(lib.bd_twohot_decode_backward(ptr(s.v_head), K, ptr(s.d_v), s.Mi, K, d.critic_bin_range, ptr(d_v), K,
+                                                         s.st))
+            self.mlp_backward(s.Mi, d_v, K, s.v_layers, s.v_acts + [None], None, din0=s.difeat, ld0=s.F, w0=s.F, accumulate=True)
 
     def _returns_and_sums(self, s) -> None:
         """Lambda-returns and the logged sums; pipelined, ev_ret marks them for the critic's stream."""
@@ -2447,7 +2497,7 @@ class DreamerEngine:
         d, noise, stats = self.d, s.noise, self._buf["sv_act_stats"]
         tail = (ptr(s.wts), s.Hm, s.N, d.A, s.mix, s.inv_mi, s.dentropy, int(not s.dyn), ptr(s.d_aout), s.sc, SLOT_RF, s.ws, s.st)
         with self.span("actor_reinforce"):
-            b0, _, _ = self.dense_forward("critic_target", "tgt", "ib0", s.feat, s.F, s.N, 1, sidx=s.start_sidx)
+            b0 = self._target_value("ib0", s.feat, s.N, sidx=s.start_sidx)[0]
             head = ((ptr(s.act),) if d.discrete_actions else (ptr(noise["action"]), ptr(s.act_us))) + (
                 ptr(stats), ptr(s.returns), ptr(b0), ptr(s.v_out))
             if s.rn is not None:        # the advantage term over the step's return scale (the entropy term is not divided)
@@ -2485,21 +2535,33 @@ class DreamerEngine:
         """Critic update (src/dreamer.py:370-391) on the current stream: forward on the detached imagined features,
         Normal(v, 1) NLL against the detached returns, dgrad chain, grouped weight gradients, clip + Adam, re-pack."""
         d, hp, ifeat, returns, Mi, F, wts = self.d, self.hp, s.ifeat, s.returns, s.Mi, s.F, s.wts
+        K = d.critic_out
         with self.span("critic_fwd_bwd"):
-            c_out, c_acts, c_layers = self.dense_forward("critic", "cri", "ic", ifeat, F, Mi, 1, sidx=s.isidx)
-            d_c = self.buf("d_ic_out", Mi, 1)
-            cabi.check(lib.bd_normal_nll(ptr(c_out), 1, ptr(returns), 1, Mi, 1, s.inv_mi, ptr(d_c), 1, s.sc, SLOT_VAL, ptr(red_ws),
-                                         cabi.stream()))
-            if s.diag:
-                self._diag.moments("critic", "mom_cr", [(c_out, None), (returns, c_out)])
-            if wts is not None:     # use_discount=True: -(discount * log_prob).mean() (src/dreamer.py:378-379)
-                d_c.view(Mi).mul_(wts)
-                diff = c_out.view(Mi) - returns
-                self.scalars[SLOT_VAL] = (wts * (0.5 * diff * diff + 0.9189385332046727)).sum()
+            c_out, c_acts, c_layers = self.dense_forward("critic", "cri", "ic", ifeat, F, Mi, K, sidx=s.isidx)
+            d_c = self.buf("d_ic_out", Mi, K)
+            if d.twohot:
+                # cross-entropy against the two-hot encoding of symlog(returns); use_discount: the cumulative discount
+                # weights are the row weights (src/dreamer.py:378-379).  The row losses are summed in bd_sum's fixed order.
+                row_loss = self.buf("ic_row_loss", Mi)
+                c_val = self.buf("ic_val", Mi) if s.diag else None
+                cabi.check(lib.bd_twohot_nll(ptr(c_out), K, ptr(returns), ptr(wts), Mi, K, d.critic_bin_range, s.inv_mi, ptr(d_c),
+                                             K, ptr(c_val), ptr(row_loss), cabi.stream()))
+                cabi.check(lib.bd_sum(ptr(row_loss), Mi, s.sc, SLOT_VAL, ptr(red_ws), cabi.stream()))
+                if s.diag:
+                    self._diag.moments("critic", "mom_cr", [(c_val, None), (returns, c_val)])
+            else:
+                cabi.check(lib.bd_normal_nll(ptr(c_out), 1, ptr(returns), 1, Mi, 1, s.inv_mi, ptr(d_c), 1, s.sc, SLOT_VAL,
+                                             ptr(red_ws), cabi.stream()))
+                if s.diag:
+                    self._diag.moments("critic", "mom_cr", [(c_out, None), (returns, c_out)])
+                if wts is not None:     # use_discount=True: -(discount * log_prob).mean() (src/dreamer.py:378-379)
+                    d_c.view(Mi).mul_(wts)
+                    diff = c_out.view(Mi) - returns
+                    self.scalars[SLOT_VAL] = (wts * (0.5 * diff * diff + 0.9189385332046727)).sum()
             c_dpre = [self.buf(f"ic_dpre{l}", Mi, d.Hd) for l in range(DENSE_LAYERS)] + [d_c]
-            self.mlp_backward(Mi, d_c, 1, c_layers, c_acts + [None], c_dpre[:-1] + [None])
+            self.mlp_backward(Mi, d_c, K, c_layers, c_acts + [None], c_dpre[:-1] + [None])
         wc = self._wbatch["critic"]
-        self._dense_wgrads(wc, "critic", Mi, c_dpre, ifeat, F, c_acts, [F] + [d.Hd] * DENSE_LAYERS + [1])
+        self._dense_wgrads(wc, "critic", Mi, c_dpre, ifeat, F, c_acts, [F] + [d.Hd] * DENSE_LAYERS + [K])
         with self.span("wgrad_critic"):
             wc.run()
         self._optimizer_step_or_defer("opt_critic", "critic", SLOT_GN_CRITIC, hp["value_learning_rate"], red_ws)

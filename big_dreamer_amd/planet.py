@@ -24,6 +24,8 @@ class Planet(Dreamer):
             raise ValueError("action_distribution=Categorical: PlaNet's CEM planner searches a continuous action space")
         if params["ActorCritic"].get("return_normalization", "none") != "none":
             raise ValueError("return_normalization=percentile: PlaNet has no actor objective to normalise")
+        if params["ActorCritic"].get("critic_head", "normal") != "normal":
+            raise ValueError("critic_head=twohot: PlaNet has no critic")
         p = dict(params)
         p["kl_balance"] = -1           # Planet._kl_loss ignores kl_balance: max(KL.sum(2), free_nats).mean()
         super().__init__(p, env, **kw)

@@ -18,6 +18,7 @@ import numpy as np
 
 
 CNN_ACTIVATIONS = ("ELU", "ReLU", "Tanh")     # torch.nn class names, as the reference resolves them (getattr(nn, name))
+CRITIC_HEADS = ("normal", "twohot")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -40,10 +41,15 @@ class Dims:
     use_discount: bool = False   # discount_model head + Bernoulli loss + discounted actor objective (src/dreamer.py:80-86,239-251,346-351)
     discrete_actions: bool = False   # action_distribution="Categorical": one-hot actions over A classes ("Discrete actions")
     cnn_act: str = "ELU"  # cnn_activation_function: activation of the pixel conv stacks, "ELU" | "ReLU" | "Tanh" (src/planet.py:186-192)
+    critic_head: str = "normal"     # ActorCritic.critic_head: "normal" (width 1, Normal(v, 1)) | "twohot" ("Two-hot critic")
+    critic_bins: int = 255          # twohot: K logits over bins uniform in symlog space
+    critic_bin_range: float = 20.0  # twohot: the bins span [-Z, Z] in symlog space
 
     def __post_init__(self):
         if self.cnn_act not in CNN_ACTIVATIONS:
             raise ValueError(f"cnn_activation_function must be one of {CNN_ACTIVATIONS}, got {self.cnn_act!r}")
+        if self.critic_head not in CRITIC_HEADS:
+            raise ValueError(f"critic_head must be one of {CRITIC_HEADS}, got {self.critic_head!r}")
         assert (self.cat_D == 0) == (self.cat_C == 0) and (self.cat_D == 0 or self.S == self.cat_D * self.cat_C), \
             "Categorical latents: state_size = discrete_latent_dimensions * discrete_latent_classes"
 
@@ -60,6 +66,15 @@ class Dims:
     def actor_out(self) -> int:
         """Output width of the actor: (mean, raw std) of a tanh-Normal, or the A logits of a Categorical."""
         return self.A if self.discrete_actions else 2 * self.A
+
+    @property
+    def twohot(self) -> bool:
+        return self.critic_head == "twohot"
+
+    @property
+    def critic_out(self) -> int:
+        """Output width of critic / critic_target: the value, or the K logits of the two-hot head."""
+        return self.critic_bins if self.twohot else 1
 
     @property
     def T(self) -> int:
@@ -152,7 +167,7 @@ def param_shapes(d: Dims) -> Dict[str, List[Tuple[str, Tuple[int, ...]]]]:
         "reward_model": strip(_mlp_shapes("x", [feat] + hid + [1])),
         "encoder": enc,
         "actor": strip(_mlp_shapes("x", [feat] + hid + [d.actor_out])),
-        "critic": strip(_mlp_shapes("x", [feat] + hid + [1])),
+        "critic": strip(_mlp_shapes("x", [feat] + hid + [d.critic_out])),
     }
     if d.use_discount:      # DenseModel(belief + state, hidden) (src/dreamer.py:80-85); joins the model optimiser last (:167-169)
         out["discount_model"] = strip(_mlp_shapes("x", [feat] + hid + [1]))

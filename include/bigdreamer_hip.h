@@ -1108,6 +1108,29 @@ int bd_return_range(const float* returns, int M, int k_lo, int k_hi, double deca
 int bd_return_seed(const float* range, float dret_const, const float* weight, size_t n, float* dreturns, float* scalars,
                    int slot, void* stream);
 
+/* ---- two-hot critic head in symlog space (csrc/twohot.hip; ActorCritic.critic_head = twohot) ---------------------
+ * A row holds K logits l_0 .. l_{K-1} (2 <= K <= 1024) over bins that are uniform in symlog space,
+ *     z_i = -Z + i delta,  delta = 2 Z / (K - 1),  Z = zmax in (0, 80]       (formed as (2 i - (K - 1)) Z / (K - 1), so
+ *     that z_i = -z_{K-1-i} exactly; computed in the kernel, never read),
+ * with symlog(y) = sign(y) log1p(|y|) and symexp(z) = sign(z) expm1(|z|).
+ * bd_twohot_decode:   p = softmax(l) (maximum subtracted),  m = sum_i p_i z_i,  value[r] = symexp(m),  mean[r] = m (mean
+ *     may be NULL).
+ * bd_twohot_decode_backward:   dlogits[r, i] = dvalue[r] exp(|m|) p_i (z_i - m)   (stored).
+ * bd_twohot_nll: target y = target[r], row weight w_r = weight[r] (weight NULL: 1):
+ *     t = clamp(symlog(y), -Z, Z),  u = (t + Z) / delta,  k = min(floor(u), K - 2),  w = u - k,  q_k = 1 - w,  q_{k+1} = w,
+ *     row_loss[r] = w_r (logsumexp(l) - (1 - w) l_k - w l_{k+1}),    dlogits[r, i] = grad_scale w_r (p_i - q_i)   (stored),
+ *     value[r] = symexp(m) of the same logits (value may be NULL).
+ *   The row L1 norm of dlogits is at most 2 grad_scale w_r whatever the target.  A NaN target gives a NaN row_loss.
+ * logits / dlogits are row-major with leading dimensions ld, ldd >= K; nothing beyond column K of a row or beyond row
+ * `rows` is written, every output element exactly once.  One wave per row, the sums of a row in a fixed order: the same
+ * bits on every launch.  4-byte alignment.  Asynchronous on `stream`; never allocate, never synchronise; bad arguments
+ * (NULLs, ld < K, K or zmax outside the ranges above, rows <= 0) are refused before anything is enqueued. */
+int bd_twohot_decode(const float* logits, int ld, int rows, int K, float zmax, float* value, float* mean, void* stream);
+int bd_twohot_decode_backward(const float* logits, int ld, const float* dvalue, int rows, int K, float zmax, float* dlogits,
+                              int ldd, void* stream);
+int bd_twohot_nll(const float* logits, int ld, const float* target, const float* weight, int rows, int K, float zmax,
+                  float grad_scale, float* dlogits, int ldd, float* value, float* row_loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,8 @@ def my_app(argv):
         raise NotImplementedError(f'algorithm {params["algorithm"]} is not yet implemented.')
     from big_dreamer_amd.engine import RETURN_NORM_KEYS, check_return_normalization
     check_return_normalization(*(params["ActorCritic"][k] for k in RETURN_NORM_KEYS), algorithm=params["algorithm"])
+    from big_dreamer_amd.engine import CRITIC_HEAD_KEYS, check_critic_head
+    check_critic_head(*(params["ActorCritic"][k] for k in CRITIC_HEAD_KEYS), algorithm=params["algorithm"])
     from big_dreamer_amd import checkpoint as ck
     for key in ("models", "experience_replay"):                    # multi-GPU: every rank loads its own ..._rank<r> file
         params[key] = ck.for_rank(params[key], rank, world)
