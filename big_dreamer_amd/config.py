@@ -2,10 +2,14 @@
 overrides such as ``ActorCritic.entropy_weight=1e-4``) without Hydra/OmegaConf, which are not installed."""
 from __future__ import annotations
 
+import math
 import os
 from typing import Any, Dict, List
 
+import numpy as np
 import yaml
+
+from .synth import CNN_ACTIVATIONS
 
 ACTION_MODES = ("sample", "mode", "mean")        # eval_action, and action_mode of the acting step
 
@@ -26,6 +30,98 @@ def check_diagnostics_interval(interval) -> int:
     if isinstance(interval, bool) or not isinstance(interval, (int, float)) or int(interval) != interval or interval < 0:
         raise ValueError(f"diagnostics_interval={interval!r} is not an integer >= 0")
     return int(interval)
+
+
+RETURN_NORMALIZATIONS = ("none", "percentile")
+RETURN_NORM_KEYS = ("return_normalization", "return_norm_low", "return_norm_high", "return_norm_decay", "return_norm_floor")
+
+
+def check_return_normalization(mode="none", low=0.05, high=0.95, decay=0.99, floor=1.0, algorithm=None) -> tuple:
+    """ActorCritic.return_normalization and its four numbers ("Return normalisation"): "none" (the reference's
+    objective) or "percentile" -- the returns of the actor objective divided by max(floor, P_high - P_low) of the imagined
+    lambda-returns, smoothed with `decay`.  Quantiles 0 <= low < high <= 1, 0 <= decay < 1, floor > 0.  PlaNet
+    (`algorithm`) has no actor and refuses "percentile".  Returns the five values, the numbers as floats."""
+    if mode not in RETURN_NORMALIZATIONS:
+        raise ValueError(f"return_normalization must be one of {RETURN_NORMALIZATIONS}, got {mode!r}")
+    num = {}
+    for key, v in (("return_norm_low", low), ("return_norm_high", high), ("return_norm_decay", decay),
+                   ("return_norm_floor", floor)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{key} must be a finite number, got {v!r}")
+        num[key] = float(v)
+    low, high, decay, floor = num.values()
+    if not 0.0 <= low < high <= 1.0:
+        raise ValueError(f"return_norm_low / return_norm_high must satisfy 0 <= low < high <= 1, got {low!r}, {high!r}")
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"return_norm_decay must be in [0, 1), got {decay!r}")
+    if not 0.0 < floor <= 3.0e38:
+        raise ValueError(f"return_norm_floor must be a positive fp32 number, got {floor!r}")
+    if mode != "none" and algorithm == "planet":
+        raise ValueError("return_normalization=percentile: PlaNet has no actor objective to normalise")
+    return mode, low, high, decay, floor
+
+
+CRITIC_HEAD_KEYS = ("critic_head", "critic_bins", "critic_bin_range")
+CRITIC_HEAD_DEFAULTS = dict(critic_head="normal", critic_bins=255, critic_bin_range=20.0)
+CRITIC_BINS_MAX = 1024
+CRITIC_BIN_RANGE_MAX = 80.0        # expm1 of more overflows fp32
+
+
+def check_critic_head(head="normal", bins=255, bin_range=20.0, algorithm=None) -> tuple:
+    """ActorCritic.critic_head and its two numbers ("Two-hot critic"): "normal" (the reference's width-1 critic
+    under a Normal(v, 1) loss) or "twohot" -- `bins` logits over bins uniform in symlog space on [-bin_range, bin_range],
+    decoded as symexp of the softmax mean, trained with the cross-entropy against the two-hot encoding of symlog(return).
+    bins: integer K, 2 <= K <= 1024; bin_range: Z, 0 < Z <= 80.  PlaNet (`algorithm`) has no critic and refuses "twohot".
+    Returns (head, int K, float Z)."""
+    from .synth import CRITIC_HEADS
+    if head not in CRITIC_HEADS:
+        raise ValueError(f"critic_head must be one of {CRITIC_HEADS}, got {head!r}")
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= CRITIC_BINS_MAX:
+        raise ValueError(f"critic_bins must be an integer in [2, {CRITIC_BINS_MAX}], got {bins!r}")
+    if (isinstance(bin_range, bool) or not isinstance(bin_range, (int, float)) or not math.isfinite(bin_range)
+            or not 0.0 < bin_range <= CRITIC_BIN_RANGE_MAX):
+        raise ValueError(f"critic_bin_range must be a number in (0, {CRITIC_BIN_RANGE_MAX:g}], got {bin_range!r}")
+    if head != "normal" and algorithm == "planet":
+        raise ValueError("critic_head=twohot: PlaNet has no critic")
+    return head, int(bins), float(bin_range)
+
+
+def check_gradient_mixing(value) -> float:
+    """ActorCritic.gradient_mixing: -1 (the reference's objective, backpropagation through the learned dynamics) or
+    rho in [0, 1], DreamerV2's ``actor_grad_mix`` -- the weight of the dynamics term against REINFORCE (1 = -1)."""
+    try:
+        rho = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"gradient_mixing must be -1 or a number in [0, 1], got {value!r}") from None
+    if not (rho == -1 or 0.0 <= rho <= 1.0):
+        raise ValueError(f"gradient_mixing must be -1 or a number in [0, 1], got {value!r}")
+    return rho
+
+
+def check_cnn_activation(value) -> str:
+    """cnn_activation_function: the activation of CnnImageEncoder / ObservationModel, a torch.nn class name as in the
+    reference (src/planet.py:186-192): "ELU" (default), "ReLU" or "Tanh" (epilogue codes of csrc/conv.hip)."""
+    if value not in CNN_ACTIVATIONS:
+        raise ValueError(f"cnn_activation_function must be one of {CNN_ACTIVATIONS}, got {value!r}")
+    return value
+
+
+def check_dense_activation(value) -> str:
+    """dense_activation_function: ELU is written into the epilogues of the scan, head and planner kernels."""
+    if value != "ELU":
+        raise NotImplementedError("the HIP path implements the reference default activation (ELU)")
+    return value
+
+
+ACTION_DISTRIBUTIONS = ("Gaussian", "Categorical")
+
+
+def check_action_distribution(value) -> str:
+    """action_distribution: "Gaussian" (the tanh-Normal actor) or "Categorical" (one-hot actions over A classes with a
+    straight-through sample, DESIGN.md "Discrete actions")."""
+    if value not in ACTION_DISTRIBUTIONS:
+        raise ValueError(f"action_distribution must be one of {ACTION_DISTRIBUTIONS}, got {value!r}")
+    return value
 
 
 DEFAULT_CONFIG =os.path.join(os.path.dirname(os.path.abspath(__file__)), "conf", "config.yaml")

@@ -18,10 +18,10 @@ from torch import Tensor
 
 from . import _cabi as cabi
 from .collect import check_collect_envs
-from .config import ACTION_MODES
-from .engine import (DEFAULT_HP, DreamerEngine, check_action_distribution, check_cnn_activation, check_dense_activation,
-                     check_critic_head, check_gradient_mixing, check_return_normalization, CRITIC_HEAD_DEFAULTS,
-                     CRITIC_HEAD_KEYS, RETURN_NORM_KEYS)
+from .config import (ACTION_MODES, CRITIC_HEAD_DEFAULTS, CRITIC_HEAD_KEYS, RETURN_NORM_KEYS, check_action_distribution,
+                     check_cnn_activation, check_critic_head, check_dense_activation, check_gradient_mixing,
+                     check_return_normalization)
+from .engine import DEFAULT_HP, DreamerEngine
 from .memory import ExperienceReplay
 from .models import ActorModel, CnnImageEncoder, DenseModel, ObservationModel, TransitionModel, encoder_for
 from .synth import Dims

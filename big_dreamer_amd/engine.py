@@ -12,10 +12,8 @@ become observe/imagine/MLP backward kernels + weight-gradient GEMMs).
 """
 from __future__ import annotations
 
-import collections.abc
 import contextlib
 import ctypes as C
-import math
 import os
 import weakref
 from functools import partial
@@ -27,10 +25,19 @@ import torch
 
 from . import _cabi as cabi
 from . import diagnostics
-from .config import check_replica_options
+from .config import (ACTION_DISTRIBUTIONS, CRITIC_BIN_RANGE_MAX, CRITIC_BINS_MAX, CRITIC_HEAD_DEFAULTS,  # noqa: F401
+                     CRITIC_HEAD_KEYS, RETURN_NORM_KEYS, RETURN_NORMALIZATIONS, check_action_distribution,
+                     check_cnn_activation, check_critic_head, check_dense_activation, check_gradient_mixing,
+                     check_return_normalization)
+from .diagnostics_device import _Diagnostics
+from .logs import (N_SLOTS, SLOT_DISC, SLOT_ENT, SLOT_GN_ACTOR, SLOT_GN_CRITIC, SLOT_GN_MODEL, SLOT_KL,  # noqa: F401
+                   SLOT_OBS, SLOT_RET, SLOT_REW, SLOT_RF, SLOT_RN, SLOT_VAL, SLOT_WOBJ, LazyLogs, LogRing, _LogRecord,
+                   logs_from)
 from .parallel import DataParallel
 from .params import ParamGroup, _adam_state_dict, _load_adam_state_dict
-from .synth import CNN_ACTIVATIONS, DENSE_LAYERS, MODEL_MODULES, Dims, model_modules, param_shapes
+from .replica import ReplicaMismatch, ReplicaWatch  # noqa: F401
+from .retnorm import _ReturnNorm
+from .synth import DENSE_LAYERS, MODEL_MODULES, Dims, model_modules, param_shapes
 
 lib = cabi.lib
 ptr = cabi.ptr
@@ -48,248 +55,14 @@ ACT_RAW_INIT_STD = float(torch.log(torch.exp(torch.tensor(5.0)) - 1))
 ACT_MIN_STD = 1e-4
 ACT_MEAN_SCALE = 5.0
 
-# scalar-board slots (raw sums; see include/bigdreamer_hip.h "losses")
-SLOT_OBS, SLOT_REW, SLOT_KL, SLOT_RET, SLOT_ENT, SLOT_VAL, SLOT_GN_MODEL, SLOT_GN_ACTOR, SLOT_GN_CRITIC = range(9)
-SLOT_DISC, SLOT_WOBJ = 9, 10       # use_discount=True: Bernoulli loss sum (model phase); weighted actor objective sum
-SLOT_RF = 11                       # gradient_mixing in [0, 1): sum of w * log pi(a) * (R - b), the REINFORCE objective
-SLOT_RN = 12                       # return_normalization=percentile: the scale, low and high the step used (slots 12..14)
-N_SLOTS = 16
-
-RETURN_NORMALIZATIONS = ("none", "percentile")
-RETURN_NORM_KEYS = ("return_normalization", "return_norm_low", "return_norm_high", "return_norm_decay", "return_norm_floor")
-
-
-def check_return_normalization(mode="none", low=0.05, high=0.95, decay=0.99, floor=1.0, algorithm=None) -> tuple:
-    """ActorCritic.return_normalization and its four numbers ("Return normalisation"): "none" (the reference's
-    objective) or "percentile" -- the returns of the actor objective divided by max(floor, P_high - P_low) of the imagined
-    lambda-returns, smoothed with `decay`.  Quantiles 0 <= low < high <= 1, 0 <= decay < 1, floor > 0.  PlaNet
-    (`algorithm`) has no actor and refuses "percentile".  Returns the five values, the numbers as floats."""
-    if mode not in RETURN_NORMALIZATIONS:
-        raise ValueError(f"return_normalization must be one of {RETURN_NORMALIZATIONS}, got {mode!r}")
-    num = {}
-    for key, v in (("return_norm_low", low), ("return_norm_high", high), ("return_norm_decay", decay),
-                   ("return_norm_floor", floor)):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
-            raise ValueError(f"{key} must be a finite number, got {v!r}")
-        num[key] = float(v)
-    low, high, decay, floor = num.values()
-    if not 0.0 <= low < high <= 1.0:
-        raise ValueError(f"return_norm_low / return_norm_high must satisfy 0 <= low < high <= 1, got {low!r}, {high!r}")
-    if not 0.0 <= decay < 1.0:
-        raise ValueError(f"return_norm_decay must be in [0, 1), got {decay!r}")
-    if not 0.0 < floor <= 3.0e38:
-        raise ValueError(f"return_norm_floor must be a positive fp32 number, got {floor!r}")
-    if mode != "none" and algorithm == "planet":
-        raise ValueError("return_normalization=percentile: PlaNet has no actor objective to normalise")
-    return mode, low, high, decay, floor
-
-
-CRITIC_HEAD_KEYS = ("critic_head", "critic_bins", "critic_bin_range")
-CRITIC_HEAD_DEFAULTS = dict(critic_head="normal", critic_bins=255, critic_bin_range=20.0)
-CRITIC_BINS_MAX = 1024
-CRITIC_BIN_RANGE_MAX = 80.0        # expm1 of more overflows fp32
-
-
-def check_critic_head(head="normal", bins=255, bin_range=20.0, algorithm=None) -> tuple:
-    """ActorCritic.critic_head and its two numbers ("Two-hot critic"): "normal" (the reference's width-1 critic
-    under a Normal(v, 1) loss) or "twohot" -- `bins` logits over bins uniform in symlog space on [-bin_range, bin_range],
-    decoded as symexp of the softmax mean, trained with the cross-entropy against the two-hot encoding of symlog(return).
-    bins: integer K, 2 <= K <= 1024; bin_range: Z, 0 < Z <= 80.  PlaNet (`algorithm`) has no critic and refuses "twohot".
-    Returns (head, int K, float Z)."""
-    from .synth import CRITIC_HEADS
-    if head not in CRITIC_HEADS:
-        raise ValueError(f"critic_head must be one of {CRITIC_HEADS}, got {head!r}")
-    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= CRITIC_BINS_MAX:
-        raise ValueError(f"critic_bins must be an integer in [2, {CRITIC_BINS_MAX}], got {bins!r}")
-    if (isinstance(bin_range, bool) or not isinstance(bin_range, (int, float)) or not math.isfinite(bin_range)
-            or not 0.0 < bin_range <= CRITIC_BIN_RANGE_MAX):
-        raise ValueError(f"critic_bin_range must be a number in (0, {CRITIC_BIN_RANGE_MAX:g}], got {bin_range!r}")
-    if head != "normal" and algorithm == "planet":
-        raise ValueError("critic_head=twohot: PlaNet has no critic")
-    return head, int(bins), float(bin_range)
-
-
-def check_gradient_mixing(value) -> float:
-    """ActorCritic.gradient_mixing: -1 (the reference's objective, backpropagation through the learned dynamics) or
-    rho in [0, 1], DreamerV2's ``actor_grad_mix`` -- the weight of the dynamics term against REINFORCE (1 = -1)."""
-    try:
-        rho = float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"gradient_mixing must be -1 or a number in [0, 1], got {value!r}") from None
-    if not (rho == -1 or 0.0 <= rho <= 1.0):
-        raise ValueError(f"gradient_mixing must be -1 or a number in [0, 1], got {value!r}")
-    return rho
-
-
-def check_cnn_activation(value) -> str:
-    """cnn_activation_function: the activation of CnnImageEncoder / ObservationModel, a torch.nn class name as in the
-    reference (src/planet.py:186-192): "ELU" (default), "ReLU" or "Tanh" (epilogue codes of csrc/conv.hip)."""
-    if value not in CNN_ACTIVATIONS:
-        raise ValueError(f"cnn_activation_function must be one of {CNN_ACTIVATIONS}, got {value!r}")
-    return value
-
-
-def check_dense_activation(value) -> str:
-    """dense_activation_function: ELU is written into the epilogues of the scan, head and planner kernels."""
-    if value != "ELU":
-        raise NotImplementedError("the HIP path implements the reference default activation (ELU)")
-    return value
-
-
-ACTION_DISTRIBUTIONS = ("Gaussian", "Categorical")
-
-
-def check_action_distribution(value) -> str:
-    """action_distribution: "Gaussian" (the tanh-Normal actor) or "Categorical" (one-hot actions over A classes with a
-    straight-through sample, DESIGN.md "Discrete actions")."""
-    if value not in ACTION_DISTRIBUTIONS:
-        raise ValueError(f"action_distribution must be one of {ACTION_DISTRIBUTIONS}, got {value!r}")
-    return value
-
-
-class ReplicaMismatch(RuntimeError):
-    """Data-parallel replicas no longer hold bit-identical weights, Adam moments or step counts."""
-
-
-class _ReplicaVerdict:
-    """One periodic replica check in flight: pinned host memory for the step counts going up and the verdict coming
-    down, and the event behind the D2H copy."""
-
-    def __init__(self, n_buf: int):
-        self.steps = torch.zeros(3, dtype=torch.int64).pin_memory()
-        self.host = torch.zeros(2 * (2 * n_buf + 3), dtype=torch.int64).pin_memory()     # max | min over ranks of the words
-        self.event: Optional[torch.cuda.Event] = None
-        self.step = 0
-        self.collective = False
-
-
-class _LogRecord:
-    """Pinned host copy of the scalar board of ONE train step, filled by three asynchronous D2H copies (one per
-    optimiser phase, each on the stream that wrote the slots) -- reading it never stalls the pipeline streams."""
-
-    ROW = {"model": 0, "actor": 1, "critic": 2}
-
-    def __init__(self):
-        self.host = torch.zeros(3, N_SLOTS + 1, dtype=torch.float32).pin_memory()     # last column: cluster error word
-        self.events: List[Optional[torch.cuda.Event]] = [None, None, None]
-        self.counts: Optional[dict] = None
-        self.owner = None          # weakref to the LazyLogs handed to the caller
-        self.need = (0, 1, 2)
-        # diagnosed steps only: pinned copy of the step's diagnostic block, a region per phase behind the same three events
-        self.diag: Optional[torch.Tensor] = None
-        self.diag_mem: Optional[torch.Tensor] = None
-
-
-class LazyLogs(collections.abc.MutableMapping):
-    """The reference's log dict (src/dreamer.py:293-296,359-360,383), resolved on first read.
-
-    ``Dreamer.train_step`` returns one per step; nothing synchronises until a key is read, so the reference loop's
-    ``for _ in range(collect_interval): logs = model.train_step()`` (src/main.py:105-108) runs the cross-step pipeline
-    and only the burst's last dict -- the one the loop reads -- waits for the GPU.  Keys and values are exactly those
-    of the eager dict; extra keys may be written (``logs["weight_update_per_sec"] = ...``, src/main.py:108)."""
-
-    def __init__(self, eng: "DreamerEngine", rec: _LogRecord, drop_prefix: Tuple[str, ...] = ()):
-        self._eng, self._rec, self._drop = eng, rec, drop_prefix
-        self._vals: Optional[Dict[str, float]] = None
-        self._extra: Dict[str, object] = {}
-
-    def resolve(self) -> Dict[str, float]:
-        if self._vals is None:
-            vals = self._eng._resolve_record(self._rec)
-            self._vals = {k: v for k, v in vals.items() if not k.startswith(self._drop)} if self._drop else vals
-            self._rec = None
-        return self._vals
-
-    def __getitem__(self, k):
-        return self._extra[k] if k in self._extra else self.resolve()[k]
-
-    def __setitem__(self, k, v):
-        self._extra[k] = v
-
-    def __delitem__(self, k):
-        del self._extra[k]
-
-    def __iter__(self):
-        yield from self.resolve()
-        yield from (k for k in self._extra if k not in self._vals)
-
-    def __len__(self):
-        return len(set(self.resolve()) | set(self._extra))
-
-    def __repr__(self):
-        return repr(dict(self.items()))
-
-
-class _ReturnNorm:
-    """Device side of the percentile return normalisation ("Return normalisation"), built only when it is on:
-    the running range `state` = (lo, hi, count, skipped) in fp64, and `range`, two rows of (scale, lo, hi) in fp32.  A step
-    reads row `cur` -- the range as it stood before the step -- and bd_return_range writes the other row for the next
-    step, so two steps in flight never share a row.  `ev` is the end of the latest bd_return_range."""
-
-    def __init__(self, eng: "DreamerEngine"):
-        hp = eng.hp
-        self.decay, self.floor = hp["return_norm_decay"], hp["return_norm_floor"]
-        self.q = (hp["return_norm_low"], hp["return_norm_high"])
-        self.state = torch.zeros(4, dtype=torch.float64, device=eng.dev)
-        self.range = torch.zeros(2, 4, dtype=torch.float32, device=eng.dev)
-        self.cur = 0
-        self.ev: Optional[torch.cuda.Event] = None
-        self.load(dict(lo=0.0, hi=0.0, count=0.0, skipped=0.0))
-
-    def ranks(self, M: int) -> Tuple[int, int]:
-        """k_q = floor(q (M - 1)), in Python floats."""
-        return tuple(int(math.floor(q * (M - 1))) for q in self.q)
-
-    def load(self, d: dict) -> None:
-        lo, hi = float(d["lo"]), float(d["hi"])
-        self.state.copy_(torch.tensor([lo, hi, float(d["count"]), float(d["skipped"])], dtype=torch.float64))
-        row = torch.tensor([max(self.floor, hi - lo), lo, hi, 0.0], dtype=torch.float64).to(torch.float32)
-        self.range.copy_(row.expand(2, 4))
-
-
-class _Diagnostics:
-    """Device side of the training diagnostics ("Training diagnostics"), built when the interval is first set
-    above 0: the diagnostic block (diagnostics.Layout), one reduction workspace per phase stream, and the per-module
-    segment tables of the three optimisers' flat buffers."""
-
-    def __init__(self, eng: "DreamerEngine"):
-        d = eng.d
-        segs = {g: eng.groups[g].module_segments() for g in diagnostics.REGIONS}
-        self.lay = diagnostics.Layout(d.categorical, d.cat_D if d.categorical else d.S, d.cat_C, True, d.discrete_actions,
-                                      d.A, {g: names for g, (names, _) in segs.items()})
-        self.block = torch.zeros(self.lay.size, dtype=torch.float64, device=eng.dev)
-        n_ws = int(lib.bd_diag_ws_floats())
-        self.ws = {g: torch.zeros(n_ws, dtype=torch.float32, device=eng.dev) for g in diagnostics.REGIONS}
-        self.offsets = {g: (C.c_size_t * len(offs))(*offs) for g, (_, offs) in segs.items()}
-        self.n_seg = {g: len(names) for g, (names, _) in segs.items()}
-        self.colsum_ws = (torch.zeros(int(lib.bd_colsum_ws_floats(d.A)), dtype=torch.float32, device=eng.dev)
-                          if d.discrete_actions else None)
-
-    def at(self, field: str, word: int = 0) -> int:
-        """Device address of double `word` of a field of the block."""
-        return self.block.data_ptr() + 8 * (self.lay.fields[field][0] + word)
-
-    def moments(self, group: str, field: str, entries) -> None:
-        """One bd_moments launch on the current stream: entries = [(p, q or None), ...] -> consecutive sextuples of `field`."""
-        a = cabi.MomentsArgs()
-        a.n_buf = len(entries)
-        for i, (p, q) in enumerate(entries):
-            a.buf[i].p, a.buf[i].q, a.buf[i].n = ptr(p), ptr(q), p.numel()
-        cabi.check(lib.bd_moments(C.byref(a), self.at(field), ptr(self.ws[group]), cabi.stream()))
-
-    def norms(self, group: str, g: ParamGroup) -> None:
-        """Per-module sums of squares of the group's gradient and weights, on the current stream."""
-        for field, buf in (("gsq_", g.grad), ("wsq_", g.flat)):
-            cabi.check(lib.bd_segment_sumsq(ptr(buf), self.n_seg[group], self.offsets[group], self.at(field + group),
-                                            ptr(self.ws[group]), cabi.stream()))
-
 
 class WgradBatch:
     """All weight-gradient GEMMs of one backward pass -> one bd_wgrad_grouped launch (+ one grouped reduce).
     The descriptor table lives in HBM and is rebuilt only when a buffer pointer or size changes."""
 
-    def __init__(self, eng: "DreamerEngine", name: str, ws_attr: str = "_wgrad_ws"):
-        self.eng, self.name, self.ws_attr = eng, name, ws_attr
+    def __init__(self, eng: "DreamerEngine", name: str):
+        self.eng, self.name = eng, name
+        self.ws = torch.zeros(1, dtype=torch.float32, device=eng.dev)
         self.items: List[tuple] = []
         self.chains: List[tuple] = []
         self._cache: Dict[tuple, tuple] = {}
@@ -330,13 +103,13 @@ class WgradBatch:
             # (a pageable H2D copy synchronises with the device: tables are cached per operand-pointer set -- the
             # double-buffered features and the replay's output ring make a handful of sets that then repeat)
             table = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(eng.dev)
-            if getattr(eng, self.ws_attr).numel() < wsf.value:
-                setattr(eng, self.ws_attr, torch.zeros(wsf.value, dtype=torch.float32, device=eng.dev))
+            if self.ws.numel() < wsf.value:
+                self.ws = torch.zeros(wsf.value, dtype=torch.float32, device=eng.dev)
             if len(self._cache) >= 16:
                 self._cache.pop(next(iter(self._cache)))
             hit = self._cache[key] = (table, n, tb.value, tr.value)
         table, n, tb, tr = hit
-        ws = ptr(getattr(eng, self.ws_attr))
+        ws = ptr(self.ws)
         if eng._timers_on:       # bracket the slab-GEMM kernel alone (one launch) with HIP events; the reduce follows
             with eng.span("wgrad_gemm_" + self.name):
                 cabi.check(lib.bd_wgrad_grouped_phase(table.data_ptr(), n, tb, tr, ws, 1, cabi.stream()))
@@ -383,8 +156,9 @@ class DreamerEngine:
     def __init__(self, dims: Dims, hp: Optional[dict] = None, device="cuda", params: Optional[dict] = None,
                  world_size: int = 1, process_group=None, phase_groups: Optional[dict] = None,
                  replica_check_interval: int = 0, replica_on_mismatch: str = "raise", diagnostics_interval: int = 0):
-        self.d = dims
-        self.set_replica_check(replica_check_interval, replica_on_mismatch)
+        self.d = d = dims
+        # replica watch ("Replica agreement"): it touches nothing while replica_check_interval is 0
+        self.replica = ReplicaWatch(self, replica_check_interval, replica_on_mismatch)
         # training diagnostics ("Training diagnostics"): nothing is built, launched or logged while the interval is 0
         self.diagnostics_interval = diagnostics.check_interval(diagnostics_interval)
         self._diag: Optional[_Diagnostics] = None
@@ -401,6 +175,7 @@ class DreamerEngine:
         check_critic_head(dims.critic_head, dims.critic_bins, dims.critic_bin_range)
         self.dev = torch.device(device)
         assert self.dev.type == "cuda", "the HIP path needs a GPU (there is no CPU fallback)"
+        # ---- parallel setup
         self.world_size = world_size
         self.pg = process_group
         # One RCCL communicator per optimiser (+ the caller's for the KL scalar) unless the caller brought its own.  All
@@ -426,7 +201,19 @@ class DreamerEngine:
             for g in (None, "model", "actor", "critic"):
                 self.dp.allreduce_sum_(tiny, g)
             torch.cuda.synchronize(self.dev)
-        d = dims
+        # data-parallel: actor / critic optimiser steps (their all-reduces) are issued one host step late, see
+        # _optimizer_step_or_defer; BD_DEFER_OPT=1 forces the same order on one GPU (tests)
+        # (needed only where the three optimisers share ONE communicator: with one communicator each -- the default, above --
+        # the all-reduces cannot queue behind one another and the updates are issued where the serial schedule has them; held
+        # back, the actor's update of step k would wait for the host to queue all of dynamics learning k+1 first: +2 ms per
+        # step in the rehearsal of the pixel configuration)
+        shared_comm = not all(g in self.dp.groups for g in ("model", "actor", "critic"))
+        self.defer_opt = (world_size > 1 and shared_comm) or os.environ.get("BD_DEFER_OPT", "0") == "1"
+        if os.environ.get("BD_FORCE_DP", "0") == "1" and torch.distributed.is_initialized():
+            self.dp.force = True                       # single-rank rehearsal of the data-parallel schedule
+            self.defer_opt = shared_comm or os.environ.get("BD_DEFER_OPT", "0") == "1"
+        self._pending_opt: List[tuple] = []
+        # ---- parameter groups
         shapes = param_shapes(d)
         # pixel mode: the conv stacks run on this library's gather-GEMM kernels (csrc/conv.hip, conv_stack.py) and their
         # weights are STORED (d0, ky, kx, d1) (ParamGroup).  (The MIOpen / torch-autograd comparator of rounds 1-2 is a test
@@ -442,36 +229,11 @@ class DreamerEngine:
         self._mod_group.update(actor="actor", critic="critic", critic_target="critic_target")
         if params is not None:
             self.load_params(params)
-        self.scalars = torch.zeros(N_SLOTS, dtype=torch.float32, device=self.dev)
-        # percentile return normalisation: nothing is allocated, launched or logged while it is "none"
-        self._rn = _ReturnNorm(self) if self.hp["return_normalization"] == "percentile" else None
-        self.red_ws = torch.zeros(int(lib.bd_reduce_ws_floats()), dtype=torch.float32, device=self.dev)
-        self._wgrad_ws = torch.zeros(1, dtype=torch.float32, device=self.dev)
-        self._wgrad_ws_side = torch.zeros(1, dtype=torch.float32, device=self.dev)
-        self._wgrad_ws_early = torch.zeros(1, dtype=torch.float32, device=self.dev)
-        self.red_ws_side = torch.zeros(int(lib.bd_reduce_ws_floats()), dtype=torch.float32, device=self.dev)
-        self._wbatch = {"model": WgradBatch(self, "model"), "model_early": WgradBatch(self, "model_early", "_wgrad_ws_early"),
-                        "actor": WgradBatch(self, "actor", "_wgrad_ws_bh"),
-                        "critic": WgradBatch(self, "critic", "_wgrad_ws_side")}
+        self._opt_over: Dict[str, dict] = {}
+        # ---- streams and events
         self._side = _engine_stream(self.dev, "side", int(os.environ.get("BD_SIDE_PRIO", "0")))    # critic (pipelined)
-        # Frozen imagined heads (reward_model, critic_target) forward + dgrad in one launch (csrc/heads.hip) on the
-        # dynamics-backprop path with Gaussian latents; BD_HEADS_FUSED=0 keeps the separate forward / backward chains
-        # (mlp.hip) for the A/B.  The fused kernel is a width-1 kernel: the two-hot critic takes the separate chains.
-        self.heads_fused = (os.environ.get("BD_HEADS_FUSED", "1") != "0" and not self.d.categorical and not self.d.twohot
-                            and bool(lib.bd_img_heads_supported(self.d.Be + self.d.S, self.d.Hd)))
         # pixel mode: decoder weight gradients under the observe scan
         self._s_early = _engine_stream(self.dev, "early", int(os.environ.get("BD_EARLY_PRIO", "0")))
-        # Behaviour chunk plan (DESIGN.md, "Chunked behaviour chain"): the forward imagination scan runs as K launches over
-        # consecutive time steps, and the fused heads of a finished chunk run on the CUs the scan leaves idle while the
-        # scan walks on.  They run on `_side`, the critic's stream (no fifth active stream: the process has four
-        # hardware queues; the decoder-wgrad stream `_s_early`, idle with state observations, was slower in the A/B).
-        # bh_chunks: None = the default rule (behaviour_plan), 1 = single launches, K = K near-equal chunks, a tuple =
-        # the chunk lengths (BD_BH_CHUNKS: "", "1", "3", "5,5,4").
-        self.bh_chunks = _parse_bh_chunks(os.environ.get("BD_BH_CHUNKS", ""))
-        # Composed encoder tail (DESIGN.md section 3, "Composed encoder tail"): with state observations the encoder's
-        # linear last layer and the posterior's hoisted projection are trained as their product.  None = the default
-        # rule (composed_encoder_tail), True / False force a form.
-        self.encoder_composed: Optional[bool] = None
         # Cross-step software pipeline (on unless BD_PIPELINE=0).  Dynamics learning of step k+1 reads only the world
         # model that step k's model optimiser wrote, never what step k's behaviour learning (imagination, actor,
         # critic) produces, while behaviour learning k needs the world model k and the posteriors k.  So the two
@@ -486,21 +248,6 @@ class DreamerEngine:
         # learning should only fill its gaps (BD_BH_PRIO overrides: -1 high, 0 normal)
         bh_prio = int(os.environ.get("BD_BH_PRIO", "0" if self.pixel else "-1"))
         self._s_bh = _engine_stream(self.dev, "bh", bh_prio)      # critic: _side
-        self._ev_bh_wm_free: Optional[torch.cuda.Event] = None
-        self._bh_plan_used: Optional[Tuple[int, ...]] = None       # the plan of the last train step
-        self._ev_bh_done: List[Optional[torch.cuda.Event]] = [None, None]
-        self._ev_cr_done: List[Optional[torch.cuda.Event]] = [None, None]
-        # data-parallel: actor / critic optimiser steps (their all-reduces) are issued one host step late, see
-        # _optimizer_step_or_defer; BD_DEFER_OPT=1 forces the same order on one GPU (tests)
-        # (needed only where the three optimisers share ONE communicator: with one communicator each -- the default, above --
-        # the all-reduces cannot queue behind one another and the updates are issued where the serial schedule has them; held
-        # back, the actor's update of step k would wait for the host to queue all of dynamics learning k+1 first: +2 ms per
-        # step in the rehearsal of the pixel configuration)
-        shared_comm = not all(g in self.dp.groups for g in ("model", "actor", "critic"))
-        self.defer_opt = (world_size > 1 and shared_comm) or os.environ.get("BD_DEFER_OPT", "0") == "1"
-        if os.environ.get("BD_FORCE_DP", "0") == "1" and torch.distributed.is_initialized():
-            self.dp.force = True                       # single-rank rehearsal of the data-parallel schedule
-            self.defer_opt = shared_comm or os.environ.get("BD_DEFER_OPT", "0") == "1"
         if (world_size > 1 or self.dp.force) and torch.cuda.current_stream(self.dev) == torch.cuda.default_stream(self.dev):
             # The legacy null stream synchronises implicitly with every BLOCKING stream of the process, and RCCL's is
             # one: with collectives in flight, each replay gather / stream hand-over the caller issues on the null
@@ -509,16 +256,49 @@ class DreamerEngine:
             # 5.33 ms/step).  Data-parallel runs therefore move the calling thread to a non-blocking stream.
             self._main_stream = _engine_stream(self.dev, "main", 0)
             torch.cuda.set_stream(self._main_stream)
-        self._pending_opt: List[tuple] = []
-        self._opt_over: Dict[str, dict] = {}
-        # replica watch ("Replica agreement"): nothing below is touched while replica_check_interval is 0
-        self._fp: Optional[tuple] = None                     # (buffer names, bd_fingerprint argument block)
+        self._ev_bh_wm_free: Optional[torch.cuda.Event] = None
+        self._ev_bh_done: List[Optional[torch.cuda.Event]] = [None, None]
+        self._ev_cr_done: List[Optional[torch.cuda.Event]] = [None, None]
+        self._wm_done_hist: List[torch.cuda.Event] = []
+        self._parity = 0
+        # steps the host may run ahead of the GPU before train_step waits (0: no limit): two keep the launch queues fed and stay
+        # far below the depth at which the HIP runtime stalls the host to retire commands in bulk (5-6 steps of configs[1])
+        self.host_ahead = int(os.environ.get("BD_HOST_AHEAD", "2"))
+        self._bh_hist: List["torch.cuda.Event"] = []
         self._n_train_steps = 0
-        self._checks_out: List[_ReplicaVerdict] = []         # issued, not yet read; oldest first
-        self._check_pool: List[_ReplicaVerdict] = []
-        self._ev_fp: Optional[torch.cuda.Event] = None       # end of the latest periodic fingerprint
-        self._fp_wait: set = set()                           # optimisers that have not yet been ordered behind it
-        self._resync_warned = False
+        # Frozen imagined heads (reward_model, critic_target) forward + dgrad in one launch (csrc/heads.hip) on the
+        # dynamics-backprop path with Gaussian latents; BD_HEADS_FUSED=0 keeps the separate forward / backward chains
+        # (mlp.hip) for the A/B.  The fused kernel is a width-1 kernel: the two-hot critic takes the separate chains.
+        self.heads_fused = (os.environ.get("BD_HEADS_FUSED", "1") != "0" and not self.d.categorical and not self.d.twohot
+                            and bool(lib.bd_img_heads_supported(self.d.Be + self.d.S, self.d.Hd)))
+        # Behaviour chunk plan (DESIGN.md, "Chunked behaviour chain"): the forward imagination scan runs as K launches over
+        # consecutive time steps, and the fused heads of a finished chunk run on the CUs the scan leaves idle while the
+        # scan walks on.  They run on `_side`, the critic's stream (no fifth active stream: the process has four
+        # hardware queues; the decoder-wgrad stream `_s_early`, idle with state observations, was slower in the A/B).
+        # bh_chunks: None = the default rule (behaviour_plan), 1 = single launches, K = K near-equal chunks, a tuple =
+        # the chunk lengths (BD_BH_CHUNKS: "", "1", "3", "5,5,4").
+        self.bh_chunks = _parse_bh_chunks(os.environ.get("BD_BH_CHUNKS", ""))
+        self._bh_plan_used: Optional[Tuple[int, ...]] = None       # the plan of the last train step
+        # Composed encoder tail (DESIGN.md section 3, "Composed encoder tail"): with state observations the encoder's
+        # linear last layer and the posterior's hoisted projection are trained as their product.  None = the default
+        # rule (composed_encoder_tail), True / False force a form.
+        self.encoder_composed: Optional[bool] = None
+        # cluster variant of the observe scan (several CUs per 16-row tile): on unless BD_OBS_CLUSTER=0
+        self.use_obs_cluster = os.environ.get("BD_OBS_CLUSTER", "1") != "0"
+        # ---- workspaces
+        self.scalars = torch.zeros(N_SLOTS, dtype=torch.float32, device=self.dev)
+        self.red_ws = torch.zeros(int(lib.bd_reduce_ws_floats()), dtype=torch.float32, device=self.dev)
+        self.red_ws_side = torch.zeros(int(lib.bd_reduce_ws_floats()), dtype=torch.float32, device=self.dev)
+        self.red_ws_bh = torch.zeros(int(lib.bd_reduce_ws_floats()), dtype=torch.float32, device=self.dev)
+        self._wgrad_ws = torch.zeros(1, dtype=torch.float32, device=self.dev)        # of wgrad(), the single-GEMM form
+        self._buf: Dict[str, torch.Tensor] = {}
+        self._obs_ws: Optional[torch.Tensor] = None
+        self._obs_err_off: Optional[int] = None
+        # ---- helpers
+        # percentile return normalisation: nothing is allocated, launched or logged while it is "none"
+        self._rn = _ReturnNorm(self) if self.hp["return_normalization"] == "percentile" else None
+        self._wbatch = {name: WgradBatch(self, name) for name in ("model", "model_early", "actor", "critic")}
+        self._logs = LogRing()
         # perf-mode noise: Philox keyed by the process seed (torch.manual_seed before building the agent, src/main.py:56-58)
         # and the rank, counter = step index per phase
         # (read at the FIRST perf-mode draw, so that seeding torch any time before training reproduces the run)
@@ -527,25 +307,10 @@ class DreamerEngine:
         self._rng_entropy_step = 0
         self._act_parity = 0                 # act_step: which of its two output buffer sets the next call writes
         self.last_act_stats = self.last_act_mode_index = None     # act_step with an evaluation policy: what it left
-        self._log_ring: List[_LogRecord] = []
-        self._log_i = 0
-        self._cur_rec: Optional[_LogRecord] = None
-        self._wm_done_hist: List[torch.cuda.Event] = []
-        self._parity = 0
-        self._wgrad_ws_bh = torch.zeros(1, dtype=torch.float32, device=self.dev)
-        self.red_ws_bh = torch.zeros(int(lib.bd_reduce_ws_floats()), dtype=torch.float32, device=self.dev)
-        self._buf: Dict[str, torch.Tensor] = {}
-        # cluster variant of the observe scan (several CUs per 16-row tile): on unless BD_OBS_CLUSTER=0
-        # steps the host may run ahead of the GPU before train_step waits (0: no limit): two keep the launch queues fed and stay
-        # far below the depth at which the HIP runtime stalls the host to retire commands in bulk (5-6 steps of configs[1])
-        self.host_ahead = int(os.environ.get("BD_HOST_AHEAD", "2"))
-        self._bh_hist: List["torch.cuda.Event"] = []
-        self.use_obs_cluster = os.environ.get("BD_OBS_CLUSTER", "1") != "0"
-        self._obs_ws: Optional[torch.Tensor] = None
-        self._obs_err_off: Optional[int] = None
         self._timers_on, self._timer_every, self._timer_tick = False, 1, 0
         self._timer_events: Dict[str, List[Tuple[torch.cuda.Event, torch.cuda.Event]]] = {}
         self._timer_more: Dict[str, List[Tuple[torch.cuda.Event, torch.cuda.Event]]] = {}     # span(name, more=True)
+        # ---- packs
         self._build_pack_tables()
         self.conv = None
         if self.pixel:
@@ -829,9 +594,7 @@ class DreamerEngine:
         this update belongs to is a diagnosed one (None: the step being queued)."""
         g = self.groups[group]
         red_ws = self.red_ws if red_ws is None else red_ws
-        if group in self._fp_wait:           # a periodic fingerprint read these buffers on another stream: write after it
-            self._fp_wait.discard(group)
-            torch.cuda.current_stream().wait_event(self._ev_fp)
+        self.replica.order_write(group)
         self._allreduce(g.grad, group)     # grads already carry 1/global-count: SUM over ranks = global-mean gradient
         g.step += 1
         hp = self.hp
@@ -846,44 +609,12 @@ class DreamerEngine:
                                     eps, wd, g.step, hp["grad_clip_norm"],
                                     ptr(self.scalars), slot, cabi.stream()))
         self.pack(group)
-        rec = rec if rec is not None else self._cur_rec
+        rec = rec if rec is not None else self._logs.cur
         if rec is not None:
-            self._snapshot(rec, _LogRecord.ROW[group])
+            word = group == "model" and self._obs_ws is not None and self._obs_err_off is not None
+            rec.snapshot(_LogRecord.ROW[group], self.scalars, self._cluster_error_word if word else None, self._diag)
 
     # ------------------------------------------------------------------------------------------ lazy logs
-    def _new_record(self) -> _LogRecord:
-        """Next record of a ring of eight; a record still referenced by an unread LazyLogs is resolved first."""
-        if len(self._log_ring) < 8:
-            self._log_ring.append(_LogRecord())
-            rec = self._log_ring[-1]
-        else:
-            rec = self._log_ring[self._log_i]
-            self._log_i = (self._log_i + 1) % 8
-            owner = rec.owner() if rec.owner is not None else None
-            if owner is not None and owner._vals is None:
-                owner.resolve()
-        rec.events = [None, None, None]
-        rec.owner, rec.counts = None, None
-        rec.diag = None
-        if self._diag_now:
-            if rec.diag_mem is None or rec.diag_mem.numel() != self._diag.lay.size:
-                rec.diag_mem = torch.zeros(self._diag.lay.size, dtype=torch.float64).pin_memory()
-            rec.diag = rec.diag_mem
-        return rec
-
-    def _snapshot(self, rec: _LogRecord, row: int) -> None:
-        """Asynchronous D2H of the scalar board (+ the cluster scan's sticky error word) into `rec`, on the current
-        stream, behind the kernels of this phase that wrote its slots."""
-        rec.host[row, :N_SLOTS].copy_(self.scalars, non_blocking=True)
-        if row == 0 and self._obs_ws is not None and self._obs_err_off is not None:
-            rec.host[row, N_SLOTS:].copy_(self._cluster_error_word(), non_blocking=True)
-        if rec.diag is not None:
-            lo, hi = self._diag.lay.region[diagnostics.REGIONS[row]]
-            rec.diag[lo:hi].copy_(self._diag.block[lo:hi], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        rec.events[row] = ev
-
     def _resolve_record(self, rec: _LogRecord) -> Dict[str, float]:
         # The actor / critic updates of the LATEST step may still be held back on the host (deferred schedule).  Issuing
         # them contains all-reduces: with several ranks a dict read -- which only one rank may make (rank 0 logging), or
@@ -896,16 +627,8 @@ class DreamerEngine:
                                    "flush_optimizers() on EVERY rank before reading it -- reading a log dict never issues "
                                    "collectives")
             self.flush_optimizers()
-        for row in rec.need:
-            assert rec.events[row] is not None, "log record read before its step was queued"
-            rec.events[row].synchronize()
-        h = rec.host.numpy()
-        s = h[0, :N_SLOTS].copy()
-        for slot in (SLOT_RET, SLOT_ENT, SLOT_GN_ACTOR, SLOT_WOBJ, SLOT_RF, SLOT_RN, SLOT_RN + 1, SLOT_RN + 2):
-            s[slot] = h[1, slot]
-        for slot in (SLOT_VAL, SLOT_GN_CRITIC):
-            s[slot] = h[2, slot]
-        self._raise_on_cluster_error(int(h[0, N_SLOTS:].view(np.uint32)[0]))
+        s, word = rec.read()
+        self._raise_on_cluster_error(word)
         out = self._logs_from(s, rec.counts)
         if rec.diag is not None:
             out.update(diagnostics.entries(rec.diag.numpy(), self._diag.lay, rec.counts["N"], rec.counts["Mi"]))
@@ -943,16 +666,37 @@ class DreamerEngine:
         self.pack("critic_target")
 
     # ------------------------------------------------------------------------------------------ replica agreement
-    # DESIGN.md, "Replica agreement".  The data-parallel step is exact only while every rank holds bit-identical weights,
-    # Adam moments and step counts; one bd_fingerprint launch reduces each flat buffer to a 64-bit word (and a count of
-    # non-finite elements) on the device, one small MAX all-reduce compares the words.
-    _FP_BUFFERS = tuple((g, b) for g in ("model", "actor", "critic") for b in ("flat", "m", "v")) + (("critic_target", "flat"),)
-    _STEP_GROUPS = ("model", "actor", "critic")
-
+    # (replica.ReplicaWatch; DESIGN.md, "Replica agreement")
     def set_replica_check(self, interval: int = 0, on_mismatch: str = "raise") -> None:
         """The periodic check of train_step: every `interval`-th step (0 = off); a mismatch raises ReplicaMismatch
         ("raise") or warns once and broadcasts rank 0's state ("resync").  Every rank sets the same values."""
-        self.replica_check_interval, self.replica_on_mismatch = check_replica_options(interval, on_mismatch)
+        self.replica.set(interval, on_mismatch)
+
+    def fingerprint(self):
+        """(words, names): a device int64 tensor [n_buf, 2] of (hash, non-finite count) per flat buffer -- flat, m, v of
+        model, actor and critic, flat of critic_target, padding floats included -- and the buffers' names in table order,
+        e.g. ("actor", "flat").  Ordered behind pending optimiser work as optimizer_state_dict is (data-parallel: a
+        collective, it issues the held-back optimiser steps), without the host synchronisation."""
+        return self.replica.fingerprint()
+
+    def check_replicas(self) -> dict:
+        """{"agree": bool, "mismatch": [names], "nonfinite": {name: count}}, the same on every rank.  Synchronous, and a
+        COLLECTIVE on the caller's communicator: every rank calls it at the same point.  One rank: the non-finite counts
+        only (agree = True).  Verdicts of periodic checks still in flight are resolved first."""
+        return self.replica.check()
+
+    def sync_replicas(self, src: int = 0) -> None:
+        """Make every rank a bit-identical copy of rank `src`: flat, m, v of the three optimisers, the critic target, the
+        Adam step counts and checkpoint hyper-parameters adopted by load_optimizer_state_dict; then everything derived
+        from the weights is rebuilt as __init__ does (pack() of the four groups: packed weights, the Categorical plain
+        copies, the conv stacks' packs).  A COLLECTIVE on the caller's communicator; synchronous."""
+        self.replica.sync(src)
+
+    def resolve_replica_checks(self, upto: Optional[int] = None) -> None:
+        """Read the verdicts of the periodic checks issued at train steps <= `upto` (None: all), oldest first, and act on
+        them.  Data-parallel: every rank calls it at the same host step (train_step does; so do check_replicas,
+        sync_replicas and optimizer_state_dict, hence Dreamer.save) -- "resync" is a collective."""
+        self.replica.resolve(upto)
 
     def set_diagnostics(self, interval: int = 0) -> None:
         """Training diagnostics on every `interval`-th train step (0 = off): the steps whose count so far is a multiple of
@@ -970,184 +714,18 @@ class DreamerEngine:
             self._diag = _Diagnostics(self)
         return count % k == 0
 
-    def _fp_table(self):
-        if self._fp is None:
-            a = cabi.FingerprintArgs()
-            a.n_buf = len(self._FP_BUFFERS)
-            for i, (g, b) in enumerate(self._FP_BUFFERS):
-                t = getattr(self.groups[g], b)
-                a.buf[i].p, a.buf[i].n = t.data_ptr(), t.numel()
-            self._fp = (self._FP_BUFFERS, a)
-        return self._fp
-
-    def _fingerprint_into(self, out: torch.Tensor) -> None:
-        """ONE launch over every flat buffer, on the current stream."""
-        cabi.check(lib.bd_fingerprint(C.byref(self._fp_table()[1]), out.data_ptr(), cabi.stream()))
-
-    def fingerprint(self):
-        """(words, names): a device int64 tensor [n_buf, 2] of (hash, non-finite count) per flat buffer -- flat, m, v of
-        model, actor and critic, flat of critic_target, padding floats included -- and the buffers' names in table order,
-        e.g. ("actor", "flat").  Ordered behind pending optimiser work as optimizer_state_dict is (data-parallel: a
-        collective, it issues the held-back optimiser steps), without the host synchronisation."""
-        self.flush_optimizers()
-        self.join()
-        names = self._fp_table()[0]
-        out = torch.empty(len(names), 2, dtype=torch.int64, device=self.dev)
-        self._fingerprint_into(out)
-        return out, list(names)
-
-    def _replica_words(self, fp: torch.Tensor, steps: torch.Tensor) -> torch.Tensor:
-        """What the ranks compare: the hashes, the three Adam step counts, then the non-finite counts (whose maximum over
-        ranks tells every rank about a NaN on any).  Not the Philox key or counters: they differ per rank by design."""
-        return torch.cat([fp[:, 0], steps, fp[:, 1]])
-
-    def _replica_names(self) -> List[str]:
-        return [f"{g}.{b}" for g, b in self._FP_BUFFERS] + [f"{g}.step" for g in self._STEP_GROUPS]
-
-    def _read_verdict(self, hi: np.ndarray, lo: np.ndarray) -> dict:
-        n, names = len(self._FP_BUFFERS), self._replica_names()
-        mismatch = [names[i] for i in range(n + 3) if hi[i] != lo[i]]
-        nonfinite = {names[i]: int(hi[n + 3 + i]) for i in range(n) if hi[n + 3 + i] != 0}
-        return {"agree": not mismatch, "mismatch": mismatch, "nonfinite": nonfinite}
-
-    def check_replicas(self) -> dict:
-        """{"agree": bool, "mismatch": [names], "nonfinite": {name: count}}, the same on every rank.  Synchronous, and a
-        COLLECTIVE on the caller's communicator: every rank calls it at the same point.  One rank: the non-finite counts
-        only (agree = True).  Verdicts of periodic checks still in flight are resolved first."""
-        self.resolve_replica_checks()
-        fp, _ = self.fingerprint()
-        steps = torch.tensor([self.groups[g].step for g in self._STEP_GROUPS], dtype=torch.int64, device=self.dev)
-        hi, lo = self.dp.max_min_(self._replica_words(fp, steps))
-        return self._read_verdict(hi.cpu().numpy(), lo.cpu().numpy())
-
-    def sync_replicas(self, src: int = 0) -> None:
-        """Make every rank a bit-identical copy of rank `src`: flat, m, v of the three optimisers, the critic target, the
-        Adam step counts and checkpoint hyper-parameters adopted by load_optimizer_state_dict; then everything derived
-        from the weights is rebuilt as __init__ does (pack() of the four groups: packed weights, the Categorical plain
-        copies, the conv stacks' packs).  A COLLECTIVE on the caller's communicator; synchronous."""
-        self.resolve_replica_checks()
-        self.flush_optimizers()
-        self.join()
-        if self.world_size > 1:
-            for g, b in self._FP_BUFFERS:
-                self.dp.broadcast_(getattr(self.groups[g], b), src)
-            keys = ("lr", "eps", "weight_decay")
-            meta = [float(self.groups[g].step) for g in self._STEP_GROUPS]
-            for g in self._STEP_GROUPS:
-                ov = self._opt_over.get(g) or {}
-                meta += [x for k in keys for x in (float(k in ov), float(ov.get(k, 0.0)))]
-            meta = self.dp.broadcast_(torch.tensor(meta, dtype=torch.float64, device=self.dev), src).cpu().tolist()
-            for i, g in enumerate(self._STEP_GROUPS):
-                self.groups[g].step = int(meta[i])
-                part = meta[3 + 6 * i:9 + 6 * i]
-                ov = {k: part[2 * j + 1] for j, k in enumerate(keys) if part[2 * j]}
-                if ov:
-                    self._opt_over[g] = ov
-                else:
-                    self._opt_over.pop(g, None)
-        for g in ("model", "actor", "critic", "critic_target"):
-            self.pack(g)
-        if self._rn is not None and self.world_size > 1:      # each rank's own shard's range until now (DESIGN.md section 6)
-            self._rn_join()
-            st = self.dp.broadcast_(self._rn.state.clone(), src).cpu().tolist()
-            self._rn.load(dict(zip(("lo", "hi", "count", "skipped"), st)))
-        torch.cuda.current_stream().synchronize()
-
     # ------------------------------------------------------------------------------------------ return normalisation
     def return_norm_state(self) -> dict:
         """The running range of the percentile return normalisation as plain floats: {"lo", "hi", "count", "skipped"}
         (all zero on a fresh engine, and always with return_normalization="none").  Orders the pipeline streams before
         the read (join()) and synchronises; no collective."""
-        if self._rn is None:
-            return dict(lo=0.0, hi=0.0, count=0.0, skipped=0.0)
-        self._rn_join()
-        return dict(zip(("lo", "hi", "count", "skipped"), self._rn.state.cpu().tolist()))
-
-    def _rn_join(self) -> None:
-        """join(), and the latest bd_return_range wherever it was queued."""
-        self.join()
-        if self._rn.ev is not None:
-            torch.cuda.current_stream().wait_event(self._rn.ev)
+        return self._rn.state_dict() if self._rn is not None else dict(lo=0.0, hi=0.0, count=0.0, skipped=0.0)
 
     def load_return_norm_state(self, d: dict) -> None:
         """Set what return_norm_state returned; the next step's scale is max(floor, hi - lo) of it."""
         if self._rn is None:
             raise ValueError("load_return_norm_state: return_normalization is 'none'")
-        lo, hi, count, skipped = (float(d[k]) for k in ("lo", "hi", "count", "skipped"))
-        if not (math.isfinite(lo) and math.isfinite(hi) and count >= 0 and skipped >= 0):
-            raise ValueError(f"load_return_norm_state: not a range state: {d!r}")
-        self._rn_join()
-        self._rn.load(dict(lo=lo, hi=hi, count=count, skipped=skipped))
-        self._rn.ev = torch.cuda.Event()
-        self._rn.ev.record(torch.cuda.current_stream())
-
-    def _replica_check_due(self) -> bool:
-        """Is this train step one that issues the periodic check?  If so, first read the verdicts train_step has not read
-        (without the host throttle nothing else reads them), on the caller's stream: "resync" is a collective there."""
-        k = self.replica_check_interval
-        if k <= 0 or self._n_train_steps % k:
-            return False
-        if self._checks_out:
-            throttled = self.pipeline and self.host_ahead > 0
-            self.resolve_replica_checks(self._n_train_steps - self.host_ahead if throttled else None)
-        return True
-
-    def _enqueue_replica_check(self) -> None:
-        """Fingerprint + agree + asynchronous D2H of the verdict, on the current stream, which the caller has ordered behind
-        the optimiser steps issued so far.  One rank: the fingerprint alone (the NaN watch), no collective."""
-        n = len(self._FP_BUFFERS)
-        rec = self._check_pool.pop() if self._check_pool else _ReplicaVerdict(n)
-        rec.step, rec.collective = self._n_train_steps, self.world_size > 1 or self.dp.force
-        fp = torch.empty(n, 2, dtype=torch.int64, device=self.dev)
-        self._fingerprint_into(fp)
-        self._ev_fp = torch.cuda.Event()
-        self._ev_fp.record(torch.cuda.current_stream())
-        self._fp_wait = set(self._STEP_GROUPS)
-        if rec.collective:
-            for i, g in enumerate(self._STEP_GROUPS):
-                rec.steps[i] = self.groups[g].step
-            steps = rec.steps.to(self.dev, non_blocking=True)
-            # the critic's communicator, from the critic's stream: behind the critic all-reduce of the previous step and
-            # before this step's, never in front of a KL / world-model collective
-            hi, lo = self.dp.max_min_(self._replica_words(fp, steps), "critic")
-            rec.host.copy_(torch.cat([hi, lo]), non_blocking=True)
-        else:
-            rec.host[:2 * n].copy_(fp.view(-1), non_blocking=True)
-        rec.event = torch.cuda.Event()
-        rec.event.record(torch.cuda.current_stream())
-        self._checks_out.append(rec)
-
-    def resolve_replica_checks(self, upto: Optional[int] = None) -> None:
-        """Read the verdicts of the periodic checks issued at train steps <= `upto` (None: all), oldest first, and act on
-        them.  Data-parallel: every rank calls it at the same host step (train_step does; so do check_replicas,
-        sync_replicas and optimizer_state_dict, hence Dreamer.save) -- "resync" is a collective."""
-        while self._checks_out and (upto is None or self._checks_out[0].step <= upto):
-            rec = self._checks_out.pop(0)
-            rec.event.synchronize()
-            h, n = rec.host.numpy(), len(self._FP_BUFFERS)
-            if rec.collective:
-                v = self._read_verdict(h[:2 * n + 3].copy(), h[2 * n + 3:].copy())
-            else:
-                names = self._replica_names()
-                v = {"mismatch": [], "nonfinite": {names[i]: int(h[2 * i + 1]) for i in range(n) if h[2 * i + 1] != 0}}
-            self._check_pool.append(rec)
-            if v["nonfinite"]:       # under both policies: copying NaNs around repairs nothing
-                raise FloatingPointError(f"replica check at train step {rec.step}: non-finite values in "
-                                         + ", ".join(f"{k} ({c})" for k, c in v["nonfinite"].items()))
-            if v["mismatch"]:
-                text = (f"replica check at train step {rec.step}: the ranks differ in " + ", ".join(v["mismatch"])
-                        + " (data-parallel replicas must be bit-identical)")
-                if self.replica_on_mismatch == "raise":
-                    raise ReplicaMismatch(text)
-                if not self._resync_warned:
-                    import warnings
-                    warnings.warn(text + ": broadcasting rank 0's state (replica_on_mismatch='resync')")
-                    self._resync_warned = True
-                for r in self._checks_out:           # issued before the repair: stale
-                    r.event.synchronize()
-                self._check_pool += self._checks_out
-                self._checks_out = []
-                self.sync_replicas(0)
+        self._rn.load_state(d)
 
     # ------------------------------------------------------------------------------------------ forward pieces
     def encode(self, obs2d: torch.Tensor, M: int, save: bool = True):
@@ -1880,7 +1458,7 @@ class DreamerEngine:
         front of the KL / world-model all-reduces of step k+1 and stall dynamics learning k+1 half-way.  Deferred, the
         order per host step is kl, model (k+1), actor, critic (k): each is ready by the time its turn comes."""
         if self.pipeline and self.defer_opt:
-            self._pending_opt.append((span, group, slot, lr, red_ws, torch.cuda.current_stream(), self._cur_rec,
+            self._pending_opt.append((span, group, slot, lr, red_ws, torch.cuda.current_stream(), self._logs.cur,
                                       self._diag_now))
             return
         with self.span(span):
@@ -1925,13 +1503,13 @@ class DreamerEngine:
         self._diag_regions = diagnostics.REGIONS if self._diag_now else ()
         self._n_train_steps += 1
         lazy = sync_logs == "lazy"
-        rec = self._cur_rec = self._new_record() if lazy else None
+        rec = self._logs.cur = self._logs.new_record(self._diag if self._diag_now else None) if lazy else None
         if not self.pipeline:
             if noise is None:
                 noise = self.make_noise(B)
             feat = self._dynamics_phase(batch, noise, "")
-            if self._replica_check_due():
-                self._enqueue_replica_check()
+            if self.replica.due():
+                self.replica.enqueue()
             self._behaviour_phase(feat, noise, obs.shape[0] - 1, B, self.red_ws, None)
             return self._finish_step(rec, sync_logs)
         cur = torch.cuda.current_stream()
@@ -1961,7 +1539,7 @@ class DreamerEngine:
             if os.environ.get("BD_BATCH_GUARD", "1") != "0":      # "0": diagnosis only (tests show the race without it)
                 cur.wait_event(ev_old)
         self._flush_pending_opt()                   # actor / critic updates of the previous step (data-parallel runs)
-        if self._replica_check_due():
+        if self.replica.due():
             # The replica check, at the one point of a host step where every optimiser step issued so far is whole and the
             # same on every rank: world model k (ev_wm_done), actor and critic k - 1 (issued by now also on the deferred
             # schedule).  It runs on the critic's stream, which has a step of slack and carries the critic update k - 1
@@ -1971,7 +1549,7 @@ class DreamerEngine:
             with torch.cuda.stream(self._side):
                 self._side.wait_event(ev_wm_done)
                 self._side.wait_stream(s_bh)
-                self._enqueue_replica_check()
+                self.replica.enqueue()
         with torch.cuda.stream(s_bh):
             s_bh.wait_event(ev_wm_done)
             nz = noise if noise is not None else self.make_noise(B, "bh")
@@ -1987,15 +1565,15 @@ class DreamerEngine:
             self._bh_hist.append(self._ev_bh_done[par])
             if len(self._bh_hist) > self.host_ahead:
                 self._bh_hist.pop(0).synchronize()
-            if self._checks_out:                    # the verdict of `host_ahead` steps ago: complete, the same step on every rank
-                self.resolve_replica_checks(self._n_train_steps - self.host_ahead)
+            # the verdict of `host_ahead` steps ago, if one is out: complete, the same step on every rank
+            self.replica.resolve(self._n_train_steps - self.host_ahead)
         return self._finish_step(rec, sync_logs)
 
     def _finish_step(self, rec: Optional[_LogRecord], sync_logs):
         if rec is not None:                      # sync_logs == "lazy"
             rec.counts = dict(self._counts)
-            self._cur_rec = None
-            out = LazyLogs(self, rec)
+            self._logs.cur = None
+            out = LazyLogs(self._resolve_record, rec)
             rec.owner = weakref.ref(out)
             return out
         return self.logs() if sync_logs else {}
@@ -2619,40 +2197,4 @@ class DreamerEngine:
                                    self._diag_regions)
 
     def _logs_from(self, s: np.ndarray, c: dict) -> Dict[str, float]:
-        hp = self.hp
-        f32 = np.float32
-        N, Mi = f32(c["N"]), f32(c["Mi"])
-        obs, rew = s[SLOT_OBS] / N, s[SLOT_REW] / N
-        if c["sum_form"]:
-            kl = s[SLOT_KL] / N
-        else:
-            mean = s[SLOT_KL] / f32(c["N"] * c["S"] * self.world_size)
-            x = np.maximum(mean, f32(hp["free_nats"]))
-            kl = f32(hp["kl_balance"]) * x + f32(1 - hp["kl_balance"]) * x
-        ew = f32(hp["entropy_weight"]) if hp["entropy_weight"] != -1 else f32(0)
-        model_loss = obs + rew + kl * f32(hp["kl_loss_weight"])
-        mix = self._mix
-        # return normalisation: the return terms over the scale the step used; the entropy term is not divided
-        scale = s[SLOT_RN] if self._rn is not None and s[SLOT_RN] > 0 else f32(1)      # (0: no behaviour phase has run)
-        if mix is None:
-            objective = s[SLOT_RET] / scale + ew * s[SLOT_ENT]
-        else:           # w (rho R + (1 - rho) log pi(a) sg(R - b) + eta H), summed ("Mixed actor gradient")
-            objective = (f32(mix) * s[SLOT_RET] + f32(1 - mix) * s[SLOT_RF]) / scale + ew * s[SLOT_ENT]
-        out = {}
-        if self.d.use_discount:         # src/dreamer.py:287-290, 346-352
-            disc = s[SLOT_DISC] / N
-            model_loss = model_loss + disc * f32(hp["discount_weight"])
-            out["discount_loss"] = float(disc)
-            objective = s[SLOT_WOBJ] if mix is None else s[SLOT_WOBJ] + f32(1 - mix) * s[SLOT_RF] / scale
-        out.update({
-            "observation_loss": float(obs), "reward_loss": float(rew), "kl_loss": float(kl),
-            "model_loss": float(model_loss),
-            "actor_loss": float(-objective / Mi),
-            "policy_entropy": float(s[SLOT_ENT] / Mi),
-            "value_loss": float(s[SLOT_VAL] / Mi),
-            "grad_norm_model": float(math.sqrt(s[SLOT_GN_MODEL])), "grad_norm_actor": float(math.sqrt(s[SLOT_GN_ACTOR])),
-            "grad_norm_critic": float(math.sqrt(s[SLOT_GN_CRITIC])),
-        })
-        if self._rn is not None:
-            out.update(return_scale=float(s[SLOT_RN]), return_p_low=float(s[SLOT_RN + 1]), return_p_high=float(s[SLOT_RN + 2]))
-        return out
+        return logs_from(s, c, self.hp, self.world_size, self.d.use_discount, self._mix, self._rn is not None)

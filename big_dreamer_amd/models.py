@@ -15,7 +15,8 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from .engine import DreamerEngine, check_cnn_activation
+from .config import check_cnn_activation
+from .engine import DreamerEngine
 from .synth import DENSE_LAYERS
 
 

@@ -155,9 +155,9 @@ def my_app(argv):
     random.seed(params["seed"] + rank)
     if params["algorithm"] not in ("planet", "dreamer", "dreamerV2"):     # as src/main.py:73-81
         raise NotImplementedError(f'algorithm {params["algorithm"]} is not yet implemented.')
-    from big_dreamer_amd.engine import RETURN_NORM_KEYS, check_return_normalization
+    from big_dreamer_amd.config import RETURN_NORM_KEYS, check_return_normalization
     check_return_normalization(*(params["ActorCritic"][k] for k in RETURN_NORM_KEYS), algorithm=params["algorithm"])
-    from big_dreamer_amd.engine import CRITIC_HEAD_KEYS, check_critic_head
+    from big_dreamer_amd.config import CRITIC_HEAD_KEYS, check_critic_head
     check_critic_head(*(params["ActorCritic"][k] for k in CRITIC_HEAD_KEYS), algorithm=params["algorithm"])
     from big_dreamer_amd import checkpoint as ck
     for key in ("models", "experience_replay"):                    # multi-GPU: every rank loads its own ..._rank<r> file

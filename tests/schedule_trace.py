@@ -9,7 +9,8 @@ from big_dreamer_amd import _cabi as cabi
 from big_dreamer_amd import synth
 from tests.helpers import CASES as GAUSS, CAT_CASES
 
-PATCHED_MODULES = ("big_dreamer_amd.engine", "big_dreamer_amd.conv", "big_dreamer_amd.conv_stack")
+PATCHED_MODULES = ("big_dreamer_amd.engine", "big_dreamer_amd.conv", "big_dreamer_amd.conv_stack", "big_dreamer_amd.replica",
+                   "big_dreamer_amd.diagnostics_device")
 ROLES = (("wm", "_s_wm"), ("bh", "_s_bh"), ("side", "_side"), ("early", "_s_early"))
 # fields of the argument block that select a kernel form or an accumulation
 BLOCK_SCALARS = {

@@ -74,16 +74,16 @@ def test_equal_engines_have_equal_fingerprints_before_and_after_training(case):
 
 def test_the_watch_perturbs_nothing(case):
     plain, watched = engine(case), engine(case, replica_check_interval=1)
-    assert plain.replica_check_interval == 0 and plain.replica_on_mismatch == "raise"
+    assert plain.replica.interval == 0 and plain.replica.on_mismatch == "raise"
     steps(plain, case, 3)
     steps(watched, case, 3)
-    assert len(watched._checks_out) <= max(watched.host_ahead, 1) and not plain._checks_out
+    assert len(watched.replica._checks_out) <= max(watched.host_ahead, 1) and not plain.replica._checks_out
     watched.resolve_replica_checks()
-    assert not watched._checks_out
+    assert not watched.replica._checks_out
     assert words(plain) == words(watched)
     every_other = engine(case, replica_check_interval=2)
     steps(every_other, case, 3)
-    assert [r.step for r in every_other._checks_out] == [2]
+    assert [r.step for r in every_other.replica._checks_out] == [2]
     assert words(every_other) == words(plain)
 
 
@@ -96,7 +96,7 @@ def test_nan_in_a_world_model_weight_raises_at_the_next_check(case):
         eng.train_step(case["batch"][1], case["noise"][1], sync_logs=False)
         eng.resolve_replica_checks()            # at the latest here; never later
     assert "train step 2" in str(exc.value)
-    assert not any(r.step == 2 for r in eng._checks_out)
+    assert not any(r.step == 2 for r in eng.replica._checks_out)
     torch.cuda.synchronize()
 
 
@@ -109,11 +109,11 @@ def test_without_the_host_throttle_the_next_check_reads_the_verdict(case, monkey
     assert (eng.host_ahead == 0) if switch == "BD_HOST_AHEAD" else (not eng.pipeline)
     steps(plain, case, 2)
     steps(eng, case, 2)
-    assert [r.step for r in eng._checks_out] == [2]
+    assert [r.step for r in eng.replica._checks_out] == [2]
     assert words(plain) == words(eng)
     eng.groups["model"].flat[7] = float("nan")
     eng.train_step(case["batch"][2], case["noise"][2], sync_logs=False)          # check 3 sees it; check 2 is read, clean
-    assert [r.step for r in eng._checks_out] == [3]
+    assert [r.step for r in eng.replica._checks_out] == [3]
     with pytest.raises(FloatingPointError, match=r"train step 3: .*model\.flat"):
         eng.train_step(case["batch"][0], case["noise"][0], sync_logs=False)      # the next check reads verdict 3
     torch.cuda.synchronize()
@@ -129,7 +129,7 @@ def test_interval_zero_raises_nothing_and_check_replicas_counts(case):
     assert v == {"agree": True, "mismatch": [], "nonfinite": {"model.flat": 1, "critic.v": 1}}
     eng.train_step(case["batch"][1], case["noise"][1], sync_logs=False)
     eng.resolve_replica_checks()
-    assert not eng._checks_out
+    assert not eng.replica._checks_out
     v = eng.check_replicas()
     assert v["agree"] and v["nonfinite"]["model.flat"] >= 1
     torch.cuda.synchronize()
@@ -152,7 +152,7 @@ def test_agent_fingerprint_and_sync_with_one_rank():
           f"seq_len={D.L}", f"planning_horizon={D.H}", "experience_size=100", "replica_check_interval=5"]
     torch.manual_seed(0)
     agent = Dreamer(load_config(ov), Env())
-    assert agent.engine.replica_check_interval == 5
+    assert agent.engine.replica.interval == 5
     fp = agent.fingerprint()
     assert list(fp) == [f"{g}.{b}" for g, b in NAMES]
     for (g, b) in NAMES:

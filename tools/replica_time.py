@@ -94,7 +94,7 @@ def timed_ms(fn, n=7):
 
 
 def fingerprint_launch_us(eng, n=21):
-    names = eng._fp_table()[0]
+    names = eng.replica._fp_table()[0]
     out = torch.empty(len(names), 2, dtype=torch.int64, device=eng.dev)
     eng.flush_optimizers()
     eng.join()
@@ -103,7 +103,7 @@ def fingerprint_launch_us(eng, n=21):
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        eng._fingerprint_into(out)
+        eng.replica._fingerprint_into(out)
         e1.record()
         e1.synchronize()
         ts.append(e0.elapsed_time(e1) * 1e3)
