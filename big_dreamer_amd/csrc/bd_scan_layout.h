@@ -144,7 +144,9 @@ struct ImagineFwdLds {
     int mean_s, std_s, lp_rj;                   // [16][A] each
     int part;                                   // [kWaves][16][A][3] entropy partial sums
     int scratch, total;                         // split-K scratch (kSplitScratchFloats)
-    __host__ __device__ __forceinline__ ImagineFwdLds(const ScanDims& d, int A) {
+    // discrete (the Categorical actor): mean_s holds the logits image and nothing reads std_s, lp_rj or part, so the scratch
+    // starts where std_s would (432 A floats less: A = 64 fits the CU's 160 KiB, which it never does with them)
+    __host__ __device__ __forceinline__ ImagineFwdLds(const ScanDims& d, int A, bool discrete = false) {
         const int nh = d.Kb_h * kFragFloats, nhd = d.Kb_hd * kFragFloats;
         h_cur = 0;
         h_nxt = h_cur + nh;
@@ -157,7 +159,7 @@ struct ImagineFwdLds {
         std_s = mean_s + 16 * A;
         lp_rj = std_s + 16 * A;
         part = lp_rj + 16 * A;
-        scratch = part + kWaves * 16 * A * 3;
+        scratch = discrete ? std_s : part + kWaves * 16 * A * 3;
         total = scratch + kSplitScratchFloats;
     }
     __host__ __device__ bool vec_ok() const { return ((h_cur | h_nxt | xf | bufA | bufB | sf | af | scratch) & 3) == 0; }

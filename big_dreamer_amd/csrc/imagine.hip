@@ -42,7 +42,7 @@ __global__ __launch_bounds__(kThreads) void imagine_fwd_kernel(bd_imagine_fwd_ar
     const ScanDims d(a.Be, a.S, a.A, a.Hd);
     const int row0 = blockIdx.x * 16;
     const int F = a.Be + a.S, A = a.A;
-    const ImagineFwdLds L(d, A);
+    const ImagineFwdLds L(d, A, a.discrete_actions != 0);
     // (chained off the layout's offsets: the same addresses as `smem + L.region`, in the form that keeps this kernel's
     // registers and floating-point contraction where they were -- bd_scan_layout.h)
     float* h_cur = smem + L.h_cur;
@@ -627,8 +627,8 @@ int bd_debug_dstamps(unsigned long long* out64) {
 #endif
 
 static int imagine_forward_scan(const bd_imagine_fwd_args* a, void* stream) {
-    BD_REQUIRE(a && a->N > 0 && a->Hm > 0 && a->Be > 0 && a->S > 0 && a->A > 0 && a->A <= kMaxA && a->Hd > 0 &&
-                   a->n_samples > 0, "bd_imagine_forward: bad dims");
+    BD_REQUIRE(a && a->N > 0 && a->Hm > 0 && a->Be > 0 && a->S > 0 && a->A > 0 && a->Hd > 0 && a->n_samples > 0,
+               "bd_imagine_forward: bad dims");
     BD_REQUIRE(a->S <= kHeadMaxN && a->A <= kHeadMaxN, "bd_imagine_forward: state / action width above %d", kHeadMaxN);
     BD_REQUIRE(a->w_embed_s && a->w_embed_a && a->b_embed && a->w_ir && a->w_iz && a->w_in && a->w_hr && a->w_hz &&
                    a->w_hn && a->b_ih && a->b_hh && a->w_p1 && a->b_p1 && a->w_p2m && a->w_p2s && a->b_p2,
@@ -643,7 +643,7 @@ static int imagine_forward_scan(const bd_imagine_fwd_args* a, void* stream) {
                "the caller's bd_actor_entropy / bd_actor_entropy_rng launch)");
     BD_REQUIRE(a->feat && a->prior_std && a->entropy && a->action, "bd_imagine_forward: missing outputs");
     const ScanDims d(a->Be, a->S, a->A, a->Hd);
-    const ImagineFwdLds L(d, a->A);
+    const ImagineFwdLds L(d, a->A, a->discrete_actions != 0);
     BD_REQUIRE(L.vec_ok(), "bd_imagine_forward: misaligned LDS layout");
     const size_t lds = (size_t)L.total * sizeof(float);
     BD_REQUIRE(lds <= (size_t)kMaxLds, "bd_imagine_forward: needs %zu B of LDS", lds);
@@ -686,8 +686,8 @@ int bd_imagine_forward(const bd_imagine_fwd_args* a, void* stream) {
 }
 
 int bd_imagine_backward(const bd_imagine_bwd_args* a, void* stream) {
-    BD_REQUIRE(a && a->N > 0 && a->Hm > 0 && a->Be > 0 && a->S > 0 && a->A > 0 && a->A <= kMaxA && a->Hd > 0,
-               "bd_imagine_backward: bad dims");
+    BD_REQUIRE(a && a->N > 0 && a->Hm > 0 && a->Be > 0 && a->S > 0 && a->A > 0 && a->Hd > 0, "bd_imagine_backward: bad dims");
+    BD_REQUIRE(a->A <= kMaxA, "bd_imagine_backward: action width %d above %d", a->A, kMaxA);
     BD_REQUIRE(a->wt_embed_s && a->wt_embed_a && a->wt_ir && a->wt_iz && a->wt_in && a->wt_hr && a->wt_hz && a->wt_hn &&
                    a->wt_p1 && a->wt_p2m && a->wt_p2s && a->wt_a[0] && a->wt_a[1] && a->wt_a[2] &&
                    (a->discrete_actions || (a->wt_a4m && a->wt_a4s)),

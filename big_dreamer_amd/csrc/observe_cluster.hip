@@ -593,7 +593,7 @@ size_t bd_scan_lds_bytes(int kernel, int Be, int S, int D, int C, int A, int Hd,
         BD_LAYOUT(BD_SCAN_OBSERVE_CBWD, ObserveBwdLds L(d, S, kObsCbwdScratch));
         BD_LAYOUT(BD_SCAN_OBSERVE_KFWD, KsplitFwdLds L(d, S));
         BD_LAYOUT(BD_SCAN_OBSERVE_KBWD, KsplitBwdLds L(d, S));
-        BD_LAYOUT(BD_SCAN_IMAGINE_FWD, ImagineFwdLds L(d, A));
+        BD_LAYOUT(BD_SCAN_IMAGINE_FWD, ImagineFwdLds L(d, A));   // the tanh-Normal actor's layout (the Categorical one's is smaller)
         BD_LAYOUT(BD_SCAN_IMAGINE_BWD, ImagineBwdLds L(d, S));
         BD_LAYOUT(BD_SCAN_OBSERVE_CAT_FWD, CatObserveFwdLds L(d, Be, D, CatFull(D, C), 0));
         BD_LAYOUT(BD_SCAN_OBSERVE_CAT_BWD, CatObserveBwdLds L(d, CatGeo(D, C), 0));

@@ -1012,6 +1012,7 @@ int bd_imagine_cat_forward(const bd_imagine_cat_fwd_args* a, void* stream) {
 int bd_imagine_cat_backward(const bd_imagine_cat_bwd_args* a, void* stream) {
     BD_REQUIRE(a && a->N > 0 && a->Hm > 0 && a->Be > 0 && a->A > 0 && a->Hd > 0, "bd_imagine_cat_backward: bad dims");
     BD_CAT_GEO("bd_imagine_cat_backward");
+    BD_REQUIRE(a->A <= kHeadMaxN, "bd_imagine_cat_backward: action width %d above %d", a->A, kHeadMaxN);
     BD_REQUIRE(a->wt_embed_s && a->wt_embed_a && a->wt_ir && a->wt_iz && a->wt_in && a->wt_hr && a->wt_hz && a->wt_hn &&
                    a->wt_p1 && a->wt_p2 && a->wt_a[0] && a->wt_a[1] && a->wt_a[2] &&
                    (a->discrete_actions || (a->wt_a4m && a->wt_a4s)),

@@ -1,6 +1,7 @@
 """Float64 references, one step and one layer at a time, for the Categorical RSSM scan kernels: the observe scan in its
 one-workgroup and cluster forms (csrc/scan_cat.hip, observe_cat_cluster.hip) and the imagination scan with the tanh-Normal
-actor (csrc/scan_cat.hip), heads and one-hot state helpers from csrc/bd_categorical.h.  The method, the `(value, S, A)`
+actor or the Categorical one (csrc/scan_cat.hip; the latter restated in tests/scan_ref.py), heads and one-hot state
+helpers from csrc/bd_categorical.h.  The method, the `(value, S, A)`
 triples, `check_layers` / `fill_layers` and every allowance are those of tests/scan_ref.py (read its docstring first);
 this file adds what the one-hot state changes.
 
@@ -53,8 +54,8 @@ import torch.nn.functional as F
 
 from tests import scan_ref as R
 from tests.dense_ref import elu64
-from tests.reduce_ref import TINY, cat_probs_ref
-from tests.scan_ref import ALL, D64, HW, U, cdiv, lin
+from tests.scan_ref import (ALL, D64, HW, U, cdiv, discrete_actor_layers, discrete_actor_tail, exp1, first_max,  # noqa: F401
+                            jacobian, lin, ratios64)
 
 _CD = namedtuple("CDims", "T B Be D C A Hd")     # imagination: T = Hm, B = N
 
@@ -69,10 +70,10 @@ class CDims(_CD):
 
 # ---- parameters, inputs -------------------------------------------------------------------------------------------------
 
-def make_weights(d: CDims, seed: int, device="cpu", imagine: bool = False, bias_high: bool = False):
+def make_weights(d: CDims, seed: int, device="cpu", imagine: bool = False, bias_high: bool = False, actor=None):
     """scan_ref.make_weights with the head narrowed to S logits.  bias_high: b_2 raised on the upper half of the classes,
     so that class indices >= C / 2 are the ones sampled (C = 256: indices that do not fit a signed byte)."""
-    W = R.make_weights(d, seed, device, imagine)
+    W = R.make_weights(d, seed, device, imagine, actor)
     W["W_2"], W["b_2"] = W["W_2"][:d.S].contiguous(), W["b_2"][:d.S].contiguous()
     if bias_high:
         W["b_2"].view(d.D, d.C)[:, d.C // 2:] += 6.0
@@ -97,10 +98,6 @@ def make_state(B, D, C, kind, g):
     return s
 
 
-def exp1(g, *shape):
-    return torch.empty(*shape).exponential_(generator=g).clamp_min(1e-6)
-
-
 def make_observe_inputs(d: CDims, seed: int, device="cpu", nonterm="zeros", init="mixed"):
     I = R.make_observe_inputs(d, seed, "cpu", nonterm=nonterm)
     g = torch.Generator().manual_seed(seed + 5000)
@@ -116,17 +113,23 @@ def make_observe_grads(d: CDims, seed: int, device="cpu", dpl=True):
     return dict(dfeat=r(d.T, d.B, d.Be + d.S), dpost_logits=r(d.T, d.B, d.S) if dpl else None)
 
 
-def make_imagine_inputs(d: CDims, seed: int, device="cpu", start="mixed", discrete=False):
-    """discrete: eps_action holds the Exp(1) draws of the Categorical actor's sampler."""
+def make_imagine_inputs(d: CDims, seed: int, device="cpu", start="mixed", discrete=False, saturated=False):
+    """discrete: eps_action holds the Exp(1) draws of the Categorical actor's sampler; saturated: scan_ref.set_sat_gate."""
     g = torch.Generator().manual_seed(seed + 3000)
     r = lambda *s: torch.randn(*s, generator=g)
     h = torch.tanh(r(d.B, d.Be))
     I = dict(eps_action=exp1(g, d.T, d.B, d.A) if discrete else r(d.T, d.B, d.A), q_prior=exp1(g, d.T, d.B, d.S))
     I["start_feat"] = torch.cat([h, make_state(d.B, d.D, d.C, start, g)], 1)
+    if saturated:
+        R.set_sat_gate(I["start_feat"])
     return {k: v.to(device) for k, v in I.items()}
 
 
 make_imagine_grads = R.make_imagine_grads
+
+
+def make_discrete_case(d, seed, variant="regular", device="cpu"):
+    return R.make_discrete_case(d, seed, variant, device, make_weights, make_imagine_inputs)
 
 
 # ---- the sample ---------------------------------------------------------------------------------------------------------
@@ -142,16 +145,10 @@ def sample_margin(dk, dstar, C: int, path: str):
     return (2 * dk.abs() + 2 * dstar.abs() + 2 * math.log(max(C, 1)) + 8) * U
 
 
-def ratios64(logits, q, D, C):
-    l = logits.double().reshape(-1, D, C)
-    d = l - l.max(-1, keepdim=True).values
-    assert float(d.min()) > -80.0 and float(q.min()) >= 1e-30, "ratios outside the normal range: the margin does not hold"
-    return torch.softmax(l, -1) / q.double().reshape(-1, D, C), d
-
-
-def sample_check(logits, q, sidx, D, C, path, tag=""):
+def sample_check(logits, q, sidx, D, C, path, tag="", margin_C=None):
     """Every (row, factor): the kernel's class within the margin of the float64 winner.  Returns (ambiguous factors,
-    factors, factors whose class is >= 128)."""
+    factors, factors whose class is >= 128).  margin_C: the class count of the margin's ln C where it is not C."""
+    mC = margin_C or C
     r, d = ratios64(logits, q, D, C)
     k = sidx.long().reshape(-1, D, 1)
     assert int(k.min()) >= 0 and int(k.max()) < C, f"{tag}class index outside [0, {C})"
@@ -159,7 +156,7 @@ def sample_check(logits, q, sidx, D, C, path, tag=""):
     star = top.indices[..., :1]
     rk, rs = r.gather(-1, k), top.values[..., :1]
     dk, dst = d.gather(-1, k), d.gather(-1, star)
-    bad = ~(rk >= (1 - sample_margin(dk, dst, C, path)) * rs)
+    bad = ~(rk >= (1 - sample_margin(dk, dst, mC, path)) * rs)
     if bool(bad.any()):
         row, f, _ = (int(i) for i in bad.nonzero()[0])
         raise AssertionError(f"{tag}sample[row={row}, factor={f}]: {int(bad.sum())} of {bad.numel()} outside the margin; class "
@@ -168,13 +165,40 @@ def sample_check(logits, q, sidx, D, C, path, tag=""):
     amb = 0
     if C > 1:
         second = top.indices[..., 1:2]
-        amb = int((top.values[..., 1:2] >= (1 - sample_margin(d.gather(-1, second), dst, C, path)) * rs).sum())
+        amb = int((top.values[..., 1:2] >= (1 - sample_margin(d.gather(-1, second), dst, mC, path)) * rs).sum())
     return amb, bad.numel(), int((k >= 128).sum())
 
 
-def first_max(logits, q, D, C):
-    """argmax of the float64 ratios, the first maximum winning (the chained reference's sampler)."""
-    return ratios64(logits, q, D, C)[0].argmax(-1)
+def actor_sample_check(norm, q, action, A, rows=None, dup=None, tag="", path="libm"):
+    """The Categorical actor's draws of one step: the class read from `action` [N x A] against the margin on the kernel's
+    norm [N x A] (one factor of A classes, the libm path in both builds: bd_discrete.h has no hardware-exponential branch;
+    `path` lets the CPU tests count the ambiguous draws under the narrower hardware margin as well).
+    rows: the rows to check (the `saturated` variant passes its regular rows: the others are outside ratios64's domain and
+    are asserted exactly by the layers).  dup = (lo, hi): class hi is a planted copy of class lo, so their ratios tie by
+    construction and every row the pair wins would count as ambiguous; hi must never be the class (asserted), its column
+    is left out of the count, and the margin keeps ln A (lse runs over all A classes).  Returns sample_check's triple."""
+    k = action.argmax(-1, keepdim=True)
+    if rows is not None:
+        norm, q, k = norm[rows], q[rows], k[rows]
+    if dup is not None:
+        lo, hi = dup
+        assert not bool((k == hi).any()), f"{tag}class {hi} sampled although class {lo} ties with it"
+        keep = [c for c in range(A) if c != hi]
+        norm, q, k = norm[:, keep], q[:, keep], k - (k > hi).long()
+    if norm.shape[0] == 0:
+        return 0, 0, 0
+    return sample_check(norm, q, k, 1, norm.shape[1], path, tag, margin_C=A)
+
+
+def actor_checks(d, norm, eps, action, sat=None, dup=None, tag="", path="libm"):
+    """actor_sample_check over every step of a case ([T x N x A] tensors) and, with a planted pair, the duplicate check.
+    Returns (ambiguous draws, draws checked, times the planted pair won or None)."""
+    rows = None if sat is None else ~sat
+    amb = n = 0
+    for t in range(d.T):
+        a, m, _ = actor_sample_check(norm[t], eps[t], action[t], d.A, rows, dup, f"{tag}action t={t} ", path)
+        amb, n = amb + a, n + m
+    return amb, n, (R.actor_duplicate_check(d, norm, action) if dup is not None else None)
 
 
 DUP_LO, DUP_HI = 3, 11
@@ -237,20 +261,6 @@ def observe_fwd_layers(d: CDims, W, I, K, AL=HW, chain=False):
 
 # ---- observe backward ---------------------------------------------------------------------------------------------------
 
-def jacobian(logits, g, Sg, Ag, D, C):
-    """Straight-through softmax Jacobian per factor as a (value, S, A) triple: p (g - sum_c p g), p from `logits`."""
-    sh = g.shape
-    p, Sp, _ = cat_probs_ref(logits.reshape(-1, D, C))
-    g, Sg = g.reshape(-1, D, C), Sg.reshape(-1, D, C)
-    Ag = Ag.reshape(-1, D, C) if torch.is_tensor(Ag) else Ag + 0.0 * g
-    dot = (p * g).sum(-1, keepdim=True)
-    Sdot = (Sp * g.abs() + p * Sg).sum(-1, keepdim=True) + (p * g).abs().sum(-1, keepdim=True)
-    v = p * (g - dot)
-    Sv = Sp * (g - dot).abs() + p * (Sg + Sdot + (g - dot).abs()) + v.abs()
-    Av = p * (Ag + (p * Ag).sum(-1, keepdim=True)) + TINY * (g.abs() + dot.abs())
-    return v.reshape(sh), Sv.reshape(sh), Av.reshape(sh)
-
-
 def observe_bwd_layers(d: CDims, W, I, K, G, AL=HW):
     """I: forward inputs plus the forward's tensors the backward reads (feat, post_logits, sv_x, sv_gates, sv_q);
     G: dfeat / dpost_logits (None allowed); K: the five d_* tensors."""
@@ -301,53 +311,7 @@ def img_fwd_tensors(d: CDims, discrete=False):
     return t
 
 
-def discrete_actor_layers(d, W, x, I, K, t, AL=HW, chain=False):
-    """The Categorical actor (discrete_actions = 1, csrc/bd_discrete.h; tests/discrete_oracle.py's discrete_head): the A
-    outputs `out`, norm = out - logsumexp(out) (saved as sv_act_stats [.. x A]), p = softmax(norm), k = argmax(p / q) with
-    q = eps_action, action = (onehot(k) + p) - p, entropy = -sum p norm.
-    - norm: d lse = sum_c p_c d out_c <= max_c S_out, the fp32 exponentials, their sum over A <= 64 classes and the
-      logarithm move lse by less than (A + 6) u <= 8 C_TOL, the two additions round by u |lse| and u |norm|.
-    - action: the sampled class is read from the kernel's action (its entry above 0.5) and checked by `sample_check` on
-      the kernel's norm (one factor of A classes, libm margin); every other entry is (0 + p) - p = 0 exactly, the hot
-      entry fl(fl(1 + p) - p) lies within 2u (1 + p) <= 4u of 1.
-    - entropy from the kernel's norm: p carries cat_probs_ref's S_p."""
-    for l in range(4):
-        pre, S = lin(x, W["W_a0"] if l == 0 else W["W_a"][l - 1], W["b_a"][l])
-        yield f"sv_actor{l}", t, ALL, elu64(pre), S, AL.act
-        x = K[f"sv_actor{l}"][t]
-    out, So = lin(x, W["W_a4"][:d.A], W["b_a4"][:d.A])
-    lse = out.logsumexp(-1, keepdim=True)
-    yield "sv_act_stats", t, ALL, out - lse, So + So.max(-1, keepdim=True).values + out.abs() + 2 * lse.abs() + (out - lse).abs() + 8, 0.0
-    nk = K["sv_act_stats"][t]
-    if chain:
-        K["action"][t] = F.one_hot(first_max(nk, I["eps_action"][t], 1, d.A)[:, 0], d.A).to(D64)
-    hot = (K["action"][t] > 0.5).to(D64)
-    assert bool((hot.sum(-1) == 1).all()), f"action[t={t}]: not one class per row"
-    yield "action", t, ALL, hot, 0.0 * hot, 4 * U * hot
-    p, Sp, _ = cat_probs_ref(nk)
-    H = -(p * nk).sum(-1, keepdim=True)
-    yield "entropy", t, ALL, H, (Sp * nk.abs() + (p * nk).abs()).sum(-1, keepdim=True) + H.abs(), 0.0
-
-
-def discrete_actor_tail(d, I, K, G, dentropy):
-    """d_actor_out [.. x A] of the Categorical actor from the d loss / d action triple:
-    p (g - p.g) + dent (-p (norm + H)), p and H from the saved norm (bd_discrete.h disc_head_grad)."""
-    dent0 = R.f32(dentropy)
-
-    def tail(t, dA):
-        nk = I["sv_act_stats"][t]
-        v, Sv, Av = jacobian(nk, dA[0], dA[1], dA[2], 1, d.A)
-        p, Sp, _ = cat_probs_ref(nk)
-        H = -(p * nk).sum(-1, keepdim=True)
-        SH = (Sp * nk.abs() + (p * nk).abs()).sum(-1, keepdim=True) + H.abs()
-        dent = dent0 * G["ent_weight"][t][:, None] if G.get("ent_weight") is not None else dent0
-        e = -dent * p * (nk + H)
-        Se = abs(dent) * (Sp * (nk + H).abs() + p * (nk.abs() + SH + (nk + H).abs())) + 2 * e.abs()
-        yield "d_actor_out", t, ALL, v + e, Sv + Se + (v + e).abs(), Av
-    return tail
-
-
-def imagine_fwd_layers(d: CDims, W, I, K, AL=HW, chain=False, discrete=False):
+def imagine_fwd_layers(d: CDims, W, I, K, AL=HW, chain=False, discrete=False, sat=None):
     """bd_imagine_cat_forward with sv_act_stats given; tanh-Normal actor, or the Categorical one (discrete).  The start
     state is the dense I["start_feat"][:, Be:] (what start_sidx == NULL reads; with start_sidx the caller passes its
     one-hot image there)."""
@@ -356,7 +320,7 @@ def imagine_fwd_layers(d: CDims, W, I, K, AL=HW, chain=False, discrete=False):
         h_prev = K["feat"][t - 1][:, :Be] if t else I["start_feat"][:, :Be]
         s_prev = one_hot_rows(K["sidx"][t - 1], d.C) if t else I["start_feat"][:, Be:]
         if discrete:
-            yield from discrete_actor_layers(d, W, torch.cat([h_prev, s_prev], 1), I, K, t, AL, chain)
+            yield from discrete_actor_layers(d, W, torch.cat([h_prev, s_prev], 1), I, K, t, AL, chain, sat)
         else:
             yield from R.actor_layers(d, W, torch.cat([h_prev, s_prev], 1), I, K, t, AL)
         pre, S = lin(torch.cat([s_prev, K["action"][t]], 1), W["W_e"], W["b_e"])
@@ -372,12 +336,13 @@ def imagine_fwd_layers(d: CDims, W, I, K, AL=HW, chain=False, discrete=False):
         yield "feat", t, slice(Be, Be + d.S), hot, 0.0 * hot, 0.0
 
 
-def imagine_bwd_layers(d: CDims, W, I, K, G, dentropy, AL=HW, actor_pre=True, discrete=False):
+def imagine_bwd_layers(d: CDims, W, I, K, G, dentropy, AL=HW, actor_pre=True, discrete=False, sat=None):
     """scan_ref.imagine_bwd_layers with the Categorical prior head: I additionally holds prior_logits.  discrete: the
-    Categorical actor (sv_act_stats = norm [.. x A], d_actor_out [.. x A], no d_actor_pre)."""
+    Categorical actor (sv_act_stats = norm [.. x A], d_actor_out [.. x A]; d_actor_pre0..3 as the caller's bd_mlp_backward
+    writes them from d_actor_out).  sat: the saturated rows (scan_ref.discrete_actor_layers)."""
     def head(t, dm, Sdm, Adm):
         return R._mm(*jacobian(I["prior_logits"][t], dm, Sdm, Adm, d.D, d.C), W["W_2"])
-    tail = discrete_actor_tail(d, I, K, G, dentropy) if discrete else None
+    tail = discrete_actor_tail(d, I, K, G, dentropy, sat) if discrete else None
     yield from R.imagine_bwd_layers(d, W, I, K, G, dentropy, 0.0, AL, actor_pre, head=head, actor_tail=tail)
 
 
@@ -556,9 +521,16 @@ IMAGINE_SHAPES = {
     # region: 10752 floats against 10240 of split-K scratch and 1152 of logit image
     "a28": CDims(2, 17, 24, 4, 16, 28, 32),
 }
+# the Categorical actor (scan_ref.DISCRETE_SHAPES, read its comment): the A edges, one row with one class, and the tile
+# loop of cat_grid (257 tiles on 129 workgroups, as "tile_loop") with a second column block of actor logits
+DISCRETE_SHAPES = {
+    **{f"a{A}": CDims(3, 19, 40, 4, 16, A, 32) for A in (2, 16, 17, 33, 64)},
+    "n1_a1": CDims(1, 1, 40, 4, 16, 1, 32),
+    "tile_loop_a17": CDims(2, 4112, 32, 4, 8, 17, 32),
+}
 # dynamic LDS above 64 KiB: entry point -> shape names on the far side (every other shape of the table is below)
 OBSERVE_BIG_LDS = {"observe_fwd": {"c32_d32", "c64_d16", "full_width"},
                    "observe_bwd": {"c32_d32", "c32_d12", "c16_d20", "c64_d16", "c16_d17", "hd256", "full_width"}}
 # (tile_loop asks for the CU's whole LDS whatever its formula says: cat_grid keeps two of its workgroups off one CU)
 IMAGINE_BIG_LDS = {"imagine_fwd": {"c32_d32_a17"}, "imagine_bwd": {"c32_d32_a17", "c32_d12", "c16_d20"}}
-SEEDS = (11, 12, 24)      # the GPU tests' seeds: the CPU test asserts the ambiguous share of each on the float64 reference
+SEEDS = R.SEEDS           # the GPU tests' seeds: the CPU test asserts the ambiguous share of each on the float64 reference

@@ -1,6 +1,8 @@
 """Float64 references, one step and one layer at a time, for the Gaussian RSSM scan kernels: the observe scan in its three
 forms (csrc/observe.hip, observe_cluster.hip, observe_ksplit.hip) and the imagination scan with the tanh-Normal actor
-(csrc/imagine.hip).  Plain helpers like dense_ref.py / reduce_ref.py: the CPU tests run them on CPU tensors, the GPU
+or the Categorical one (csrc/imagine.hip; the Categorical actor's restatement, csrc/bd_discrete.h, lives here for both
+latent kinds: `discrete_actor_layers`, `discrete_actor_tail`, its variants `peaked` / `saturated` / duplicate classes in
+`make_discrete_case`).  Plain helpers like dense_ref.py / reduce_ref.py: the CPU tests run them on CPU tensors, the GPU
 tests on device tensors.
 
 Method.  A recurrence amplifies rounding error, so nothing here compares a whole sequence.  Every layer of every step is
@@ -69,7 +71,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.dense_ref import ACT_ALLOW, C_TOL, elu64, elu_grad_from_out64
-from tests.reduce_ref import SOFTPLUS_ALLOW
+from tests.reduce_ref import SOFTPLUS_ALLOW, TINY, cat_probs_ref
 
 U = 2.0 ** -24
 SIGMOID_ALLOW = 4 * U      # derivation in the module docstring
@@ -102,8 +104,57 @@ def to64(d):
 Dims = namedtuple("Dims", "T B Be S A Hd")      # imagination: T = Hm, B = N
 
 
-def make_weights(d: Dims, seed: int, device="cpu", imagine: bool = False):
-    """Random fp32 parameters in the PyTorch (out, in) layout; fan-in scaling keeps pre-activations O(1)."""
+ACTOR_KINDS = (None, "regular", "peaked", "saturated")
+PEAK_FACTOR = 10.0          # factor 30 reaches norm - max = -73, factor 60 leaves ratios64's domain (-80)
+SAT_LEAD = 120.0            # expf(-104) is already 0 in fp32; 120 leaves room for the spread of the other logits
+SAT_GATE, SAT_W = 100.0, 2.0
+
+
+def sat_class(A: int) -> int:
+    return A - 1
+
+
+def sat_rows(B: int, device="cpu"):
+    """The rows the `saturated` variant saturates: the even ones."""
+    return torch.arange(B, device=device) % 2 == 0
+
+
+def plant_saturated(d, W):
+    """The weight side of the `saturated` variant of the Categorical actor.  A bias is shared by all rows, so raising
+    b_a4[k] alone would saturate every row; the rows are told apart by a gate instead.  Belief unit 0 is carried
+    unchanged through every step (its update gate is sigmoid(40) = 1 in fp32: h_0[t] = 0 * n + 1 * h_0[t-1]) and holds
+    +0.9 on the even rows, -0.9 on the odd ones (make_imagine_inputs).  Actor unit 0 of every hidden layer reads only
+    the gate: ELU(100 * h_0) = 90 on even rows, -1 on odd rows (exp(-90) is below half an ulp of 1), then ELU of the unit
+    itself: 90 / ELU^3(-1) = -0.37.  Class k = A - 1 reads it with weight 2 and no other class reads it: on even rows
+    class k leads every other logit by 180 minus their O(1) spread (`discrete_actor_layers` asserts >= SAT_LEAD on the
+    float64 logits), on odd rows it moves by -0.75 and the row stays regular."""
+    Be, k = d.Be, sat_class(d.A)
+    W["W_ih"][Be], W["W_hh"][Be], W["b_ih"][Be], W["b_hh"][Be] = 0.0, 0.0, 40.0, 0.0
+    W["W_a0"][0], W["b_a"][0][0] = 0.0, 0.0
+    W["W_a0"][0, 0] = SAT_GATE
+    for l in range(3):
+        W["W_a"][l][0], W["W_a"][l][:, 0], W["b_a"][l + 1][0] = 0.0, 0.0, 0.0
+        W["W_a"][l][0, 0] = 1.0
+    W["W_a4"][:, 0] = 0.0
+    W["W_a4"][k, 0] = SAT_W
+
+
+def make_weights(d: Dims, seed: int, device="cpu", imagine: bool = False, actor=None):
+    """Random fp32 parameters in the PyTorch (out, in) layout; fan-in scaling keeps pre-activations O(1).
+    actor (the Categorical actor's variants): 'peaked' multiplies the A logit rows of W_a4 / b_a4 by PEAK_FACTOR (entropy
+    mean 1.4 / 2.3 at A = 17 / 64 instead of ln A - 0.1); 'saturated': plant_saturated."""
+    assert actor in ACTOR_KINDS, actor
+    W = _make_weights(d, seed, imagine)
+    if actor == "peaked":
+        W["W_a4"][:d.A] *= PEAK_FACTOR
+        W["b_a4"][:d.A] *= PEAK_FACTOR
+    elif actor == "saturated":
+        plant_saturated(d, W)
+    return {k: ([w.to(device) for w in v] if isinstance(v, list) else v.to(device)) for k, v in W.items()}
+
+
+def _make_weights(d: Dims, seed: int, imagine: bool):
+    device = "cpu"
     g = torch.Generator().manual_seed(seed)
 
     def w(n, k, gain=1.0):
@@ -149,12 +200,49 @@ def make_observe_grads(d: Dims, seed: int, device="cpu", dpm=True, dps=True):
                 dpost_std=r(d.T, d.B, d.S) if dps else None)
 
 
-def make_imagine_inputs(d: Dims, seed: int, device="cpu"):
+def exp1(g, *shape):
+    return torch.empty(*shape).exponential_(generator=g).clamp_min(1e-6)
+
+
+def set_sat_gate(start_feat):
+    """Belief unit 0 of the `saturated` variant: +0.9 on the even rows, -0.9 on the odd ones (plant_saturated)."""
+    start_feat[:, 0] = torch.where(sat_rows(start_feat.shape[0], start_feat.device), 0.9, -0.9).to(start_feat.dtype)
+
+
+def make_imagine_inputs(d: Dims, seed: int, device="cpu", discrete=False, saturated=False):
+    """discrete: eps_action holds the Exp(1) draws of the Categorical actor's sampler."""
     g = torch.Generator().manual_seed(seed + 3000)
     r = lambda *s: torch.randn(*s, generator=g)
     sf = torch.cat([torch.tanh(r(d.B, d.Be)), r(d.B, d.S)], 1)
-    I = dict(start_feat=sf, eps_action=r(d.T, d.B, d.A), eps_prior=r(d.T, d.B, d.S))
+    I = dict(start_feat=sf, eps_action=exp1(g, d.T, d.B, d.A) if discrete else r(d.T, d.B, d.A), eps_prior=r(d.T, d.B, d.S))
+    if saturated:
+        set_sat_gate(sf)
     return {k: v.to(device) for k, v in I.items()}
+
+
+DISCRETE_VARIANTS = ("peaked", "saturated", "duplicate")     # at A = 17 and A = 64; "regular" at every shape
+ACTOR_DUP = {17: (3, 11), 64: (5, 37)}      # inside one 16-lane group; across the xor-32 stage of disc_sample's butterfly
+
+
+def plant_actor_duplicate(d, W, eps_action):
+    """The duplicate-class case of the Categorical actor (scan_cat_ref.plant_duplicate for the prior's factors): class `hi`
+    gets the W_a4 row, the bias (raised by 3.0, so that the pair wins often) and the draws of class `lo`.  Their p / q tie
+    bit for bit; the first maximum, `lo`, must be the class sampled."""
+    lo, hi = ACTOR_DUP[d.A]
+    W["b_a4"][lo] += 3.0
+    W["W_a4"][hi], W["b_a4"][hi] = W["W_a4"][lo], W["b_a4"][lo]
+    eps_action[..., hi] = eps_action[..., lo]
+    return lo, hi
+
+
+def actor_duplicate_check(d, norm, action):
+    """Bit-equal log-probabilities of the planted pair, and never the higher index sampled.  Returns how often the pair won."""
+    lo, hi = ACTOR_DUP[d.A]
+    assert torch.equal(norm[..., lo], norm[..., hi]), "the log-probabilities of two identical classes differ in bits"
+    k = action.argmax(-1)
+    assert not bool((k == hi).any()), f"class {hi} sampled although class {lo} ties with it"
+    assert not bool((action[..., hi] != 0).any()), f"action entry {hi} nonzero although class {lo} ties with it"
+    return int((k == lo).sum())
 
 
 def make_imagine_grads(d: Dims, seed: int, device="cpu", ent_weight=True):
@@ -163,6 +251,16 @@ def make_imagine_grads(d: Dims, seed: int, device="cpu", ent_weight=True):
     r = lambda *s: torch.randn(*s, generator=g).to(device)
     return dict(dfeat=r(d.T, d.B, d.Be + d.S), slot2=r(d.T, d.B, d.A), slot3=r(d.T, d.B, d.A),
                 ent_weight=(torch.rand(d.T, d.B, generator=g).to(device) + 0.5) if ent_weight else None)
+
+
+def make_discrete_case(d, seed, variant="regular", device="cpu", weights=None, inputs=None):
+    """Weights and inputs of one case of the Categorical actor: (W, I, saturated rows or None, planted pair or None).
+    `weights` / `inputs`: make_weights / make_imagine_inputs of the latent kind (default: the Gaussian ones)."""
+    assert variant in ("regular",) + DISCRETE_VARIANTS, variant
+    W = (weights or make_weights)(d, seed, device, imagine=True, actor=variant if variant in ("peaked", "saturated") else None)
+    I = (inputs or make_imagine_inputs)(d, seed, device, discrete=True, saturated=variant == "saturated")
+    dup = plant_actor_duplicate(d, W, I["eps_action"]) if variant == "duplicate" else None
+    return W, I, (sat_rows(d.B, device) if variant == "saturated" else None), dup
 
 
 # ---- layer pieces ------------------------------------------------------------------------------------------------------
@@ -306,9 +404,11 @@ def observe_bwd_layers(d: Dims, W, I, K, G, min_std, AL=HW):
 
 # ---- imagination forward -----------------------------------------------------------------------------------------------
 
-def img_fwd_tensors(d: Dims):
-    t = dict(feat=d.Be + d.S, prior_mean=d.S, prior_std=d.S, action=d.A, sv_act_stats=4 * d.A, sv_x=d.Be, sv_gates=4 * d.Be,
-             sv_p=d.Hd, sv_act_us=2 * d.A)
+def img_fwd_tensors(d: Dims, discrete=False):
+    """discrete (the Categorical actor): sv_act_stats is A wide and holds norm, `entropy` is written by the scan, there is
+    no sv_act_us."""
+    t = dict(feat=d.Be + d.S, prior_mean=d.S, prior_std=d.S, action=d.A, sv_x=d.Be, sv_gates=4 * d.Be, sv_p=d.Hd)
+    t.update(dict(sv_act_stats=d.A, entropy=1) if discrete else dict(sv_act_stats=4 * d.A, sv_act_us=2 * d.A))
     t.update({f"sv_actor{l}": d.Hd for l in range(4)})
     return t
 
@@ -344,14 +444,120 @@ def actor_layers(d, W, x, I, K, t, AL=HW):
     yield "action", t, ALL, a, (1 - a * a) * Su + a.abs(), AL.tanh
 
 
-def imagine_fwd_layers(d: Dims, W, I, K, min_std, AL=HW):
-    """bd_imagine_forward_scan with sv_act_stats given, tanh-Normal actor.  K may lack prior_mean / sv_act_us (NULL)."""
+# ---- the Categorical actor (discrete_actions = 1), shared by both latent kinds ---------------------------------------------
+
+def ratios64(logits, q, D, C):
+    """softmax(l)_c / q_c per factor in float64 and d_c = l_c - max l (scan_cat_ref.py: "The sample")."""
+    l = logits.double().reshape(-1, D, C)
+    d = l - l.max(-1, keepdim=True).values
+    assert float(d.min()) > -80.0 and float(q.min()) >= 1e-30, "ratios outside the normal range: the margin does not hold"
+    return torch.softmax(l, -1) / q.double().reshape(-1, D, C), d
+
+
+def first_max(logits, q, D, C):
+    """argmax of the float64 ratios, the first maximum winning (the chained reference's sampler)."""
+    return ratios64(logits, q, D, C)[0].argmax(-1)
+
+
+def jacobian(logits, g, Sg, Ag, D, C):
+    """Straight-through softmax Jacobian per factor as a (value, S, A) triple: p (g - sum_c p g), p from `logits`."""
+    sh = g.shape
+    p, Sp, _ = cat_probs_ref(logits.reshape(-1, D, C))
+    g, Sg = g.reshape(-1, D, C), Sg.reshape(-1, D, C)
+    Ag = Ag.reshape(-1, D, C) if torch.is_tensor(Ag) else Ag + 0.0 * g
+    dot = (p * g).sum(-1, keepdim=True)
+    Sdot = (Sp * g.abs() + p * Sg).sum(-1, keepdim=True) + (p * g).abs().sum(-1, keepdim=True)
+    v = p * (g - dot)
+    Sv = Sp * (g - dot).abs() + p * (Sg + Sdot + (g - dot).abs()) + v.abs()
+    Av = p * (Ag + (p * Ag).sum(-1, keepdim=True)) + TINY * (g.abs() + dot.abs())
+    return v.reshape(sh), Sv.reshape(sh), Av.reshape(sh)
+
+
+def discrete_actor_layers(d, W, x, I, K, t, AL=HW, chain=False, sat=None):
+    """The Categorical actor (discrete_actions = 1, csrc/bd_discrete.h; tests/discrete_oracle.py's discrete_head): the A
+    outputs `out`, norm = out - logsumexp(out) (saved as sv_act_stats [.. x A]), p = softmax(norm), k = argmax(p / q) with
+    q = eps_action, action = (onehot(k) + p) - p, entropy = -sum p norm.
+    - norm: d lse = sum_c p_c d out_c <= max_c S_out, the fp32 exponentials, their sum over A <= 64 classes and the
+      logarithm move lse by less than (A + 6) u <= 8 C_TOL, the two additions round by u |lse| and u |norm|.
+    - action: the sampled class is read from the kernel's action (its entry above 0.5) and checked by `sample_check` on
+      the kernel's norm (one factor of A classes, libm margin); every other entry is (0 + p) - p = 0 exactly, the hot
+      entry fl(fl(1 + p) - p) lies within 2u (1 + p) <= 4u of 1.
+    - entropy from the kernel's norm: p carries cat_probs_ref's S_p.
+    sat (bool [N], the `saturated` variant): rows whose leading logit is at least SAT_LEAD above every other one
+    (asserted here on the float64 logits).  expf(-104) is 0 in fp32, so the kernel's numbers of such a row are determined
+    without a margin: s = 1 + 0, norm_k = 0, p = onehot(k) exactly, action = onehot(k) with hot entry
+    fl(fl(1 + 1) - 1) = 1, entropy = -(1 * 0 + sum 0 * norm) = 0.  Action and entropy of these rows are yielded with
+    S = 0 and no allowance: an exact comparison (norm keeps its bound).  The float64 values they replace are below 1e-49."""
+    for l in range(4):
+        pre, S = lin(x, W["W_a0"] if l == 0 else W["W_a"][l - 1], W["b_a"][l])
+        yield f"sv_actor{l}", t, ALL, elu64(pre), S, AL.act
+        x = K[f"sv_actor{l}"][t]
+    out, So = lin(x, W["W_a4"][:d.A], W["b_a4"][:d.A])
+    lse = out.logsumexp(-1, keepdim=True)
+    yield "sv_act_stats", t, ALL, out - lse, So + So.max(-1, keepdim=True).values + out.abs() + 2 * lse.abs() + (out - lse).abs() + 8, 0.0
+    nk = K["sv_act_stats"][t]
+    reg = torch.ones(out.shape[0], dtype=torch.bool, device=out.device) if sat is None else ~sat
+    if sat is not None:
+        top = out[sat].topk(2, -1).values
+        assert float((top[:, 0] - top[:, 1]).min()) >= SAT_LEAD, f"t={t}: a saturated row leads by less than {SAT_LEAD}"
+    if chain:
+        k = out.argmax(-1)
+        k[reg] = first_max(nk[reg], I["eps_action"][t][reg], 1, d.A)[:, 0]
+        K["action"][t] = F.one_hot(k, d.A).to(D64)
+    hot = (K["action"][t] > 0.5).to(D64)
+    assert bool((hot.sum(-1) == 1).all()), f"action[t={t}]: not one class per row"
+    hot = torch.where(reg[:, None], hot, F.one_hot(out.argmax(-1), d.A).to(D64))
+    yield "action", t, ALL, hot, 0.0 * hot, 4 * U * hot * reg[:, None]
+    p, Sp, _ = cat_probs_ref(nk)
+    H = -(p * nk).sum(-1, keepdim=True) * reg[:, None]
+    yield "entropy", t, ALL, H, ((Sp * nk.abs() + (p * nk).abs()).sum(-1, keepdim=True) + H.abs()) * reg[:, None], 0.0
+
+
+def discrete_actor_tail(d, I, K, G, dentropy, sat=None):
+    """d_actor_out [.. x A] of the Categorical actor from the d loss / d action triple:
+    p (g - p.g) + dent (-p (norm + H)), p and H from the saved norm (bd_discrete.h disc_head_grad).
+    sat: the saturated rows (discrete_actor_layers).  There p = onehot(k) exactly, so p.g = g_k, p_k (g_k - p.g) = 0,
+    p_c (...) = 0 for every other class and p (norm + H) = 0 (norm_k = H = 0): every entry is exactly 0, yielded with
+    S = 0 and no allowance."""
+    dent0 = f32(dentropy)
+
+    def tail(t, dA):
+        nk = I["sv_act_stats"][t]
+        v, Sv, Av = jacobian(nk, dA[0], dA[1], dA[2], 1, d.A)
+        p, Sp, _ = cat_probs_ref(nk)
+        H = -(p * nk).sum(-1, keepdim=True)
+        SH = (Sp * nk.abs() + (p * nk).abs()).sum(-1, keepdim=True) + H.abs()
+        dent = dent0 * G["ent_weight"][t][:, None] if G.get("ent_weight") is not None else dent0
+        e = -dent * p * (nk + H)
+        Se = abs(dent) * (Sp * (nk + H).abs() + p * (nk.abs() + SH + (nk + H).abs())) + 2 * e.abs()
+        reg = 1.0 if sat is None else (~sat)[:, None].to(D64)
+        yield "d_actor_out", t, ALL, (v + e) * reg, (Sv + Se + (v + e).abs()) * reg, Av * reg
+    return tail
+
+
+def saturated_exact(d, Kf, Kb, sat, tag=""):
+    """The exact statements about the saturated rows, spelled out on the tensors ([T x N x width]; Kb may be None)."""
+    hot = F.one_hot(torch.tensor(sat_class(d.A)), d.A).to(Kf["action"].dtype).to(Kf["action"].device)
+    assert bool((Kf["action"][:, sat] == hot).all()), f"{tag}saturated rows: the action is not the one-hot of class {sat_class(d.A)} with 1"
+    assert bool((Kf["entropy"][:, sat].abs() == 0).all()), f"{tag}saturated rows: |entropy| != 0"
+    assert bool((Kf["sv_act_stats"][:, sat][..., sat_class(d.A)] == 0).all()), f"{tag}saturated rows: norm of the leading class != 0"
+    if Kb is not None:
+        assert bool((Kb["d_actor_out"][:, sat] == 0).all()), f"{tag}saturated rows: d_actor_out != 0"
+    return int(sat.sum()) * d.T
+
+
+def imagine_fwd_layers(d: Dims, W, I, K, min_std, AL=HW, discrete=False, chain=False, sat=None):
+    """bd_imagine_forward_scan with sv_act_stats given; tanh-Normal actor, or the Categorical one (discrete; chain: the
+    action is set from the float64 ratios, the chained reference).  K may lack prior_mean / sv_act_us (NULL)."""
     ms = f32(min_std)
     Be = d.Be
     for t in range(d.T):
         fp = K["feat"][t - 1] if t else I["start_feat"]
         h_prev, s_prev = fp[:, :Be], fp[:, Be:]
-        yield from actor_layers(d, W, fp, I, K, t, AL)
+        if discrete:
+            yield from discrete_actor_layers(d, W, fp, I, K, t, AL, chain, sat)
+        else:
+            yield from actor_layers(d, W, fp, I, K, t, AL)
         pre, S = lin(torch.cat([s_prev, K["action"][t]], 1), W["W_e"], W["b_e"])
         yield "sv_x", t, ALL, elu64(pre), S, AL.act
         yield from gru_layers(W, K["sv_x"][t], h_prev, K, t, AL, Be)
@@ -381,13 +587,27 @@ def gauss_head_carry(W, I, min_std, AL):
     return head
 
 
-def imagine_bwd_layers(d: Dims, W, I, K, G, dentropy, min_std, AL=HW, actor_pre=True, head=None, actor_tail=None):
+def actor_pre_layers(W, I, K, t, AL, W_out):
+    """d_actor_pre3..0 of step t, each from the kernel's own gradient of the layer above (d_actor_out first, through
+    W_out: W_a4, or its A logit rows for the Categorical actor)."""
+    dn, Wn = K["d_actor_out"][t], W_out
+    for l in (3, 2, 1, 0):
+        yield (f"d_actor_pre{l}", t, ALL) + dgrad(dn, Wn, I[f"sv_actor{l}"][t], AL)
+        dn, Wn = K[f"d_actor_pre{l}"][t], W["W_a"][l - 1] if l else None
+
+
+def imagine_bwd_layers(d: Dims, W, I, K, G, dentropy, min_std, AL=HW, actor_pre=True, head=None, actor_tail=None,
+                       discrete=False, sat=None):
     """`head`: the prior head's backward (default: the Gaussian one; scan_cat_ref.py passes the Categorical one).
-    `actor_tail(t, dA)`: the layers from the d loss / d action triple on (default: the tanh-Normal actor below).
+    `actor_tail(t, dA)`: the layers from the d loss / d action triple up to d_actor_out (default: the tanh-Normal actor
+    below; discrete_actor_tail: the Categorical one, whose d_actor_pre chain starts from the A logit rows of W_a4).
+    discrete (with sat, the saturated rows): actor_tail = discrete_actor_tail.
     I: forward inputs and tensors (start_feat, feat, prior_std, action, eps_*, sv_actor0..3, sv_act_stats with the
     caller's slots 2, 3, sv_x, sv_gates, sv_p), float64; G: dfeat, ent_weight (or None); K: d_actor_out and, with
     actor_pre, d_actor_pre0..3 (written by the scan or by the caller's bd_mlp_backward: the same contract)."""
     dent0 = f32(dentropy)
+    if discrete and actor_tail is None:
+        actor_tail = discrete_actor_tail(d, I, K, G, dentropy, sat)
     head = head or gauss_head_carry(W, I, min_std, AL)
     Be, S_, A = d.Be, d.S, d.A
     dev = W["W_e"].device
@@ -418,6 +638,8 @@ def imagine_bwd_layers(d: Dims, W, I, K, G, dentropy, min_std, AL=HW, actor_pre=
         dA = _mm(*dE, Wea)
         if actor_tail is not None:
             yield from actor_tail(t, dA)
+            if actor_pre:
+                yield from actor_pre_layers(W, I, K, t, AL, W["W_a4"][:A])
             continue
         act, epa, st = I["action"][t], I["eps_action"][t], I["sv_act_stats"][t]
         th, sg, s2, s3 = st[:, :A], st[:, A:2 * A], st[:, 2 * A:3 * A], st[:, 3 * A:]
@@ -431,10 +653,7 @@ def imagine_bwd_layers(d: Dims, W, I, K, G, dentropy, min_std, AL=HW, actor_pre=
         yield "d_actor_out", t, slice(0, A), dmean * ft, Smean * ft + dmean.abs() + (dmean * ft).abs(), Axa * ft
         yield "d_actor_out", t, slice(A, 2 * A), dstd * sg, Sstd * sg + (dstd * sg).abs(), Axa * epa.abs() * sg
         if actor_pre:
-            dn, Wn = K["d_actor_out"][t], W["W_a4"]
-            for l in (3, 2, 1, 0):
-                yield (f"d_actor_pre{l}", t, ALL) + dgrad(dn, Wn, I[f"sv_actor{l}"][t], AL)
-                dn, Wn = K[f"d_actor_pre{l}"][t], W["W_a"][l - 1] if l else None
+            yield from actor_pre_layers(W, I, K, t, AL, W["W_a4"])
 
 
 # ---- drivers -----------------------------------------------------------------------------------------------------------
@@ -510,8 +729,11 @@ def observe_forms(B, Be, S, A, Hd):
     return forms
 
 
-def lds_bytes(entry: str, Be, S, A, Hd) -> int:
-    """Dynamic LDS of every entry point; the CPU test holds it to the library at every table shape (bd_scan_lds_bytes)."""
+def lds_bytes(entry: str, Be, S, A, Hd, discrete: bool = False) -> int:
+    """Dynamic LDS of every entry point; the CPU test holds it to the library at every table shape (bd_scan_lds_bytes).
+    discrete: the imagination forward with the Categorical actor keeps only the logits image of the four action regions
+    (bd_scan_layout.h ImagineFwdLds); the library's query describes the tanh-Normal layout, so the CPU test holds this
+    figure to the "needs N B of LDS" refusal of a shape above 160 KiB instead."""
     h, s, a, hd = cdiv(Be, 16), cdiv(S, 16), cdiv(A, 16), cdiv(Hd, 16)
     if entry == "observe_fwd":
         n = (3 * h + hd + s + a) * K_FRAG + 16 * S + K_SPLIT_SCRATCH
@@ -527,7 +749,7 @@ def lds_bytes(entry: str, Be, S, A, Hd) -> int:
     elif entry == "ksplit_bwd":
         n = 2 * s * K_FRAG + (K_WAVES // s) * ((16 * S + 3) & ~3) + 2 * K_WAVES * 256
     elif entry == "imagine_fwd":
-        n = (3 * h + 2 * hd + s + a) * K_FRAG + (3 * 16 + K_WAVES * 16 * 3) * A + K_SPLIT_SCRATCH
+        n = (3 * h + 2 * hd + s + a) * K_FRAG + (16 if discrete else 3 * 16 + K_WAVES * 16 * 3) * A + K_SPLIT_SCRATCH
     elif entry == "imagine_bwd":
         n = (6 * h + 3 * hd + 2 * s + 2 * a) * K_FRAG + 16 * S + K_SPLIT_PARTIAL
     else:
@@ -574,3 +796,23 @@ IMAGINE_SHAPES = {
     "n2450": Dims(2, 2450, 200, 30, 6, 200),
 }
 IMAGINE_BIG_LDS = {"imagine_fwd": {"n17_h2", "n17_h14", "a17", "n2450"}, "imagine_bwd": {"n2450"}}
+
+
+# ---- the Categorical actor (discrete_actions = 1) in the imagination scan -------------------------------------------------
+# A = 2 / 16: one column block of the logits GEMM, part of it / all of it; 17: a second block with one column; 33: a third;
+# 64: no invalid lane.  n1_a1: one row, one class (norm = 0, p = 1, H = 0, gradient 0).  n32_a17: N a multiple of 16.
+DISCRETE_SHAPES = {
+    **{f"a{A}": Dims(3, 19, 40, 10, A, 32) for A in (2, 16, 17, 33, 64)},
+    "n1_a1": Dims(1, 1, 40, 10, 1, 32),
+    "n32_a17": Dims(2, 32, 40, 10, 17, 32),
+    "ragged_a18": Dims(3, 19, 42, 9, 18, 30),
+}
+DISCRETE_EXACT = (("a17", "regular"), ("a64", "peaked"))      # the cases of the -DBD_EXACT_MATH twin
+# the seeds of the GPU tests that sample (the Categorical scans, the Categorical actor: its cases use the last one); the
+# CPU tests assert the ambiguous share of each on the float64 reference
+SEEDS = (11, 12, 24)
+
+
+def discrete_cases(shapes):
+    """(shape name, variant) of every GPU case of the Categorical actor."""
+    return [(n, "regular") for n in shapes] + [(n, v) for n in ("a17", "a64") for v in DISCRETE_VARIANTS]

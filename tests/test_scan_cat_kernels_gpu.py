@@ -225,10 +225,15 @@ N_SAMPLES = 3
 
 
 class ImagineCase:
-    def __init__(self, d, seed, ent_weight=True, start="mixed", dentropy=-0.37, bias_high=False, discrete=False):
-        self.d, self.dentropy, self.discrete = d, dentropy, discrete
-        self.W = W = RC.make_weights(d, seed, "cuda", imagine=True, bias_high=bias_high)
-        self.I = I = RC.make_imagine_inputs(d, seed, "cuda", start=start, discrete=discrete)
+    def __init__(self, d, seed, ent_weight=True, start="mixed", dentropy=-0.37, bias_high=False, discrete=False, variant=None):
+        """variant: one of the Categorical actor's variants (scan_ref.make_discrete_case; implies discrete)."""
+        self.d, self.dentropy, self.discrete, self.sat, self.dup = d, dentropy, discrete or variant is not None, None, None
+        if variant is not None:
+            self.W, self.I, self.sat, self.dup = RC.make_discrete_case(d, seed, variant, "cuda")
+        else:
+            self.W = RC.make_weights(d, seed, "cuda", imagine=True, bias_high=bias_high)
+            self.I = RC.make_imagine_inputs(d, seed, "cuda", start=start, discrete=discrete)
+        W, I = self.W, self.I
         self.G = G = RC.make_imagine_grads(d, seed, "cuda", ent_weight=ent_weight)
         g = torch.Generator().manual_seed(seed + 6000)
         self.eps_entropy = torch.randn(d.T, N_SAMPLES, d.B, d.A, generator=g).cuda()
@@ -317,8 +322,11 @@ class ImagineCase:
         return K
 
     def backward(self, fwd, actor_pre=True, chain=False, ent_weight=True):
+        """chain: the scan with d_actor_pre = NULL followed by the caller's bd_mlp_backward over all rows, bound as the engine
+        binds it (the Categorical actor: lddo = A and the transposed pack of W_a4's A logit rows as the last layer)."""
         c, d, pkT, p = cabi(), self.d, self.pkT, self.pin
         M, A = d.T * d.B, d.A
+        Ao = A if self.discrete else 2 * A
         b = c.ImagineCatBwdArgs()
         b.N, b.Hm, b.Be, b.D, b.C, b.A, b.Hd = d.B, d.T, d.Be, d.D, d.C, d.A, d.Hd
         b.wt_embed_s, b.wt_embed_a = pkT["embed_s"].data_ptr(), pkT["embed_a"].data_ptr()
@@ -327,7 +335,7 @@ class ImagineCase:
         b.wt_p1, b.wt_p2 = pkT["p1"].data_ptr(), pkT["p2"].data_ptr()
         for l in range(3):
             b.wt_a[l] = pkT[f"a{l + 1}"].data_ptr()
-        b.wt_a4m, b.wt_a4s = pkT["a4m"].data_ptr(), pkT["a4s"].data_ptr()
+        b.wt_a4m, b.wt_a4s = pkT["a4m"].data_ptr(), (None if self.discrete else pkT["a4s"].data_ptr())
         stats = fwd["sv_act_stats"].view.clone()
         if not self.discrete:
             stats[:, 2 * A:3 * A], stats[:, 3 * A:] = self.G["slot2"].reshape(M, A), self.G["slot3"].reshape(M, A)
@@ -337,18 +345,18 @@ class ImagineCase:
             setattr(b, k, v.ptr)
         b.start_feat, b.eps_action = p["start_feat"].ptr, p["eps_action"].ptr
         b.dfeat, b.dentropy, b.ent_weight = p["dfeat"].ptr, self.dentropy, (ptr(p["ent_weight"]) if ent_weight else None)
-        out = dict(d_actor_out=pout(M, A if self.discrete else 2 * A), d_actor_pre=pout(4 * M, d.Hd) if (actor_pre or chain) else None)
+        out = dict(d_actor_out=pout(M, Ao), d_actor_pre=pout(4 * M, d.Hd) if (actor_pre or chain) else None)
         b.d_actor_out, b.d_actor_pre = out["d_actor_out"].ptr, (out["d_actor_pre"].ptr if actor_pre else None)
         b.discrete_actions = int(self.discrete)
         c.check(c.lib.bd_imagine_cat_backward(C.byref(b), c.stream()))
         sync()
         if chain:       # the actor's hidden layers as the caller's dense chain over all rows (d_actor_pre = NULL form)
             m = c.MlpBwdArgs()
-            m.M, m.dout, m.lddo, m.dout_scale, m.n_layers = M, out["d_actor_out"].ptr, 2 * A, 1.0, 5
+            m.M, m.dout, m.lddo, m.dout_scale, m.n_layers = M, out["d_actor_out"].ptr, Ao, 1.0, 5
             for l in range(4):
                 m.layer[l] = c.LayerBwd(pkT[f"a{l}"].data_ptr() if l else None, keep["sv_actor"].ptr + 4 * l * M * d.Hd, d.Hd,
                                         d.Hd if l else d.Be + d.S, c.ACT_ELU, out["d_actor_pre"].ptr + 4 * l * M * d.Hd)
-            m.layer[4] = c.LayerBwd(pkT["a4"].data_ptr(), None, 2 * A, d.Hd, c.ACT_NONE, None)
+            m.layer[4] = c.LayerBwd(pkT["a4m" if self.discrete else "a4"].data_ptr(), None, Ao, d.Hd, c.ACT_NONE, None)
             c.check(c.lib.bd_mlp_backward(C.byref(m), c.stream()))
             sync()
         for k, v in out.items():
@@ -356,14 +364,16 @@ class ImagineCase:
         return out, stats.reshape(d.T, d.B, -1).double()
 
     def check_forward(self, out, AL=R.HW, exact=False, report=None, I64=None):
+        """Returns the float64 views and (ambiguous, draws, draws of a class >= 128): the prior's factors and, with the
+        Categorical actor, the actor's draws, counted together.  self.pair_won: how often the planted pair won (or None)."""
         d, I64 = self.d, I64 or self.I64
         K = self.tensors64(out)
-        R.check_layers(RC.imagine_fwd_layers(d, self.W64, I64, K, AL, discrete=self.discrete), K, report, "imagine ")
+        R.check_layers(RC.imagine_fwd_layers(d, self.W64, I64, K, AL, discrete=self.discrete, sat=self.sat), K, report, "imagine ")
         counts = [0, 0, 0]
+        if self.discrete:           # the actor's sampled class, read from the action, against the margin on the kernel's norm
+            amb, n, self.pair_won = RC.actor_checks(d, K["sv_act_stats"], I64["eps_action"], K["action"], self.sat, self.dup, "imagine ")
+            counts = [amb, n, 0]
         for t in range(d.T):
-            if self.discrete:       # the actor's sampled class, read from the action, against the margin on the kernel's norm
-                RC.sample_check(K["sv_act_stats"][t], I64["eps_action"][t], K["action"][t].argmax(-1, keepdim=True), 1, d.A, "libm",
-                                f"imagine action t={t} ")
             res = RC.sample_check(K["prior_logits"][t], I64["q_prior"][t], K["sidx"][t], d.D, d.C, RC.sample_path(d.C, exact),
                                   f"imagine t={t} ")
             counts = [x + y for x, y in zip(counts, res)]
@@ -379,7 +389,8 @@ class ImagineCase:
         I["sv_act_stats"] = stats64
         G = self.G64 if ent_weight else dict(self.G64, ent_weight=None)
         R.check_layers(RC.imagine_bwd_layers(d, self.W64, I, K, G, self.dentropy, AL, actor_pre=bwd["d_actor_pre"] is not None,
-                                             discrete=self.discrete), K, report, "imagine ")
+                                             discrete=self.discrete, sat=self.sat), K, report, "imagine ")
+        return K
 
 
 def run_imagine_shape(name, AL=R.HW, exact=False, extras=False):
@@ -438,11 +449,52 @@ def test_imagine_scan_against_float64(name):
         assert high > n // 2
 
 
+# ---- imagination with the Categorical actor at its own shapes and variants ------------------------------------------------------
+
+def run_discrete_case(name, variant, AL=R.HW, exact=False, extras=True):
+    """One case of scan_cat_ref.DISCRETE_SHAPES, as test_scan_kernels_gpu.run_discrete_case runs the Gaussian-latent ones:
+    forward and backward layer by layer, the backward as the engine runs it (the scan with d_actor_pre = NULL, then
+    bd_mlp_backward), ent_weight given and NULL, the draws of the actor and of the prior against their margins, the exact
+    statements of the saturated rows, second runs bit for bit.  Returns (worst ratios, (ambiguous, draws), pair wins)."""
+    d = RC.DISCRETE_SHAPES[name]
+    case = ImagineCase(d, RC.SEEDS[2], variant=variant)
+    rep = {}
+    fwd = case.forward()
+    Kf, (amb, n, _) = case.check_forward(fwd, AL, exact, rep)
+    bwd, stats = case.backward(fwd, actor_pre=False, chain=True)
+    Kb = case.check_backward(Kf, bwd, stats, AL, rep)
+    assert all(f"d_actor_pre{l}" in Kb for l in range(4))
+    bwd_nw, _ = case.backward(fwd, actor_pre=False, ent_weight=False)
+    Kb_nw = case.check_backward(Kf, bwd_nw, stats, AL, rep, ent_weight=False)
+    if case.sat is not None:
+        assert R.saturated_exact(d, Kf, Kb, case.sat, f"{name} ") > 0 and R.saturated_exact(d, Kf, Kb_nw, case.sat, f"{name} ") > 0
+    if d.A == 1:        # one class: norm = 0, p = 1, H = 0 and no gradient, exactly
+        assert bool((Kf["sv_act_stats"] == 0).all() and (Kf["action"] == 1).all() and (Kf["entropy"].abs() == 0).all())
+        assert bool((Kb["d_actor_out"] == 0).all())
+    if extras:
+        same_bits(fwd, case.forward(), f"{name} {variant} forward, second run")
+        bwd2, _ = case.backward(fwd, actor_pre=False, chain=True)
+        same_bits(bwd, bwd2, f"{name} {variant} backward and actor chain, second run")
+    return rep, (amb, n), case.pair_won
+
+
+@pytest.mark.parametrize("name,variant", R.discrete_cases(RC.DISCRETE_SHAPES))
+def test_imagine_scan_with_the_categorical_actor_against_float64(name, variant):
+    d = RC.DISCRETE_SHAPES[name]
+    if name == "tile_loop_a17":
+        assert RC.cdiv(d.B, 16) == 257 and RC.cat_grid(d.B) == 129     # workgroups walk two tiles, the last walks one
+    rep, (amb, n), won = run_discrete_case(name, variant)
+    print("SCAN_CAT_RATIOS imagine discrete", name, variant, json.dumps(rep), f"ambiguous {amb} of {n}" + (f", pair won {won}" if won is not None else ""))
+    assert rep and max(rep.values()) < 1.0, rep
+    assert amb <= 1e-3 * n, (amb, n)
+    assert won is None or won > 0, "the planted pair never won: the case checks nothing"
+
+
 # ---- the -DBD_EXACT_MATH twin, in a fresh process ------------------------------------------------------------------------
 
 def test_exact_math_twin_against_float64():
-    """c32_d12 and c16_d20, observe in every form and imagine, on libbigdreamer_hip_exact.so with the libm-grade
-    allowances and the libm sampler margin."""
+    """c32_d12 and c16_d20, observe in every form and imagine, and the Categorical actor's cases scan_ref.DISCRETE_EXACT, on
+    libbigdreamer_hip_exact.so with the libm-grade allowances and the libm sampler margin."""
     lib = os.path.join(ROOT, "big_dreamer_amd", "libbigdreamer_hip_exact.so")
     assert os.path.exists(lib), "build() makes the exact-math twin"
     env = dict(os.environ, BD_LIB=lib)
@@ -457,4 +509,7 @@ def test_exact_math_twin_against_float64():
         assert set(rep["observe"][name]) == {"single", "cluster4"}
         for group in list(rep["observe"][name].values()) + [rep["imagine"][name]]:
             assert group and max(group.values()) < 1.0, rep
+    assert set(rep["discrete"]) == {f"{n}:{v}" for n, v in R.DISCRETE_EXACT}
+    for group in rep["discrete"].values():
+        assert group and max(group.values()) < 1.0, rep
     assert rep["ambiguous"] <= 1e-3 * rep["factors"], rep

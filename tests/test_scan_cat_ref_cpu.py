@@ -13,7 +13,6 @@ from oracle import dreamer_oracle as O
 from tests import scan_cat_ref as RC
 from tests import scan_ref as R
 from tests import test_scan_ref_cpu as GC
-from tests.discrete_oracle import discrete_head
 
 D64 = torch.float64
 _cast, _gru, _elug, _gate_bwd, k64, rel_close, _leaves = GC._cast, GC._gru, GC._elug, GC._gate_bwd, GC.k64, GC.rel_close, GC._leaves
@@ -168,10 +167,10 @@ def emu_imagine_fwd(d, W, I, dtype, fault=None, exact=False, st=False, discrete=
             x = F.elu(pre)
             step[f"sv_actor{l}"] = x
         out = x @ W["W_a4"].t() + W["b_a4"]
-        if discrete:         # the Categorical actor as tests/discrete_oracle.py states it
+        if discrete:         # the Categorical actor as tests/discrete_oracle.py states it (or with a planted fault)
             out = out[:, :A]
-            a, ent, norm, _k = discrete_head(out, I["eps_action"][t])
-            step.update(sv_act_stats=norm, entropy=ent[:, None])
+            a, ent, norm, ae = GC.emu_discrete_head(out, I["eps_action"][t], fault)
+            step.update(sv_act_stats=norm, entropy=ent)
             th = mean = pre_s = sd = u = out
         else:
             th = torch.tanh(out[:, :A] / scale)
@@ -179,8 +178,8 @@ def emu_imagine_fwd(d, W, I, dtype, fault=None, exact=False, st=False, discrete=
             pre_s = out[:, A:] + init
             sd = F.softplus(pre_s) + amin
             u = mean + sd * I["eps_action"][t]
-            a = torch.tanh(u)
-        xe = F.elu(torch.cat([s, a], 1) @ W["W_e"].t() + W["b_e"])
+            a = ae = torch.tanh(u)
+        xe = F.elu(torch.cat([s, ae], 1) @ W["W_e"].t() + W["b_e"])
         hn, gates = _gru(W, xe, h, Be, None, [])
         pp = F.elu(hn @ W["W_1"].t() + W["b_1"])
         lg = pp @ W["W_2"].t() + W["b_2"]
@@ -200,7 +199,7 @@ def emu_imagine_fwd(d, W, I, dtype, fault=None, exact=False, st=False, discrete=
     return {k: torch.stack(v) for k, v in K.items()}, pres
 
 
-def emu_imagine_bwd(d, W, I, G, dentropy, dtype, exact=False, discrete=False):
+def emu_imagine_bwd(d, W, I, G, dentropy, dtype, exact=False, discrete=False, fault=None):
     W, I, G = _cast(W, dtype), _cast(I, dtype), _cast(G, dtype)
     path = RC.sample_path(d.C, exact)
     dent0 = dentropy if dtype == D64 else R.f32(dentropy)
@@ -221,17 +220,14 @@ def emu_imagine_bwd(d, W, I, G, dentropy, dtype, exact=False, discrete=False):
         dA = dE @ W["W_e"][:, S_:]
         st, act = I["sv_act_stats"][t], I["action"][t]
         dent = dent0 * G["ent_weight"][t][:, None] if G["ent_weight"] is not None else dent0
-        if discrete:
-            pa = torch.softmax(st, -1)
-            Hn = -(pa * st).sum(-1, keepdim=True)
-            K["d_actor_out"][t] = pa * (dA - (pa * dA).sum(-1, keepdim=True)) + dent * (-pa * (st + Hn))
-            continue
-        dxa = dA * (1 - act * act)
-        dmean = dxa + dent * st[:, 2 * A:3 * A]
-        dstd = dxa * I["eps_action"][t] + dent * st[:, 3 * A:]
-        dn = torch.cat([dmean * (1 - st[:, :A] ** 2), dstd * st[:, A:2 * A]], 1)
+        if discrete:        # the hidden layers below: the caller's bd_mlp_backward from d_actor_out through W_a4's A logit rows
+            dn, Wn = GC.emu_discrete_grad(st, dA, dent, fault), W["W_a4"][:A]
+        else:
+            dxa = dA * (1 - act * act)
+            dmean = dxa + dent * st[:, 2 * A:3 * A]
+            dstd = dxa * I["eps_action"][t] + dent * st[:, 3 * A:]
+            dn, Wn = torch.cat([dmean * (1 - st[:, :A] ** 2), dstd * st[:, A:2 * A]], 1), W["W_a4"]
         K["d_actor_out"][t] = dn
-        Wn = W["W_a4"]
         for l in (3, 2, 1, 0):
             dn = (dn @ Wn) * _elug(I[f"sv_actor{l}"][t])
             K[f"d_actor_pre{l}"][t] = dn
@@ -428,25 +424,93 @@ def test_discrete_actor_reference_equals_autograd_and_emulation_passes(monkeypat
         assert torch.equal(Ke[k], Kc[k]) if k == "sidx" else rel_close(Ke[k], Kc[k]) is None, k
     w = G6["ent_weight"][:, :, None] if G6["ent_weight"] is not None else 1.0
     loss = (Ke["feat"] * G6["dfeat"]).sum() + (-0.37 * w * Ke["entropy"]).sum()
-    ag = torch.stack(torch.autograd.grad(loss, pres["out"]))[..., :d.A]
-    Kb = R.empty_set({"d_actor_out": d.A}, d)
-    R.fill_layers(RC.imagine_bwd_layers(d, W6, dict(I6, **Kc), Kb, G6, -0.37, actor_pre=False, discrete=True), Kb)
-    rel_close(Kb["d_actor_out"], ag)
+    grads = torch.autograd.grad(loss, [p for k in ("out", "a0", "a1", "a2", "a3") for p in pres[k]])
+    ag = {k: torch.stack(grads[i * d.T:(i + 1) * d.T]) for i, k in
+          enumerate(("d_actor_out", "d_actor_pre0", "d_actor_pre1", "d_actor_pre2", "d_actor_pre3"))}
+    Kb = R.empty_set({"d_actor_out": d.A, **{f"d_actor_pre{l}": d.Hd for l in range(4)}}, d)
+    R.fill_layers(RC.imagine_bwd_layers(d, W6, dict(I6, **Kc), Kb, G6, -0.37, discrete=True), Kb)
+    for k in Kb:        # d_actor_pre0..3: the chain the caller's bd_mlp_backward runs from d_actor_out
+        rel_close(Kb[k], ag[k][..., :d.A] if k == "d_actor_out" else ag[k])
 
 
-@pytest.mark.parametrize("name", list(RC.OBSERVE_SHAPES) + ["img:" + n for n in RC.IMAGINE_SHAPES])
+# ---- the Categorical actor at its own shapes and variants (scan_ref.DISCRETE_VARIANTS) -----------------------------------------
+
+def _discrete_emulated(d, seed, variant, ew=True, fault=None, exact=False):
+    W, I, sat, dup = RC.make_discrete_case(d, seed, variant)
+    G = RC.make_imagine_grads(d, seed, ent_weight=ew)
+    with torch.no_grad():
+        Kf, pres = emu_imagine_fwd(d, W, I, torch.float32, fault, exact, discrete=True)
+        Kb = emu_imagine_bwd(d, W, dict(I, **Kf), G, -0.37, torch.float32, exact, discrete=True, fault=fault)
+    return R.to64(W), R.to64(I), R.to64(G), k64i(Kf), k64(Kb), sat, dup, pres
+
+
+def _check_discrete(d, W, I, G, Kf, Kb, sat, dup, rep=None):
+    """Every check the GPU test makes of a case; returns (ambiguous draws, draws, times the planted pair won), the prior's
+    factors counted with the actor's draws."""
+    R.check_layers(RC.imagine_fwd_layers(d, W, I, Kf, discrete=True, sat=sat), Kf, rep)
+    amb, n, won = RC.actor_checks(d, Kf["sv_act_stats"], I["eps_action"], Kf["action"], sat, dup)
+    for t in range(d.T):
+        a, m, _ = RC.sample_check(Kf["prior_logits"][t], I["q_prior"][t], Kf["sidx"][t], d.D, d.C, RC.sample_path(d.C))
+        amb, n = amb + a, n + m
+    R.check_layers(RC.imagine_bwd_layers(d, W, dict(I, **Kf), Kb, G, -0.37, discrete=True, sat=sat), Kb, rep)
+    if sat is not None:
+        assert R.saturated_exact(d, Kf, Kb, sat) > 0
+    return amb, n, won
+
+
+@pytest.mark.parametrize("name,variant", R.discrete_cases(RC.DISCRETE_SHAPES))
+def test_fp32_emulation_of_the_discrete_actor_passes(name, variant):
+    d = RC.DISCRETE_SHAPES[name]
+    for ew in (True, False):
+        W, I, G, Kf, Kb, sat, dup, pres = _discrete_emulated(d, RC.SEEDS[2], variant, ew)
+        rep = {}
+        amb, n, won = _check_discrete(d, W, I, G, Kf, Kb, sat, dup, rep)
+        assert max(rep.values()) < 1.0, rep
+        assert set(rep) >= ({"sv_act_stats", "action", "entropy", "d_actor_out", "d_actor_pre0", "d_actor_pre3"} if d.A > 1 else {"action"}), rep
+        assert share_ok(amb, n) and n == d.T * ((d.B if sat is None else int((~sat).sum())) + d.B * d.D), (amb, n)
+        assert won is None or won > 0, "the planted pair never won: the case checks nothing"
+        assert R.near_decision_fraction([p.double() for l in range(4) for p in pres[f"a{l}"]]) <= 1e-3
+
+
+@pytest.mark.parametrize("fault", list(GC.DISCRETE_FAULTS))
+def test_planted_discrete_actor_fault_fails(fault):
+    name, variant = GC.DISCRETE_FAULTS[fault]
+    d = RC.DISCRETE_SHAPES[name]
+    W, I, G, Kf, Kb, sat, dup, _ = _discrete_emulated(d, RC.SEEDS[2], variant, fault=fault)
+    with pytest.raises(AssertionError):
+        _check_discrete(d, W, I, G, Kf, Kb, sat, dup)
+
+
+@pytest.mark.parametrize("name", ["a17", "a64"])
+def test_planted_last_maximum_fails_the_actor_duplicate_check(name):
+    d = RC.DISCRETE_SHAPES[name]
+    W, I, G, Kf, Kb, sat, dup, _ = _discrete_emulated(d, RC.SEEDS[2], "duplicate", fault="sampler_ge")
+    R.check_layers(RC.imagine_fwd_layers(d, W, I, Kf, discrete=True), Kf)
+    RC.actor_checks(d, Kf["sv_act_stats"], I["eps_action"], Kf["action"])       # the margin alone does not see it
+    with pytest.raises(AssertionError):
+        RC.actor_checks(d, Kf["sv_act_stats"], I["eps_action"], Kf["action"], dup=dup)
+
+
+@pytest.mark.parametrize("name", list(RC.OBSERVE_SHAPES) + ["img:" + n for n in RC.IMAGINE_SHAPES] +
+                         [f"disc:{n}:{v}" for n, v in R.discrete_cases(RC.DISCRETE_SHAPES)])
 def test_ambiguous_share_of_the_float64_reference(name):
-    """On the chained float64 reference alone: at most 0.1 % of the factors have a runner-up within the margin of the
-    best, for every shape of the tables and every seed the GPU tests use."""
-    img = name.startswith("img:")
-    d = RC.IMAGINE_SHAPES[name[4:]] if img else RC.OBSERVE_SHAPES[name][0]
+    """On the chained float64 reference alone: at most 0.1 % of the draws -- the prior's or posterior's factors and, with
+    the Categorical actor, the actor's draws, counted together as the GPU tests count them -- have a runner-up within the
+    margin of the best, for every shape and variant of the tables and every seed the GPU tests use."""
+    img, dcase = name.startswith("img:"), name.startswith("disc:")
+    d = RC.DISCRETE_SHAPES[name.split(":")[1]] if dcase else RC.IMAGINE_SHAPES[name[4:]] if img else RC.OBSERVE_SHAPES[name][0]
     high = name.endswith("c256_d2")
     for seed in RC.SEEDS:
-        if img:
-            disc = name == "img:discrete"
-            W, I = R.to64(RC.make_weights(d, seed, imagine=True, bias_high=high)), R.to64(RC.make_imagine_inputs(d, seed, discrete=disc))
+        sat = dup = None
+        if img or dcase:
+            disc = dcase or name == "img:discrete"
+            if dcase:
+                W, I, sat, dup = RC.make_discrete_case(d, seed, name.split(":")[2])
+                W, I = R.to64(W), R.to64(I)
+            else:
+                W, I = R.to64(RC.make_weights(d, seed, imagine=True, bias_high=high)), R.to64(RC.make_imagine_inputs(d, seed, discrete=disc))
             K = RC.empty_set(RC.img_fwd_tensors(d, disc), d)
-            R.fill_layers(RC.imagine_fwd_layers(d, W, I, K, chain=True, discrete=disc), K)
+            R.fill_layers(RC.imagine_fwd_layers(d, W, I, K, chain=True, discrete=disc, sat=sat), K)
             lg, q = K["prior_logits"], I["q_prior"]
         else:
             nt, init, _ = RC.observe_variant(name)
@@ -455,8 +519,12 @@ def test_ambiguous_share_of_the_float64_reference(name):
             R.fill_layers(RC.observe_fwd_layers(d, W, I, K, chain=True), K)
             lg, q = K["post_logits"], I["q_post"]
         for path in ("hw", "libm"):
-            amb = sum(RC.sample_check(lg[t], q[t], K["sidx"][t], d.D, d.C, path)[0] for t in range(d.T))
-            assert share_ok(amb, d.T * d.B * d.D), (name, seed, path, amb)
+            amb, n = sum(RC.sample_check(lg[t], q[t], K["sidx"][t], d.D, d.C, path)[0] for t in range(d.T)), d.T * d.B * d.D
+            if img and disc or dcase:
+                a, m, won = RC.actor_checks(d, K["sv_act_stats"], I["eps_action"], K["action"], sat, dup, path=path)
+                assert m == d.T * (d.B if sat is None else int((~sat).sum())) and (won is None or won > 0), (name, seed, m, won)
+                amb, n = amb + a, n + m
+            assert share_ok(amb, n), (name, seed, path, amb, n)
 
 
 # ---- planted faults fail, each at the shape named for it ---------------------------------------------------------------
@@ -649,3 +717,10 @@ def test_rejecting_paths_return_without_a_launch():
     assert lib.bd_imagine_cat_forward(C.byref(f), None) != 0 and b"sv_act_us" in lib.bd_last_error()
     g = _fake(cabi.ImagineCatBwdArgs(), dict(img, discrete_actions=1))
     assert lib.bd_imagine_cat_backward(C.byref(g), None) != 0 and b"d_actor_pre" in lib.bd_last_error()
+    # A = 65: one lane per class does not reach class 64; both entry points say so themselves, for either actor (without a GPU
+    # every call fails: the message shows that this check came first)
+    for disc in (0, 1):
+        f = _fake(cabi.ImagineCatFwdArgs(), dict(img, A=65, n_samples=1, discrete_actions=disc), null=("sv_act_us",) if disc else ())
+        assert lib.bd_imagine_cat_forward(C.byref(f), None) != 0 and b"action width 65 above 64" in lib.bd_last_error(), lib.bd_last_error()
+        g = _fake(cabi.ImagineCatBwdArgs(), dict(img, A=65, discrete_actions=disc), null=("d_actor_pre",) if disc else ())
+        assert lib.bd_imagine_cat_backward(C.byref(g), None) != 0 and b"action width 65 above 64" in lib.bd_last_error(), lib.bd_last_error()

@@ -1,6 +1,6 @@
 """GPU tests of the Gaussian RSSM scan kernels against tests/scan_ref.py: bd_observe_forward / bd_observe_backward, the
-cluster calls in their K-split and round-1 forms, bd_imagine_forward_scan and bd_imagine_backward, called through the C
-ABI, every layer of every step checked in float64 from the kernel's own tensors of the layer before.  Every launch is
+cluster calls in their K-split and round-1 forms, bd_imagine_forward_scan and bd_imagine_backward (with the tanh-Normal actor
+and with the Categorical one, discrete_actions = 1), called through the C ABI, every layer of every step checked in float64 from the kernel's own tensors of the layer before.  Every launch is
 followed by a synchronise (which raises on a device error) before the next one; nothing retries.  Each test prints the
 worst err / bound ratio per tensor and form (run with -s to see them)."""
 import ctypes as C
@@ -12,6 +12,7 @@ import sys
 import pytest
 import torch
 
+from tests import scan_cat_ref as RC
 from tests import scan_ref as R
 from tests.dense_ref import SENTINEL, Placed, pack, placed_input
 
@@ -194,10 +195,16 @@ def test_observe_inference_and_partial_saves_are_bit_identical(name):
 # ---- imagination --------------------------------------------------------------------------------------------------------
 
 class ImagineCase:
-    def __init__(self, d, seed, ent_weight=True, min_std=0.1, dentropy=-0.37):
-        self.d, self.min_std, self.dentropy = d, min_std, dentropy
-        self.W = W = R.make_weights(d, seed, "cuda", imagine=True)
-        self.I = I = R.make_imagine_inputs(d, seed, "cuda")
+    """discrete: the Categorical actor (discrete_actions = 1) in one of its variants (scan_ref.make_discrete_case):
+    w_a4s and sv_act_us NULL, sv_act_stats A wide, the entropy written by the scan, the backward with d_actor_pre = NULL."""
+
+    def __init__(self, d, seed, ent_weight=True, min_std=0.1, dentropy=-0.37, discrete=False, variant="regular"):
+        self.d, self.min_std, self.dentropy, self.discrete, self.sat, self.dup = d, min_std, dentropy, discrete, None, None
+        if discrete:
+            self.W, self.I, self.sat, self.dup = R.make_discrete_case(d, seed, variant, "cuda")
+        else:
+            self.W, self.I = R.make_weights(d, seed, "cuda", imagine=True), R.make_imagine_inputs(d, seed, "cuda")
+        W, I = self.W, self.I
         self.G = G = R.make_imagine_grads(d, seed, "cuda", ent_weight=ent_weight)
         Be, S_, A = d.Be, d.S, d.A
         blocks = dict(embed_s=W["W_e"][:, :S_], embed_a=W["W_e"][:, S_:], p1=W["W_1"], p2m=W["W_2"][:S_], p2s=W["W_2"][S_:],
@@ -215,6 +222,9 @@ class ImagineCase:
 
     def widths(self):
         d = self.d
+        if self.discrete:
+            return dict(feat=d.Be + d.S, prior_mean=d.S, prior_std=d.S, action=d.A, sv_act_stats=d.A, sv_x=d.Be, sv_gates=4 * d.Be,
+                        sv_p=d.Hd, entropy=1)
         return dict(feat=d.Be + d.S, prior_mean=d.S, prior_std=d.S, action=d.A, sv_act_stats=4 * d.A, sv_x=d.Be, sv_gates=4 * d.Be,
                     sv_p=d.Hd, sv_act_us=2 * d.A, entropy=1)
 
@@ -226,7 +236,7 @@ class ImagineCase:
         M = d.T * d.B
         out = {k: pout(M, w) for k, w in self.widths().items()}
         out["sv_actor"] = pout(4 * M, d.Hd)
-        if not with_us:
+        if not with_us and not self.discrete:
             out["sv_act_us"] = None
         if not with_mean:
             out["prior_mean"] = None
@@ -246,7 +256,7 @@ class ImagineCase:
                 a.w_a[l] = pk[f"a{l + 1}"].data_ptr()
             for l in range(4):
                 a.b_a[l] = self.W["b_a"][l].data_ptr()
-            a.w_a4m, a.w_a4s, a.b_a4 = pk["a4m"].data_ptr(), pk["a4s"].data_ptr(), self.W["b_a4"].data_ptr()
+            a.w_a4m, a.w_a4s, a.b_a4 = pk["a4m"].data_ptr(), (None if self.discrete else pk["a4s"].data_ptr()), self.W["b_a4"].data_ptr()
             shift = lambda pl, w: None if pl is None else pl.ptr + 4 * t0 * d.B * w
             a.start_feat = p["start_feat"].ptr if t0 == 0 else shift(out["feat"], d.Be + d.S) - 4 * d.B * (d.Be + d.S)
             a.eps_action, a.eps_prior = shift(p["eps_action"], d.A), shift(p["eps_prior"], d.S)
@@ -255,25 +265,29 @@ class ImagineCase:
             for k, w in self.widths().items():
                 setattr(a, k, shift(out[k], w))
             a.sv_actor, a.sv_actor_stride = shift(out["sv_actor"], d.Hd), M * d.Hd
-            a.discrete_actions = 0
+            a.discrete_actions = int(self.discrete)
             c.check((c.lib.bd_imagine_forward if wrapper else c.lib.bd_imagine_forward_scan)(C.byref(a), c.stream()))
             sync()
         for k, v in out.items():
             assert v is None or v.outside_unchanged(), f"imagine forward: {k} written outside its rows"
-        if stats and not (wrapper and eps_entropy is not None):
+        if stats and not self.discrete and not (wrapper and eps_entropy is not None):
             assert bool((out["entropy"].buf == SENTINEL).all()), "the scan wrote an entropy although sv_act_stats was given"
         return out
 
     def tensors64(self, out):
         d = self.d
-        K = {k: (view64(v, d, v.cols) if v is not None else None) for k, v in out.items() if k not in ("sv_actor", "entropy")}
+        skip = ("sv_actor",) if self.discrete else ("sv_actor", "entropy")
+        K = {k: (view64(v, d, v.cols) if v is not None else None) for k, v in out.items() if k not in skip}
         sa = out["sv_actor"].view.reshape(4, d.T, d.B, d.Hd).double()
         K.update({f"sv_actor{l}": sa[l] for l in range(4)})
         return K
 
-    def backward(self, fwd, actor_pre=True, chain=False):
+    def backward(self, fwd, actor_pre=True, chain=False, ent_weight=True):
+        """chain: the scan with d_actor_pre = NULL followed by the caller's bd_mlp_backward over all rows, bound as the engine
+        binds it (the Categorical actor: lddo = A and the transposed pack of W_a4's A logit rows as the last layer)."""
         c, d, pkT, p = cabi(), self.d, self.pkT, self.pin
         M, A = d.T * d.B, d.A
+        Ao = A if self.discrete else 2 * A
         b = c.ImagineBwdArgs()
         b.N, b.Hm, b.Be, b.S, b.A, b.Hd = d.B, d.T, d.Be, d.S, d.A, d.Hd
         b.wt_embed_s, b.wt_embed_a = pkT["embed_s"].data_ptr(), pkT["embed_a"].data_ptr()
@@ -282,49 +296,59 @@ class ImagineCase:
         b.wt_p1, b.wt_p2m, b.wt_p2s = pkT["p1"].data_ptr(), pkT["p2m"].data_ptr(), pkT["p2s"].data_ptr()
         for l in range(3):
             b.wt_a[l] = pkT[f"a{l + 1}"].data_ptr()
-        b.wt_a4m, b.wt_a4s = pkT["a4m"].data_ptr(), pkT["a4s"].data_ptr()
+        b.wt_a4m, b.wt_a4s = pkT["a4m"].data_ptr(), (None if self.discrete else pkT["a4s"].data_ptr())
         stats = fwd["sv_act_stats"].view.clone()
-        stats[:, 2 * A:3 * A], stats[:, 3 * A:] = self.G["slot2"].reshape(M, A), self.G["slot3"].reshape(M, A)
+        if not self.discrete:
+            stats[:, 2 * A:3 * A], stats[:, 3 * A:] = self.G["slot2"].reshape(M, A), self.G["slot3"].reshape(M, A)
         keep = {k: placed_input(fwd[k].view.clone(), fwd[k].cols) for k in ("feat", "prior_std", "action", "sv_actor", "sv_x", "sv_gates", "sv_p")}
-        keep["sv_act_stats"] = placed_input(stats, 4 * A)
+        keep["sv_act_stats"] = placed_input(stats, stats.shape[1])
         for k, v in keep.items():
             setattr(b, k, v.ptr)
         b.start_feat, b.eps_action, b.eps_prior = p["start_feat"].ptr, p["eps_action"].ptr, p["eps_prior"].ptr
-        b.min_std, b.dfeat, b.dentropy, b.ent_weight = self.min_std, p["dfeat"].ptr, self.dentropy, ptr(p["ent_weight"])
-        out = dict(d_actor_out=pout(M, 2 * A), d_actor_pre=pout(4 * M, d.Hd) if (actor_pre or chain) else None)
+        b.min_std, b.dfeat, b.dentropy = self.min_std, p["dfeat"].ptr, self.dentropy
+        b.ent_weight = ptr(p["ent_weight"]) if ent_weight else None
+        out = dict(d_actor_out=pout(M, Ao), d_actor_pre=pout(4 * M, d.Hd) if (actor_pre or chain) else None)
         b.d_actor_out, b.d_actor_pre = out["d_actor_out"].ptr, (out["d_actor_pre"].ptr if actor_pre else None)
-        b.discrete_actions = 0
+        b.discrete_actions = int(self.discrete)
         c.check(c.lib.bd_imagine_backward(C.byref(b), c.stream()))
         sync()
         if chain:       # the actor's hidden layers as the caller's dense chain over all rows (d_actor_pre = NULL form)
             m = c.MlpBwdArgs()
-            m.M, m.dout, m.lddo, m.dout_scale, m.n_layers = M, out["d_actor_out"].ptr, 2 * A, 1.0, 5
+            m.M, m.dout, m.lddo, m.dout_scale, m.n_layers = M, out["d_actor_out"].ptr, Ao, 1.0, 5
             for l in range(4):
                 m.layer[l] = c.LayerBwd(pkT[f"a{l}"].data_ptr() if l else None, keep["sv_actor"].ptr + 4 * l * M * d.Hd, d.Hd,
                                         d.Hd if l else d.Be + d.S, c.ACT_ELU, out["d_actor_pre"].ptr + 4 * l * M * d.Hd)
-            m.layer[4] = c.LayerBwd(pkT["a4"].data_ptr(), None, 2 * A, d.Hd, c.ACT_NONE, None)
+            m.layer[4] = c.LayerBwd(pkT["a4m" if self.discrete else "a4"].data_ptr(), None, Ao, d.Hd, c.ACT_NONE, None)
             c.check(c.lib.bd_mlp_backward(C.byref(m), c.stream()))
             sync()
         for k, v in out.items():
             assert v is None or v.outside_unchanged(), f"imagine backward: {k} written outside its rows"
-        stats64 = stats.reshape(d.T, d.B, 4 * A).double()
+        stats64 = stats.reshape(d.T, d.B, -1).double()
         return out, stats64
 
     def check_forward(self, out, AL=R.HW, report=None):
         K = self.tensors64(out)
-        R.check_layers(R.imagine_fwd_layers(self.d, self.W64, self.I64, K, self.min_std, AL), K, report, "imagine ")
+        R.check_layers(R.imagine_fwd_layers(self.d, self.W64, self.I64, K, self.min_std, AL, discrete=self.discrete, sat=self.sat),
+                       K, report, "imagine ")
         return K
 
-    def check_backward(self, Kf, bwd, stats64, AL=R.HW, report=None):
+    def check_actor(self, K):
+        """The Categorical actor's sampled classes against the margin on the kernel's own norm (and the planted pair):
+        (ambiguous draws, draws, times the pair won or None)."""
+        return RC.actor_checks(self.d, K["sv_act_stats"], self.I64["eps_action"], K["action"], self.sat, self.dup, "imagine ")
+
+    def check_backward(self, Kf, bwd, stats64, AL=R.HW, report=None, ent_weight=True):
         d = self.d
-        K = dict(d_actor_out=view64(bwd["d_actor_out"], d, 2 * d.A))
+        K = dict(d_actor_out=view64(bwd["d_actor_out"], d, bwd["d_actor_out"].cols))
         if bwd["d_actor_pre"] is not None:
             ap = bwd["d_actor_pre"].view.reshape(4, d.T, d.B, d.Hd).double()
             K.update({f"d_actor_pre{l}": ap[l] for l in range(4)})
         I = dict(self.I64, **{k: v for k, v in Kf.items() if v is not None})
         I["sv_act_stats"] = stats64
-        R.check_layers(R.imagine_bwd_layers(d, self.W64, I, K, self.G64, self.dentropy, self.min_std, AL,
-                                            actor_pre=bwd["d_actor_pre"] is not None), K, report, "imagine ")
+        G = self.G64 if ent_weight else dict(self.G64, ent_weight=None)
+        R.check_layers(R.imagine_bwd_layers(d, self.W64, I, K, G, self.dentropy, self.min_std, AL, actor_pre=bwd["d_actor_pre"] is not None,
+                                            discrete=self.discrete, sat=self.sat), K, report, "imagine ")
+        return K
 
 
 def run_imagine_shape(name, AL=R.HW, ent_weight=True, extras=True):
@@ -357,10 +381,52 @@ def test_imagine_scan_against_float64(name):
         assert rep and max(rep.values()) < 1.0, rep
 
 
+# ---- imagination with the Categorical actor (discrete_actions = 1) -------------------------------------------------------------
+
+def run_discrete_case(name, variant, AL=R.HW, extras=True):
+    """One case of scan_ref.DISCRETE_SHAPES: forward and backward layer by layer, the backward as the engine runs it (the scan
+    with d_actor_pre = NULL, then bd_mlp_backward: d_actor_pre0..3 against the float64 chain), ent_weight given and NULL,
+    the actor's draws against the margin, the exact statements of the saturated rows; with extras the second runs and the
+    forward in two time segments, bit for bit.  Returns (worst err / bound per tensor, (ambiguous, draws, pair wins))."""
+    d = R.DISCRETE_SHAPES[name]
+    case = ImagineCase(d, R.SEEDS[2], discrete=True, variant=variant)
+    rep = {}
+    fwd = case.forward()
+    Kf = case.check_forward(fwd, AL, rep)
+    counts = case.check_actor(Kf)
+    bwd, stats = case.backward(fwd, actor_pre=False, chain=True)
+    Kb = case.check_backward(Kf, bwd, stats, AL, rep)
+    assert all(f"d_actor_pre{l}" in Kb for l in range(4))
+    bwd_nw, _ = case.backward(fwd, actor_pre=False, ent_weight=False)
+    Kb_nw = case.check_backward(Kf, bwd_nw, stats, AL, rep, ent_weight=False)
+    if case.sat is not None:
+        assert R.saturated_exact(d, Kf, Kb, case.sat, f"{name} ") > 0 and R.saturated_exact(d, Kf, Kb_nw, case.sat, f"{name} ") > 0
+    if d.A == 1:        # one class: norm = 0, p = 1, H = 0 and no gradient, exactly
+        assert bool((Kf["sv_act_stats"] == 0).all() and (Kf["action"] == 1).all() and (Kf["entropy"].abs() == 0).all())
+        assert bool((Kb["d_actor_out"] == 0).all())
+    if extras:
+        same_bits(fwd, case.forward(), f"{name} {variant} forward, second run")
+        bwd2, _ = case.backward(fwd, actor_pre=False, chain=True)
+        same_bits(bwd, bwd2, f"{name} {variant} backward and actor chain, second run")
+        if d.T >= 2:        # the chunked behaviour chain: two time segments through sv_actor_stride
+            same_bits(fwd, case.forward(split=d.T // 2), f"{name} {variant} forward in two time segments")
+    return rep, counts
+
+
+@pytest.mark.parametrize("name,variant", R.discrete_cases(R.DISCRETE_SHAPES))
+def test_imagine_scan_with_the_categorical_actor_against_float64(name, variant):
+    rep, (amb, n, won) = run_discrete_case(name, variant)
+    print("SCAN_RATIOS imagine discrete", name, variant, json.dumps(rep), f"ambiguous {amb} of {n}" + (f", pair won {won}" if won is not None else ""))
+    assert rep and max(rep.values()) < 1.0, rep
+    assert amb <= 1e-3 * n, (amb, n)
+    assert won is None or won > 0, "the planted pair never won: the case checks nothing"
+
+
 # ---- the -DBD_EXACT_MATH twin, in a fresh process ------------------------------------------------------------------------
 
 def test_exact_math_twin_against_float64():
-    """One observe case per form and one imagine case on libbigdreamer_hip_exact.so with the libm-grade allowances."""
+    """One observe case per form, one imagine case and the two cases of scan_ref.DISCRETE_EXACT (the Categorical actor) on
+    libbigdreamer_hip_exact.so with the libm-grade allowances."""
     lib = os.path.join(ROOT, "big_dreamer_amd", "libbigdreamer_hip_exact.so")
     assert os.path.exists(lib), "build() makes the exact-math twin"
     env = dict(os.environ, BD_LIB=lib)
@@ -372,5 +438,7 @@ def test_exact_math_twin_against_float64():
     rep = json.loads(line[-1][len("SCAN_EXACT_RESULT "):])
     print("SCAN_RATIOS exact", json.dumps(rep))
     assert set(rep["observe"]) == {"single", "ksplit", "round1"}
-    for group in list(rep["observe"].values()) + [rep["imagine"]]:
+    assert set(rep["discrete"]) == {f"{n}:{v}" for n, v in R.DISCRETE_EXACT}
+    for group in list(rep["observe"].values()) + [rep["imagine"]] + list(rep["discrete"].values()):
         assert group and max(group.values()) < 1.0, rep
+    assert rep["ambiguous"] <= 1e-3 * rep["draws"], rep

@@ -1,6 +1,8 @@
 """CPU tests of tests/scan_ref.py: the per-step float64 references of the observe and imagination scans chain to the
 oracle and to autograd; an fp32 emulation of the kernels' order of operations passes every tolerance at every shape of
-the GPU tables; planted faults fail; the host dispatch (cluster size, form, LDS side, rejections) matches the tables."""
+the GPU tables; planted faults fail; the host dispatch (cluster size, form, LDS side, rejections) matches the tables.  The
+Categorical actor (discrete_actions = 1) in the imagination scan: chain against autograd, emulation at every GPU case,
+planted faults, and the ambiguous share of its draws on the float64 reference."""
 import ctypes as C
 import types
 
@@ -9,7 +11,9 @@ import torch
 import torch.nn.functional as F
 
 from oracle import dreamer_oracle as O
+from tests import scan_cat_ref as RC
 from tests import scan_ref as R
+from tests.discrete_oracle import FLOAT_MIN, discrete_head
 
 D64 = torch.float64
 
@@ -115,13 +119,50 @@ def emu_observe_bwd(d, W, I, G, min_std, dtype, fault=None):
     return {k: torch.stack(v) for k, v in K.items()}
 
 
-def emu_imagine_fwd(d, W, I, min_std, dtype, with_us=True, with_mean=True):
+def emu_discrete_head(out, q, fault=None):
+    """The Categorical actor's row pass (csrc/bd_discrete.h) in the dtype of `out`: (action, entropy [N x 1], norm, the
+    action as the embed layer reads it).  Without a fault it is tests/discrete_oracle.discrete_head itself."""
+    A = out.shape[1]
+    if fault is None:
+        a, ent, norm, _k = discrete_head(out, q)
+        return a, ent[:, None], norm, a
+    o = torch.cat([out[:, :16], 0 * out[:, 16:]], 1) if fault == "cols16_dropped" else out     # logit image columns >= 16 unwritten
+    if fault == "no_max":                   # exp(out) instead of exp(out - max)
+        lse = torch.log(torch.exp(o).sum(-1, keepdim=True))
+    elif fault == "lane63_invalid":         # lane < A - 1: the last class never enters a reduction
+        lse = o[:, :A - 1].logsumexp(-1, keepdim=True)
+    else:
+        lse = o.logsumexp(-1, keepdim=True)
+    norm = o - lse
+    p = F.softmax(norm, -1)
+    if fault == "lane63_invalid":
+        p = torch.cat([F.softmax(norm[:, :A - 1], -1), 0 * p[:, A - 1:]], 1)
+    r = p / q
+    k = (A - 1 - r.flip(-1).argmax(-1)) if fault == "sampler_ge" else r.argmax(-1)       # r >= best: the LAST maximum wins
+    a = (F.one_hot(k, A).to(p.dtype) + p) - p
+    ent = -(torch.clamp(norm, min=FLOAT_MIN) * p).sum(-1, keepdim=True)
+    ae = torch.cat([a[:, :16], 0 * a[:, 16:]], 1) if fault == "af16_dropped" else a       # action fragment columns >= 16 unwritten
+    return a, ent, norm, ae
+
+
+def emu_discrete_grad(norm, dA, dent, fault=None):
+    """d_actor_out of the Categorical actor from the saved norm (bd_discrete.h disc_rows_bwd)."""
+    if fault == "ent_dropped":
+        dent = 0 * dent
+    elif fault == "ent_sign":
+        dent = -dent
+    p = torch.softmax(norm, -1)
+    H = -(p * norm).sum(-1, keepdim=True)
+    return p * (dA - (p * dA).sum(-1, keepdim=True)) + dent * (-p * (norm + H))
+
+
+def emu_imagine_fwd(d, W, I, min_std, dtype, with_us=True, with_mean=True, discrete=False, fault=None):
     W, I = _cast(W, dtype), _cast(I, dtype)
     exact = dtype == D64
     ms, init, amin, scale = [(v if exact else R.f32(v)) for v in (min_std, R.ACT_RAW_INIT_STD, R.ACT_MIN_STD, R.ACT_MEAN_SCALE)]
     Be, A = d.Be, d.A
     fp = I["start_feat"]
-    names = list(R.img_fwd_tensors(d))
+    names = list(R.img_fwd_tensors(d, discrete))
     K = {k: [] for k in names}
     pres = {f"a{l}": [] for l in range(4)}
     pres.update(out=[], mean=[], std=[])
@@ -134,32 +175,38 @@ def emu_imagine_fwd(d, W, I, min_std, dtype, with_us=True, with_mean=True):
             x = F.elu(pre)
             step[f"sv_actor{l}"] = x
         out = x @ W["W_a4"].t() + W["b_a4"]
-        th = torch.tanh(out[:, :A] / scale)
-        mean = scale * th
-        pre_s = out[:, A:] + init
-        sd = F.softplus(pre_s) + amin
-        u = mean + sd * I["eps_action"][t]
-        a = torch.tanh(u)
-        xe = F.elu(torch.cat([fp[:, Be:], a], 1) @ W["W_e"].t() + W["b_e"])
+        if discrete:
+            out = out[:, :A]
+            a, ent, norm, ae = emu_discrete_head(out, I["eps_action"][t], fault)
+            step.update(sv_act_stats=norm, entropy=ent)
+            mean = sd = out
+        else:
+            th = torch.tanh(out[:, :A] / scale)
+            mean = scale * th
+            pre_s = out[:, A:] + init
+            sd = F.softplus(pre_s) + amin
+            u = mean + sd * I["eps_action"][t]
+            a = ae = torch.tanh(u)
+            step.update(sv_act_stats=torch.cat([th, torch.sigmoid(pre_s), mean, sd], 1), sv_act_us=torch.cat([u, sd], 1))
+        xe = F.elu(torch.cat([fp[:, Be:], ae], 1) @ W["W_e"].t() + W["b_e"])
         hn, gates = _gru(W, xe, fp[:, :Be], Be, None, [])
         p = F.elu(hn @ W["W_1"].t() + W["b_1"])
         _o, pm, ps, st = _head(W, p, I["eps_prior"][t], ms, None)
         fp = torch.cat([hn, st], 1)
-        step.update(feat=fp, prior_mean=pm, prior_std=ps, action=a, sv_x=xe, sv_gates=gates, sv_p=p,
-                    sv_act_stats=torch.cat([th, torch.sigmoid(pre_s), mean, sd], 1), sv_act_us=torch.cat([u, sd], 1))
+        step.update(feat=fp, prior_mean=pm, prior_std=ps, action=a, sv_x=xe, sv_gates=gates, sv_p=p)
         for k in names:
             K[k].append(step[k])
         for k, v in dict(out=out, mean=mean, std=sd).items():
             pres[k].append(v)
     K = {k: torch.stack(v) for k, v in K.items()}
-    if not with_us:
+    if not with_us and not discrete:
         K["sv_act_us"] = None
     if not with_mean:
         K["prior_mean"] = None
     return K, pres
 
 
-def emu_imagine_bwd(d, W, I, G, dentropy, min_std, dtype, fault=None):
+def emu_imagine_bwd(d, W, I, G, dentropy, min_std, dtype, fault=None, discrete=False):
     W, I, G = _cast(W, dtype), _cast(I, dtype), _cast(G, dtype)
     ms = min_std if dtype == D64 else R.f32(min_std)
     dent0 = dentropy if dtype == D64 else R.f32(dentropy)
@@ -178,13 +225,15 @@ def emu_imagine_bwd(d, W, I, G, dentropy, min_std, dtype, fault=None):
         ds = dE @ W["W_e"][:, :S_]
         dA = dE @ W["W_e"][:, S_:]
         st, act = I["sv_act_stats"][t], I["action"][t]
-        dxa = dA if fault == "no_tanh_grad" else dA * (1 - act * act)
         dent = dent0 * G["ent_weight"][t][:, None] if (G["ent_weight"] is not None and fault != "no_ent_weight") else dent0
-        dmean = dxa + dent * st[:, 2 * A:3 * A]
-        dstd = dxa * I["eps_action"][t] + dent * st[:, 3 * A:]
-        dn = torch.cat([dmean * (1 - st[:, :A] ** 2), dstd * st[:, A:2 * A]], 1)
+        if discrete:        # the hidden layers below: the caller's bd_mlp_backward from d_actor_out through W_a4's A logit rows
+            dn, Wn = emu_discrete_grad(st, dA, dent, fault), W["W_a4"][:A]
+        else:
+            dxa = dA if fault == "no_tanh_grad" else dA * (1 - act * act)
+            dmean = dxa + dent * st[:, 2 * A:3 * A]
+            dstd = dxa * I["eps_action"][t] + dent * st[:, 3 * A:]
+            dn, Wn = torch.cat([dmean * (1 - st[:, :A] ** 2), dstd * st[:, A:2 * A]], 1), W["W_a4"]
         K["d_actor_out"][t] = dn
-        Wn = W["W_a4"]
         for l in (3, 2, 1, 0):
             dn = (dn @ Wn) * _elug(I[f"sv_actor{l}"][t])
             K[f"d_actor_pre{l}"][t] = dn
@@ -385,7 +434,155 @@ def test_planted_imagine_fault_fails(fault):
         R.check_layers(R.imagine_bwd_layers(d, W, imagine_bwd_inputs(I, full, G), Kb, G, -0.37, 0.1), Kb)
 
 
+# ---- the Categorical actor (discrete_actions = 1) in the Gaussian-latent imagination scan -----------------------------------
+
+def share_ok(amb, n):
+    return amb <= 1e-3 * n
+
+
+def _discrete_emulated(d, seed, variant, ew=True, fault=None):
+    W, I, sat, dup = R.make_discrete_case(d, seed, variant)
+    G = R.make_imagine_grads(d, seed, ent_weight=ew)
+    with torch.no_grad():
+        Kf, pres = emu_imagine_fwd(d, W, I, 0.1, torch.float32, discrete=True, fault=fault)
+        Kb = emu_imagine_bwd(d, W, dict(I, **Kf), G, -0.37, 0.1, torch.float32, fault, discrete=True)
+    return R.to64(W), R.to64(I), R.to64(G), k64(Kf), k64(Kb), sat, dup, pres
+
+
+def _check_discrete(d, W, I, G, Kf, Kb, sat, dup, rep=None):
+    """Every check the GPU test makes of a case; returns (ambiguous draws, draws, times the planted pair won)."""
+    R.check_layers(R.imagine_fwd_layers(d, W, I, Kf, 0.1, discrete=True, sat=sat), Kf, rep)
+    counts = RC.actor_checks(d, Kf["sv_act_stats"], I["eps_action"], Kf["action"], sat, dup)
+    R.check_layers(R.imagine_bwd_layers(d, W, dict(I, **Kf), Kb, G, -0.37, 0.1, discrete=True, sat=sat), Kb, rep)
+    if sat is not None:
+        assert R.saturated_exact(d, Kf, Kb, sat) > 0
+    return counts
+
+
+@pytest.mark.parametrize("name,variant", R.discrete_cases(R.DISCRETE_SHAPES))
+def test_fp32_emulation_of_the_discrete_actor_passes(name, variant):
+    """Every GPU case of the Categorical actor: the fp32 emulation passes every bound, the margin of every draw and the
+    exact statements of the saturated rows; its ambiguous share is within the cap; the planted pair wins somewhere."""
+    d = R.DISCRETE_SHAPES[name]
+    for ew in (True, False):
+        W, I, G, Kf, Kb, sat, dup, pres = _discrete_emulated(d, R.SEEDS[2], variant, ew)
+        rep = {}
+        amb, n, won = _check_discrete(d, W, I, G, Kf, Kb, sat, dup, rep)
+        assert max(rep.values()) < 1.0, rep
+        # (one class: every gradient is exactly zero under a zero bound, which the report does not list)
+        assert set(rep) >= ({"sv_act_stats", "action", "entropy", "d_actor_out", "d_actor_pre0", "d_actor_pre3"} if d.A > 1 else {"action"}), rep
+        assert share_ok(amb, n) and n == d.T * (d.B if sat is None else int((~sat).sum())), (amb, n)
+        assert won is None or won > 0, "the planted pair never won: the case checks nothing"
+        assert R.near_decision_fraction([p.double() for l in range(4) for p in pres[f"a{l}"]]) <= 1e-3
+
+
+@pytest.mark.parametrize("variant", ["regular", "peaked", "saturated"])
+def test_discrete_actor_reference_equals_autograd(monkeypatch, variant):
+    """The chained float64 reference of the Categorical actor in the Gaussian-latent scan equals the float64 emulation
+    (tests/discrete_oracle.discrete_head) and autograd through it, d_actor_pre0..3 included (1e-10)."""
+    monkeypatch.setattr(R, "f32", lambda x: x)
+    d = R.Dims(4, 6, 22, 6, 5, 19)
+    for ew in (True, False):
+        W, I, sat, _ = R.make_discrete_case(d, 4, variant)
+        W, I, G = R.to64(W), R.to64(I), R.to64(R.make_imagine_grads(d, 4, ent_weight=ew))
+        Kc = R.empty_set(R.img_fwd_tensors(d, True), d)
+        R.fill_layers(R.imagine_fwd_layers(d, W, I, Kc, 0.1, discrete=True, chain=True, sat=sat), Kc)
+        Ke, pres = emu_imagine_fwd(d, _leaves(W), I, 0.1, D64, discrete=True)
+        for k in Kc:
+            rel_close(Ke[k], Kc[k])
+        w = G["ent_weight"][:, :, None] if ew else 1.0
+        loss = (Ke["feat"] * G["dfeat"]).sum() + (-0.37 * w * Ke["entropy"]).sum()
+        grads = torch.autograd.grad(loss, [p for k in ("out", "a0", "a1", "a2", "a3") for p in pres[k]])
+        ag = {k: torch.stack(grads[i * d.T:(i + 1) * d.T]) for i, k in
+              enumerate(("d_actor_out", "d_actor_pre0", "d_actor_pre1", "d_actor_pre2", "d_actor_pre3"))}
+        Kb = R.empty_set({"d_actor_out": d.A, **{f"d_actor_pre{l}": d.Hd for l in range(4)}}, d)
+        R.fill_layers(R.imagine_bwd_layers(d, W, dict(I, **Kc), Kb, G, -0.37, 0.1, discrete=True, sat=sat), Kb)
+        for k in Kb:
+            rel_close(Kb[k], ag[k][..., :d.A] if k == "d_actor_out" else ag[k])
+        if variant == "peaked":
+            assert float(Kc["entropy"].mean()) < 0.75 * float(torch.log(torch.tensor(float(d.A))))
+
+
+# fault -> (shape, variant) at which the reference's checks must see it.  no_max sits at `saturated`, not `peaked`: expf
+# overflows above 88.7 and the peaked logits stay below 16 (exp(out) without the maximum is then the same number to
+# rounding and passes every bound, as it should), while the saturated rows' leading logit is near 180: inf - inf.
+DISCRETE_FAULTS = {"ent_dropped": ("a17", "regular"),         # the entropy term of d_actor_out dropped
+                   "ent_sign": ("a17", "peaked"),             # dentropy with the wrong sign
+                   "cols16_dropped": ("a17", "regular"),      # classes >= 16 of the logits image never written
+                   "lane63_invalid": ("a64", "regular"),      # lane 63 treated as invalid
+                   "no_max": ("a64", "saturated"),            # the maximum not subtracted before the exponential
+                   "af16_dropped": ("a17", "regular")}        # action fragment columns >= 16 not fed to the embed layer
+
+
+@pytest.mark.parametrize("fault", list(DISCRETE_FAULTS))
+def test_planted_discrete_actor_fault_fails(fault):
+    name, variant = DISCRETE_FAULTS[fault]
+    d = R.DISCRETE_SHAPES[name]
+    W, I, G, Kf, Kb, sat, dup, _ = _discrete_emulated(d, R.SEEDS[2], variant, fault=fault)
+    with pytest.raises(AssertionError):
+        _check_discrete(d, W, I, G, Kf, Kb, sat, dup)
+
+
+@pytest.mark.parametrize("name", ["a17", "a64"])
+def test_planted_last_maximum_fails_the_actor_duplicate_check(name):
+    """`>=` for `>` in disc_sample: invisible to the margin (the two classes tie), caught by the duplicate-class case."""
+    d = R.DISCRETE_SHAPES[name]
+    W, I, G, Kf, Kb, sat, dup, _ = _discrete_emulated(d, R.SEEDS[2], "duplicate", fault="sampler_ge")
+    R.check_layers(R.imagine_fwd_layers(d, W, I, Kf, 0.1, discrete=True), Kf)
+    RC.actor_checks(d, Kf["sv_act_stats"], I["eps_action"], Kf["action"])       # the margin alone does not see it
+    with pytest.raises(AssertionError):
+        RC.actor_checks(d, Kf["sv_act_stats"], I["eps_action"], Kf["action"], dup=dup)
+
+
+@pytest.mark.parametrize("name,variant", R.discrete_cases(R.DISCRETE_SHAPES))
+def test_ambiguous_share_of_the_float64_reference(name, variant):
+    """On the chained float64 reference alone: at most 0.1 % of the actor's draws have a runner-up within the margin of
+    the best, for every case of the Categorical actor and every seed, under both margins."""
+    d = R.DISCRETE_SHAPES[name]
+    for seed in R.SEEDS:
+        W, I, sat, dup = R.make_discrete_case(d, seed, variant)
+        W, I = R.to64(W), R.to64(I)
+        K = R.empty_set(R.img_fwd_tensors(d, True), d)
+        R.fill_layers(R.imagine_fwd_layers(d, W, I, K, 0.1, discrete=True, chain=True, sat=sat), K)
+        for path in ("hw", "libm"):
+            amb, n, won = RC.actor_checks(d, K["sv_act_stats"], I["eps_action"], K["action"], sat, dup, path=path)
+            assert share_ok(amb, n) and n > 0, (name, variant, seed, path, amb, n)
+            assert won is None or won > 0
+
+
+def test_discrete_actor_shapes_fit_and_the_lds_mirror_matches_the_refusal():
+    """With the Categorical actor the forward keeps one of its four action regions (bd_scan_layout.h ImagineFwdLds), which
+    is what lets A = 64 run at all; bd_scan_lds_bytes describes the tanh-Normal layout, so the mirror's discrete figure is
+    held to the "needs N B of LDS" refusal of shapes above 160 KiB."""
+    import re
+    from big_dreamer_amd import _cabi as cabi
+    for name, d in R.DISCRETE_SHAPES.items():
+        assert R.lds_bytes("imagine_fwd", d.Be, d.S, d.A, d.Hd, discrete=True) <= R.K_MAX_LDS, name
+        assert R.lds_bytes("imagine_bwd", d.Be, d.S, d.A, d.Hd) <= R.K_MAX_LDS, name
+    d = R.DISCRETE_SHAPES["a64"]
+    assert R.lds_bytes("imagine_fwd", d.Be, d.S, d.A, d.Hd) > R.K_MAX_LDS      # the tanh-Normal actor does not fit there
+    for Be, S, A, Hd in ((1000, 30, 64, 200), (1200, 10, 17, 32)):
+        for disc in (0, 1):
+            f = _fake_imagine_fwd(cabi, N=20, Hm=2, Be=Be, S=S, A=A, Hd=Hd, discrete_actions=disc)
+            want = R.lds_bytes("imagine_fwd", Be, S, A, Hd, discrete=bool(disc))
+            assert want > R.K_MAX_LDS and cabi.lib.bd_imagine_forward_scan(C.byref(f), None) != 0
+            m = re.search(rb"needs (\d+) B of LDS", cabi.lib.bd_last_error())
+            assert m and int(m.group(1)) == want, (Be, S, A, Hd, disc, cabi.lib.bd_last_error(), want)
+
+
 # ---- host checks (no launch) --------------------------------------------------------------------------------------------
+
+def _fake_imagine_fwd(cabi, **dims):
+    f = _fake_ptrs(cabi.ImagineFwdArgs(), ("sv_act_us",) if dims.get("discrete_actions") else ())
+    f.n_samples = 1
+    for k, v in dims.items():
+        setattr(f, k, v)
+    for i in range(3):
+        f.w_a[i] = 4096
+    for i in range(4):
+        f.b_a[i] = 4096
+    return f
+
 
 def test_dispatch_tables_match_the_library():
     from big_dreamer_amd import _cabi as cabi
@@ -490,6 +687,17 @@ def test_rejecting_paths_return_without_a_launch():
     for i in range(3):
         g.wt_a[i] = 4096
     assert lib.bd_imagine_backward(C.byref(g), None) != 0 and b"missing outputs" in lib.bd_last_error()
+    # A = 65: one lane per class does not reach class 64; both entry points say so themselves, for either actor (without a GPU
+    # every call fails: the message shows that this check came first)
+    for disc in (0, 1):
+        f = _fake_imagine_fwd(cabi, N=17, Hm=2, Be=40, S=10, A=65, Hd=32, discrete_actions=disc)
+        assert lib.bd_imagine_forward_scan(C.byref(f), None) != 0 and b"action width above 64" in lib.bd_last_error(), lib.bd_last_error()
+        assert lib.bd_imagine_forward(C.byref(f), None) != 0 and b"action width above 64" in lib.bd_last_error(), lib.bd_last_error()
+        g = _fake_ptrs(cabi.ImagineBwdArgs(), ("d_actor_pre",) if disc else ())
+        g.N, g.Hm, g.Be, g.S, g.A, g.Hd, g.discrete_actions = 17, 2, 40, 10, 65, 32, disc
+        for i in range(3):
+            g.wt_a[i] = 4096
+        assert lib.bd_imagine_backward(C.byref(g), None) != 0 and b"action width 65 above 64" in lib.bd_last_error(), lib.bd_last_error()
     assert lib.bd_observe_cluster_set_ksplit(7) != 0 and b"set_ksplit" in lib.bd_last_error()
     assert lib.bd_observe_cluster_set_ksplit(-1) == 0
 
