@@ -356,6 +356,8 @@ _SIGS = {
     "bd_twohot_decode": (I32, [P, I32, I32, I32, F32, P, P, P]),
     "bd_twohot_decode_backward": (I32, [P, I32, P, I32, I32, F32, P, I32, P]),
     "bd_twohot_nll": (I32, [P, I32, P, P, I32, I32, F32, F32, P, I32, P, P, P]),
+    "bd_symlog": (I32, [P, C.c_size_t, P, P]),
+    "bd_symexp": (I32, [P, C.c_size_t, P, P]),
 }
 
 for _name, (_res, _args) in _SIGS.items():

@@ -86,6 +86,45 @@ def check_critic_head(head="normal", bins=255, bin_range=20.0, algorithm=None) -
     return head, int(bins), float(bin_range)
 
 
+REWARD_HEAD_KEYS = ("reward_head", "reward_bins", "reward_bin_range")
+REWARD_HEAD_DEFAULTS = dict(reward_head="normal", reward_bins=255, reward_bin_range=20.0)
+REWARD_BINS_MAX = CRITIC_BINS_MAX
+REWARD_BIN_RANGE_MAX = CRITIC_BIN_RANGE_MAX
+
+
+def check_reward_head(head="normal", bins=255, bin_range=20.0, algorithm=None) -> tuple:
+    """reward_head and its two numbers ("World-model heads on any scale"): "normal" (the reference's width-1
+    reward model under a Normal(r, 1) loss) or "twohot" -- `bins` logits over bins uniform in symlog space on
+    [-bin_range, bin_range], decoded as symexp of the softmax mean, trained with the cross-entropy against the two-hot
+    encoding of symlog(reward).  bins: integer K, 2 <= K <= 1024; bin_range: Z, 0 < Z <= 80.  PlaNet (`algorithm`) plans
+    with a fused width-1 reward model and refuses "twohot".  Returns (head, int K, float Z)."""
+    from .synth import REWARD_HEADS
+    if head not in REWARD_HEADS:
+        raise ValueError(f"reward_head must be one of {REWARD_HEADS}, got {head!r}")
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= REWARD_BINS_MAX:
+        raise ValueError(f"reward_bins must be an integer in [2, {REWARD_BINS_MAX}], got {bins!r}")
+    if (isinstance(bin_range, bool) or not isinstance(bin_range, (int, float)) or not math.isfinite(bin_range)
+            or not 0.0 < bin_range <= REWARD_BIN_RANGE_MAX):
+        raise ValueError(f"reward_bin_range must be a number in (0, {REWARD_BIN_RANGE_MAX:g}], got {bin_range!r}")
+    if head != "normal" and algorithm == "planet":
+        raise ValueError("reward_head=twohot: PlaNet's CEM rollout evaluates a width-1 reward model")
+    return head, int(bins), float(bin_range)
+
+
+def check_symlog_observations(value=False, pixel=False, algorithm=None) -> bool:
+    """symlog_observations ("World-model heads on any scale"): a boolean; true makes the encoder read
+    symlog(obs) and observation_loss the Normal(., 1) loss against symlog(obs).  Vector observations only (pixels are
+    bounded already: DreamerV3 applies symlog to vector inputs), and not with PlaNet (`algorithm`)."""
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"symlog_observations must be a boolean, got {value!r}")
+    if value and pixel:
+        raise ValueError("symlog_observations=true: pixel observations are bounded already; symlog applies to vector "
+                         "observations (pixel_observation=false)")
+    if value and algorithm == "planet":
+        raise ValueError("symlog_observations=true: PlaNet is not supported (its planner and train step read raw observations)")
+    return bool(value)
+
+
 def check_gradient_mixing(value) -> float:
     """ActorCritic.gradient_mixing: -1 (the reference's objective, backpropagation through the learned dynamics) or
     rho in [0, 1], DreamerV2's ``actor_grad_mix`` -- the weight of the dynamics term against REINFORCE (1 = -1)."""
@@ -167,6 +206,9 @@ def load_config(overrides: List[str] = (), path: str = DEFAULT_CONFIG) -> Dict[s
         raise ValueError(f"sample_on_device={cfg['sample_on_device']!r} is not a boolean")
     check_replica_options(cfg.get("replica_check_interval", 0), cfg.get("replica_on_mismatch", "raise"))
     check_diagnostics_interval(cfg.get("diagnostics_interval", 0))
+    check_reward_head(*(cfg.get(k, REWARD_HEAD_DEFAULTS[k]) for k in REWARD_HEAD_KEYS), algorithm=cfg.get("algorithm"))
+    check_symlog_observations(cfg.get("symlog_observations", False), bool(cfg.get("pixel_observation", False)),
+                              cfg.get("algorithm"))
     if not isinstance(cfg.get("replica_sync_at_start", False), bool):
         raise ValueError(f"replica_sync_at_start={cfg['replica_sync_at_start']!r} is not a boolean")
     return cfg

@@ -18,9 +18,10 @@ from torch import Tensor
 
 from . import _cabi as cabi
 from .collect import check_collect_envs
-from .config import (ACTION_MODES, CRITIC_HEAD_DEFAULTS, CRITIC_HEAD_KEYS, RETURN_NORM_KEYS, check_action_distribution,
-                     check_cnn_activation, check_critic_head, check_dense_activation, check_gradient_mixing,
-                     check_return_normalization)
+from .config import (ACTION_MODES, CRITIC_HEAD_DEFAULTS, CRITIC_HEAD_KEYS, RETURN_NORM_KEYS, REWARD_HEAD_DEFAULTS,
+                     REWARD_HEAD_KEYS, check_action_distribution, check_cnn_activation, check_critic_head,
+                     check_dense_activation, check_gradient_mixing, check_return_normalization, check_reward_head,
+                     check_symlog_observations)
 from .engine import DEFAULT_HP, DreamerEngine
 from .memory import ExperienceReplay
 from .models import ActorModel, CnnImageEncoder, DenseModel, ObservationModel, TransitionModel, encoder_for
@@ -57,6 +58,12 @@ class Dreamer:
         # "normal": the reference's width-1 critic; "twohot" (DreamerV3): K logits over symlog bins ("Two-hot critic")
         self.critic_head, self.critic_bins, self.critic_bin_range = check_critic_head(
             *(params["ActorCritic"].get(k, CRITIC_HEAD_DEFAULTS[k]) for k in CRITIC_HEAD_KEYS), algorithm=params.get("algorithm"))
+        # the world model's heads ("World-model heads on any scale"): "twohot" reward logits over symlog bins,
+        # symlog on vector observations; both off: the reference's world model
+        self.reward_head, self.reward_bins, self.reward_bin_range = check_reward_head(
+            *(params.get(k, REWARD_HEAD_DEFAULTS[k]) for k in REWARD_HEAD_KEYS), algorithm=params.get("algorithm"))
+        self.symlog_observations = check_symlog_observations(
+            params.get("symlog_observations", False), bool(params.get("pixel_observation", False)), params.get("algorithm"))
         # the pixel conv stacks take ELU / ReLU / Tanh (no effect on state observations, as in the reference); the dense
         # chains and scans are ELU only, and say so instead of ignoring the key
         self.cnn_activation_function = check_cnn_activation(params.get("cnn_activation_function", "ELU"))
@@ -91,7 +98,8 @@ class Dreamer:
                          O=obs_size, pixel=self.pixel_observation, cat_D=cat_D, cat_C=cat_C,
                          use_discount=self.use_discount, discrete_actions=self.action_distribution == "Categorical",
                          cnn_act=self.cnn_activation_function, critic_head=self.critic_head, critic_bins=self.critic_bins,
-                         critic_bin_range=self.critic_bin_range)
+                         critic_bin_range=self.critic_bin_range, reward_head=self.reward_head, reward_bins=self.reward_bins,
+                         reward_bin_range=self.reward_bin_range, symlog_obs=self.symlog_observations)
         self.engine = DreamerEngine(self.dims, _hp_from_params(params), self.device, world_size=world_size,
                                     process_group=process_group,
                                     replica_check_interval=params.get("replica_check_interval", 0),
@@ -107,7 +115,7 @@ class Dreamer:
             ("transition_model", lambda: _ref_init_transition(self.dims)),
             ("observation_model", (lambda: _ref_init_decoder(feat, E)) if px else
              (lambda: _ref_init_dense(feat, self.hidden_size, env.observation_size))),
-            ("reward_model", lambda: _ref_init_dense(feat, self.hidden_size, 1)),
+            ("reward_model", lambda: _ref_init_dense(feat, self.hidden_size, self.dims.reward_out)),
             ("encoder", (lambda: _ref_init_cnn(E)) if px else
              (lambda: _ref_init_dense(env.observation_size, self.hidden_size, self.embedding_size))),
             ("actor", lambda: _ref_init_dense(feat, self.hidden_size, self.dims.actor_out)),
@@ -130,7 +138,8 @@ class Dreamer:
             self.observation_model = DenseModel(feat, self.hidden_size, env.observation_size, engine=e,
                                                 module="observation_model", prefix="obs")
             self.encoder = encoder_for(e, env.observation_size, self.hidden_size, self.embedding_size)
-        self.reward_model = DenseModel(feat, self.hidden_size, 1, engine=e, module="reward_model", prefix="rew")
+        self.reward_model = DenseModel(feat, self.hidden_size, self.dims.reward_out, engine=e, module="reward_model",
+                                       prefix="rew")
         self.actor = ActorModel(self.belief_size, self.state_size, self.hidden_size, self.action_size,
                                 action_distribution=self.action_distribution, engine=e)
         self.critic = DenseModel(feat, self.hidden_size, self.dims.critic_out, engine=e, module="critic", prefix="cri")
@@ -153,6 +162,7 @@ class Dreamer:
         if path and os.path.exists(path):
             d = torch.load(path, map_location="cpu", weights_only=True)
             self._check_checkpoint_head(d)          # before anything is copied
+            self._check_checkpoint_world_model(d)
             for key in ("transition_model", "observation_model", "reward_model", "encoder"):
                 getattr(self, key).load_state_dict(d[key])
             if "model_optimizer" in d:
@@ -184,6 +194,24 @@ class Dreamer:
         if dict(theirs) != mine:
             raise ValueError(f"checkpoint critic head {dict(theirs)} does not match the agent's {mine} "
                              "(ActorCritic.critic_head / critic_bins / critic_bin_range)")
+
+    def _reward_head_record(self) -> Dict[str, Any]:
+        if self.reward_head == "normal":
+            return {"kind": "normal"}
+        return {"kind": self.reward_head, "bins": int(self.reward_bins), "range": float(self.reward_bin_range)}
+
+    def _check_checkpoint_world_model(self, d: Dict[str, Any]) -> None:
+        """ValueError unless the checkpoint's reward head is this agent's in kind, K and Z and its world model was trained
+        on the same observation transform (a checkpoint without the records -- the reference's files among them -- holds
+        the width-1 reward model on raw observations)."""
+        rs = d.get("run_state") or {}
+        theirs, mine = dict(rs.get("reward_head") or {"kind": "normal"}), self._reward_head_record()
+        if theirs != mine:
+            raise ValueError(f"checkpoint reward head {theirs} does not match the agent's {mine} "
+                             "(reward_head / reward_bins / reward_bin_range)")
+        theirs, mine = bool(rs.get("symlog_observations", False)), bool(self.symlog_observations)
+        if theirs != mine:
+            raise ValueError(f"checkpoint symlog_observations={theirs} does not match the agent's symlog_observations={mine}")
 
     def save(self, path: str, extra: Optional[Dict[str, Any]] = None) -> None:
         """Checkpoint in the layout ``Planet.load`` reads (src/planet.py:109-114: transition_model, observation_model,
@@ -217,6 +245,10 @@ class Dreamer:
             d["run_state"]["return_norm"] = e.return_norm_state()
         if self.critic_head != "normal":
             d["run_state"]["critic_head"] = self._critic_head_record()
+        if self.reward_head != "normal":
+            d["run_state"]["reward_head"] = self._reward_head_record()
+        if self.symlog_observations:
+            d["run_state"]["symlog_observations"] = True
         atomic_write(path, lambda fh: torch.save(d, fh))
 
     def load_run_state(self, path: str) -> Dict[str, Any]:
@@ -322,6 +354,29 @@ class Dreamer:
         logits = out.reshape(-1, K).contiguous()
         val = torch.empty(logits.shape[0], dtype=torch.float32, device=logits.device)
         return self.engine.twohot_decode(logits, logits.shape[0], val).view(*lead, 1)
+
+    @torch.no_grad()
+    def reward(self, belief: Tensor, state: Tensor) -> Tensor:
+        """The reward model's prediction for (belief, state), (..., 1): what the module returns with reward_head="normal",
+        the decoded logits -- symexp of the softmax mean over the bins, bd_twohot_decode -- with "twohot", where
+        ``reward_model`` itself returns the logits (..., K)."""
+        out = self.reward_model(belief, state)
+        if self.reward_head == "normal":
+            return out
+        lead, K = out.shape[:-1], self.reward_bins
+        logits = out.reshape(-1, K).contiguous()
+        val = torch.empty(logits.shape[0], dtype=torch.float32, device=logits.device)
+        return self.engine.twohot_decode(logits, logits.shape[0], val, head="reward").view(*lead, 1)
+
+    def encoder_input(self, observation: Tensor) -> Tensor:
+        """What the encoder reads for `observation` (on the device): the observation itself, or -- symlog_observations --
+        symlog of it in a fresh tensor (bd_symlog); the caller's tensor is never modified."""
+        obs = observation.to(self.device)
+        if not self.symlog_observations:
+            return obs
+        obs = obs.float().contiguous()
+        self.engine.join()
+        return self.engine.symlog(obs, torch.empty_like(obs))
 
     # ---------------------------------------------------------------------------------------- acting / imagination
     @torch.no_grad()
@@ -503,7 +558,7 @@ class Dreamer:
         # `_noise` (parity tests): the reference's draws in its RNG order -- "prior" (B,S), "post" (B,S), "action" (B,A),
         # "entropy" (100,B,A), and with explore "explore" (B,A)
         nz = _noise
-        embedding = self.encoder(observation.to(self.device)).unsqueeze(dim=0)
+        embedding = self.encoder(self.encoder_input(observation)).unsqueeze(dim=0)
         B = belief.shape[0]
         if state_mean:
             # the mean of the posterior: its sample at zero normal noise, or -- Categorical -- at q = 1 for every class

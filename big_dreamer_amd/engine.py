@@ -28,7 +28,7 @@ from . import diagnostics
 from .config import (ACTION_DISTRIBUTIONS, CRITIC_BIN_RANGE_MAX, CRITIC_BINS_MAX, CRITIC_HEAD_DEFAULTS,  # noqa: F401
                      CRITIC_HEAD_KEYS, RETURN_NORM_KEYS, RETURN_NORMALIZATIONS, check_action_distribution,
                      check_cnn_activation, check_critic_head, check_dense_activation, check_gradient_mixing,
-                     check_return_normalization)
+                     check_return_normalization, check_reward_head, check_symlog_observations)
 from .diagnostics_device import _Diagnostics
 from .logs import (N_SLOTS, SLOT_DISC, SLOT_ENT, SLOT_GN_ACTOR, SLOT_GN_CRITIC, SLOT_GN_MODEL, SLOT_KL,  # noqa: F401
                    SLOT_OBS, SLOT_RET, SLOT_REW, SLOT_RF, SLOT_RN, SLOT_VAL, SLOT_WOBJ, LazyLogs, LogRing, _LogRecord,
@@ -173,6 +173,8 @@ class DreamerEngine:
         self.hp["gradient_mixing"] = check_gradient_mixing(self.hp["gradient_mixing"])
         self.hp.update(zip(RETURN_NORM_KEYS, check_return_normalization(*(self.hp[k] for k in RETURN_NORM_KEYS))))
         check_critic_head(dims.critic_head, dims.critic_bins, dims.critic_bin_range)
+        check_reward_head(dims.reward_head, dims.reward_bins, dims.reward_bin_range)
+        check_symlog_observations(dims.symlog_obs, dims.pixel)
         self.dev = torch.device(device)
         assert self.dev.type == "cuda", "the HIP path needs a GPU (there is no CPU fallback)"
         # ---- parallel setup
@@ -268,9 +270,10 @@ class DreamerEngine:
         self._n_train_steps = 0
         # Frozen imagined heads (reward_model, critic_target) forward + dgrad in one launch (csrc/heads.hip) on the
         # dynamics-backprop path with Gaussian latents; BD_HEADS_FUSED=0 keeps the separate forward / backward chains
-        # (mlp.hip) for the A/B.  The fused kernel is a width-1 kernel: the two-hot critic takes the separate chains.
+        # (mlp.hip) for the A/B.  The fused kernel is a width-1 kernel: a two-hot critic or reward head takes the separate
+        # chains.
         self.heads_fused = (os.environ.get("BD_HEADS_FUSED", "1") != "0" and not self.d.categorical and not self.d.twohot
-                            and bool(lib.bd_img_heads_supported(self.d.Be + self.d.S, self.d.Hd)))
+                            and not self.d.reward_twohot and bool(lib.bd_img_heads_supported(self.d.Be + self.d.S, self.d.Hd)))
         # Behaviour chunk plan ("Chunked behaviour chain"): the forward imagination scan runs as K launches over
         # consecutive time steps, and the fused heads of a finished chunk run on the CUs the scan leaves idle while the
         # scan walks on.  They run on `_side`, the critic's stream (no fifth active stream: the process has four
@@ -986,11 +989,31 @@ class DreamerEngine:
         self.mlp_forward(M, x, ldx, w_in, fl, acts + [None], out, out_width, gather=gather)
         return out, acts, layers
 
-    def twohot_decode(self, logits: torch.Tensor, M: int, out: torch.Tensor) -> torch.Tensor:
-        """Two-hot critic: out[M] = symexp(softmax(logits [M x K]) . bins) on the current stream (bd_twohot_decode)."""
+    def twohot_decode(self, logits: torch.Tensor, M: int, out: torch.Tensor, head: str = "critic") -> torch.Tensor:
+        """Two-hot head: out[M] = symexp(softmax(logits [M x K]) . bins) on the current stream (bd_twohot_decode), with
+        (K, Z) of `head`: "critic" (critic_bins, critic_bin_range) or "reward" (reward_bins, reward_bin_range)."""
         d = self.d
-        cabi.check(lib.bd_twohot_decode(ptr(logits), d.critic_bins, M, d.critic_bins, d.critic_bin_range, ptr(out), None,
-                                        cabi.stream()))
+        K, Z = (d.reward_bins, d.reward_bin_range) if head == "reward" else (d.critic_bins, d.critic_bin_range)
+        cabi.check(lib.bd_twohot_decode(ptr(logits), K, M, K, Z, ptr(out), None, cabi.stream()))
+        return out
+
+    def _reward_value(self, tag: str, x, M: int, sidx=None):
+        """reward_model over M rows of x = [h; s]: (rewards [M], saved activations, layers, head output).  The head output
+        is the reward itself ("normal") or the K logits the rewards were decoded from ("twohot")."""
+        d = self.d
+        out, acts, layers = self.dense_forward("reward_model", "rew", tag, x, d.Be + d.S, M, d.reward_out, sidx=sidx)
+        if not d.reward_twohot:
+            return out, acts, layers, out
+        return self.twohot_decode(out, M, self.buf(f"{tag}_val", M), head="reward"), acts, layers, out
+
+    def symlog(self, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """out = sign(x) log1p(|x|) over all elements on the current stream (bd_symlog); x is left as it is."""
+        cabi.check(lib.bd_symlog(ptr(x), x.numel(), ptr(out), cabi.stream()))
+        return out
+
+    def symexp(self, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """out = sign(x) expm1(|x|) over all elements on the current stream (bd_symexp); x is left as it is."""
+        cabi.check(lib.bd_symexp(ptr(x), x.numel(), ptr(out), cabi.stream()))
         return out
 
     def _target_value(self, tag: str, x, M: int, sidx=None):
@@ -1194,7 +1217,10 @@ class DreamerEngine:
         a.B, a.Be, a.S, a.A, a.Hd, a.E = B, d.Be, d.S, d.A, d.Hd, d.E
         a.latent_cat, a.actor_cat = int(d.categorical), int(d.discrete_actions)
         if embedding is None:
-            a.O, a.obs = d.O, ptr(f(obs).view(B, d.O))
+            obs = f(obs).view(B, d.O)
+            if d.symlog_obs:        # one more launch in front of the fused step, into a buffer of the engine's
+                obs = self.symlog(obs, self.buf("act_obs_symlog", B, d.O))
+            a.O, a.obs = d.O, ptr(obs)
             for l in range(DENSE_LAYERS + 1):
                 a.w_enc[l], a.b_enc[l] = ptr(pk[f"enc{l}"]), ptr(self.W("encoder", f"model.{2 * l}.bias"))
         else:
@@ -1283,6 +1309,8 @@ class DreamerEngine:
         """bd_plan_args with the dims, latent_cat and every weight of the engine's latent kind; inputs, outputs and noise
         are the caller's."""
         d, pk = self.d, self.pk
+        if d.reward_twohot:
+            raise ValueError("reward_head=twohot: the CEM planner's rollout evaluates a width-1 reward model")
         tm = lambda n: self.W("transition_model", n)
         a = cabi.PlanArgs()
         a.rows, a.H, a.cand, a.Be, a.S, a.A, a.Hd, a.latent_cat = rows, H, cand, d.Be, d.S, d.A, d.Hd, int(d.categorical)
@@ -1609,6 +1637,8 @@ class DreamerEngine:
         w = SimpleNamespace(T=T, B=B, N=N, F=F, actions=actions[:-1], nonterm=nonterm[:-1], eps_post=noise["obs_post"],
                             om_acts=None, om_dpre=None, dc_acts=None, dc_dpre=None)
         obs_t = obs[1:].reshape(N, d.O)                     # targets and encoder input
+        if d.symlog_obs:        # transformed once: the encoder and the observation loss read this buffer, the batch stays raw
+            obs_t = self.symlog(obs_t, self.buf("obs_symlog", N, d.O))
         w.composed = self.composed_encoder_tail(N)
         with self.span("encoder_fwd"):
             if w.composed:
@@ -1629,7 +1659,7 @@ class DreamerEngine:
                 obs_t = self.conv.acts_enc[0].view(N, d.O)      # the same images in the NHWC order of the prediction
             else:
                 om_out, w.om_acts, om_layers = self.dense_forward("observation_model", "obs", "om", feat, F, N, d.O, sidx=sidx)
-            rw_out, w.rw_acts, rw_layers = self.dense_forward("reward_model", "rew", "rw", feat, F, N, 1, sidx=sidx)
+            rw_out, w.rw_acts, rw_layers = self.dense_forward("reward_model", "rew", "rw", feat, F, N, d.reward_out, sidx=sidx)
         w.obs_t = obs_t
         inv_rows = self.dp.mean_grad_scale(N)
         if d.use_discount:      # _discount_loss (src/dreamer.py:239-251): Bernoulli(logits).log_prob(nonterminal), weight 5
@@ -1637,9 +1667,21 @@ class DreamerEngine:
             d_dc = self.buf("d_dc_out", N, 1)
             cabi.check(lib.bd_bernoulli_nll(ptr(dc_out), ptr(w.nonterm), N, hp["discount_weight"] * inv_rows, ptr(d_dc), sc,
                                             SLOT_DISC, ws, st))
-        d_om, d_rw = self.buf("d_om_out", N, d.O), self.buf("d_rw_out", N, 1)
+        RK = d.reward_out
+        d_om, d_rw = self.buf("d_om_out", N, d.O), self.buf("d_rw_out", N, RK)
         cabi.check(lib.bd_normal_nll(ptr(om_out), d.O, ptr(obs_t), d.O, N, d.O, inv_rows, ptr(d_om), d.O, sc, SLOT_OBS, ws, st))
-        cabi.check(lib.bd_normal_nll(ptr(rw_out), 1, ptr(rewards[:-1]), 1, N, 1, inv_rows, ptr(d_rw), 1, sc, SLOT_REW, ws, st))
+        rw_val = rw_out             # the predicted rewards the diagnostics read
+        if d.reward_twohot:
+            # cross-entropy against the two-hot encoding of symlog(reward); the row losses are summed in bd_sum's fixed
+            # order (the mean over rows: the Normal form's per-row constant has no counterpart)
+            rw_row_loss = self.buf("rw_row_loss", N)
+            rw_val = self.buf("rw_val", N) if self._diag_now else None
+            cabi.check(lib.bd_twohot_nll(ptr(rw_out), RK, ptr(rewards[:-1]), None, N, RK, d.reward_bin_range, inv_rows,
+                                         ptr(d_rw), RK, ptr(rw_val), ptr(rw_row_loss), st))
+            cabi.check(lib.bd_sum(ptr(rw_row_loss), N, sc, SLOT_REW, ws, st))
+        else:
+            cabi.check(lib.bd_normal_nll(ptr(rw_out), 1, ptr(rewards[:-1]), 1, N, 1, inv_rows, ptr(d_rw), 1, sc, SLOT_REW, ws,
+                                         st))
         sum_form = int(hp["kl_balance"] == -1)
         kl_n = d.cat_D if cat else d.S                      # KL terms per row: one per factor / per state dimension
         if cat:     # Categorical branch of _kl_loss (src/dreamer.py:102-106,119-144): qm / pm are the logits
@@ -1656,7 +1698,7 @@ class DreamerEngine:
             else:
                 cabi.check(lib.bd_latent_stats(ptr(qm), ptr(qs), ptr(pm), ptr(ps), N, d.S, dg.at("latent"), dg.at("kl_cols"),
                                                ptr(dg.ws["model"]), st))
-            dg.moments("model", "mom_wm", [(rewards[:-1], None), (rw_out, None)])
+            dg.moments("model", "mom_wm", [(rewards[:-1], None), (rw_val, None)])
         if W > 1 and not sum_form:                          # the free-nats clamp acts on the GLOBAL mean
             self._kl_local = self.scalars[SLOT_KL:SLOT_KL + 1].clone()
             self._allreduce(self.scalars[SLOT_KL:SLOT_KL + 1], "model")
@@ -1676,7 +1718,7 @@ class DreamerEngine:
         dfeat = self.buf("dfeat", N, F)
         w.rw_dpre = [self.buf(f"rw_dpre{l}", N, d.Hd) for l in range(DENSE_LAYERS)] + [d_rw]
         if self.pixel:
-            self.mlp_backward(N, d_rw, 1, rw_layers, w.rw_acts + [None], w.rw_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F)
+            self.mlp_backward(N, d_rw, RK, rw_layers, w.rw_acts + [None], w.rw_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F)
             with self.span("decoder_bwd"):
                 # the decoder's weight-gradient GEMMs (60 % of the pass) are ready here: they run on their own stream
                 # underneath the observe-scan backward (52 CUs) instead of after it
@@ -1687,7 +1729,7 @@ class DreamerEngine:
         else:
             w.om_dpre = [self.buf(f"om_dpre{l}", N, d.Hd) for l in range(DENSE_LAYERS)] + [d_om]
             self.mlp_backward(N, d_om, d.O, om_layers, w.om_acts + [None], w.om_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F)
-            self.mlp_backward(N, d_rw, 1, rw_layers, w.rw_acts + [None], w.rw_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F,
+            self.mlp_backward(N, d_rw, RK, rw_layers, w.rw_acts + [None], w.rw_dpre[:-1] + [None], din0=dfeat, ld0=F, w0=F,
                               accumulate=True)
         if d.use_discount:
             w.dc_dpre = [self.buf(f"dc_dpre{l}", N, d.Hd) for l in range(DENSE_LAYERS)] + [d_dc]
@@ -1788,7 +1830,7 @@ class DreamerEngine:
         wb.add(w.d_q2, HO, self._buf["sv_q"], d.Hd, N, HO, d.Hd, Gt("belief_posterior.model.2.weight"), d.Hd,
                Gt("belief_posterior.model.2.bias"))
         dense_sizes = lambda i, o: [i] + [d.Hd] * DENSE_LAYERS + [o]
-        self._dense_wgrads(wb, "reward_model", N, w.rw_dpre, feat, F, w.rw_acts, dense_sizes(F, 1))
+        self._dense_wgrads(wb, "reward_model", N, w.rw_dpre, feat, F, w.rw_acts, dense_sizes(F, d.reward_out))
         if w.dc_dpre is not None:
             self._dense_wgrads(wb, "discount_model", N, w.dc_dpre, feat, F, w.dc_acts, dense_sizes(F, 1))
         if not self.pixel:      # (pixel mode: the conv stacks queued their weight gradients themselves)
@@ -1963,16 +2005,23 @@ class DreamerEngine:
             self._heads_rows(s, 0, Hm, s.ifeat)
         else:
             with self.span("img_heads_fwd"):
-                s.r_out, s.r_acts, s.r_layers = self.dense_forward("reward_model", "rew", "ir", s.ifeat, F, Mi, 1, sidx=s.isidx)
+                s.r_out, s.r_acts, s.r_layers, s.r_head = self._reward_value("ir", s.ifeat, Mi, sidx=s.isidx)
                 s.v_out, s.v_acts, s.v_layers, s.v_head = self._target_value("iv", s.ifeat, Mi, sidx=s.isidx)
 
     def _imagined_heads_backward(self, s) -> None:
         """The separate heads: d returns, then the two dgrad chains into difeat.  Two-hot critic: d values goes through
-        the decode backward into the K-wide chain of the frozen target."""
+        the decode backward into the K-wide chain of the frozen target; two-hot reward head: d rewards likewise into the
+        K-wide chain of the frozen reward model."""
         d = self.d
         self._returns_backward(s)
         with self.span("img_heads_bwd"):
-            self.mlp_backward(s.Mi, s.d_r, 1, s.r_layers, s.r_acts + [None], None, din0=s.difeat, ld0=s.F, w0=s.F)
+            d_r, RK = s.d_r, 1
+            if d.reward_twohot:
+                RK = d.reward_bins
+                d_r = self.buf("d_ir_logits", s.Mi, RK)
+                cabi.check(lib.bd_twohot_decode_backward(ptr(s.r_head), RK, ptr(s.d_r), s.Mi, RK, d.reward_bin_range, ptr(d_r),
+                                                         RK, s.st))
+            self.mlp_backward(s.Mi, d_r, RK, s.r_layers, s.r_acts + [None], None, din0=s.difeat, ld0=s.F, w0=s.F)
             d_v, K = s.d_v, 1
             if d.twohot:
                 K = d.critic_bins

@@ -40,7 +40,11 @@ class _EngineBacked(nn.Module):
 
 
 class DenseModel(_EngineBacked):
-    """src/models.py:365-408: build_mlp(input, hidden, output, n_layers=4) -> ``model.{0,2,4,6,8}``."""
+    """src/models.py:365-408: build_mlp(input, hidden, output, n_layers=4) -> ``model.{0,2,4,6,8}``.
+    ``forward`` returns what the chain computes: with a two-hot head (critic, critic_target, reward_model) the K logits
+    (``Dreamer.value`` / ``Dreamer.reward`` decode them); as the observation model or the encoder of an agent with
+    ``symlog_observations`` it predicts / reads symlog(obs) -- the module itself applies no transform
+    (``Dreamer.encoder_input`` does)."""
 
     def __init__(self, input_size: int, hidden_size: int, output_size: int = 1, activation: str = "ELU",
                  n_layers: int = DENSE_LAYERS, distribution: str = "normal", *, engine: DreamerEngine, module: str,

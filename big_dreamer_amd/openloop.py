@@ -43,6 +43,9 @@ def run_open_loop(agent, batch: Sequence[torch.Tensor], context: int, video: Opt
                  states s[0:c];
       open loop  transition_model(s[c-1], actions[c:T], b[c-1], None, nonterminals[c:T]) -> b[c:T], sampled PRIOR states s[c:T];
       decode     model[t] = observation_model(b[t], s[t]), all T n rows in one pass; truth[t] = obs[t + 1].
+    With ``symlog_observations`` the world model lives in symlog(obs) space: the context is filtered on
+    ``agent.encoder_input(obs)`` = symlog(obs), and the decoder's output goes through bd_symexp before the error, so the curve
+    stays in observation units and is comparable across settings.
     `_noise` (tests): {"post": (c, n, S), "prior": (T - c, n, S)} -- standard normals, or Exp(1) variates for Categorical
     latents -- in place of the draws the two forward calls make.  `video`: None = for pixel observations; state observations
     have none.  Returns ``openl_obs_mse`` (T,) float32 -- per step the mean of (model - truth)^2 over the sequences and all
@@ -57,7 +60,8 @@ def run_open_loop(agent, batch: Sequence[torch.Tensor], context: int, video: Opt
     pixel = obs.dim() == 5
     want_video = pixel and (video is None or bool(video))
     agent.eval()
-    embedding = agent.encoder(obs[1:c + 1])
+    symlog = bool(getattr(agent, "symlog_observations", False))     # the world model lives in symlog(obs) space
+    embedding = agent.encoder(agent.encoder_input(obs[1:c + 1]) if symlog else obs[1:c + 1])
     kw_post = {} if _noise is None else {"_noise": (_noise["post"], _noise["post"])}     # (unused prior draw, posterior draw)
     kw_prior = {} if _noise is None else {"_noise": (_noise["prior"],)}
     b_ctx, _, _, s_ctx, _ = agent.transition_model(torch.zeros(n, agent.state_size, device=dev), actions[:c],
@@ -75,6 +79,9 @@ def run_open_loop(agent, batch: Sequence[torch.Tensor], context: int, video: Opt
         curve = agent.engine.openl_error(truth, model, T, n, 3 * IMG * IMG, True)
     else:
         model = agent.observation_model(beliefs, states)
+        if symlog:          # back to observation units: the curve stays comparable across settings
+            model = model.contiguous()
+            model = agent.engine.symexp(model, torch.empty_like(model))
         curve = agent.engine.openl_error(truth, model, T, n, int(model.shape[-1]), False)
     agent.train()
     curve = curve.cpu().numpy().astype(np.float32, copy=False)

@@ -19,6 +19,7 @@ import numpy as np
 
 CNN_ACTIVATIONS = ("ELU", "ReLU", "Tanh")     # torch.nn class names, as the reference resolves them (getattr(nn, name))
 CRITIC_HEADS = ("normal", "twohot")
+REWARD_HEADS = ("normal", "twohot")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -44,12 +45,20 @@ class Dims:
     critic_head: str = "normal"     # ActorCritic.critic_head: "normal" (width 1, Normal(v, 1)) | "twohot" ("Two-hot critic")
     critic_bins: int = 255          # twohot: K logits over bins uniform in symlog space
     critic_bin_range: float = 20.0  # twohot: the bins span [-Z, Z] in symlog space
+    reward_head: str = "normal"     # reward_head: "normal" (width 1, Normal(r, 1)) | "twohot" ("World-model heads on any scale")
+    reward_bins: int = 255          # twohot: K logits over bins uniform in symlog space
+    reward_bin_range: float = 20.0  # twohot: the bins span [-Z, Z] in symlog space
+    symlog_obs: bool = False        # symlog_observations: the encoder reads, and the decoder is regressed onto, symlog(obs)
 
     def __post_init__(self):
         if self.cnn_act not in CNN_ACTIVATIONS:
             raise ValueError(f"cnn_activation_function must be one of {CNN_ACTIVATIONS}, got {self.cnn_act!r}")
         if self.critic_head not in CRITIC_HEADS:
             raise ValueError(f"critic_head must be one of {CRITIC_HEADS}, got {self.critic_head!r}")
+        if self.reward_head not in REWARD_HEADS:
+            raise ValueError(f"reward_head must be one of {REWARD_HEADS}, got {self.reward_head!r}")
+        if self.symlog_obs and self.pixel:
+            raise ValueError("symlog_observations applies to vector observations, not to pixels")
         assert (self.cat_D == 0) == (self.cat_C == 0) and (self.cat_D == 0 or self.S == self.cat_D * self.cat_C), \
             "Categorical latents: state_size = discrete_latent_dimensions * discrete_latent_classes"
 
@@ -75,6 +84,15 @@ class Dims:
     def critic_out(self) -> int:
         """Output width of critic / critic_target: the value, or the K logits of the two-hot head."""
         return self.critic_bins if self.twohot else 1
+
+    @property
+    def reward_twohot(self) -> bool:
+        return self.reward_head == "twohot"
+
+    @property
+    def reward_out(self) -> int:
+        """Output width of reward_model: the reward, or the K logits of the two-hot head."""
+        return self.reward_bins if self.reward_twohot else 1
 
     @property
     def T(self) -> int:
@@ -164,7 +182,7 @@ def param_shapes(d: Dims) -> Dict[str, List[Tuple[str, Tuple[int, ...]]]]:
     out = {
         "transition_model": tm,
         "observation_model": obs,
-        "reward_model": strip(_mlp_shapes("x", [feat] + hid + [1])),
+        "reward_model": strip(_mlp_shapes("x", [feat] + hid + [d.reward_out])),
         "encoder": enc,
         "actor": strip(_mlp_shapes("x", [feat] + hid + [d.actor_out])),
         "critic": strip(_mlp_shapes("x", [feat] + hid + [d.critic_out])),

@@ -1131,6 +1131,18 @@ int bd_twohot_decode_backward(const float* logits, int ld, const float* dvalue, 
 int bd_twohot_nll(const float* logits, int ld, const float* target, const float* weight, int rows, int K, float zmax,
                   float grad_scale, float* dlogits, int ldd, float* value, float* row_loss, void* stream);
 
+/* ---- symlog / symexp of a flat fp32 array (csrc/symlog.hip; symlog_observations) -----------------------------------
+ * bd_symlog: out[i] = sign(x[i]) log1p(|x[i]|);   bd_symexp: out[i] = sign(x[i]) expm1(|x[i]|),   0 <= i < n.
+ * Precise log1pf / expm1f under copysignf: +-0 -> +-0, f(-x) = -f(x) bit for bit, NaN -> NaN, +-inf -> +-inf; symexp
+ * overflows to +-inf where expm1f does (|x| above about 88.72).
+ * Out of place: out == x, or any other overlap of the two arrays, is refused.  4-byte alignment; where x and out sit at
+ * the same offset from a 16-byte boundary the body moves as 16-byte loads and stores, with a dword path for the head up
+ * to the boundary and for the tail, else every element takes the dword path.  Every output element is written exactly
+ * once, nothing before out[0] or from out[n] on.  No LDS, no atomics.  Asynchronous on `stream`; never allocate, never
+ * synchronise; NULLs, n = 0 and overlapping arrays are refused before anything is enqueued. */
+int bd_symlog(const float* x, size_t n, float* out, void* stream);
+int bd_symexp(const float* x, size_t n, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,9 @@ def my_app(argv):
     check_return_normalization(*(params["ActorCritic"][k] for k in RETURN_NORM_KEYS), algorithm=params["algorithm"])
     from big_dreamer_amd.config import CRITIC_HEAD_KEYS, check_critic_head
     check_critic_head(*(params["ActorCritic"][k] for k in CRITIC_HEAD_KEYS), algorithm=params["algorithm"])
+    from big_dreamer_amd.config import REWARD_HEAD_KEYS, check_reward_head, check_symlog_observations
+    check_reward_head(*(params[k] for k in REWARD_HEAD_KEYS), algorithm=params["algorithm"])
+    check_symlog_observations(params["symlog_observations"], params["pixel_observation"], params["algorithm"])
     from big_dreamer_amd import checkpoint as ck
     for key in ("models", "experience_replay"):                    # multi-GPU: every rank loads its own ..._rank<r> file
         params[key] = ck.for_rank(params[key], rank, world)
